@@ -10,6 +10,11 @@ itself (same launcher, a free port on 127.0.0.1) after checking that N devices a
 test).  `--share-device`: all ranks on cuda:0 with host-staged collectives -- verification of the N > 1 data path on a 1-GPU
 box, never a measurement.
 
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line (`value`, `ms_per_step`, `config`).  `--full`
+adds everything else the benchmark reports: per-kernel HIP events and the roofline rows, kernels timed alone after the timed region,
+the measured copy ceiling, the strict-fp32 and strong-scaling sub-records, the dssm metric pass and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
+
 A "step" = hash -> fused gather+pool+FM forward -> DNN forward -> sigmoid-CE -> DNN backward ->
 scatter-add backward, with the SGD update fused into the wgrad / scatter kernels (no work skipped).
 Inputs (raw keys, dense features, labels) are resident in HBM before the timed region.
@@ -86,8 +91,15 @@ def parse():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong scaling: the batch of the WHOLE job (BASELINE config 3 as worded: 65536 over 8 GPUs); per-GPU batch = this / N")
     ap.add_argument("--events", choices=["auto", "on", "off"], default="auto",
-                    help="per-kernel HIP events in the timed region (roofline rows).  auto: off for steps too short to carry two event "
-                         "records per kernel (first-layer GEMM < 4 GFLOP, e.g. the MovieLens shape)")
+                    help="with --full: per-kernel HIP events in the timed region (roofline rows).  auto: off for steps too short to carry "
+                         "two event records per kernel (first-layer GEMM < 4 GFLOP, e.g. the MovieLens shape)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel events and roofline rows, kernels timed alone, the copy ceiling, the "
+                         "strict-fp32 and strong-scaling sub-records, the dssm metric pass, the CPU baseline.  Without it a run sets up, "
+                         "warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, predictions, dense parameters, seeded "
+                         "samples of the embedding tables) as DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--items", type=int, default=1_000_000, help="dssm: corpus size")
     ap.add_argument("--users", type=int, default=1_000_000, help="dssm: user hash buckets")
     ap.add_argument("--towers", type=str, default="256,128", help="dssm: tower widths (last = embedding dim of the retrieval space)")
@@ -100,6 +112,8 @@ def parse():
                     help="N > 1 ranks all on cuda:0, collectives staged through the host over gloo (sharded.HostStagedTransport): checks "
                          "the N > 1 data path with the real kernels on a 1-GPU box; the printed rate is NOT a measurement")
     a = ap.parse_args()
+    if a.events == "on" and not a.full:
+        ap.error("--events on: per-kernel events are part of --full")
     if a.preset == "c2":
         a.fields, a.vocab, a.dim, a.dense, a.batch = 7, 10_000, 16, 0, 4096
     if a.model == "dssm":
@@ -133,6 +147,44 @@ def synth_batches(a, device, rank):
         labels = (torch.rand(a.batch, device=device, generator=g) < 0.25).float()
         out.append((keys, dense, labels))
     return out
+
+
+DUMP_ROWS = 16384         # rows per table sample (twice: among the rows the last batch touched, and among all rows)
+DUMP_WHOLE = 1 << 20      # a flat parameter buffer up to this many elements is written whole, a larger one as a sample of this size
+
+
+def dump_outputs(eng, out_dir, touched):
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy -- the loss it returned, the predictions, the dense
+    parameters it updated and seeded row samples of the embedding tables it updated (about 20 MB at the default shapes).  `touched`: per
+    table, the device tensor of the rows the last batch read (None for a sharded table, whose rows are not global ids).  The samples
+    depend only on fixed seeds and the shapes, so two runs with the same arguments write files that compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(20240)
+
+    def pick(n, k):
+        return torch.randint(0, n, (k,), generator=g) if n > k else torch.arange(n)
+
+    out = {"loss": eng.loss.reshape(-1)}
+    if getattr(eng, "prob", None) is not None:
+        out["prob"] = eng.prob
+    flat = getattr(eng, "flat_params", None)
+    if flat is None:      # engines without one flat buffer: cross layers, MLP layers, towers, in declaration order
+        parts = [t for nm in ("cross_W", "cross_b", "Ws", "bs") for t in getattr(eng, nm, [])]
+        parts += [t for tw in ("q_tower", "c_tower") for nm in ("Ws", "bs") for t in getattr(getattr(eng, tw, None), nm, [])]
+        flat = torch.cat([t.reshape(-1) for t in parts]) if parts else None
+    if flat is not None:
+        out["dense_params"] = flat if flat.numel() <= DUMP_WHOLE else flat[pick(flat.numel(), DUMP_WHOLE).to(flat.device)]
+    for name, table, lin, rows in touched:
+        idx = pick(table.shape[0], DUMP_ROWS).to(table.device)
+        if rows is not None:
+            rows = rows.reshape(-1)
+            idx = torch.cat([rows[pick(rows.numel(), DUMP_ROWS).to(rows.device)], idx])
+        out[name + "_rows"] = table[idx]
+        if lin is not None:
+            out[name + "_lin_rows"] = lin[idx]
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def _median_rate(step_fn, batch, warmup, min_steps, cap_s):
@@ -414,7 +466,7 @@ def main():
     prof = getattr(eng, "enable_kernel_events", None)
     first_gemm_flops = 2.0 * a.batch * (a.fields * a.dim + a.dense) * (dnn_units[0] if dnn_units else 1)
     events_on = a.events == "on" or (a.events == "auto" and (a.model != "deepfm" or first_gemm_flops >= 4e9))
-    if os.environ.get("DR_BENCH_EVENTS", "1") == "0" or not events_on:
+    if os.environ.get("DR_BENCH_EVENTS", "1") == "0" or not events_on or not a.full:
         prof = None
     ev_every = 1
     # The sharded step drives four streams; a step with event records on them takes anywhere from 1.1 x to 5 x as long as one without
@@ -464,27 +516,18 @@ def main():
     torch.cuda.synchronize()
     if prof is not None:
         ev_every = events_begin()        # (the settling blocks run what the timed region runs; their samples are dropped below)
-    # Settling (single process only; untimed, like the warm-up): further blocks of 20 steps until two consecutive blocks agree within 2 %
-    # (or 5 s have passed).  The W warm-up steps cover the chip's ramp; this covers the HOST: the step needs 0.33 ms of launch work per
-    # 1.14 ms of GPU work, and on a box that is still busy with its own start-up (seen twice as the first command of a call: 1.52 and
-    # 2.69 ms lines whose per-kernel times were normal) the launches fall behind for a few seconds.  Normally 2 blocks = 46 ms.
+    # Settling (single process only; untimed, like the warm-up): SETTLE_STEPS further steps.  The W warm-up steps cover the chip's ramp;
+    # this covers the HOST: the step needs 0.33 ms of launch work per 1.14 ms of GPU work, and on a box that is still busy with its own
+    # start-up (seen twice as the first command of a call: 1.52 and 2.69 ms lines whose per-kernel times were normal) the launches fall
+    # behind for a while.  A fixed count, not "until two blocks agree": the model state the timed steps start from -- and so what
+    # --dump-outputs writes -- must not depend on how busy the host was.  40 = where the adaptive rule of rounds 1 - 6 normally stopped.
+    SETTLE_STEPS = 40
     settle_steps = 0
     if dist is None and a.warmup > 0 and os.environ.get("DR_BENCH_SETTLE", "1") == "1":
-        prev_t, best_t, t_begin = None, None, time.perf_counter()
-        while settle_steps < 6000 and time.perf_counter() - t_begin < 5.0:
-            t1 = time.perf_counter()
-            for i in range(20):
-                step(a.warmup + settle_steps + i)
-            torch.cuda.synchronize()
-            cur_t = time.perf_counter() - t1
-            settle_steps += 20
-            best_t = cur_t if best_t is None else min(best_t, cur_t)
-            # (round 6: two blocks that agree are not enough -- on a host busy with its neighbours' start-up the launches fall behind at
-            # a STABLE slow rate for a second or two, seen as a 1.31 ms line between 1.03 ms ones; the block must also be within 5 % of
-            # the fastest block seen so far)
-            if prev_t is not None and abs(cur_t - prev_t) <= 0.02 * prev_t and cur_t <= 1.05 * best_t:
-                break
-            prev_t = cur_t
+        for i in range(SETTLE_STEPS):
+            step(a.warmup + i)
+        settle_steps = SETTLE_STEPS
+        torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     # ---- timed region: exactly K steps; per-kernel HIP events ride along on the launch stream -------
@@ -505,6 +548,14 @@ def main():
     loss = float(eng.loss.item())
     ms = dt / a.steps * 1e3
     value = a.batch * world * a.steps / dt
+    if a.dump_outputs and rank == 0:      # (before anything below runs further steps or kernels on the engine's state)
+        if a.model == "dssm":
+            last_items = batches[(a.warmup + settle_steps + a.steps - 1) % len(batches)][1]
+            tables = [("user_table", eng.user_table, None, None if sharded else eng.uid[:a.batch]),
+                      ("item_table", eng.item_table, None, None if sharded else last_items)]
+        else:
+            tables = [("table", eng.table, getattr(eng, "lin_w", None), None if sharded else eng.ids + eng.row_base)]
+        dump_outputs(eng, a.dump_outputs, tables)
     kernels_timed = None
     if headline_only:
         # the headline kernel's samples of the timed region; then every kernel of EV_EXTRA further steps for the other rows
@@ -530,7 +581,7 @@ def main():
     # scaling) -- so that one driver command yields both scaling curves.  A second engine on every rank (per-rank
     # batch = batch / N), 5 warm-up + 20 timed steps bracketed like the main region; failures are reported, never fatal.
     strong = None
-    if (world > 1 and not a.global_batch and a.model == "deepfm" and sharded and os.environ.get("DR_BENCH_STRONG", "1") == "1"
+    if (a.full and world > 1 and not a.global_batch and a.model == "deepfm" and sharded and os.environ.get("DR_BENCH_STRONG", "1") == "1"
             and a.batch % world == 0):
         try:
             from deep_recommenders_amd.sharded import ShardedDeepFMEngine
@@ -565,7 +616,7 @@ def main():
     # the slot plan K4 needs, ALONE on the idle chip (after the timed region): what it would add to K4 if it did not run beside the
     # previous step's K4 -- the overlapped event time in `overlapped_side_stream` is stretched by that sharing
     plan_alone_us = None
-    if a.model == "deepfm" and not sharded and getattr(eng, "sorted_bwd", False) and hasattr(eng, "plan"):
+    if a.full and a.model == "deepfm" and not sharded and getattr(eng, "sorted_bwd", False) and hasattr(eng, "plan"):
         from deep_recommenders_amd import ops as _ops
         torch.cuda.synchronize()
         for _ in range(3):
@@ -631,7 +682,7 @@ def main():
         exchange["backend"] = dist.get_backend() if dist is not None else None
     if prof is not None:
         eng.enable_kernel_events(False)
-    if a.model == "dssm":
+    if a.full and a.model == "dssm":
         # FactorizedTopK pass (factorized_top_k.py:489-512): corpus index = item tower over all items, then exact top-k of
         # every query against it; reported next to the training step (Retrieval.call(compute_metrics=True) does both)
         torch.cuda.synchronize()
@@ -657,37 +708,38 @@ def main():
     # passes of this same command (profiles/, see `traffic_source`), only for the default configuration they were taken on
     traffic, traffic_source = {}, None
     traffic_note = "HBM counters need the profiler (rocprofv3 --pmc passes of this command, tools/collect_profiles.sh); not collected inside bench.py"
-    try:
-        src = next(("profiles/%s_pmc_traffic.json" % r for r in ("r06", "r05", "r04", "r03", "r02", "r01")
-                    if os.path.exists(os.path.join(ROOT, "profiles", "%s_pmc_traffic.json" % r))), "profiles/r01_pmc_traffic.json")
-        pmc = json.load(open(os.path.join(ROOT, src)))
-        name_map = pmc.get("event_names") or {}
-        # the static figures describe the LIBRARY they were collected on (tools/collect_profiles.sh records its sha256): a kernel change
-        # that doubled the traffic must not keep printing the old number -- a different library gets no figure
-        lib_sha = _lib_sha256()
-        if not pmc.get("lib_sha256"):
-            raise RuntimeError("%s records no library hash (collected before round 6): re-collect with tools/collect_profiles.sh" % src)
-        if not lib_sha or pmc["lib_sha256"] != lib_sha:
-            raise RuntimeError("%s was collected on libdr_hotpath.so %s..., this run loads %s...: re-collect with tools/collect_profiles.sh"
-                               % (src, pmc["lib_sha256"][:12], (lib_sha or "?")[:12]))
-        default_cfg = (a.model, a.batch, a.fields, a.vocab, a.dim, a.dense, a.dnn, a.optimizer, a.gemm) == \
-            ("deepfm", 65536, 26, 10_000_000, 64, 13, "256,32", "sgd", "bf16x3")
-        if default_cfg and world == 1 and not force_sharded:
-            traffic = {ev: int(pmc["kernels"][k]["hbm_bytes_corrected"]) for ev, k in name_map.items() if k in pmc["kernels"]}
-            traffic_source = src + (" (static: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command by tools/collect_profiles.sh, "
-                                    "not this run; collected on the library this run loads: sha256 %s)" % (lib_sha or "?")[:400])
-            if getattr(eng, "h2", False) and pmc.get("gemm_split", "bf16x3") != "f16x2":
-                # the committed passes were taken with the first layer's GEMMs in the bf16x3 mode: their byte counts (three weight planes
-                # per k-tile, not two) do not describe the f16x2 kernels this run timed.  K4 and the tail kernels are the same code.
-                for ev in H2_KERNELS:
-                    traffic.pop(ev, None)
-                traffic_source += "; the three first-layer GEMM rows carry no figure: the passes predate the f16x2 mode (profiles/README.md)"
-        else:
-            traffic_note = ("the committed PMC passes (%s) were taken on the default configuration (deepfm, B 65536, 26 x 10 M x 64, DNN 256,32, sgd, "
-                            "bf16x3, one GPU); this run differs, so no traffic figure applies" % src)
-    except Exception as e:
-        traffic = {}
-        traffic_note = "no static PMC figure applies (%s)" % (e,)
+    if a.full:
+        try:
+            src = next(("profiles/%s_pmc_traffic.json" % r for r in ("r06", "r05", "r04", "r03", "r02", "r01")
+                        if os.path.exists(os.path.join(ROOT, "profiles", "%s_pmc_traffic.json" % r))), "profiles/r01_pmc_traffic.json")
+            pmc = json.load(open(os.path.join(ROOT, src)))
+            name_map = pmc.get("event_names") or {}
+            # the static figures describe the LIBRARY they were collected on (tools/collect_profiles.sh records its sha256): a kernel change
+            # that doubled the traffic must not keep printing the old number -- a different library gets no figure
+            lib_sha = _lib_sha256()
+            if not pmc.get("lib_sha256"):
+                raise RuntimeError("%s records no library hash (collected before round 6): re-collect with tools/collect_profiles.sh" % src)
+            if not lib_sha or pmc["lib_sha256"] != lib_sha:
+                raise RuntimeError("%s was collected on libdr_hotpath.so %s..., this run loads %s...: re-collect with tools/collect_profiles.sh"
+                                   % (src, pmc["lib_sha256"][:12], (lib_sha or "?")[:12]))
+            default_cfg = (a.model, a.batch, a.fields, a.vocab, a.dim, a.dense, a.dnn, a.optimizer, a.gemm) == \
+                ("deepfm", 65536, 26, 10_000_000, 64, 13, "256,32", "sgd", "bf16x3")
+            if default_cfg and world == 1 and not force_sharded:
+                traffic = {ev: int(pmc["kernels"][k]["hbm_bytes_corrected"]) for ev, k in name_map.items() if k in pmc["kernels"]}
+                traffic_source = src + (" (static: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command by tools/collect_profiles.sh, "
+                                        "not this run; collected on the library this run loads: sha256 %s)" % (lib_sha or "?")[:400])
+                if getattr(eng, "h2", False) and pmc.get("gemm_split", "bf16x3") != "f16x2":
+                    # the committed passes were taken with the first layer's GEMMs in the bf16x3 mode: their byte counts (three weight planes
+                    # per k-tile, not two) do not describe the f16x2 kernels this run timed.  K4 and the tail kernels are the same code.
+                    for ev in H2_KERNELS:
+                        traffic.pop(ev, None)
+                    traffic_source += "; the three first-layer GEMM rows carry no figure: the passes predate the f16x2 mode (profiles/README.md)"
+            else:
+                traffic_note = ("the committed PMC passes (%s) were taken on the default configuration (deepfm, B 65536, 26 x 10 M x 64, DNN 256,32, sgd, "
+                                "bf16x3, one GPU); this run differs, so no traffic figure applies" % src)
+        except Exception as e:
+            traffic = {}
+            traffic_note = "no static PMC figure applies (%s)" % (e,)
     roof_all = []
     comm_phases = {}
     overlapped = {}
@@ -822,7 +874,7 @@ def main():
     # which K4 exceeded: not a ceiling.)
     copy_gbs = None
     try:
-        if world == 1 or not a.share_device:
+        if a.full and (world == 1 or not a.share_device):
             src_c = torch.empty(1 << 28, dtype=torch.float32, device=device)
             dst_c = torch.empty_like(src_c)
             src_c.zero_()
@@ -900,9 +952,9 @@ def main():
                        **({"per_kernel_events_scope": "the headline kernel inside the timed region; the other rows from %d fully bracketed steps after it" % EV_EXTRA}
                           if headline_only else {}),
                        "settle_steps_untimed": settle_steps},
-            "roofline": roofline,
-            "roofline_all": roof_all,
         }
+        if a.full:
+            out["roofline"], out["roofline_all"] = roofline, roof_all
         if roofline_mfma is not None:
             out["roofline_mfma"] = roofline_mfma
         if roofline_fwd_bare is not None:
@@ -929,7 +981,7 @@ def main():
         # The same job with every product formed from EXACT operand splits (six bf16 MFMA products: 24-bit operands, i.e. fp32 operand
         # arithmetic) beside the headline, whose first-layer GEMMs carry 22-bit operands (f16x2 split): a second engine, same seed, same
         # batches, as many steps as the headline engine had run when its loss was read; the last 20 of them timed.
-        if (world == 1 and not force_sharded and a.model == "deepfm" and a.gemm == "bf16x3" and getattr(eng, "h2", False)
+        if (a.full and world == 1 and not force_sharded and a.model == "deepfm" and a.gemm == "bf16x3" and getattr(eng, "h2", False)
                 and a.optimizer == "sgd" and os.environ.get("DR_BENCH_STRICT", "1") == "1"):
             prev_split = dr_ops.set_gemm_split("bf16x3")
             try:
@@ -956,7 +1008,7 @@ def main():
                 out["strict_fp32"] = {"failed": repr(e)}
             finally:
                 dr_ops.set_gemm_split(prev_split)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(a, dnn_units)
             except Exception as e:     # the baseline is reported, never the thing measured

@@ -542,6 +542,7 @@ class ShardedDeepFMEngine:
         self.table = torch.empty((F * rps, D), **f32)
         if init_tables is not None:
             full_table, full_lin = init_tables           # tests: shard a given global table
+            self.table.zero_()                           # (a shard short of rps rows per field keeps defined padding rows)
             self.lin_w = torch.zeros(F * rps, **f32)
             for f in range(F):
                 ids = torch.arange(self.rank, V, W)
@@ -1239,6 +1240,7 @@ class ShardedDCNEngine:
         self.table = torch.empty((F * rps, D), **f32)
         if init_tables is not None:
             full_table = init_tables
+            self.table.zero_()
             for f in range(F):
                 ids = torch.arange(self.rank, V, W)
                 self.table[f * rps:f * rps + len(ids)] = full_table[f * V + ids].to(device)

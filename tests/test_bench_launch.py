@@ -100,7 +100,7 @@ def test_share_device_two_ranks_on_one_gpu():
     ranks on cuda:0 and the collectives staged through the host: the line must carry n_gpus = 2, the exchange report and a finite
     loss.  (Timing is meaningless here and flagged as such in the line.)"""
     rc, out, err = _run(["--gpus", "2", "--share-device", "--steps", "3", "--warmup", "1", "--batch", "4096", "--vocab", "20000",
-                         "--no-cpu-baseline", "--events", "on"], timeout=500)
+                         "--no-cpu-baseline", "--events", "on", "--full"], timeout=500)
     assert rc == 0, err[-3000:]
     lines = _json_lines(out)
     assert len(lines) == 1, out

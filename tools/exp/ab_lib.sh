@@ -9,7 +9,7 @@ cp $L /tmp/ab_new.so
 for rep in $(seq 1 $REPS); do
   for n in new alt; do
     if [ $n = new ]; then cp /tmp/ab_new.so $L; else cp $ALT $L; fi
-    timeout 300 python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1 > /tmp/ab_line.json
+    timeout 300 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1 > /tmp/ab_line.json
     python - $n <<'PY'
 import json,sys
 try:

@@ -12,7 +12,7 @@ cp $L /tmp/ab_base.so
 for rep in $(seq 1 $REPS); do
   for n in base "${ALTS[@]}"; do
     if [ $n = base ]; then cp /tmp/ab_base.so $L; else cp $n $L; fi
-    timeout 300 python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1 > /tmp/ab_line.json
+    timeout 300 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1 > /tmp/ab_line.json
     python - $(basename $n .so | sed 's/libdr_hotpath_//') <<'PY'
 import json,sys
 try:

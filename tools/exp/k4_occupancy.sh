@@ -17,12 +17,13 @@ if [ "$1" = build ]; then
 fi
 L=deep_recommenders_amd/lib/libdr_hotpath.so
 cp $L /tmp/new.so
-mkdir -p gpurun_out/k4occ
+OUTD=${OUT:-collect_out}/k4occ
+mkdir -p $OUTD
 for rep in 1 2; do
 for n in base mw5 mw6 mw8 u2 u8 u2mw8; do
   if [ $n = base ]; then cp /tmp/new.so $L; else cp tools/exp/_alt/libdr_hotpath_k4_$n.so $L; fi
-  timeout 300 python bench.py --no-cpu-baseline --steps 30 2>/dev/null > gpurun_out/k4occ/bench_${n}_$rep.json
-  python - gpurun_out/k4occ/bench_${n}_$rep.json $n <<'PY'
+  timeout 300 python bench.py --full --no-cpu-baseline --steps 30 2>/dev/null > $OUTD/bench_${n}_$rep.json
+  python - $OUTD/bench_${n}_$rep.json $n <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[2], d["ms_per_step"], [(r["kernel"], r["avg_us"]) for r in d["roofline_all"] if r["kernel"]=="emb_pool_bwd"])
