@@ -87,6 +87,10 @@ struct GemmArgs {
     float* cand_s; int32_t* cand_c;   // [M][cand_cap] scores / column numbers
     int32_t* cand_cnt;            // [M] append cursors (may exceed cand_cap: the consumer clamps; cap == N never overflows)
     int64_t cand_cap;
+    // grouped launches (template GRP, gridDim.z = groups): block z offsets every operand by z times its group stride; with
+    // `partial` set, the EPI_ATOMIC column sums go to partial[split][M][N] + [split][N] (summed by the grouped reduce)
+    int32_t groups;
+    int64_t a_gs, b_gs, c_gs, bias_gs, e0_gs, cs_gs, part_gs;
 };
 
 // exp() of a non-positive softmax argument; masked logits sit at ~-5e36 (MIN_FLOAT / temperature), far outside the
@@ -164,8 +168,16 @@ __device__ __forceinline__ void put4_bf3(__bf16* __restrict__ plane0, int plane_
 // Occupancy: 3 blocks per CU for the wide tile (168 VGPRs).  At 4 (128 VGPRs) the next k-tile's 8 prefetch registers
 // cannot stay live across the MFMA block without spilling, so the compiler sinks the global loads BELOW the 64 MFMAs
 // and their latency is exposed in front of every barrier; pinned ahead of the MFMAs at 3 blocks/CU is 2-4 % faster.
-template <bool A_RC, bool B_RC, int EPI, bool NARROW, bool OCC4 = false, bool BF3 = false>
+template <bool A_RC, bool B_RC, int EPI, bool NARROW, bool OCC4 = false, bool BF3 = false, bool GRP = false>
 __global__ __launch_bounds__(256, BF3 ? 2 : ((NARROW || OCC4) ? 4 : 3)) void gemm_f32_mfma_kernel(GemmArgs g) {
+    if constexpr (GRP) {
+        const int64_t z = blockIdx.z;
+        g.A += z * g.a_gs; g.B += z * g.b_gs; g.C += z * g.c_gs;
+        if (g.bias != nullptr) g.bias += z * g.bias_gs;
+        if (g.e0 != nullptr) g.e0 += z * g.e0_gs;
+        if (g.colsum_dst != nullptr) g.colsum_dst += z * g.cs_gs;
+        if (g.partial != nullptr) g.partial += z * g.part_gs;
+    }
     // wide: 2 x 2 waves, each 2 x 2 MFMA tiles (128 x 128);  narrow: 4 x 1 waves, each 1 x 1 tile (128 x 32)
     constexpr int BN = NARROW ? 32 : 128;
     constexpr int TM = NARROW ? 1 : 2, TN = NARROW ? 1 : 2;
@@ -742,7 +754,12 @@ __global__ __launch_bounds__(256, BF3 ? 2 : ((NARROW || OCC4) ? 4 : 3)) void gem
             }
         }
     }
-    if (do_colsum && n0 + tid < g.N) unsafeAtomicAdd(g.colsum_dst + n0 + tid, g.alpha * colsum);
+    if (do_colsum && n0 + tid < g.N) {
+        if (GRP && g.partial != nullptr)
+            g.partial[(int64_t)g.split * g.M * g.N + (int64_t)blockIdx.y * g.N + n0 + tid] = colsum;
+        else
+            unsafeAtomicAdd(g.colsum_dst + n0 + tid, g.alpha * colsum);
+    }
 }
 
 
@@ -761,7 +778,7 @@ static int gemm_split_default() {
 }
 static std::atomic<int> g_gemm_split{gemm_split_default()};
 
-template <bool A_RC, bool B_RC, int EPI>
+template <bool A_RC, bool B_RC, int EPI, bool GRP = false>
 int launch(GemmArgs& g, hipStream_t s) {
 
     g.a_vec = ((reinterpret_cast<uintptr_t>(g.A) & 15) == 0 && (g.lda & 3) == 0) ? 1 : 0;
@@ -772,10 +789,10 @@ int launch(GemmArgs& g, hipStream_t s) {
     const int tiles_n = (g.N + bn - 1) / bn;
     const int64_t tiles_m = (g.M + bm - 1) / bm;
     if (tiles_m * tiles_n > 0x7fffffff) return DR_EINVAL;
-    dim3 grid((unsigned)(tiles_m * tiles_n), EPI == EPI_ATOMIC ? g.split : 1);
+    dim3 grid((unsigned)(tiles_m * tiles_n), EPI == EPI_ATOMIC ? g.split : 1, GRP ? g.groups : 1);
     if (narrow) {
         if constexpr (EPI == EPI_BIAS_ACT || EPI == EPI_MASK || EPI == EPI_ATOMIC || EPI == EPI_HEAD)
-            hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, true>), grid, dim3(256), 0, s, g);
+            hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, true, false, false, GRP>), grid, dim3(256), 0, s, g);
     } else {
         if constexpr (EPI == EPI_HEAD) return DR_ESHAPE;
         else if constexpr (EPI == EPI_FILTER || EPI == EPI_LSE || EPI == EPI_SMGRAD) {
@@ -787,18 +804,18 @@ int launch(GemmArgs& g, hipStream_t s) {
             // The in-batch softmax pair (LSE forward / gradient) stays on the fp32 MFMA (bf16x3 measured 3 % slower there).
             if (EPI == EPI_FILTER && g_gemm_mode.load(std::memory_order_relaxed) == DR_GEMM_BF16X3) {
                 if constexpr (EPI == EPI_FILTER)
-                    hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false, false, true>), grid, dim3(256), 0, s, g);
+                    hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false, false, true, GRP>), grid, dim3(256), 0, s, g);
             } else if (g.R <= 256)
-                hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false, true>), grid, dim3(256), 0, s, g);
+                hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false, true, false, GRP>), grid, dim3(256), 0, s, g);
             else
-                hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false>), grid, dim3(256), 0, s, g);
+                hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false, false, false, GRP>), grid, dim3(256), 0, s, g);
         } else if constexpr (EPI == EPI_BIAS_ACT || EPI == EPI_CROSS || EPI == EPI_MASK || EPI == EPI_FMGRAD || EPI == EPI_ATOMIC) {
             // the tower / cross-layer GEMMs: fp32 products on the bf16 matrix pipe unless the caller asked for the native one
             if (g_gemm_mode.load(std::memory_order_relaxed) == DR_GEMM_BF16X3)
-                hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false, false, true>), grid, dim3(256), 0, s, g);
+                hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false, false, true, GRP>), grid, dim3(256), 0, s, g);
             else
-                hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false>), grid, dim3(256), 0, s, g);
-        } else hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false>), grid, dim3(256), 0, s, g);
+                hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false, false, false, GRP>), grid, dim3(256), 0, s, g);
+        } else hipLaunchKernelGGL((gemm_f32_mfma_kernel<A_RC, B_RC, EPI, false, false, false, GRP>), grid, dim3(256), 0, s, g);
     }
     DR_CHECK_LAUNCH();
     return DR_OK;
@@ -867,10 +884,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 
 // ---- skinny shapes (min(K, N) < 4: the Dense(1) heads) : streaming kernels, no MFMA -------------------------------
 // y[m][n] = act(sum_k x[m][k] W[k][n] + b[n]) ; one lane group of 16 per row, k strided over the lanes
-__global__ __launch_bounds__(256) void skinny_fwd_kernel(const float* __restrict__ x, int64_t ldx,
-                                                         const float* __restrict__ W, int64_t ldw,
-                                                         const float* __restrict__ b, int64_t M, int32_t K, int32_t N,
-                                                         int32_t act, float* __restrict__ y, int64_t ldy) {
+__device__ __forceinline__ void skinny_fwd_body(const float* __restrict__ x, int64_t ldx, const float* __restrict__ W, int64_t ldw,
+                                                const float* __restrict__ b, int64_t M, int32_t K, int32_t N, int32_t act,
+                                                float* __restrict__ y, int64_t ldy) {
     const int lane = threadIdx.x & 15;
     const int64_t groups = (int64_t)gridDim.x * (blockDim.x >> 4);
     for (int64_t m = (int64_t)blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4); m < M; m += groups) {
@@ -887,11 +903,25 @@ __global__ __launch_bounds__(256) void skinny_fwd_kernel(const float* __restrict
         }
     }
 }
+__global__ __launch_bounds__(256) void skinny_fwd_kernel(const float* __restrict__ x, int64_t ldx,
+                                                         const float* __restrict__ W, int64_t ldw,
+                                                         const float* __restrict__ b, int64_t M, int32_t K, int32_t N,
+                                                         int32_t act, float* __restrict__ y, int64_t ldy) {
+    skinny_fwd_body(x, ldx, W, ldw, b, M, K, N, act, y, ldy);
+}
+// grouped: group blockIdx.y reads x / W / b and writes y at its group offsets
+__global__ __launch_bounds__(256) void skinny_fwd_grouped_kernel(const float* __restrict__ x, int64_t ldx, int64_t x_gs,
+                                                                 const float* __restrict__ W, int64_t ldw, int64_t w_gs,
+                                                                 const float* __restrict__ b, int64_t b_gs, int64_t M, int32_t K,
+                                                                 int32_t N, int32_t act, float* __restrict__ y, int64_t ldy,
+                                                                 int64_t y_gs) {
+    const int64_t z = blockIdx.y;
+    skinny_fwd_body(x + z * x_gs, ldx, W + z * w_gs, ldw, b != nullptr ? b + z * b_gs : nullptr, M, K, N, act, y + z * y_gs, ldy);
+}
 // dx[m][k] = (sum_n dy[m][n] W[k][n]) * (relu_src[m][k] > 0) (+ dx)
-__global__ __launch_bounds__(256) void skinny_dx_kernel(const float* __restrict__ dy, int64_t lddy,
-                                                        const float* __restrict__ W, int64_t ldw, int64_t M, int32_t K,
-                                                        int32_t N, const float* __restrict__ rs, int64_t ldrs,
-                                                        int32_t accumulate, float* __restrict__ dx, int64_t lddx) {
+__device__ __forceinline__ void skinny_dx_body(const float* __restrict__ dy, int64_t lddy, const float* __restrict__ W, int64_t ldw,
+                                               int64_t M, int32_t K, int32_t N, const float* __restrict__ rs, int64_t ldrs,
+                                               int32_t accumulate, float* __restrict__ dx, int64_t lddx) {
     const int64_t total = M * K;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
@@ -903,6 +933,21 @@ __global__ __launch_bounds__(256) void skinny_dx_kernel(const float* __restrict_
         if (accumulate) acc += dx[m * lddx + k];
         dx[m * lddx + k] = acc;
     }
+}
+__global__ __launch_bounds__(256) void skinny_dx_kernel(const float* __restrict__ dy, int64_t lddy,
+                                                        const float* __restrict__ W, int64_t ldw, int64_t M, int32_t K,
+                                                        int32_t N, const float* __restrict__ rs, int64_t ldrs,
+                                                        int32_t accumulate, float* __restrict__ dx, int64_t lddx) {
+    skinny_dx_body(dy, lddy, W, ldw, M, K, N, rs, ldrs, accumulate, dx, lddx);
+}
+__global__ __launch_bounds__(256) void skinny_dx_grouped_kernel(const float* __restrict__ dy, int64_t lddy, int64_t dy_gs,
+                                                                const float* __restrict__ W, int64_t ldw, int64_t w_gs, int64_t M,
+                                                                int32_t K, int32_t N, const float* __restrict__ rs, int64_t ldrs,
+                                                                int64_t rs_gs, int32_t accumulate, float* __restrict__ dx,
+                                                                int64_t lddx, int64_t dx_gs) {
+    const int64_t z = blockIdx.y;
+    skinny_dx_body(dy + z * dy_gs, lddy, W + z * w_gs, ldw, M, K, N, rs != nullptr ? rs + z * rs_gs : nullptr, ldrs, accumulate,
+                   dx + z * dx_gs, lddx);
 }
 // dst[k][n] += scale * sum_m x[m][k] dy[m][n] ; dstb[n] += scale * sum_m dy[m][n].  A block owns a slab of rows and
 // all (k, n) pairs (strided over its threads), accumulates in registers, then one atomic per (k, n) per block.
@@ -956,6 +1001,94 @@ __global__ __launch_bounds__(256) void skinny_dw_kernel(const float* __restrict_
                 unsafeAtomicAdd(dstb + n, scale * t);
             }
             __syncthreads();
+        }
+    }
+}
+
+// grouped skinny weight gradient: block (x = row slab, y = group) as skinny_dw_kernel; with `partial` the block's sums are stored
+// to partial[group][slab][K*N] (+ [slab][N] for the bias) and summed in slab order by grouped_reduce_kernel (deterministic)
+__global__ __launch_bounds__(256) void skinny_dw_grouped_kernel(const float* __restrict__ x, int64_t ldx, int64_t x_gs,
+                                                                const float* __restrict__ dy, int64_t lddy, int64_t dy_gs, int64_t M,
+                                                                int32_t K, int32_t N, float scale, float* __restrict__ dst,
+                                                                int64_t ldw, int64_t w_gs, float* __restrict__ dstb, int64_t b_gs,
+                                                                float* __restrict__ partial, int64_t part_gs) {
+    __shared__ float sm[256];
+    const int64_t z = blockIdx.y;
+    x += z * x_gs;
+    dy += z * dy_gs;
+    dst += z * w_gs;
+    if (dstb != nullptr) dstb += z * b_gs;
+    const int nslab = gridDim.x;
+    const int64_t m0 = (int64_t)blockIdx.x * SK_ROWS;
+    const int64_t m1 = m0 + SK_ROWS < M ? m0 + SK_ROWS : M;
+    const int KN = K * N;
+    float* part = partial != nullptr ? partial + z * part_gs : nullptr;
+    const int lanes_e = KN < 256 ? KN : 256;
+    const int R = 256 / lanes_e;
+    const int e0 = threadIdx.x % lanes_e, rl = threadIdx.x / lanes_e;
+    for (int eb = 0; eb < KN; eb += lanes_e) {
+        const int e = eb + e0;
+        float acc = 0.f;
+        if (e < KN && rl < R) {
+            const int k = e / N, n = e - k * N;
+            for (int64_t m = m0 + rl; m < m1; m += R) acc = fmaf(x[m * ldx + k], dy[m * lddy + n], acc);
+        }
+        sm[threadIdx.x] = acc;
+        __syncthreads();
+        if (rl == 0 && e < KN) {
+            float t = 0.f;
+            for (int r = 0; r < R; ++r) t += sm[e0 + r * lanes_e];
+            const int k = e / N, n = e - k * N;
+            if (part != nullptr) part[(int64_t)blockIdx.x * KN + e] = t;
+            else unsafeAtomicAdd(dst + (int64_t)k * ldw + n, scale * t);
+        }
+        __syncthreads();
+    }
+    if (dstb != nullptr) {
+        const int ln = N < 256 ? N : 256;
+        const int Rb = 256 / ln;
+        const int n0 = threadIdx.x % ln, rb = threadIdx.x / ln;
+        for (int nb = 0; nb < N; nb += ln) {
+            const int n = nb + n0;
+            float acc = 0.f;
+            if (n < N && rb < Rb)
+                for (int64_t m = m0 + rb; m < m1; m += Rb) acc += dy[m * lddy + n];
+            sm[threadIdx.x] = acc;
+            __syncthreads();
+            if (rb == 0 && n < N) {
+                float t = 0.f;
+                for (int r = 0; r < Rb; ++r) t += sm[n0 + r * ln];
+                if (part != nullptr) part[(int64_t)nslab * KN + (int64_t)blockIdx.x * N + n] = t;
+                else unsafeAtomicAdd(dstb + n, scale * t);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// dst[g][k][n] += scale * sum_s partial[g][s][k][n] ; dstb[g][n] += scale * sum_s partial[g][split][s][n]  (grid.y = group).
+// The weight part sums in the order of splitk_reduce_kernel, so a group's dW equals the single-group call's bit for bit.
+__global__ __launch_bounds__(256) void grouped_reduce_kernel(const float* __restrict__ partial, int64_t part_gs, int32_t split,
+                                                             int64_t K, int32_t N, float scale, float* __restrict__ dst, int64_t ld,
+                                                             int64_t w_gs, float* __restrict__ dstb, int64_t b_gs) {
+    const int64_t z = blockIdx.y;
+    const float* part = partial + z * part_gs;
+    dst += z * w_gs;
+    const int64_t kn = K * N;
+    const int64_t total = kn + (dstb != nullptr ? N : 0);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        float acc = 0.f;
+        if (i < kn) {
+            for (int s = 0; s < split; ++s) acc += part[(int64_t)s * kn + i];
+            const int64_t k = i / N;
+            const int n = (int)(i - k * N);
+            dst[k * ld + n] = fmaf(scale, acc, dst[k * ld + n]);
+        } else {
+            const int64_t n = i - kn;
+            for (int s = 0; s < split; ++s) acc += part[(int64_t)split * kn + (int64_t)s * N + n];
+            float* db = dstb + z * b_gs;
+            db[n] = fmaf(scale, acc, db[n]);
         }
     }
 }
@@ -1195,6 +1328,110 @@ extern "C" int dr_linear_bwd_dw(const float* x, int64_t ld_x, const float* dy, i
     if (use_ws) {
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(dr_grid_for((int64_t)K * N, 256)), dim3(256), 0, dr_s(stream), workspace,
                            g.split, (int64_t)K, N, scale, dstW, ld_w);
+        DR_CHECK_LAUNCH();
+    }
+    return DR_OK;
+}
+
+// ---- grouped dense layers: G independent problems of one shape in one launch (gridDim.z = G on the tile kernel, grid.y on the
+// skinny kernels).  Group g reads x from x + g*x_gs (pitch ld_x), W from W + g*w_gs, b from b + g*b_gs and writes y + g*y_gs.
+static bool bad_group(int32_t G, int64_t a, int64_t b, int64_t c, int64_t d) {
+    return G < 1 || a < 0 || b < 0 || c < 0 || d < 0;
+}
+
+extern "C" int dr_linear_fwd_grouped(const float* x, int64_t ld_x, int64_t x_gs, const float* W, int64_t ld_w, int64_t w_gs,
+                                     const float* b, int64_t b_gs, int64_t M, int32_t K, int32_t N, int32_t G, int32_t act,
+                                     float* y, int64_t ld_y, int64_t y_gs, dr_stream_t stream) {
+    if (M < 0 || K <= 0 || N <= 0 || act < 0 || act > 1 || bad_group(G, x_gs, w_gs, b_gs, y_gs)) return DR_EINVAL;
+    if (G > 65535) return DR_ESHAPE;
+    if (M == 0) return DR_OK;
+    if (!x || !W || !y || bad_ld(ld_x, K) || bad_ld(ld_w, N) || ld_y < N || misaligned(x) || misaligned(W)) return DR_EINVAL;
+    if (K < 4 || N < 4) {
+        hipLaunchKernelGGL(skinny_fwd_grouped_kernel, dim3(dr_grid_for(M, 16, 2048 / G > 0 ? 2048 / G : 1), G), dim3(256), 0,
+                           dr_s(stream), x, ld_x, x_gs, W, ld_w, w_gs, b, b_gs, M, K, N, act, y, ld_y, y_gs);
+        DR_CHECK_LAUNCH();
+        return DR_OK;
+    }
+    GemmArgs g{};
+    g.A = x; g.lda = ld_x; g.B = W; g.ldb = ld_w; g.M = M; g.N = N; g.R = K; g.C = y; g.ldc = ld_y;
+    g.bias = b; g.act = act; g.split = 1;
+    g.groups = G; g.a_gs = x_gs; g.b_gs = w_gs; g.c_gs = y_gs; g.bias_gs = b_gs;
+    return launch<true, false, EPI_BIAS_ACT, true>(g, dr_s(stream));
+}
+
+extern "C" int dr_linear_bwd_dx_grouped(const float* dy, int64_t ld_dy, int64_t dy_gs, const float* W, int64_t ld_w, int64_t w_gs,
+                                        int64_t M, int32_t K, int32_t N, int32_t G, const float* relu_src, int64_t ld_relu_src,
+                                        int64_t rs_gs, int32_t accumulate, float* dx, int64_t ld_dx, int64_t dx_gs,
+                                        dr_stream_t stream) {
+    if (M < 0 || K <= 0 || N <= 0 || bad_group(G, dy_gs, w_gs, rs_gs, dx_gs)) return DR_EINVAL;
+    if (G > 65535) return DR_ESHAPE;
+    if (M == 0) return DR_OK;
+    if (!dy || !W || !dx || bad_ld(ld_dy, N) || bad_ld(ld_w, N) || ld_dx < K || misaligned(dy) || misaligned(W)) return DR_EINVAL;
+    if (relu_src != nullptr && ld_relu_src < K) return DR_EINVAL;
+    if (K < 4 || N < 4) {
+        hipLaunchKernelGGL(skinny_dx_grouped_kernel, dim3(dr_grid_for(M * K, 256, 2048 / G > 0 ? 2048 / G : 1), G), dim3(256), 0,
+                           dr_s(stream), dy, ld_dy, dy_gs, W, ld_w, w_gs, M, K, N, relu_src, ld_relu_src, rs_gs, accumulate, dx,
+                           ld_dx, dx_gs);
+        DR_CHECK_LAUNCH();
+        return DR_OK;
+    }
+    GemmArgs g{};
+    g.A = dy; g.lda = ld_dy; g.B = W; g.ldb = ld_w; g.M = M; g.N = K; g.R = N; g.C = dx; g.ldc = ld_dx;
+    g.e0 = relu_src; g.lde0 = ld_relu_src; g.accumulate = accumulate; g.split = 1;
+    g.groups = G; g.a_gs = dy_gs; g.b_gs = w_gs; g.c_gs = dx_gs; g.e0_gs = rs_gs;
+    return launch<true, true, EPI_MASK, true>(g, dr_s(stream));
+}
+
+static bool dw_skinny(int64_t M, int32_t K, int32_t N) { return K < 4 || N < 4 || M < 4; }
+// floats of one group's partials: split slices of [K][N] and of [N]
+static int64_t dw_group_floats(int64_t M, int32_t K, int32_t N, int split) { return (int64_t)split * ((int64_t)K * N + N); }
+
+extern "C" int64_t dr_linear_bwd_dw_grouped_workspace_bytes(int64_t M, int32_t K, int32_t N, int32_t G) {
+    if (M <= 0 || K <= 0 || N <= 0 || G < 1) return 0;
+    const int split = dw_skinny(M, K, N) ? (int)((M + SK_ROWS - 1) / SK_ROWS) : dw_split_max(M, K, N);
+    return (int64_t)G * dw_group_floats(M, K, N, split) * (int64_t)sizeof(float);
+}
+
+extern "C" int dr_linear_bwd_dw_grouped(const float* x, int64_t ld_x, int64_t x_gs, const float* dy, int64_t ld_dy, int64_t dy_gs,
+                                        int64_t M, int32_t K, int32_t N, int32_t G, float scale, float* dstW, int64_t ld_w,
+                                        int64_t w_gs, float* dstb, int64_t b_gs, float* workspace, int64_t workspace_bytes,
+                                        dr_stream_t stream) {
+    if (M < 0 || K <= 0 || N <= 0 || bad_group(G, x_gs, dy_gs, w_gs, b_gs)) return DR_EINVAL;
+    if (G > 65535) return DR_ESHAPE;
+    if (M == 0) return DR_OK;
+    if (!x || !dy || !dstW || bad_ld(ld_x, K) || bad_ld(ld_dy, N) || ld_w < N || misaligned(x) || misaligned(dy)) return DR_EINVAL;
+    const bool ws_ok = workspace != nullptr && workspace_bytes >= dr_linear_bwd_dw_grouped_workspace_bytes(M, K, N, G);
+    if (dw_skinny(M, K, N)) {
+        const int nslab = (int)((M + SK_ROWS - 1) / SK_ROWS);
+        const int64_t part_gs = dw_group_floats(M, K, N, nslab);
+        hipLaunchKernelGGL(skinny_dw_grouped_kernel, dim3((unsigned)nslab, G), dim3(256), 0, dr_s(stream), x, ld_x, x_gs, dy, ld_dy,
+                           dy_gs, M, K, N, scale, dstW, ld_w, w_gs, dstb, b_gs, ws_ok ? workspace : nullptr, part_gs);
+        DR_CHECK_LAUNCH();
+        if (ws_ok) {
+            hipLaunchKernelGGL(grouped_reduce_kernel, dim3(dr_grid_for((int64_t)K * N + N, 256, 2048 / G > 0 ? 2048 / G : 1), G),
+                               dim3(256), 0, dr_s(stream), workspace, part_gs, nslab, (int64_t)K, N, scale, dstW, ld_w, w_gs, dstb,
+                               b_gs);
+            DR_CHECK_LAUNCH();
+        }
+        return DR_OK;
+    }
+    GemmArgs g{};
+    g.A = x; g.lda = ld_x; g.B = dy; g.ldb = ld_dy; g.M = K; g.N = N; g.R = M; g.C = dstW; g.ldc = ld_w;
+    g.alpha = scale; g.colsum_dst = dstb;
+    g.split = dw_split(M, K, N);
+    g.per = ((M + g.split - 1) / g.split + BK - 1) / BK * BK;     // effective slices only (see dr_linear_bwd_dw)
+    g.split = (int32_t)((M + g.per - 1) / g.per);
+    // split == 1: every output element has one writer, the atomic epilogue is already deterministic
+    const bool use_ws = ws_ok && g.split > 1;
+    const int64_t part_gs = dw_group_floats(M, K, N, g.split);
+    g.partial = use_ws ? workspace : nullptr;
+    g.groups = G; g.a_gs = x_gs; g.b_gs = dy_gs; g.c_gs = w_gs; g.cs_gs = b_gs; g.part_gs = part_gs;
+    int rc = launch<false, false, EPI_ATOMIC, true>(g, dr_s(stream));
+    if (rc != DR_OK) return rc;
+    if (use_ws) {
+        hipLaunchKernelGGL(grouped_reduce_kernel, dim3(dr_grid_for((int64_t)K * N + N, 256, 2048 / G > 0 ? 2048 / G : 1), G),
+                           dim3(256), 0, dr_s(stream), workspace, part_gs, g.split, (int64_t)K, N, scale, dstW, ld_w, w_gs, dstb,
+                           b_gs);
         DR_CHECK_LAUNCH();
     }
     return DR_OK;

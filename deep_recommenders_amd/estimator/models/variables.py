@@ -82,3 +82,28 @@ def warm_up_dicts(variables):
         elif parts[0] == "factorized":
             factorized[parts[2].replace("_embedding", "")] = np.asarray(a)
     return linear, factorized
+
+
+def export_named(model):
+    """{TF name: array} over a model that lists its variables in `var_names` and resolves them with `variable(name)` (the
+    multi-task models: their variables are views of grouped buffers)."""
+    return {n: model.variable(n).detach().cpu().numpy().copy() for n in model.var_names}
+
+
+def import_named(model, variables, strict=True):
+    """Inverse of export_named: values are copied IN PLACE (the views keep aliasing their buffers); ':0' suffixes accepted."""
+    v = {n[:-2] if n.endswith(":0") else n: a for n, a in variables.items()}
+    used = []
+    for name in model.var_names:
+        if name not in v:
+            if strict:
+                raise KeyError("variable %r not found" % name)
+            continue
+        dst = model.variable(name)
+        a = np.asarray(v[name], dtype=np.float32)
+        if tuple(a.shape) != tuple(dst.shape):
+            raise ValueError("variable %r: shape %s, expected %s" % (name, tuple(a.shape), tuple(dst.shape)))
+        with torch.no_grad():
+            dst.copy_(torch.from_numpy(np.ascontiguousarray(a)).to(dst.device))
+        used.append(name)
+    return used

@@ -234,3 +234,98 @@ def indicator_column(categorical_column):
 
 def embedding_column(categorical_column, dimension, combiner="mean", initializer=None, max_norm=None, trainable=True):
     return EmbeddingColumn(categorical_column, dimension, combiner, initializer, max_norm, trainable)
+
+
+class NumericColumn:
+    """[TF] numeric_column: a dense feature of `shape`, contributing prod(shape) columns to input_layer; `.name == key`."""
+
+    def __init__(self, key, shape=(1,), default_value=None, dtype=torch.float32, normalizer_fn=None):
+        if isinstance(shape, int):
+            shape = (shape,)
+        shape = tuple(int(s) for s in shape)
+        if len(shape) == 0 or any(s < 1 for s in shape):
+            raise ValueError("shape dimensions must be greater than 0. shape: {}, key: {}".format(shape, key))
+        if dtype not in (torch.float32, np.float32, "float32"):
+            raise NotImplementedError("only float32 numeric columns")
+        if normalizer_fn is not None and not callable(normalizer_fn):
+            raise TypeError("normalizer_fn must be a callable. Given: {}".format(normalizer_fn))
+        self.key = key
+        self.shape = shape
+        self.default_value = default_value
+        self.dtype = torch.float32
+        self.normalizer_fn = normalizer_fn
+
+    @property
+    def name(self):
+        return self.key
+
+    @property
+    def variable_shape(self):
+        return self.shape
+
+    @property
+    def width(self):
+        return int(np.prod(self.shape))
+
+    def get_config(self):
+        return {"key": self.key, "shape": self.shape, "default_value": self.default_value}
+
+    def host_block(self, features, batch_size=None):
+        """the column's [B, width] float32 block on the host (normalizer_fn applied); missing key -> default_value"""
+        if self.key in features:
+            v = features[self.key]
+            if isinstance(v, torch.Tensor):
+                v = v.detach().cpu().numpy()
+            a = np.asarray(v, dtype=np.float32)
+        elif self.default_value is not None and batch_size is not None:
+            a = np.broadcast_to(np.asarray(self.default_value, dtype=np.float32), (batch_size,) + self.shape)
+        else:
+            raise KeyError("feature {!r} is missing and numeric_column {!r} has no default_value".format(self.key, self.key))
+        a = a.reshape(a.shape[0], -1)
+        if a.shape[1] != self.width:
+            raise ValueError("feature {!r}: expected {} values per example, got {}".format(self.key, self.width, a.shape[1]))
+        if self.normalizer_fn is not None:
+            a = np.asarray(self.normalizer_fn(a), dtype=np.float32).reshape(a.shape)
+        return a
+
+
+def numeric_column(key, shape=(1,), default_value=None, dtype=torch.float32, normalizer_fn=None):
+    return NumericColumn(key, shape, default_value, dtype, normalizer_fn)
+
+
+def input_layer_layout(feature_columns):
+    """Host-only: the [B, K] layout tf.feature_column.input_layer builds -- columns sorted by `.name` (so C0, C1, C10, C100, ...),
+    each contributing a contiguous block.  Returns ([(name, column, offset, width)], K)."""
+    cols = sorted(feature_columns, key=lambda c: c.name)
+    names = [c.name for c in cols]
+    if len(set(names)) != len(names):
+        raise ValueError("duplicate feature column names: {}".format(sorted(n for n in set(names) if names.count(n) > 1)))
+    out, off = [], 0
+    for c in cols:
+        if isinstance(c, NumericColumn):
+            w = c.width
+        elif isinstance(c, EmbeddingColumn):
+            w = c.dimension
+        elif isinstance(c, IndicatorColumn):
+            raise NotImplementedError("indicator_column inside input_layer is not supported (column {!r}); use embedding_column "
+                                      "or the FM-family models' linear part".format(c.name))
+        else:
+            raise TypeError("input_layer takes numeric_column / embedding_column, got {!r}".format(c))
+        out.append((c.name, c, off, w))
+        off += w
+    return out, off
+
+
+def input_layer(features, feature_columns):
+    """tf.feature_column.input_layer(features, feature_columns) -> [B, K] float32 on the GPU.  The embedding tables of a column set
+    live in an InputLayer module cached per column list (models own theirs: estimator.models.multi_task_learning)."""
+    from .layers import InputLayer
+    key = tuple(id(c) for c in feature_columns)
+    layer = _INPUT_LAYERS.get(key)
+    if layer is None:
+        layer = InputLayer(feature_columns)
+        _INPUT_LAYERS[key] = layer
+    return layer(features)
+
+
+_INPUT_LAYERS = {}

@@ -7,6 +7,7 @@ Nothing here computes in PyTorch: forward and backward are launches of the hand-
 import math
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -388,3 +389,86 @@ class EmbeddingSlab(nn.Module):
         """[B, F]: every field's own first-order output sum_bag w[id] (no bias) -- FNN's `concat_weights`."""
         ids, col_start, row_base = self.transform(inputs, field_keys)
         return _LinFieldsFn.apply(self.lin_w, ids, len(field_keys), col_start, row_base)
+
+
+# --------------------------------------------------------------------------------------------------
+# tf.feature_column.input_layer
+# --------------------------------------------------------------------------------------------------
+class _GatherColsFn(torch.autograd.Function):
+    """x[:, j] = num[:, map[j]] or emb[:, -map[j]-1] (dr_gather_cols); the backward gathers the embedding columns back out."""
+
+    @staticmethod
+    def forward(ctx, num, emb, col_map, emb_map, K):
+        out = torch.empty((num.shape[0], K), dtype=torch.float32, device=emb.device)
+        ops.gather_cols(num, emb, col_map, out)
+        ctx.save_for_backward(emb_map)
+        ctx.emb_shape = emb.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        emb_map, = ctx.saved_tensors
+        d_out = d_out if d_out.stride(1) == 1 else d_out.contiguous()
+        d_emb = torch.empty(ctx.emb_shape, dtype=torch.float32, device=d_out.device)
+        ops.gather_cols(d_out, None, emb_map, d_emb)
+        return None, d_emb, None, None, None
+
+
+class InputLayer(nn.Module):
+    """tf.feature_column.input_layer over numeric_column and embedding_column (TF1 semantics): the columns sorted by name, each a
+    contiguous block of one [B, K] fp32 matrix.  Numeric values are assembled on the host and reach the device as ONE copy per batch;
+    the embedding columns are mean-pooled by the fused gather of an EmbeddingSlab (gradients flow into its table); a mixed set is
+    interleaved by one dr_gather_cols launch.  TF names: input_layer/<key>_embedding/embedding_weights."""
+
+    def __init__(self, feature_columns, device="cuda"):
+        super().__init__()
+        self.layout, self.K = fc.input_layer_layout(feature_columns)
+        self.numeric = [(name, c) for name, c, _, _ in self.layout if isinstance(c, fc.NumericColumn)]
+        emb = [c for _, c, _, _ in self.layout if isinstance(c, fc.EmbeddingColumn)]
+        self.slab = EmbeddingSlab(emb, device=device) if emb else None
+        self.emb_keys = [c.categorical_column.key for c in emb]
+        self.device = torch.device(device)
+        num_off, emb_off = 0, 0
+        col_map, emb_map = [], []
+        for name, c, off, w in self.layout:
+            if isinstance(c, fc.NumericColumn):
+                col_map += list(range(num_off, num_off + w))
+                num_off += w
+            else:
+                col_map += [-(emb_off + i) - 1 for i in range(w)]
+                emb_map += list(range(off, off + w))
+                emb_off += w
+        self.K_num, self.K_emb = num_off, emb_off
+        # the numeric block / the pooled embeddings ARE the input when they are all of it (no interleave launch)
+        self.mixed = self.K_num > 0 and self.K_emb > 0
+        self._col_map = torch.tensor(col_map, dtype=torch.int32, device=self.device) if self.mixed else None
+        self._emb_map = torch.tensor(emb_map, dtype=torch.int32, device=self.device) if self.mixed else None
+
+    def numeric_block(self, features, batch_size):
+        """[B, K_num] on the device: the numeric columns in name order, one host-to-device copy"""
+        blocks = [c.host_block(features, batch_size) for _, c in self.numeric]
+        host = blocks[0] if len(blocks) == 1 else np.concatenate(blocks, axis=1)
+        t = torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32))
+        if self.device.type == "cuda":
+            t = t.pin_memory() if t.numel() >= (1 << 16) else t
+            return t.to(self.device, non_blocking=True)
+        return t.to(self.device)
+
+    def batch_size(self, features):
+        for name, c, _, _ in self.layout:
+            k = c.key if isinstance(c, fc.NumericColumn) else c.categorical_column.key
+            if k in features:
+                v = features[k]
+                return int(v.shape[0]) if hasattr(v, "shape") else len(v)
+        raise KeyError("none of the input_layer's features is present")
+
+    def forward(self, features):
+        B = self.batch_size(features)
+        num = self.numeric_block(features, B) if self.K_num else None
+        if self.K_emb == 0:
+            return num
+        concat, _, _ = self.slab(features, self.emb_keys, second_order=False)
+        emb = concat[:, :self.K_emb]
+        if not self.mixed:
+            return emb
+        return _GatherColsFn.apply(num, emb, self._col_map, self._emb_map, self.K)

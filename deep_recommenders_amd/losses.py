@@ -65,3 +65,28 @@ def log_loss(labels, predictions):
 def binary_crossentropy(y_true, y_pred):
     """tf.keras.losses.binary_crossentropy on probabilities, mean over the batch ([TF] B11)."""
     return _ProbLossFn.apply(y_pred.contiguous(), y_true.to(torch.float32).contiguous(), ops.LOSS_KERAS_BCE)
+
+
+class _MseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, predictions, labels):
+        loss, d = ops.mse_fwd_bwd(predictions, labels)
+        ctx.save_for_backward(d)
+        ctx.shape = predictions.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        (d,) = ctx.saved_tensors
+        return (d * d_loss.reshape(1, -1)).reshape(ctx.shape), None
+
+
+def mean_squared_error(labels, predictions):
+    """tf.losses.mean_squared_error(labels, predictions) with unit weights (SUM_BY_NONZERO_WEIGHTS = the mean over the batch),
+    examples/train_mmoe_on_synthetic_estimator.py:39-40.  predictions [B, 1] (or [B, T]: T losses in one launch, returned [T])."""
+    p = predictions if predictions.dim() == 2 else predictions.reshape(-1, 1)
+    y = torch.as_tensor(labels, dtype=torch.float32, device=p.device).reshape(p.shape)
+    if p.shape[1] > 1 and p.stride(1) != 1:
+        p = p.contiguous()
+    loss = _MseFn.apply(p, y if y.stride(1) == 1 or y.shape[1] == 1 else y.contiguous())
+    return loss.reshape(()) if p.shape[1] == 1 else loss

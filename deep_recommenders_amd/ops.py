@@ -1543,3 +1543,142 @@ def clock_stamp(buf, index):
     (dr_clock_stamp: a one-thread kernel; measurement plumbing for bench.py's exposed-wait report)."""
     assert buf.dtype == torch.int64 and buf.is_contiguous() and 0 <= index < buf.numel()
     check(lib().dr_clock_stamp(buf.data_ptr() + 8 * int(index), stream_ptr()), "dr_clock_stamp")
+
+
+# ---- multi-task learning (csrc/multitask.hip + the grouped entry points of csrc/dense.hip) -----------------------------------------
+def _f32_2d(t, what):
+    if t.dtype != torch.float32:
+        raise TypeError("%s: expected float32, got %s" % (what, t.dtype))
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError("%s: expected a row-major 2-D tensor with unit column stride" % what)
+    return t
+
+
+def linear_fwd_grouped(x, ld_x, x_gs, W, ld_w, w_gs, b, b_gs, M, K, N, G, act, y, ld_y, y_gs):
+    """Grouped Dense forward over raw layouts: every tensor is the base of its G groups (see dr_linear_fwd_grouped)."""
+    for t in (x, W, y) + ((b,) if b is not None else ()):
+        if t.dtype != torch.float32:
+            raise TypeError("linear_fwd_grouped: float32 tensors only")
+    check(lib().dr_linear_fwd_grouped(ptr(x), ld_x, x_gs, ptr(W), ld_w, w_gs, ptr(b), b_gs, M, K, N, G, int(act), ptr(y), ld_y, y_gs,
+                                      stream_ptr()), "dr_linear_fwd_grouped")
+    return y
+
+
+def linear_bwd_dx_grouped(dy, ld_dy, dy_gs, W, ld_w, w_gs, M, K, N, G, relu_src, ld_rs, rs_gs, accumulate, dx, ld_dx, dx_gs):
+    for t in (dy, W, dx):
+        if t.dtype != torch.float32:
+            raise TypeError("linear_bwd_dx_grouped: float32 tensors only")
+    check(lib().dr_linear_bwd_dx_grouped(ptr(dy), ld_dy, dy_gs, ptr(W), ld_w, w_gs, M, K, N, G, ptr(relu_src), ld_rs, rs_gs,
+                                         int(bool(accumulate)), ptr(dx), ld_dx, dx_gs, stream_ptr()), "dr_linear_bwd_dx_grouped")
+    return dx
+
+
+def linear_bwd_dw_grouped_workspace(M, K, N, G, device):
+    return torch.empty(max(1, lib().dr_linear_bwd_dw_grouped_workspace_bytes(int(M), int(K), int(N), int(G)) // 4),
+                       dtype=torch.float32, device=device)
+
+
+def linear_bwd_dw_grouped(x, ld_x, x_gs, dy, ld_dy, dy_gs, M, K, N, G, scale, dstW, ld_w, w_gs, dstb=None, b_gs=0, workspace=None):
+    for t in (x, dy, dstW):
+        if t.dtype != torch.float32:
+            raise TypeError("linear_bwd_dw_grouped: float32 tensors only")
+    check(lib().dr_linear_bwd_dw_grouped(ptr(x), ld_x, x_gs, ptr(dy), ld_dy, dy_gs, M, K, N, G, float(scale), ptr(dstW), ld_w, w_gs,
+                                         ptr(dstb), b_gs, ptr(workspace), workspace.numel() * 4 if workspace is not None else 0,
+                                         stream_ptr()), "dr_linear_bwd_dw_grouped")
+
+
+def mmoe_gate_mix_fwd(h, logits, E, T, U):
+    """h [B, >= E*U], logits [B, >= T*E] -> (p [B, T*E], out [B, T*U])."""
+    _f32_2d(h, "h")
+    _f32_2d(logits, "logits")
+    B = h.shape[0]
+    if logits.shape[0] != B or h.shape[1] < E * U or logits.shape[1] < T * E:
+        raise ValueError("mmoe_gate_mix_fwd: h %s / logits %s do not hold E=%d, T=%d, U=%d" % (tuple(h.shape), tuple(logits.shape), E, T, U))
+    p = torch.empty((B, T * E), dtype=torch.float32, device=h.device)
+    out = torch.empty((B, T * U), dtype=torch.float32, device=h.device)
+    check(lib().dr_mmoe_gate_mix_fwd(ptr(h), h.stride(0), ptr(logits), logits.stride(0), B, E, T, U, ptr(p), p.stride(0), ptr(out),
+                                     out.stride(0), stream_ptr()), "dr_mmoe_gate_mix_fwd")
+    return p, out
+
+
+def mmoe_gate_mix_bwd(h, p, d_out, E, T, U, d_h=None, d_l=None):
+    _f32_2d(h, "h")
+    _f32_2d(p, "p")
+    _f32_2d(d_out, "d_out")
+    B = h.shape[0]
+    if p.shape[0] != B or d_out.shape[0] != B or d_out.shape[1] < T * U or p.shape[1] < T * E:
+        raise ValueError("mmoe_gate_mix_bwd: shapes do not match E=%d, T=%d, U=%d" % (E, T, U))
+    if d_h is None:
+        d_h = torch.empty((B, E * U), dtype=torch.float32, device=h.device)
+    if d_l is None:
+        d_l = torch.empty((B, T * E), dtype=torch.float32, device=h.device)
+    check(lib().dr_mmoe_gate_mix_bwd(ptr(h), h.stride(0), ptr(p), p.stride(0), ptr(d_out), d_out.stride(0), B, E, T, U, ptr(d_h),
+                                     d_h.stride(0), ptr(d_l), d_l.stride(0), stream_ptr()), "dr_mmoe_gate_mix_bwd")
+    return d_h, d_l
+
+
+def mse_fwd_bwd(pred, labels, want_grad=True):
+    """pred [B, T], labels [B, T] -> (loss [T], d_pred [B, T] or None)."""
+    _f32_2d(pred, "pred")
+    _f32_2d(labels, "labels")
+    if pred.shape != labels.shape:
+        raise ValueError("mse_fwd_bwd: pred %s vs labels %s" % (tuple(pred.shape), tuple(labels.shape)))
+    B, T = pred.shape
+    loss = torch.empty(T, dtype=torch.float32, device=pred.device)
+    d = torch.empty((B, T), dtype=torch.float32, device=pred.device) if want_grad else None
+    nbytes = lib().dr_mse_workspace_bytes(T)
+    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=pred.device)
+    check(lib().dr_mse_fwd_bwd(ptr(pred), pred.stride(0), ptr(labels), labels.stride(0), B, T, ptr(loss), ptr(d),
+                               d.stride(0) if d is not None else 0, ptr(ws), nbytes, stream_ptr()), "dr_mse_fwd_bwd")
+    return loss, d
+
+
+def esmm_head_fwd(logits):
+    """logits [B, 2] (cvr, ctr) -> p_cvr, p_ctr, p_ctcvr, each [B]."""
+    _f32_2d(logits, "logits")
+    if logits.shape[1] != 2:
+        raise ValueError("esmm_head_fwd: logits must be [B, 2], got %s" % (tuple(logits.shape),))
+    B = logits.shape[0]
+    outs = torch.empty((3, B), dtype=torch.float32, device=logits.device)
+    check(lib().dr_esmm_head_fwd(ptr(logits), logits.stride(0), B, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), stream_ptr()),
+          "dr_esmm_head_fwd")
+    return outs[0], outs[1], outs[2]
+
+
+def esmm_head_bwd(p_cvr, p_ctr, d_cvr=None, d_ctr=None, d_ctcvr=None):
+    B = p_cvr.shape[0]
+    gs = []
+    for g in (d_cvr, d_ctr, d_ctcvr):
+        if g is not None:
+            g = _c(g.reshape(-1), torch.float32)
+            if g.numel() != B:
+                raise ValueError("esmm_head_bwd: gradient of %d elements for a batch of %d" % (g.numel(), B))
+        gs.append(g)
+    d_logits = torch.empty((B, 2), dtype=torch.float32, device=p_cvr.device)
+    check(lib().dr_esmm_head_bwd(ptr(_c(p_cvr, torch.float32)), ptr(_c(p_ctr, torch.float32)), ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), B,
+                                 ptr(d_logits), d_logits.stride(0), stream_ptr()), "dr_esmm_head_bwd")
+    return d_logits
+
+
+def adam_step_2d(param, grad, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
+    """Adam on a 2-D block whose rows may be strided (a column slice of a concatenated parameter); m / v contiguous."""
+    if param.dim() == 1:
+        param, grad, m, v = (t.reshape(1, -1) for t in (param, grad, m, v))
+    for t in (param, grad, m, v):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError("adam_step_2d: 2-D float32 blocks with unit column stride")
+    rows, cols = param.shape
+    assert grad.shape == param.shape and m.shape == param.shape and v.shape == param.shape and m.stride(0) == v.stride(0)
+    check(lib().dr_adam_step_2d(ptr(param), param.stride(0), ptr(grad), grad.stride(0), ptr(m), ptr(v), m.stride(0), rows, cols,
+                                float(lr_t), float(beta1), float(beta2), float(eps), float(grad_scale), stream_ptr()),
+          "dr_adam_step_2d")
+
+
+def gather_cols(a, b, col_map, out):
+    """out[:, j] = a[:, map[j]] if map[j] >= 0 else b[:, -map[j] - 1]; col_map int32 [N] on the device."""
+    M, N = out.shape
+    if col_map.dtype != torch.int32 or col_map.numel() != N:
+        raise ValueError("gather_cols: col_map must be int32 [%d]" % N)
+    check(lib().dr_gather_cols(ptr(a), a.stride(0) if a is not None else 0, ptr(b), b.stride(0) if b is not None else 0, ptr(col_map),
+                               M, N, ptr(out), out.stride(0), stream_ptr()), "dr_gather_cols")
+    return out

@@ -870,6 +870,63 @@ int dr_dropout_bwd(const float* dy, int64_t ld_dy, const uint8_t* mask, int64_t 
 int dr_reduce_sum(const float* x, int64_t n, int32_t squared, float alpha, int32_t accumulate, float* out,
                   float* workspace, dr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multi-task learning (estimator/models/multi_task_learning/{mixture_of_experts,esmm}.py, examples/train_mmoe_on_synthetic_estimator.py)
+ *
+ * Grouped dense layers: G independent problems of one shape (M, K, N) in ONE launch -- MMoE's expert layers after the first
+ * and the task towers (mixture_of_experts.py:60-67,79-88), ESMM's two towers (esmm.py:35-51).  Group g reads x at
+ * x + g*x_gs (row pitch ld_x), W at W + g*w_gs, b at b + g*b_gs and writes y at y + g*y_gs (row pitch ld_y); dy / dx / relu_src /
+ * dW / db likewise.  Same contract as dr_linear_fwd / _bwd_dx / _bwd_dw (relu in the fwd epilogue, relu' folded into dx through
+ * relu_src; dw into a zeroed buffer with scale = 1 or into the parameter with scale = -lr).  With a workspace of
+ * dr_linear_bwd_dw_grouped_workspace_bytes() the weight AND bias gradients are combined in a fixed order (deterministic; each
+ * group's dW equals dr_linear_bwd_dw's with a workspace bit for bit); without one, fp32 atomics.  Every GEMM mode
+ * (dr_set_gemm_mode) applies.  G > 65535 returns DR_ESHAPE (the caller falls back to per-group dr_linear_* calls).
+ * ---------------------------------------------------------------------------------------- */
+int dr_linear_fwd_grouped(const float* x, int64_t ld_x, int64_t x_gs, const float* W, int64_t ld_w, int64_t w_gs, const float* b,
+                          int64_t b_gs, int64_t M, int32_t K, int32_t N, int32_t G, int32_t act, float* y, int64_t ld_y, int64_t y_gs,
+                          dr_stream_t stream);
+int dr_linear_bwd_dx_grouped(const float* dy, int64_t ld_dy, int64_t dy_gs, const float* W, int64_t ld_w, int64_t w_gs, int64_t M,
+                             int32_t K, int32_t N, int32_t G, const float* relu_src, int64_t ld_relu_src, int64_t rs_gs,
+                             int32_t accumulate, float* dx, int64_t ld_dx, int64_t dx_gs, dr_stream_t stream);
+int64_t dr_linear_bwd_dw_grouped_workspace_bytes(int64_t M, int32_t K, int32_t N, int32_t G);
+int dr_linear_bwd_dw_grouped(const float* x, int64_t ld_x, int64_t x_gs, const float* dy, int64_t ld_dy, int64_t dy_gs, int64_t M,
+                             int32_t K, int32_t N, int32_t G, float scale, float* dstW, int64_t ld_w, int64_t w_gs, float* dstb,
+                             int64_t b_gs, float* workspace, int64_t workspace_bytes, dr_stream_t stream);
+
+/* MMoE gate softmax + expert mixture (mixture_of_experts.py:71-77).  h [B, E*U] (expert e in columns e*U ..), logits [B, T*E]:
+ *   fwd  p[b,t,:] = softmax(logits[b, t*E : (t+1)*E]) (maximum subtracted), out[b, t*U+u] = sum_e p[b,t,e] h[b, e*U+u] (ascending e);
+ *        p [B, T*E] is saved for the backward.
+ *   bwd  d_h[b, e*U+u] = sum_t p[b,t,e] d_out[b, t*U+u] (ascending t);
+ *        d_l[b,t,e] = p[b,t,e] (<d_out_t, h_e> - sum_e' p[b,t,e'] <d_out_t, h_e'>).
+ * One 64-lane wave per row, no atomics (deterministic).  Domain 1 <= E <= 64, 1 <= T <= 16, U >= 1; otherwise DR_ESHAPE. */
+int dr_mmoe_gate_mix_fwd(const float* h, int64_t ld_h, const float* logits, int64_t ld_l, int64_t B, int32_t E, int32_t T, int32_t U,
+                         float* p, int64_t ld_p, float* out, int64_t ld_out, dr_stream_t stream);
+int dr_mmoe_gate_mix_bwd(const float* h, int64_t ld_h, const float* p, int64_t ld_p, const float* d_out, int64_t ld_do, int64_t B,
+                         int32_t E, int32_t T, int32_t U, float* d_h, int64_t ld_dh, float* d_l, int64_t ld_dl, dr_stream_t stream);
+
+/* T mean-squared-error losses in one call (tf.losses.mean_squared_error, SUM_BY_NONZERO_WEIGHTS with unit weights;
+ * examples/train_mmoe_on_synthetic_estimator.py:39-40): pred [B, T] and labels [B, T] row-major with pitches,
+ * loss[t] = mean_b (pred - y)^2, d_pred = 2 (pred - y) / B (may be NULL).  Fixed-order two-stage reduction. */
+int64_t dr_mse_workspace_bytes(int32_t T);
+int dr_mse_fwd_bwd(const float* pred, int64_t ld_pred, const float* labels, int64_t ld_labels, int64_t B, int32_t T, float* loss,
+                   float* d_pred, int64_t ld_dpred, float* workspace, int64_t workspace_bytes, dr_stream_t stream);
+
+/* ESMM head (esmm.py:33-55): logits [B, 2] = (cvr, ctr) -> p_cvr, p_ctr, p_ctcvr = p_ctr * p_cvr, each [B].  The backward takes
+ * any subset of the three output gradients (NULL = zero) and writes both logit gradients.  Finite for any finite logit. */
+int dr_esmm_head_fwd(const float* logits, int64_t ld_logits, int64_t B, float* p_cvr, float* p_ctr, float* p_ctcvr, dr_stream_t stream);
+int dr_esmm_head_bwd(const float* p_cvr, const float* p_ctr, const float* d_cvr, const float* d_ctr, const float* d_ctcvr, int64_t B,
+                     float* d_logits, int64_t ld_dlogits, dr_stream_t stream);
+
+/* dr_adam_step on a [rows, cols] block with a pitch per operand: the column slice of a concatenated parameter that one TF variable
+ * is (MMoE's gates); same per-element arithmetic as dr_adam_step. */
+int dr_adam_step_2d(float* param, int64_t ld_p, const float* grad, int64_t ld_g, float* m, float* v, int64_t ld_mv, int64_t rows,
+                    int32_t cols, float lr_t, float beta1, float beta2, float eps, float grad_scale, dr_stream_t stream);
+
+/* tf.feature_column.input_layer's column assembly: out[m][j] = map[j] >= 0 ? a[m][map[j]] : b[m][-map[j] - 1]  (numeric block and
+ * pooled embeddings interleaved by column name); also its backward (the pooled embeddings' gradient out of d_input). */
+int dr_gather_cols(const float* a, int64_t lda, const float* b, int64_t ldb, const int32_t* map, int64_t M, int32_t N, float* out,
+                   int64_t ldo, dr_stream_t stream);
+
 /* dr_clock_stamp: dst[0] = the device's constant-rate wall clock (100 MHz ticks) when a one-thread kernel reaches the head of
  * `stream`.  Measurement plumbing with no reference counterpart: bench.py brackets the sharded step's cross-stream waits with two
  * stamps to report the EXPOSED part of the exchange (HIP timing events around a wait serialise the step). */
