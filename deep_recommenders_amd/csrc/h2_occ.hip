@@ -24,6 +24,7 @@
 // steps in k order): results are bit-identical to that kernel's, so every tolerance and tie argument made for it carries over.
 #include "dr_common.h"
 #include "rs_args.h"
+#include <algorithm>
 #include <cstdlib>
 
 namespace drrs {
@@ -65,7 +66,8 @@ struct K4Args {
 
 // EPI: 0 = bias / ReLU, 1 = + ReLU' mask, 3 = accumulate (C +=), 8 = K4's unique-row update (above)
 // DBG (tools/exp only; 0 in the product path): 2 = no MFMAs, 32 = no fragment reads, 1 = no B DMA after the prologue, 8 = A from cache
-// (its loads re-read k-tile 0), 64 = no split / no A image writes
+// (its loads re-read k-tile 0), 64 = no split / no A image writes; EPI 8 only: 1024 = no K4 epilogue (the main loop alone), 2048 = no main loop
+// (the K4 epilogue alone, on zero accumulators)
 template <int EPI, int DBG = 0>
 __global__ __launch_bounds__(1024) void h2_occ_nt_kernel(RsArgs g, K4Args e) {
     // (EPI 8: + 8 KB behind the ring for the epilogue's per-row scalars -- ONE __shared__ object on purpose)
@@ -186,6 +188,7 @@ __global__ __launch_bounds__(1024) void h2_occ_nt_kernel(RsArgs g, K4Args e) {
 #define OCC_FENCE() __builtin_amdgcn_sched_barrier(0)
 
         // ---- prologue: B(0) by DMA, A(0) split into stage 0, A(1) into flight; then B(1) and k-step 0's fragments ---------------------
+        if constexpr (!(DBG & 2048)) {                                  // (ablation 2048: no main loop -- no MFMAs, no A / B ingest)
         issue_b(0, 0);
         load_a(0);
         OCC_FENCE();
@@ -262,6 +265,7 @@ __global__ __launch_bounds__(1024) void h2_occ_nt_kernel(RsArgs g, K4Args e) {
             OCC_FENCE();
             if constexpr (DBG & 2) acc[0][0][0] += (float)ah[0][0] + (float)ah[1][0] + (float)al[0][0] + (float)al[1][0] + (float)bh[0][0] + (float)bh[1][0] + (float)bl[0][0] + (float)bl[1][0];
         }
+        }
         // (the last k-tile's barrier was the last LDS access of the main loop: the ring is free for the epilogue)
 #undef OCC_MMA
 #undef OCC_MMA2
@@ -317,7 +321,14 @@ __global__ __launch_bounds__(1024) void h2_occ_nt_kernel(RsArgs g, K4Args e) {
                 k4_id = mk(e.ids_t + (int64_t)fc * g.M + tm0, (int64_t)k4_rows * 4);
                 k4_fl = mk(e.flags + tm0 * e.F, (int64_t)k4_rows * e.F);
             }
-            if constexpr (EPI == 8) {
+            if constexpr (EPI == 8 && (DBG & 1024)) {                  // (ablation 1024: the main loop alone, the K4 epilogue skipped)
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+#pragma unroll
+                        for (int reg = 0; reg < 16; ++reg) cmax = fmaxf(cmax, fabsf(acc[a][b][reg])), acc[a][b][reg] = 0.f;
+            } else if constexpr (EPI == 8) {
                 // ---- K4's unique-row pass on the tile's 256 x 4 slots.  What bounds it is HBM LATENCY (a table row can only be asked for once
                 // its id is known, and written once it has arrived): the fewer dependent round trips per tile and the more rows in flight per
                 // round trip, the better.  So everything a slot needs BESIDES its table row is made LDS-resident first -- the tile's 256 rows
@@ -510,6 +521,352 @@ __global__ __launch_bounds__(1024) void h2_occ_nt_kernel(RsArgs g, K4Args e) {
     }
 }
 
+
+// ---- EPI 8 with the K4 epilogue OVERLAPPED with the GEMM (round 7; dr_h2_dgrad_emb_sgd's default) -------------------------------
+// h2_occ_nt_kernel<8> runs a tile's main loop (bound by how fast the CU takes A and B in, HBM idle) and then its K4 epilogue (bound by
+// HBM latency, matrix pipe idle) back to back in the one block of the CU.  Here the block's 16 waves are two groups of 8 (waves 0-7,
+// 8-15: two of each group on every SIMD), each owning a 128 x 256 output tile (128 examples x 4 fields) with the same 64 x 64
+// accumulators per wave, and the groups run one main loop apart: in phase p the group of tile p multiplies it while the other group
+// applies K4 to tile p - 1 out of the accumulators it kept, then the roles swap.  Every phase executes the same number of block
+// barriers in both roles (NB below; the K4 side cuts its work into slices between them, the idle side only counts them): the
+// main loop keeps the ring and its one barrier per k-tile, the epilogue works out of its own LDS (sum_x panel, staging, scalars).
+// Per output element the products and their order are those of h2_occ_nt_kernel<8> and the epilogue's arithmetic is the same
+// statement for statement, so every output is bit-identical to it.
+constexpr int PM = 128;                                                 // rows of a half tile
+constexpr int PA_PLANE = PM * 64, PB_PLANE = BN * 64;                   // bytes: 128 / 256 rows x 32 fp16
+constexpr int PA_OFF = 0, PB_OFF = 2 * PA_PLANE, PSTAGE = 2 * PA_PLANE + 2 * PB_PLANE;   // a stage: A h, A l, B h, B l = 48 KB
+constexpr int P_SXP = 2 * PSTAGE;                                       // sum_x panel [128][64] (32 KB) behind the ring
+constexpr int P_STQ = P_SXP + PM * 256;                                 // accumulator staging, 8 rows x 256 bytes per wave
+constexpr int P_DLP = P_STQ + 8 * 2048;                                 // d_fm_logit [128]
+constexpr int P_LOP = P_DLP + PM * 4;                                   // saved first-order weights [8 waves][64]
+constexpr int P_UIP = P_LOP + 8 * 256;                                  // row ids [8 waves][64] (-1: not this pass's to update)
+constexpr int P_LDS = P_UIP + 8 * 256;                                  // 152 064 bytes
+constexpr int P_EPI_BARRIERS = 7;                                       // block barriers of the epilogue role per phase
+
+__global__ __launch_bounds__(1024) void h2_occ_pp_kernel(RsArgs g, K4Args e) {
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[P_LDS];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = wave >> 3, wg = wave & 7;                           // group, wave within the group
+    const int wr = wg >> 2, wc = wg & 3;
+
+    const int tiles_n = (g.N + BN - 1) / BN;
+    const int tiles_m = (int)((g.M + PM - 1) / PM);
+    const int ntiles = tiles_m * tiles_n;
+    const int nk = (g.K + BK - 1) / BK;
+    const bool ktail = (g.K % BK) != 0;
+    const int kv4 = (g.K + 3) / 4 * 4;
+    const int nb = max(nk + 1, P_EPI_BARRIERS);                         // barriers per phase, in every role
+
+    float s_a, inv_a, s_b, inv_b;
+    h2_scale_of(g.a_amax[0], s_a, inv_a);
+    h2_scale_of(g.b_amax[0], s_b, inv_b);
+    const float h2_out = inv_a * inv_b;
+    h2_mode_on();
+    float cmax = 0.f;
+
+    const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)smem;
+    const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<__bf16*>(g.B), 0, (int)min((int64_t)0x7fffffff, 2 * g.b_ps * 2), 0x00020000);
+    const int b_plane1 = (int)(g.b_ps * 2);
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int k = 0; k < 16; ++k) acc[a][b][k] = 0.f;
+
+    auto bar = [] { asm volatile("s_barrier" ::: "memory"); };
+    auto tile_of = [&](int i, int64_t& tm0, int& tn0) __attribute__((always_inline)) {
+        const int lid = xcd_remap((int)blockIdx.x + i * (int)gridDim.x, ntiles);
+        tm0 = (int64_t)(lid / tiles_n) * PM;
+        tn0 = (lid % tiles_n) * BN;
+    };
+
+    // ---- the main loop of one tile: h2_occ_nt_kernel's (prologue + one barrier per k-tile), on 128 rows -------------------------
+    auto main_loop = [&](int i) __attribute__((always_inline)) {
+        int64_t tm0; int tn0;
+        tile_of(i, tm0, tn0);
+        // (everything derived from the lane index is recomputed per tile from a laundered copy, in both roles: hoisted out of the
+        // tile loop these values would live through the other role's code, which has no registers to spare)
+        int lane_m = lane;
+        asm volatile("" : "+v"(lane_m));
+        const int l31 = lane_m & 31, hi = lane_m >> 5;
+        const int sw = (l31 >> 2) & 3;
+        const unsigned a_rd = lds0 + PA_OFF + (64 * wr + l31) * 64 + (((2 * hi) ^ sw) << 4);
+        const unsigned b_rd = lds0 + PB_OFF + (64 * wc + l31) * 64 + (((2 * hi) ^ sw) << 4);
+        const int r8 = lane_m >> 3, c4 = lane_m & 7;
+        const int arow0 = 16 * wg + r8;
+        const unsigned a_wr = lds0 + PA_OFF + arow0 * 64 + ((((c4 >> 1) ^ ((arow0 >> 2) & 3)) << 4) | ((c4 & 1) << 3));
+        const int avoff0 = (int)((arow0 * g.lda + 4 * c4) * 4), avoff1 = avoff0 + (int)(8 * g.lda * 4);
+        // B pieces: plane p, rows 128 q + 16 wg .. + 15 (q = 0, 1: rows 128 apart share the swizzle)
+        const int brow = 16 * wg + (lane_m >> 2);
+        const int bchunk = (lane_m & 3) ^ ((brow >> 2) & 3);
+        const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(g.A + tm0 * g.lda), 0, (int)min((int64_t)0x7fffffff, ((g.M - tm0 - 1) * g.lda + kv4) * 4), 0x00020000);
+        const int bvoff0 = (int)(((int64_t)min(tn0 + brow, g.N - 1) * g.b_ld + bchunk * 8) * 2);
+        const int bvoff1 = (int)(((int64_t)min(tn0 + brow + 128, g.N - 1) * g.b_ld + bchunk * 8) * 2);
+        auto issue_b = [&](int kt, int stage) __attribute__((always_inline)) {
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                unsigned char* dst = smem + stage * PSTAGE + PB_OFF + p * PB_PLANE + wg * 1024;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(brsrc, (lds_ptr_t)dst, 16, bvoff0, kt * (BK * 2) + p * b_plane1, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(brsrc, (lds_ptr_t)(dst + 128 * 64), 16, bvoff1, kt * (BK * 2) + p * b_plane1, 0, 0);
+            }
+        };
+        f32x4 an0, an1;
+        int an_kt = 0;
+        auto load_a = [&](int kt) __attribute__((always_inline)) {
+            an_kt = kt;
+            an0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, avoff0, kt * (BK * 4), 0));
+            an1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, avoff1, kt * (BK * 4), 0));
+        };
+        auto stage_a = [&](int which, int stage) __attribute__((always_inline)) {
+            f32x4 v = which == 0 ? an0 : an1;
+            if (ktail) {
+                const int k = an_kt * BK + 4 * c4;
+                v[0] = k < g.K ? v[0] : 0.f; v[1] = k + 1 < g.K ? v[1] : 0.f; v[2] = k + 2 < g.K ? v[2] : 0.f; v[3] = k + 3 < g.K ? v[3] : 0.f;
+            }
+            const f32x4 x = v * s_a;
+            const f16x4 h = __builtin_convertvector(x, f16x4);
+            const f16x4 l = __builtin_convertvector(x - __builtin_convertvector(h, f32x4), f16x4);
+            const unsigned w = (which == 0 ? a_wr : (a_wr ^ 32u) + 512u) + stage * PSTAGE;
+            OCC_DS_WRITE_B64(w, h, 0);
+            OCC_DS_WRITE_B64(w, l, PA_PLANE);
+        };
+        f16x8 ah[2], al[2], bh[2], bl[2];
+#define PP_MMA(A, B)                                                                                        \
+        _Pragma("unroll") for (int a = 0; a < 2; ++a)                                                       \
+            _Pragma("unroll") for (int b = 0; b < 2; ++b)                                                   \
+                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[a], B[b], acc[a][b], 0, 0, 0);
+#define PP_MMA2(A, B, AI)                                                                                   \
+        _Pragma("unroll") for (int b = 0; b < 2; ++b)                                                       \
+            acc[AI][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[AI], B[b], acc[AI][b], 0, 0, 0);
+#define PP_RD(DST, ADDR, OFF) OCC_DS_READ_B128(DST, ADDR, OFF);
+#define PP_FENCE() __builtin_amdgcn_sched_barrier(0)
+        issue_b(0, 0);
+        load_a(0);
+        PP_FENCE();
+        stage_a(0, 0);
+        stage_a(1, 0);
+        PP_FENCE();
+        load_a(nk > 1 ? 1 : 0);
+        PP_FENCE();
+        asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");                 // barrier 1 of the phase
+        if (nk > 1) issue_b(1, 1);
+        {
+            const unsigned aa = a_rd, bb = b_rd;
+            PP_RD(bl[0], bb, PB_PLANE) PP_RD(bl[1], bb, PB_PLANE + 2048) PP_RD(al[0], aa, PA_PLANE) PP_RD(al[1], aa, PA_PLANE + 2048)
+            PP_RD(ah[0], aa, 0) PP_RD(ah[1], aa, 2048) PP_RD(bh[0], bb, 0) PP_RD(bh[1], bb, 2048)
+        }
+        PP_FENCE();
+        // (the rolling pipeline of h2_occ_nt_kernel, unchanged but for the plane offsets and the four weight pieces per wave: the
+        // counted waits name the same positions -- the pieces are issued before the two A loads that may stay in flight)
+        for (int kt = 0; kt < nk; ++kt) {
+            const int stage = kt & 1;
+            const bool more = kt + 1 < nk;
+            const unsigned aa1 = (a_rd + stage * PSTAGE) ^ 16u, bb1 = (b_rd + stage * PSTAGE) ^ 16u;
+            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah[0]), "+v"(bl[0]), "+v"(ah[1]), "+v"(bl[1]), "+v"(al[0]), "+v"(al[1]));
+            PP_MMA(ah, bl)
+            PP_FENCE();
+            PP_RD(bl[0], bb1, PB_PLANE) PP_RD(bl[1], bb1, PB_PLANE + 2048)
+            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bh[0]), "+v"(bh[1]));
+            PP_MMA2(al, bh, 0)
+            PP_FENCE();
+            if (more) stage_a(0, stage ^ 1);
+            PP_FENCE();
+            PP_MMA2(al, bh, 1)
+            PP_FENCE();
+            PP_RD(al[0], aa1, PA_PLANE) PP_RD(al[1], aa1, PA_PLANE + 2048)
+            PP_MMA2(ah, bh, 0)
+            PP_FENCE();
+            if (more) stage_a(1, stage ^ 1);
+            PP_FENCE();
+            PP_MMA2(ah, bh, 1)
+            PP_FENCE();
+            PP_RD(ah[0], aa1, 0) PP_RD(ah[1], aa1, 2048) PP_RD(bh[0], bb1, 0) PP_RD(bh[1], bb1, 2048)
+            load_a(kt + 2 < nk ? kt + 2 : nk - 1);
+            PP_FENCE();
+            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ah[0]), "+v"(ah[1]), "+v"(bl[0]), "+v"(bl[1]), "+v"(al[0]), "+v"(al[1]));
+            PP_MMA(ah, bl)
+            PP_FENCE();
+            asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" : "+v"(bh[0]), "+v"(bh[1]) :: "memory");   // barrier 2 + kt
+            if (more) issue_b(kt + 2 < nk ? kt + 2 : nk - 1, stage);
+            const unsigned aa2 = a_rd + (stage ^ 1) * PSTAGE, bb2 = b_rd + (stage ^ 1) * PSTAGE;
+            if (more) { PP_RD(bl[0], bb2, PB_PLANE) PP_RD(bl[1], bb2, PB_PLANE + 2048) }
+            PP_FENCE();
+            PP_MMA(al, bh)
+            PP_FENCE();
+            if (more) { PP_RD(al[0], aa2, PA_PLANE) PP_RD(al[1], aa2, PA_PLANE + 2048) }
+            PP_MMA(ah, bh)
+            PP_FENCE();
+            if (more) { PP_RD(ah[0], aa2, 0) PP_RD(ah[1], aa2, 2048) PP_RD(bh[0], bb2, 0) PP_RD(bh[1], bb2, 2048) }
+            PP_FENCE();
+        }
+#undef PP_MMA
+#undef PP_MMA2
+#undef PP_RD
+#undef PP_FENCE
+        for (int b = nk + 1; b < nb; ++b) bar();                        // (short reductions: the epilogue role's barriers set the pace)
+    };
+
+    // ---- K4's unique-row pass of one tile out of the kept accumulators (h2_occ_nt_kernel<8>'s epilogue, in slices) --------------
+    auto epilogue = [&](int i) __attribute__((always_inline)) {
+        int64_t tm0; int tn0;
+        tile_of(i, tm0, tn0);
+        int lane_e = lane;
+        asm volatile("" : "+v"(lane_e));
+        const int prow = lane_e >> 4, pc4 = (lane_e & 15) * 4;
+        const int k4_f = (tn0 >> 6) + wc;
+        const bool k4_on = k4_f < e.F;
+        const int k4_rows = (int)min((int64_t)PM, g.M - tm0);
+        const int k4_ldc4 = (int)(e.ld_dc * 4);
+        auto mk = [&](const void* p, int64_t bytes) __attribute__((always_inline)) {
+            const uint64_t b = reinterpret_cast<uint64_t>(p);
+            void* q = reinterpret_cast<void*>(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
+                                              (unsigned)__builtin_amdgcn_readfirstlane((int)b));
+            return __builtin_amdgcn_make_buffer_rsrc(q, 0, (int)(unsigned)(bytes < 0xffffff00ll ? bytes : 0xffffff00ll), 0x00020000);
+        };
+        const int fc = k4_on ? k4_f : 0;
+        const int64_t rb = e.row_base[fc];
+        const bool has_lin = e.lin_w != nullptr;
+        const __amdgpu_buffer_rsrc_t k4_t = mk(e.table + rb * 64, 0xffffff00ll);
+        const __amdgpu_buffer_rsrc_t k4_dl = mk(e.d_fm_logit + tm0, (int64_t)k4_rows * 4);
+        const __amdgpu_buffer_rsrc_t k4_lo = has_lin ? mk(e.lin_old_t + (int64_t)fc * g.M + tm0, (int64_t)k4_rows * 4) : k4_dl;
+        const __amdgpu_buffer_rsrc_t k4_sx = mk(e.sum_x + tm0 * 64, (int64_t)k4_rows * 256);
+        const __amdgpu_buffer_rsrc_t k4_dc = mk(e.d_concat + tm0 * e.ld_dc + 64 * fc, ((int64_t)k4_rows - 1) * e.ld_dc * 4 + 256);
+        const __amdgpu_buffer_rsrc_t k4_lw = has_lin ? mk(e.lin_w + rb, 0x7fffffffll) : mk(e.table, 0);
+        const __amdgpu_buffer_rsrc_t k4_id = mk(e.ids_t + (int64_t)fc * g.M + tm0, (int64_t)k4_rows * 4);
+        const __amdgpu_buffer_rsrc_t k4_fl = mk(e.flags + tm0 * e.F, (int64_t)k4_rows * e.F);
+        const unsigned stq = lds0 + P_STQ + wg * 2048;                                  // this wave's 8-row staging area
+        const unsigned stq_wr = stq + (4 * (lane_e >> 5)) * 256 + (lane_e & 31) * 4;   // + (reg & 3) * 256 + b * 128
+        const unsigned stq_rd = stq + prow * 256 + pc4 * 4;                            // + 4 i * 256
+
+        // slice 0: the sum_x panel (rows 16 wg .. + 15, by LDS-DMA) and the per-row scalars of slot (row 64 wr + lane, this wave's field)
+#pragma unroll
+        for (int p4 = 0; p4 < 4; ++p4)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(k4_sx, (lds_ptr_t)(smem + P_SXP + (16 * wg + 4 * p4) * 256), 16,
+                                                     (16 * wg + 4 * p4 + (lane_e >> 4)) * 256 + (lane_e & 15) * 16, 0, 0, 0);
+        unsigned dlv = __builtin_amdgcn_raw_buffer_load_b32(k4_dl, (64 * wr + lane_e) * 4, 0, 0);
+        unsigned lov = __builtin_amdgcn_raw_buffer_load_b32(k4_lo, (64 * wr + lane_e) * 4, 0, 0);
+        int idl = (int)__builtin_amdgcn_raw_buffer_load_b32(k4_id, (64 * wr + lane_e) * 4, 0, 0);
+        int fll = (int)__builtin_amdgcn_raw_buffer_load_b8(k4_fl, (64 * wr + lane_e) * e.F + k4_f, 0, 0);
+        bar();                                                                          // barrier 1
+        // slice 1: scalars (and this wave's panel rows) landed -> LDS; pass 0's table rows in flight
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(dlv), "+v"(lov), "+v"(idl), "+v"(fll) :: "memory");
+        const int uid = (k4_on && 64 * wr + lane_e < k4_rows && idl >= 0 && fll != 0) ? idl : -1;
+        OCC_DS_WRITE_B32(lds0 + P_DLP + (64 * wr + lane_e) * 4, dlv, 0);
+        OCC_DS_WRITE_B32(lds0 + P_LOP + wg * 256 + lane_e * 4, lov, 0);
+        OCC_DS_WRITE_B32(lds0 + P_UIP + wg * 256 + lane_e * 4, uid, 0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // (a slot's row id is read from LDS where it is used rather than kept: 8 registers fewer across the wait for the rows)
+        auto uid_of = [&](int a, int it) __attribute__((always_inline)) {
+            return *reinterpret_cast<const int*>(smem + P_UIP + wg * 256 + (32 * a + 4 * it + prow) * 4);
+        };
+        u32x4 t[8];
+        auto issue_rows = [&](int a) __attribute__((always_inline)) {
+#pragma unroll
+            for (int it = 0; it < 8; ++it)
+                t[it] = __builtin_amdgcn_raw_buffer_load_b128(k4_t, (int)((unsigned)max(uid_of(a, it), 0) * 256u + (unsigned)pc4 * 4u), 0, 2);
+        };
+        // one eighth (rows 8 h .. + 7 of the 32-row block a): accumulators through the staging area, update / store of two row groups
+        auto eighth = [&](int a, int h) __attribute__((always_inline)) {
+            const int ml0 = 64 * wr + 32 * a + prow;
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int reg = 4 * h + r;
+                    const float v = acc[a][b][reg] * h2_out;
+                    acc[a][b][reg] = 0.f;
+                    switch (b * 4 + r) {                                // (immediates must be literal)
+#define PP_W(I) case I: OCC_DS_WRITE_B32(stq_wr, v, (I & 3) * 256 + (I >> 2) * 128); break;
+                        PP_W(0) PP_W(1) PP_W(2) PP_W(3) PP_W(4) PP_W(5) PP_W(6) PP_W(7)
+#undef PP_W
+                    }
+                }
+            f32x4 v[2];
+            asm volatile("s_waitcnt lgkmcnt(0)\n\tds_read_b128 %0, %2 offset:0\n\tds_read_b128 %1, %2 offset:1024\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&v"(v[0]), "=&v"(v[1]) : "v"(stq_rd) : "memory");
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int it = 2 * h + i;
+                const int ml = ml0 + 4 * it;
+                const int uidv = uid_of(a, it);
+                const bool uq = uidv >= 0;
+                const unsigned voff = (unsigned)uidv * 256u + (unsigned)pc4 * 4u;
+                const f32x4 tv = __builtin_bit_cast(f32x4, t[it]);
+                const f32x4 sv = *reinterpret_cast<const f32x4*>(smem + P_SXP + ml * 256 + pc4 * 4);
+                const float dl = *reinterpret_cast<const float*>(smem + P_DLP + ml * 4);
+                const float lo = *reinterpret_cast<const float*>(smem + P_LOP + wg * 256 + (32 * a + 4 * it + prow) * 4);
+                // emb_bwd_unique_body's arithmetic (g += dl (sx - x) ; x = fma(scale, g, x))
+                float4 gq = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
+                gq.x += dl * (sv[0] - tv[0]); gq.y += dl * (sv[1] - tv[1]);
+                gq.z += dl * (sv[2] - tv[2]); gq.w += dl * (sv[3] - tv[3]);
+                f32x4 r;
+                r[0] = fmaf(e.scale, gq.x, tv[0]); r[1] = fmaf(e.scale, gq.y, tv[1]);
+                r[2] = fmaf(e.scale, gq.z, tv[2]); r[3] = fmaf(e.scale, gq.w, tv[3]);
+                if (uq) cmax = fmaxf(cmax, fmaxf(fmaxf(fabsf(r[0]), fabsf(r[1])), fmaxf(fabsf(r[2]), fabsf(r[3]))));
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, r), k4_t, uq ? (int)voff : (int)0xffffff00u, 0, 2);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[i]), k4_dc,
+                                                       (uq || ml >= k4_rows) ? (int)0x80000000u : ml * k4_ldc4 + pc4 * 4, 0, 2);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fmaf(e.scale, dl, lo)), k4_lw,
+                                                      (uq && pc4 == 0) ? (int)(voff >> 6) : (int)0x80000000u, 0, 0);
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the eighth's reads retired before the next one's writes
+        };
+        // (an EXPLICIT wait for the rows, naming them: see h2_occ_nt_kernel<8>.  It also covers the previous stores.)
+        auto wait_rows = [&]() __attribute__((always_inline)) {
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]));
+        };
+        if (k4_on) issue_rows(0);
+        bar();                                                                          // barrier 2: every wave's panel rows visible
+        if (k4_on) { wait_rows(); eighth(0, 0); eighth(0, 1); }
+        bar();                                                                          // barrier 3
+        if (k4_on) { eighth(0, 2); eighth(0, 3); issue_rows(1); }
+        bar();                                                                          // barrier 4
+        if (k4_on) { wait_rows(); eighth(1, 0); eighth(1, 1); }
+        bar();                                                                          // barrier 5
+        if (k4_on) { eighth(1, 2); eighth(1, 3); }
+        else {
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) acc[a][b][reg] = 0.f;
+        }
+        bar();                                                                          // barrier 6
+        // no store of this tile pending into the group's next main loop's counted waits; the panel, staging and scalars are the
+        // other group's in the next phase
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        bar();                                                                          // barrier 7 (= P_EPI_BARRIERS)
+        for (int b = P_EPI_BARRIERS; b < nb; ++b) bar();
+    };
+
+    // ---- the phases: n tiles of this block -> n + 1 phases.  Tile i is group (i & 1)'s: its main loop runs in phase i, its epilogue
+    // in phase i + 1.  Group 1 sits phase 0 out; the group whose last tile is not tile n - 1 sits the last phase out.  (Written as
+    // one straight main loop -> epilogue sequence per tile, as in h2_occ_nt_kernel: with both roles under one phase switch the
+    // register allocator kept each role's values live through the other and spilled.)
+    const int n = (int)blockIdx.x < ntiles ? (ntiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
+    auto idle = [&]() __attribute__((always_inline)) { for (int b = 0; b < nb; ++b) bar(); };
+    if (grp == 1) idle();
+    for (int i = grp; i < n; i += 2) {
+        main_loop(i);
+        epilogue(i);
+    }
+    if (((n ^ grp) & 1) == 0) idle();
+    if (e.table_amax != nullptr) {
+        uint32_t m = __float_as_uint(cmax);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+        if (lane == 0 && m > __hip_atomic_load(e.table_amax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(e.table_amax, m);
+    }
+}
+
 }  // namespace
 
 int occ_nt_launch(const RsArgs& g, hipStream_t stream) {
@@ -579,10 +936,26 @@ extern "C" int dr_h2_dgrad_emb_sgd(const float* dy, int64_t ld_dy, const uint32_
     g.M = M; g.N = 64 * F; g.K = K;
     g.a_amax = dy_amax; g.b_amax = w_amax;
     K4Args e{ids_t, unique_flags, row_base, F, table, lin_w, lin_old_t, sum_x, d_fm_logit, scale, d_concat, ld_dconcat, table_amax};
-    const int64_t tiles = ((M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+    // DR_FUSED_K4_OVERLAP=0: the round-6 kernel (GEMM and K4 epilogue back to back per 256 x 256 tile) instead of the overlapped one;
+    // both compute the same bits
+    static const bool overlap = [] { const char* v = getenv("DR_FUSED_K4_OVERLAP"); return !(v && v[0] == '0' && v[1] == 0); }();
+    const int64_t tiles = ((M + (overlap ? PM : BM) - 1) / (overlap ? PM : BM)) * ((g.N + BN - 1) / BN);
     if (tiles > 0x7fffffff) return DR_EINVAL;
     const int grid = (int)(tiles < 256 ? tiles : 256);
-    hipLaunchKernelGGL((h2_occ_nt_kernel<8>), dim3(grid), dim3(1024), 0, dr_s(stream), g, e);
+#ifdef DR_OCC_ABLATE
+    {
+        static const int dbg = [] { const char* v = getenv("DR_OCC_DBG"); return v ? atoi(v) : 0; }();
+        if (dbg == 1024 || dbg == 2048) {
+            const int grid8 = (int)std::min<int64_t>(((M + BM - 1) / BM) * ((g.N + BN - 1) / BN), 256);
+            if (dbg == 1024) hipLaunchKernelGGL((h2_occ_nt_kernel<8, 1024>), dim3(grid8), dim3(1024), 0, dr_s(stream), g, e);
+            else hipLaunchKernelGGL((h2_occ_nt_kernel<8, 2048>), dim3(grid8), dim3(1024), 0, dr_s(stream), g, e);
+            DR_CHECK_LAUNCH();
+            return DR_OK;
+        }
+    }
+#endif
+    if (overlap) hipLaunchKernelGGL(h2_occ_pp_kernel, dim3(grid), dim3(1024), 0, dr_s(stream), g, e);
+    else hipLaunchKernelGGL((h2_occ_nt_kernel<8>), dim3(grid), dim3(1024), 0, dr_s(stream), g, e);
     DR_CHECK_LAUNCH();
     return DR_OK;
 }

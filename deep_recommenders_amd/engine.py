@@ -761,6 +761,8 @@ class DeepFMEngine:
                 dy = dx
                 continue
             if i == 0 and self.fuse_k4 and self._lin_old_valid and not adam and not self.overlap_dw:
+                if self.h2 and not (n > 1 and self.fuse_narrow and self.narrow_ws[1] is not None):
+                    ops.h2_amax(dy, self.dh0_amax)       # (as below: no narrow layer-1 kernel left the record the wgrad and dgrad read)
                 self._backward_l0_fused_k4(x, dy, sc, dstW, dstb, fl)
                 dy = None
                 continue

@@ -1,5 +1,8 @@
 """EXPERIMENT driver (not product): the fused first-layer dgrad + K4 (dr_h2_dgrad_emb_sgd) against dgrad + K4 at config 3's shape
-(B = 65 536, F = 26, D = 64, 256-wide layer; V rows per field from argv, default 2 M = 13 GB of tables: random rows miss every cache)."""
+(B = 65 536, F = 26, D = 64, 256-wide layer; V rows per field from argv, default 2 M = 13 GB of tables: random rows miss every cache).
+DR_FUSED_K4_OVERLAP=0 times the back-to-back kernel instead of the overlapped one.  With the library built with
+DR_HIPCC_EXTRA=-DDR_OCC_ABLATE, DR_OCC_DBG=1024 times the back-to-back kernel's main loop alone (K4 epilogue skipped) and
+DR_OCC_DBG=2048 its K4 epilogue alone (no MFMAs, no A / B ingest): the budget the overlapped kernel works with."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import torch
@@ -53,7 +56,8 @@ k4 = lambda parts: ops.emb_pool_bwd_sorted(ids, row_base, plan, D, R, d_concat, 
 dgrad = lambda: ops.h2_linear_nt(dy, dy_am, wp.w, out=d_concat[:, :in_dim])
 fused = lambda: ops.h2_dgrad_emb_sgd(dy, dy_am, wp.w, ids_t, plan, row_base, table, lin, lin_old_t, sum_x, dl, -lr, d_concat, table_amax=tab_am)
 uniq = int(plan.flags[:B * F].sum().item())
-print("FUSEDK4 V=%d %s  unique slots %.4f  occ=%s" % (V, "zipf" if zipf else "uniform", uniq / (B * F), os.environ.get("DR_H2_OCC", "1")), flush=True)
+print("FUSEDK4 V=%d %s  unique slots %.4f  occ=%s overlap=%s dbg=%s" % (V, "zipf" if zipf else "uniform", uniq / (B * F),
+      os.environ.get("DR_H2_OCC", "1"), os.environ.get("DR_FUSED_K4_OVERLAP", "1"), os.environ.get("DR_OCC_DBG", "0")), flush=True)
 for rep in range(2):
     t_d = timeit(dgrad)
     t_k = timeit(lambda: k4(1))
