@@ -155,6 +155,16 @@ SIGNATURES = {
     "dr_esmm_head_bwd": [_p, _p, _p, _p, _p, _i64, _p, _i64, _p],
     "dr_adam_step_2d": [_p, _i64, _p, _i64, _p, _p, _i64, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _p],
     "dr_gather_cols": [_p, _i64, _p, _i64, _p, _i64, _i32, _p, _i64, _p],
+    "dr_csr_plan_bytes": [_i64],
+    "dr_csr_plan_workspace_bytes": [_i64],
+    "dr_csr_plan": [_p, _i64, _i64, _p, _i64, _p, _i64, _p],
+    "dr_csr_spmm_workspace_bytes": [_i64, _i32],
+    "dr_csr_spmm": [_p, _p, _p, _i64, _i64, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _i64, _p],
+    "dr_csr_transpose_workspace_bytes": [_i64, _i64],
+    "dr_csr_transpose": [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _p],
+    "dr_softmax_rows_fwd": [_p, _i64, _i64, _i32, _p, _i64, _p],
+    "dr_softmax_rows_bwd": [_p, _i64, _p, _i64, _i64, _i32, _p, _i64, _p],
+    "dr_cce_prob_rows": [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _i64, _p],
     "dr_version": [],
     "dr_set_gemm_mode": [_i32],
     "dr_get_gemm_mode": [],
@@ -171,7 +181,9 @@ _RESTYPE = {"dr_version": ctypes.c_char_p, "dr_shard_bucket_workspace_bytes": ct
             "dr_tower_head_workspace_bytes": ctypes.c_int64,
             "dr_inbatch_softmax_workspace_bytes": ctypes.c_int64, "dr_topk_workspace_bytes": ctypes.c_int64,
             "dr_topk_index_bytes": ctypes.c_int64,
-            "dr_linear_bwd_dw_grouped_workspace_bytes": ctypes.c_int64, "dr_mse_workspace_bytes": ctypes.c_int64}
+            "dr_linear_bwd_dw_grouped_workspace_bytes": ctypes.c_int64, "dr_mse_workspace_bytes": ctypes.c_int64,
+            "dr_csr_plan_bytes": ctypes.c_int64, "dr_csr_plan_workspace_bytes": ctypes.c_int64,
+            "dr_csr_spmm_workspace_bytes": ctypes.c_int64, "dr_csr_transpose_workspace_bytes": ctypes.c_int64}
 
 DR_OK, DR_EINVAL, DR_ELAUNCH, DR_ESHAPE = 0, -1, -2, -3
 _ERR = {DR_EINVAL: "DR_EINVAL (bad argument)", DR_ELAUNCH: "DR_ELAUNCH (HIP launch error)",

@@ -472,3 +472,179 @@ class InputLayer(nn.Module):
         if not self.mixed:
             return emb
         return _GatherColsFn.apply(num, emb, self._col_map, self._emb_map, self.K)
+
+
+# --------------------------------------------------------------------------------------------------
+# graph aggregation (keras/models/retrieval/gcn.py:44-52): A @ X for a sparse or dense adjacency
+# --------------------------------------------------------------------------------------------------
+class SparseAdjacency:
+    """A graph's adjacency as a device CSR (row_ptr int64, col int32, val fp32), built once.  Accepts a torch sparse COO / CSR tensor,
+    a scipy sparse matrix or `(indices [nnz, 2], values [nnz], shape)` (a tf.SparseTensor's fields).  Duplicate coordinates are summed
+    and the indices sorted on the host, as tf.sparse.sparse_dense_matmul sums them; the long-row plan and the device-built transpose
+    (the backward's operand) are made on first use and kept."""
+
+    def __init__(self, adj, shape=None, device="cuda"):
+        import scipy.sparse as sp
+        if isinstance(adj, SparseAdjacency):
+            raise TypeError("already a SparseAdjacency")
+        if isinstance(adj, torch.Tensor):
+            if adj.layout == torch.sparse_csr:
+                adj = adj.to_sparse_coo()
+            if adj.layout != torch.sparse_coo:
+                raise TypeError("SparseAdjacency: a torch tensor must be sparse (COO or CSR); pass a dense adjacency to GCN as is")
+            adj = adj.coalesce().cpu()
+            idx = adj.indices().numpy()
+            m = sp.coo_matrix((adj.values().numpy().astype(np.float32), (idx[0], idx[1])), shape=tuple(adj.shape))
+        elif sp.issparse(adj):
+            m = adj.tocoo()
+        elif isinstance(adj, (tuple, list)) and len(adj) == 3:
+            indices, values, shp = adj
+            indices = np.asarray(indices, dtype=np.int64).reshape(-1, 2)
+            m = sp.coo_matrix((np.asarray(values, dtype=np.float32).reshape(-1), (indices[:, 0], indices[:, 1])),
+                              shape=tuple(int(s) for s in shp))
+        else:
+            raise TypeError("SparseAdjacency: expected a torch sparse tensor, a scipy sparse matrix or (indices, values, shape)")
+        if shape is not None and tuple(shape) != tuple(m.shape):
+            raise ValueError("shape %s does not match the adjacency's %s" % (tuple(shape), tuple(m.shape)))
+        n_rows, n_cols = m.shape
+        if n_rows >= 2 ** 31 or n_cols >= 2 ** 31:
+            raise ValueError("SparseAdjacency: at most 2^31 - 1 rows and columns (int32 column indices)")
+        csr = sp.csr_matrix((m.data.astype(np.float32), (m.row, m.col)), shape=m.shape)   # sums duplicates
+        csr.sum_duplicates()
+        csr.sort_indices()
+        self.shape = (int(n_rows), int(n_cols))
+        self.nnz = int(csr.nnz)
+        self.device = torch.device(device)
+        self.row_ptr = torch.from_numpy(csr.indptr.astype(np.int64)).to(self.device)
+        self.col = torch.from_numpy(csr.indices.astype(np.int32)).to(self.device)
+        self.val = torch.from_numpy(csr.data.astype(np.float32)).to(self.device)
+        self._plan = None
+        self._t = None
+        self._ws = {}
+
+    @classmethod
+    def _from_device(cls, row_ptr, col, val, shape):
+        self = cls.__new__(cls)
+        self.shape, self.nnz, self.device = tuple(shape), int(col.numel()), row_ptr.device
+        self.row_ptr, self.col, self.val = row_ptr, col, val
+        self._plan, self._t, self._ws = None, None, {}
+        return self
+
+    def plan(self):
+        if self._plan is None:
+            self._plan = ops.csr_plan(self.row_ptr, self.shape[0], self.nnz)
+        return self._plan
+
+    def transpose(self):
+        """A^T as a SparseAdjacency, built on the device once (sources ascending inside each column: a fixed backward sum order)"""
+        if self._t is None:
+            t = ops.csr_transpose(self.row_ptr, self.col, self.val, self.shape[0], self.shape[1], self.nnz)
+            self._t = SparseAdjacency._from_device(*t, (self.shape[1], self.shape[0]))
+            self._t._t = self
+        return self._t
+
+    def workspace(self, D):
+        if D not in self._ws:
+            self._ws[D] = ops.csr_spmm_workspace(self.nnz, D, self.device)
+        return self._ws[D]
+
+    def spmm(self, X, relu_src=None, accumulate=False, out=None):
+        """(A @ X) on dr_csr_spmm, no autograd"""
+        if X.shape[0] != self.shape[1]:
+            raise ValueError("A is %s, X has %d rows" % (self.shape, X.shape[0]))
+        return ops.csr_spmm(self.row_ptr, self.col, self.val, self.shape[0], self.nnz, X, self.plan(), self.workspace(X.shape[1]),
+                            relu_src=relu_src, accumulate=accumulate, out=out)
+
+    def to_dense(self):
+        """host float64 copy (tests)"""
+        import scipy.sparse as sp
+        return sp.csr_matrix((self.val.cpu().numpy(), self.col.cpu().numpy(), self.row_ptr.cpu().numpy()), shape=self.shape).toarray()
+
+
+def as_adjacency(adj, device="cuda"):
+    """SparseAdjacency for a sparse adjacency, None for a dense one"""
+    import scipy.sparse as sp
+    if isinstance(adj, SparseAdjacency):
+        return adj
+    if isinstance(adj, torch.Tensor) and adj.layout in (torch.sparse_coo, torch.sparse_csr):
+        return SparseAdjacency(adj, device=device)
+    if sp.issparse(adj) or (isinstance(adj, (tuple, list)) and len(adj) == 3):
+        return SparseAdjacency(adj, device=device)
+    return None
+
+
+class _SpmmFn(torch.autograd.Function):
+    """A @ X (tf.sparse.sparse_dense_matmul); backward dX = A^T dAgg on the transpose.  No gradient reaches A (a graph input)."""
+
+    @staticmethod
+    def forward(ctx, X, adj):
+        ctx.adj = adj
+        return adj.spmm(X)
+
+    @staticmethod
+    def backward(ctx, d):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return ctx.adj.transpose().spmm(d), None
+
+
+class _DenseAggFn(torch.autograd.Function):
+    """adj @ X for a dense adjacency (tf.linalg.matmul, gcn.py:47-48) on the GEMM path; dX = adj^T dAgg with a workspace (fixed order)"""
+
+    @staticmethod
+    def forward(ctx, X, adj):
+        ctx.save_for_backward(adj)
+        return ops.linear_fwd(adj, X)
+
+    @staticmethod
+    def backward(ctx, d):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        (adj,) = ctx.saved_tensors
+        M, K = adj.shape
+        N = d.shape[1]
+        dX = torch.zeros((K, N), dtype=torch.float32, device=d.device)
+        ops.linear_bwd_dw(adj, d, 1.0, dX, None, workspace=ops.linear_bwd_dw_workspace(M, K, N, d.device))
+        return dX, None
+
+
+def aggregate(adj, X):
+    """adj @ X with autograd: dr_csr_spmm for a SparseAdjacency, the GEMM for a dense [N, M] fp32 tensor"""
+    if isinstance(adj, SparseAdjacency):
+        return _SpmmFn.apply(X, adj)
+    return _DenseAggFn.apply(X, adj)
+
+
+class _SoftmaxRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        y = ops.softmax_rows_fwd(x)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        return ops.softmax_rows_bwd(y, dy if dy.stride(1) == 1 else dy.contiguous())
+
+
+def softmax_rows(logits):
+    """softmax over the last axis; the result remembers its logits (`_dr_logits`) so that losses.categorical_crossentropy can take
+    the fused softmax-CE path, as Keras' backend does when its input is a Softmax op"""
+    y = _SoftmaxRowsFn.apply(logits)
+    y._dr_logits = logits
+    return y
+
+
+class _AddFn(torch.autograd.Function):
+    """out + x on dr_axpy (the GCN residual, gcn.py:54-55)"""
+
+    @staticmethod
+    def forward(ctx, out, x):
+        y = out.contiguous().clone() if out.is_contiguous() else out.contiguous()
+        ops.axpy(1.0, x.contiguous(), y)
+        return y
+
+    @staticmethod
+    def backward(ctx, d):
+        return d, d

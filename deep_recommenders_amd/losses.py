@@ -2,6 +2,7 @@
 kernels.  Reference call sites (reference root): examples/train_fm_on_movielens_estimator.py:46
 (tf.losses.sigmoid_cross_entropy), examples/train_deepfm_on_movielens_estimator.py:47 (tf.losses.log_loss),
 examples/train_deepfm_on_movielens_keras.py:43 (tf.keras.losses.binary_crossentropy)."""
+import numpy as np
 import torch
 
 from . import ops
@@ -90,3 +91,53 @@ def mean_squared_error(labels, predictions):
         p = p.contiguous()
     loss = _MseFn.apply(p, y if y.stride(1) == 1 or y.shape[1] == 1 else y.contiguous())
     return loss.reshape(()) if p.shape[1] == 1 else loss
+
+
+class _SoftmaxCEFn(torch.autograd.Function):
+    """sum_r w_r * CE(softmax(logits_r), y_r) on dr_softmax_ce_rows; the gradient goes to the logits directly"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weights):
+        loss = ops.softmax_ce_rows(logits, labels, 1.0, weights)
+        ctx.save_for_backward(ops.softmax_ce_rows_bwd(logits, labels, 1.0, weights, 1.0))
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        (g,) = ctx.saved_tensors
+        return g * d_loss, None, None
+
+
+class _CceProbFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prob, labels, weights):
+        row, g = ops.cce_prob_rows(prob, labels, weights)
+        ctx.save_for_backward(g)
+        return ops.reduce_sum(row).reshape(())
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        (g,) = ctx.saved_tensors
+        return g * d_loss, None, None
+
+
+def categorical_crossentropy(y_true, y_pred, sample_weight=None):
+    """tf.keras.losses.categorical_crossentropy under compile/fit (examples/train_gcn_on_cora_keras.py:28-31): the weighted per-row
+    cross-entropies summed and divided by the number of rows, every row counted (SUM_OVER_BATCH_SIZE; sample_weight is the train
+    mask there).  When y_pred is the output of a softmax layer of this package (GCN(activation="softmax")) the loss is computed from
+    that layer's logits, unclipped, and the gradient goes straight to them -- what Keras' backend does for a Softmax op.  Any other
+    probability tensor takes Keras' formula: p / sum(p), clipped to [1e-7, 1 - 1e-7]."""
+    logits = getattr(y_pred, "_dr_logits", None)
+    p = logits if logits is not None else y_pred
+    B = p.shape[0]
+    y = torch.as_tensor(y_true, dtype=torch.float32)
+    y = (y.cuda() if not y.is_cuda else y).reshape(p.shape).contiguous()
+    if sample_weight is None:
+        w = torch.full((B,), 1.0 / B, dtype=torch.float32, device=y.device)
+    else:
+        w = torch.as_tensor(np.asarray(sample_weight, dtype=np.float64).reshape(-1) / B if not isinstance(sample_weight, torch.Tensor)
+                            else sample_weight.detach().to(torch.float64).reshape(-1).cpu().numpy() / B)
+        w = w.to(torch.float32).to(y.device)
+    if logits is not None:
+        return _SoftmaxCEFn.apply(logits.contiguous(), y, w)
+    return _CceProbFn.apply(y_pred if y_pred.stride(1) == 1 else y_pred.contiguous(), y, w)

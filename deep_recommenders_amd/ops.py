@@ -1682,3 +1682,98 @@ def gather_cols(a, b, col_map, out):
     check(lib().dr_gather_cols(ptr(a), a.stride(0) if a is not None else 0, ptr(b), b.stride(0) if b is not None else 0, ptr(col_map),
                                M, N, ptr(out), out.stride(0), stream_ptr()), "dr_gather_cols")
     return out
+
+
+# ---- graph convolution (csrc/graph.hip) -----------------------------------------------------------------------------------------
+def _ld4_f32(t):
+    """[M, D] fp32 with unit column stride, a row pitch that is a multiple of 4 floats and a 16-byte aligned base (copied into such
+    a buffer otherwise) -- the layout dr_csr_spmm takes."""
+    assert t.dim() == 2 and t.dtype == torch.float32
+    if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0:
+        return t
+    M, D = t.shape
+    buf = torch.empty((M, _pad4(D)), dtype=torch.float32, device=t.device)
+    buf[:, :D].copy_(t)
+    return buf[:, :D]
+
+
+def empty_ld4(M, D, device, zero=False):
+    buf = (torch.zeros if zero else torch.empty)((M, _pad4(D)), dtype=torch.float32, device=device)
+    return buf[:, :D]
+
+
+def csr_plan(row_ptr, n_rows, nnz):
+    """the long-row plan of a CSR (int64 device buffer), built once per graph"""
+    dev = row_ptr.device
+    plan = torch.empty(max(1, lib().dr_csr_plan_bytes(int(nnz)) // 8), dtype=torch.int64, device=dev)
+    ws = torch.empty(max(1, lib().dr_csr_plan_workspace_bytes(int(n_rows)) // 8), dtype=torch.int64, device=dev)
+    check(lib().dr_csr_plan(ptr(row_ptr), int(n_rows), int(nnz), ptr(plan), plan.numel() * 8, ptr(ws), ws.numel() * 8, stream_ptr()),
+          "dr_csr_plan")
+    return plan
+
+
+def csr_spmm_workspace(nnz, D, device):
+    n = lib().dr_csr_spmm_workspace_bytes(int(nnz), int(D))
+    return torch.empty(max(1, n // 4), dtype=torch.float32, device=device) if n > 0 else None
+
+
+def csr_spmm(row_ptr, col, val, n_rows, nnz, X, plan, workspace=None, relu_src=None, accumulate=False, out=None):
+    """out = (A @ X) [* (relu_src > 0)] [+ out]; A the CSR (row_ptr int64, col int32, val fp32)"""
+    X = _ld4_f32(X)
+    D = X.shape[1]
+    if out is None:
+        assert not accumulate
+        out = empty_ld4(n_rows, D, X.device)
+    assert out.shape == (n_rows, D)
+    if relu_src is not None:
+        relu_src = _ld4_f32(relu_src)
+    need = lib().dr_csr_spmm_workspace_bytes(int(nnz), int(D))
+    if need > 0 and (workspace is None or workspace.numel() * 4 < need):
+        workspace = csr_spmm_workspace(nnz, D, X.device)
+    check(lib().dr_csr_spmm(ptr(row_ptr), ptr(col), ptr(val), int(n_rows), int(nnz), ptr(X), X.stride(0), int(D), ptr(relu_src),
+                            relu_src.stride(0) if relu_src is not None else 0, int(bool(accumulate)), ptr(out), out.stride(0),
+                            ptr(plan), ptr(workspace), workspace.numel() * 4 if workspace is not None else 0, stream_ptr()),
+          "dr_csr_spmm")
+    return out
+
+
+def csr_transpose(row_ptr, col, val, n_rows, n_cols, nnz):
+    """(t_row_ptr, t_col, t_val): the CSR of A^T, source rows ascending inside every column"""
+    dev = row_ptr.device
+    t_row_ptr = torch.empty(n_cols + 1, dtype=torch.int64, device=dev)
+    t_col = torch.empty(max(1, nnz), dtype=torch.int32, device=dev)[:nnz]
+    t_val = torch.empty(max(1, nnz), dtype=torch.float32, device=dev)[:nnz]
+    ws = torch.empty(max(1, lib().dr_csr_transpose_workspace_bytes(int(nnz), int(n_cols))), dtype=torch.uint8, device=dev)
+    check(lib().dr_csr_transpose(ptr(row_ptr), ptr(col), ptr(val), int(n_rows), int(n_cols), int(nnz), ptr(t_row_ptr), ptr(t_col),
+                                 ptr(t_val), ptr(ws), ws.numel(), stream_ptr()), "dr_csr_transpose")
+    return t_row_ptr, t_col, t_val
+
+
+def softmax_rows_fwd(x, out=None):
+    assert x.dim() == 2 and x.stride(1) == 1
+    B, C = x.shape
+    if out is None:
+        out = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    check(lib().dr_softmax_rows_fwd(ptr(x), x.stride(0), B, C, ptr(out), out.stride(0), stream_ptr()), "dr_softmax_rows_fwd")
+    return out
+
+
+def softmax_rows_bwd(y, dy, out=None):
+    assert y.shape == dy.shape and y.stride(1) == 1 and dy.stride(1) == 1
+    B, C = y.shape
+    if out is None:
+        out = torch.empty((B, C), dtype=torch.float32, device=y.device)
+    check(lib().dr_softmax_rows_bwd(ptr(y), y.stride(0), ptr(dy), dy.stride(0), B, C, ptr(out), out.stride(0), stream_ptr()),
+          "dr_softmax_rows_bwd")
+    return out
+
+
+def cce_prob_rows(p, labels, sample_weight=None, want_grad=True):
+    """(row_loss [B], grad [B, C] or None) of Keras' categorical_crossentropy on probabilities, rows weighted by sample_weight"""
+    assert p.dim() == 2 and p.stride(1) == 1 and labels.shape == p.shape and labels.stride(1) == 1
+    B, C = p.shape
+    row = torch.empty(B, dtype=torch.float32, device=p.device)
+    grad = torch.empty((B, C), dtype=torch.float32, device=p.device) if want_grad else None
+    check(lib().dr_cce_prob_rows(ptr(p), p.stride(0), ptr(labels), labels.stride(0), B, C, ptr(sample_weight), ptr(row), ptr(grad),
+                                 grad.stride(0) if grad is not None else 0, stream_ptr()), "dr_cce_prob_rows")
+    return row, grad

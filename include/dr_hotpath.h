@@ -927,6 +927,41 @@ int dr_adam_step_2d(float* param, int64_t ld_p, const float* grad, int64_t ld_g,
 int dr_gather_cols(const float* a, int64_t lda, const float* b, int64_t ldb, const int32_t* map, int64_t M, int32_t N, float* out,
                    int64_t ldo, dr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Graph convolution (keras/models/retrieval/gcn.py:44-55, examples/train_gcn_on_cora_keras.py; csrc/graph.hip)
+ *
+ * CSR of A [n_rows, n_cols]: row_ptr int64 [n_rows + 1] (row_ptr[n_rows] == nnz), col int32 [nnz], val fp32 [nnz].  Dense operands
+ * are fp32 row-major with a row pitch that is a multiple of 4 floats and a 16-byte aligned base (DR_EINVAL otherwise).
+ *   dr_csr_spmm        out[r, :D] = (sum_k val[k] X[col[k], :D]) * (relu_src[r] > 0) (+ out[r] if accumulate), k over row r in
+ *                      ascending order (tf.sparse.sparse_dense_matmul, gcn.py:45-46); relu_src may be NULL.  Rows with more than
+ *                      DR_CSR_LONG_ROW entries are cut into fixed chunks whose partial sums are added in chunk order: no atomics,
+ *                      every call bit-identical.  Needs the plan of the same CSR (dr_csr_plan; may be NULL when
+ *                      dr_csr_spmm_workspace_bytes(nnz, D) == 0) and a workspace of that many bytes.  64-bit addressing.
+ *   dr_csr_plan        the long rows and their chunks, once per graph: plan >= dr_csr_plan_bytes(nnz) bytes, workspace >=
+ *                      dr_csr_plan_workspace_bytes(n_rows) bytes.
+ *   dr_csr_transpose   the CSR of A^T (t_row_ptr [n_cols + 1], t_col / t_val [nnz]) on the device, source rows ascending inside every
+ *                      column (a stable radix sort by column): the backward dX = A^T dAgg is dr_csr_spmm on it.  n_rows, n_cols < 2^31.
+ *   dr_softmax_rows_fwd / _bwd   y = softmax(x) per row (maximum subtracted); dx = y * (dy - sum_c y dy).  One wave per row.
+ *   dr_cce_prob_rows   tf.keras.losses.categorical_crossentropy on probabilities: q = clip(p / sum_c p, 1e-7, 1 - 1e-7),
+ *                      row_loss[r] = w_r * -sum_c y log q, grad (may be NULL) = d row_loss / d p.  sample_weight may be NULL.
+ * ---------------------------------------------------------------------------------------- */
+int64_t dr_csr_plan_bytes(int64_t nnz);
+int64_t dr_csr_plan_workspace_bytes(int64_t n_rows);
+int dr_csr_plan(const int64_t* row_ptr, int64_t n_rows, int64_t nnz, int64_t* plan, int64_t plan_bytes, void* workspace,
+                int64_t workspace_bytes, dr_stream_t stream);
+int64_t dr_csr_spmm_workspace_bytes(int64_t nnz, int32_t D);
+int dr_csr_spmm(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n_rows, int64_t nnz, const float* X, int64_t ld_x,
+                int32_t D, const float* relu_src, int64_t ld_relu_src, int32_t accumulate, float* out, int64_t ld_out,
+                const int64_t* plan, float* workspace, int64_t workspace_bytes, dr_stream_t stream);
+int64_t dr_csr_transpose_workspace_bytes(int64_t nnz, int64_t n_cols);
+int dr_csr_transpose(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                     int64_t* t_row_ptr, int32_t* t_col, float* t_val, void* workspace, int64_t workspace_bytes, dr_stream_t stream);
+int dr_softmax_rows_fwd(const float* x, int64_t ld_x, int64_t B, int32_t C, float* y, int64_t ld_y, dr_stream_t stream);
+int dr_softmax_rows_bwd(const float* y, int64_t ld_y, const float* dy, int64_t ld_dy, int64_t B, int32_t C, float* dx, int64_t ld_dx,
+                        dr_stream_t stream);
+int dr_cce_prob_rows(const float* p, int64_t ld_p, const float* labels, int64_t ld_labels, int64_t B, int32_t C,
+                     const float* sample_weight, float* row_loss, float* grad, int64_t ld_grad, dr_stream_t stream);
+
 /* dr_clock_stamp: dst[0] = the device's constant-rate wall clock (100 MHz ticks) when a one-thread kernel reaches the head of
  * `stream`.  Measurement plumbing with no reference counterpart: bench.py brackets the sharded step's cross-stream waits with two
  * stamps to report the EXPOSED part of the exchange (HIP timing events around a wait serialise the step). */
