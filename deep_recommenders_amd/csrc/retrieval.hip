@@ -630,9 +630,10 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_bwd_kernel(const float* _
 extern "C" int dr_softmax_ce_rows_bwd(const float* logits, const float* labels, int64_t B, int32_t C, float inv_temperature,
                                       const float* sample_weight, float d_loss, const int64_t* cols, float* out, int64_t ld_out,
                                       dr_stream_t stream) {
-    if (B <= 0 || C <= 0 || ld_out <= 0) return DR_EINVAL;
-    if (!logits || !labels || !out) return DR_EINVAL;
+    if (B < 0 || C <= 0 || ld_out <= 0) return DR_EINVAL;
     if (cols == nullptr && ld_out < C) return DR_EINVAL;
+    if (B == 0) return DR_OK;
+    if (!logits || !labels || !out) return DR_EINVAL;
     hipLaunchKernelGGL(softmax_ce_rows_bwd_kernel, dim3(dr_grid_for(B, 4)), dim3(256), 0, dr_s(stream), logits, labels, B, C,
                        inv_temperature, sample_weight, d_loss, cols, out, ld_out);
     DR_CHECK_LAUNCH();
@@ -641,8 +642,10 @@ extern "C" int dr_softmax_ce_rows_bwd(const float* logits, const float* labels, 
 
 extern "C" int dr_softmax_ce_rows(const float* logits, const float* labels, int64_t B, int32_t C, float inv_temperature,
                                   const float* sample_weight, float* row_loss, float* loss_out, dr_stream_t stream) {
-    if (B <= 0 || C <= 0) return DR_EINVAL;
-    if (!logits || !labels || !row_loss || !loss_out) return DR_EINVAL;
+    if (B < 0 || C <= 0 || !loss_out) return DR_EINVAL;
+    if (B == 0)                                              // the loss of no rows: 0 (nothing else is read or written)
+        return hipMemsetAsync(loss_out, 0, sizeof(float), dr_s(stream)) == hipSuccess ? DR_OK : DR_ELAUNCH;
+    if (!logits || !labels || !row_loss) return DR_EINVAL;
     hipLaunchKernelGGL(softmax_ce_rows_kernel, dim3(dr_grid_for(B, 4)), dim3(256), 0, dr_s(stream), logits, labels, B, C,
                        inv_temperature, sample_weight, row_loss);
     hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(256), 0, dr_s(stream), row_loss, B, loss_out);

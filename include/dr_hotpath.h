@@ -589,7 +589,8 @@ int dr_exclude_adjust(const float* scores, const int64_t* ids, int64_t B, int32_
 int dr_logits_adjust(const float* logits, const float* labels, int64_t B, int32_t C, const float* cand_prob,
                      const int64_t* cand_ids, float add_label_scale, float* out, dr_stream_t stream);
 /* CCE(from_logits=True, reduction=SUM) on an explicit [B, C] logits / labels pair (the hard-negative branch,
- * sbcnm.py:145-151): row_loss[B] scratch, loss_out[1] = sum_i w_i * (lse_i * sum_j y_ij - sum_j y_ij s_ij / T) */
+ * sbcnm.py:145-151): row_loss[B] scratch, loss_out[1] = sum_i w_i * (lse_i * sum_j y_ij - sum_j y_ij s_ij / T).
+ * B = 0 is an empty batch as for every other entry point: DR_OK, loss_out[0] = 0, nothing else touched (the backward: nothing written). */
 int dr_softmax_ce_rows(const float* logits, const float* labels, int64_t B, int32_t C, float inv_temperature,
                        const float* sample_weight, float* row_loss, float* loss_out, dr_stream_t stream);
 
