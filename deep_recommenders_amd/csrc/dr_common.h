@@ -28,6 +28,18 @@ __device__ __forceinline__ float dr_wave_sum(float v) {
     return v;
 }
 
+// lowbias32-style integer hash of (seed, index): well mixed, one multiply chain per element.  The dropout kernels (dr_dropout_fwd,
+// dr_attn_*, dr_token_embedding_*) keep an element iff dr_mix32(seed, index) >= dr_drop_thresh(rate).
+__host__ __device__ __forceinline__ uint32_t dr_mix32(uint64_t seed, uint64_t idx) {
+    uint64_t z = idx * 0x9E3779B97F4A7C15ull + seed;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return (uint32_t)((z ^ (z >> 31)) >> 32);
+}
+__host__ __device__ __forceinline__ uint32_t dr_drop_thresh(float rate) {
+    return (uint32_t)fminf(4294967040.f, rate * 4294967296.f);
+}
+
 // Binary cross-entropy terms of one example, logit x, label z (shared by the stand-alone loss kernel and the fused tower
 // head).  mode 0: [TF] sigmoid_cross_entropy_with_logits  max(x,0) - x z + log1p(exp(-|x|)) ; mode 1: tf.losses.log_loss
 // on p = sigmoid(x) (eps 1e-7) ; mode 2: keras binary_crossentropy (p clipped to [eps, 1-eps] first).  Outputs the

@@ -44,13 +44,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
     }
 }
 
-// lowbias32-style integer hash of (seed, index): well mixed, one multiply chain per element
-__device__ __forceinline__ uint32_t mix32(uint64_t seed, uint64_t idx) {
-    uint64_t z = idx * 0x9E3779B97F4A7C15ull + seed;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return (uint32_t)((z ^ (z >> 31)) >> 32);
-}
+// the counter hash is dr_mix32 (dr_common.h), shared with the attention and token-embedding kernels
 __global__ __launch_bounds__(256) void dropout_fwd_kernel(const float* __restrict__ x, int64_t ld_x, int64_t M, int32_t N,
                                                           float rate, uint64_t seed, float* __restrict__ y, int64_t ld_y,
                                                           uint8_t* __restrict__ mask) {
@@ -60,7 +54,7 @@ __global__ __launch_bounds__(256) void dropout_fwd_kernel(const float* __restric
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const int64_t r = i / N;
         const int64_t c = i - r * N;
-        const bool keep = mix32(seed, (uint64_t)i) >= thresh;
+        const bool keep = dr_mix32(seed, (uint64_t)i) >= thresh;
         mask[i] = keep ? 1 : 0;
         y[r * ld_y + c] = keep ? x[r * ld_x + c] * scale : 0.f;
     }

@@ -648,3 +648,124 @@ class _AddFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d):
         return d, d
+
+
+# --------------------------------------------------------------------------------------------------
+# Transformer package (keras/models/nlp of the reference) on csrc/attention.hip
+# --------------------------------------------------------------------------------------------------
+class _AttentionFn(torch.autograd.Function):
+    """ScaledDotProductAttention over the heads of projected [B, L, H * dh] tensors: dr_attn_fwd / dr_attn_bwd.  The dropout mask
+    is a function of (seed, b, h, query, key) and is regenerated in the backward; only (max, sum) per row is saved."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, key_mask, n_heads, future, rate, seed):
+        out, stats = ops.attn_fwd(q, k, v, n_heads, key_mask, future, rate, seed)
+        ctx.cfg = (n_heads, future, rate, seed)
+        ctx.key_mask = key_mask
+        ctx.save_for_backward(q, k, v, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        q, k, v, stats = ctx.saved_tensors
+        n_heads, future, rate, seed = ctx.cfg
+        dq, dk, dv = ops.attn_bwd(q, k, v, n_heads, d_out, stats, ctx.key_mask, future, rate, seed)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def attention(q, k, v, n_heads, key_mask=None, future=False, rate=0.0, seed=0):
+    """softmax(q k^T / sqrt(dh) + key_mask * (-2^32 + 1) [future: entries above the diagonal replaced]) -> dropout -> . v for every
+    head; q [B, Lq, H * dh], k, v [B, Lk, H * dh], key_mask [B, Lk] (True = padded)"""
+    return _AttentionFn.apply(q, k, v, key_mask, int(n_heads), bool(future), float(rate), int(seed))
+
+
+class _AddLayerNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, gamma, beta, eps):
+        shape = a.shape
+        a2 = a.reshape(-1, shape[-1])
+        b2 = b.reshape(-1, shape[-1]) if b is not None else None
+        y, stats = ops.add_layernorm_fwd(a2, b2, gamma, beta, eps)
+        ctx.has_b = b is not None
+        ctx.save_for_backward(a2, b2, gamma, stats)
+        return y.reshape(shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a2, b2, gamma, stats = ctx.saved_tensors
+        d_s, d_gamma, d_beta = ops.add_layernorm_bwd(a2, b2, gamma, stats, dy.reshape(a2.shape))
+        d_s = d_s.reshape(dy.shape)
+        return d_s, (d_s if ctx.has_b else None), d_gamma, d_beta, None
+
+
+def add_layer_norm(a, b, gamma, beta, eps=1e-8):
+    """LayerNormalization(a + b) over the last axis (b may be None): population variance, eps inside the root"""
+    return _AddLayerNormFn.apply(a, b, gamma, beta, float(eps))
+
+
+class _TokenEmbeddingFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, ids, pos, rate, seed):
+        ctx.cfg = (rate, seed)
+        ctx.save_for_backward(ids)
+        ctx.table_shape = table.shape
+        return ops.token_embedding_fwd(ids, table, pos, rate, seed)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        (ids,) = ctx.saved_tensors
+        rate, seed = ctx.cfg
+        d_table = torch.zeros(ctx.table_shape, dtype=torch.float32, device=d_out.device)
+        ops.token_embedding_bwd(ids, d_out, d_table, rate, seed)
+        return d_table, None, None, None, None
+
+
+def token_embedding(table, ids, pos=None, rate=0.0, seed=0):
+    """dropout(table[ids] * sqrt(D) + pos): ids [B, L] integer, pos the [L, D] position table or None; the table's gradient is
+    dense [V, D] and summed in a fixed order"""
+    return _TokenEmbeddingFn.apply(table, ids.to(torch.int64), pos, float(rate), int(seed))
+
+
+class _TiedProjectionFn(torch.autograd.Function):
+    """x @ table^T (the pre-softmax projection that shares the embedding matrix, transformer.py:264); the table's gradient
+    d_logits^T x goes through the deterministic split-K reduction"""
+
+    @staticmethod
+    def forward(ctx, x, table):
+        ctx.save_for_backward(x, table)
+        return ops.scores_nt(x, table)
+
+    @staticmethod
+    def backward(ctx, d):
+        x, table = ctx.saved_tensors
+        d = d if d.stride(1) == 1 else d.contiguous()
+        M, V = d.shape
+        D = table.shape[1]
+        dx = ops.linear_fwd(d, table) if ctx.needs_input_grad[0] else None
+        d_table = None
+        if ctx.needs_input_grad[1]:
+            d_table = torch.zeros_like(table)
+            ops.linear_bwd_dw(d, x, 1.0, d_table, None, workspace=ops.linear_bwd_dw_workspace(M, V, D, d.device))
+        return dx, d_table
+
+
+def tied_projection(x, table):
+    """x [M, D] @ table[V, D]^T -> [M, V]"""
+    return _TiedProjectionFn.apply(x, table)
+
+
+_POOL_CACHE = {}
+
+
+def global_average_pooling_1d(x):
+    """tf.keras.layers.GlobalAveragePooling1D: the mean over axis 1 of [B, L, C], as the CSR product with the [B, B * L] pooling
+    matrix (1 / L in every entry of a row's own L columns) -- dr_csr_spmm forward, its transpose backward, both in a fixed order"""
+    B, L, C = x.shape
+    key = (B, L, x.device)
+    if key not in _POOL_CACHE:
+        row_ptr = torch.arange(0, B + 1, dtype=torch.int64, device=x.device) * L
+        col = torch.arange(0, B * L, dtype=torch.int32, device=x.device)
+        val = torch.full((B * L,), 1.0 / L, dtype=torch.float32, device=x.device)
+        _POOL_CACHE.clear()
+        _POOL_CACHE[key] = SparseAdjacency._from_device(row_ptr, col, val, (B, B * L))
+    return aggregate(_POOL_CACHE[key], x.reshape(B * L, C))

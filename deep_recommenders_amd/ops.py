@@ -1777,3 +1777,140 @@ def cce_prob_rows(p, labels, sample_weight=None, want_grad=True):
     check(lib().dr_cce_prob_rows(ptr(p), p.stride(0), ptr(labels), labels.stride(0), B, C, ptr(sample_weight), ptr(row), ptr(grad),
                                  grad.stride(0) if grad is not None else 0, stream_ptr()), "dr_cce_prob_rows")
     return row, grad
+
+
+# ---- Transformer package (csrc/attention.hip) -----------------------------------------------------------------------------------------
+def _attn_view(t, what):
+    """[B, L, W] fp32 with unit column stride whose (b, l) rows are equally pitched: returns (tensor, B, L, W, pitch)"""
+    if t.dtype != torch.float32 or t.dim() != 3:
+        raise TypeError("%s must be a [B, L, H * dh] fp32 tensor" % what)
+    B, L, W = t.shape
+    if not (t.stride(2) == 1 and t.stride(1) >= W and t.stride(0) == L * t.stride(1)) and B * L > 0:
+        t = t.contiguous()
+    return t, B, L, W, (t.stride(1) if B * L > 0 else W)
+
+
+def _attn_mask(key_mask, B, Lk):
+    if key_mask is None:
+        return None
+    if key_mask.dtype == torch.bool:
+        key_mask = key_mask.view(torch.uint8) if key_mask.is_contiguous() else key_mask.contiguous().view(torch.uint8)
+    if key_mask.dtype != torch.uint8 or key_mask.shape != (B, Lk):
+        raise TypeError("key_mask must be a [B, Lk] bool / uint8 tensor (1 = padded)")
+    return key_mask.contiguous()
+
+
+def attn_fwd(q, k, v, n_heads, key_mask=None, future=False, rate=0.0, seed=0, out=None):
+    """(out [B, Lq, H * dh], stats [B * H * Lq, 2]) of dr_attn_fwd: softmax(q k^T / sqrt(dh) + mask) -> dropout -> . v per head, the
+    heads being column blocks of the projected tensors.  Refused arguments raise with the status code in the message."""
+    q, B, Lq, W, ld_q = _attn_view(q, "q")
+    k, Bk, Lk, Wk, ld_k = _attn_view(k, "k")
+    v, Bv, Lv, Wv, ld_v = _attn_view(v, "v")
+    H = int(n_heads)
+    if not (B == Bk == Bv and Lk == Lv and W == Wk == Wv and H > 0 and W % H == 0):
+        raise ValueError("attention shapes do not agree: q %s k %s v %s heads %d" % (tuple(q.shape), tuple(k.shape), tuple(v.shape), H))
+    key_mask = _attn_mask(key_mask, B, Lk)
+    if out is None:
+        out = torch.empty((B, Lq, _pad4(W)), dtype=torch.float32, device=q.device)[:, :, :W]
+    stats = torch.empty((B * H * Lq, 2), dtype=torch.float32, device=q.device)
+    check(lib().dr_attn_fwd(ptr(q), ld_q, ptr(k), ld_k, ptr(v), ld_v, ptr(key_mask), B, H, Lq, Lk, W // H, int(bool(future)),
+                            float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), out.stride(1), ptr(stats), stream_ptr()),
+          "dr_attn_fwd")
+    return out, stats
+
+
+def attn_bwd(q, k, v, n_heads, d_out, stats, key_mask=None, future=False, rate=0.0, seed=0):
+    """(dq, dk, dv) of dr_attn_bwd, in the layout of q, k, v (densely packed)"""
+    q, B, Lq, W, ld_q = _attn_view(q, "q")
+    k, _, Lk, _, ld_k = _attn_view(k, "k")
+    v, _, _, _, ld_v = _attn_view(v, "v")
+    d_out, _, _, _, ld_do = _attn_view(d_out, "d_out")
+    H = int(n_heads)
+    if d_out.shape != (B, Lq, W) or k.shape != (B, Lk, W) or v.shape != (B, Lk, W) or W % H:
+        raise ValueError("attention backward shapes do not agree")
+    key_mask = _attn_mask(key_mask, B, Lk)
+    dev = q.device
+    dq = torch.empty((B, Lq, _pad4(W)), dtype=torch.float32, device=dev)[:, :, :W]
+    dk = torch.empty((B, Lk, _pad4(W)), dtype=torch.float32, device=dev)[:, :, :W]
+    dv = torch.empty((B, Lk, _pad4(W)), dtype=torch.float32, device=dev)[:, :, :W]
+    delta = torch.empty(max(1, B * H * Lq), dtype=torch.float32, device=dev)
+    check(lib().dr_attn_bwd(ptr(q), ld_q, ptr(k), ld_k, ptr(v), ld_v, ptr(key_mask), ptr(d_out), ld_do, ptr(stats),
+                            B, H, Lq, Lk, W // H, int(bool(future)), float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(dq), dq.stride(1),
+                            ptr(dk), dk.stride(1), ptr(dv), dv.stride(1), ptr(delta), stream_ptr()), "dr_attn_bwd")
+    return dq, dk, dv
+
+
+def _rows_f32(t, what):
+    if t.dtype != torch.float32 or t.dim() != 2:
+        raise TypeError("%s must be a [M, D] fp32 tensor" % what)
+    return t if (t.stride(1) == 1 and t.stride(0) >= t.shape[1]) or t.shape[0] == 0 else t.contiguous()
+
+
+def add_layernorm_fwd(a, b, gamma, beta, eps=1e-8):
+    """(y, stats [M, 2]) with y = gamma * (s - mean) / sqrt(var + eps) + beta over the last axis, s = a + b (b may be None)"""
+    a = _rows_f32(a, "a")
+    M, D = a.shape
+    if b is not None:
+        b = _rows_f32(b, "b")
+        if b.shape != (M, D):
+            raise ValueError("add_layernorm: the addends differ in shape")
+    if gamma.shape != (D,) or beta.shape != (D,):
+        raise ValueError("add_layernorm: gamma / beta must be [D]")
+    y = torch.empty((M, D), dtype=torch.float32, device=a.device)
+    stats = torch.empty((M, 2), dtype=torch.float32, device=a.device)
+    check(lib().dr_add_layernorm_fwd(ptr(a), a.stride(0), ptr(b), b.stride(0) if b is not None else 0, ptr(_c(gamma, torch.float32)),
+                                     ptr(_c(beta, torch.float32)), M, D, float(eps), ptr(y), y.stride(0), ptr(stats), stream_ptr()),
+          "dr_add_layernorm_fwd")
+    return y, stats
+
+
+def add_layernorm_bwd(a, b, gamma, stats, dy):
+    """(d_s, d_gamma, d_beta); d_s is the gradient of both addends"""
+    a = _rows_f32(a, "a")
+    dy = _rows_f32(dy, "dy")
+    M, D = a.shape
+    if b is not None:
+        b = _rows_f32(b, "b")
+    dev = a.device
+    d_s = torch.empty((M, D), dtype=torch.float32, device=dev)
+    d_gamma = torch.empty(D, dtype=torch.float32, device=dev)
+    d_beta = torch.empty(D, dtype=torch.float32, device=dev)
+    nb = lib().dr_add_layernorm_bwd_workspace_bytes(M, D)
+    ws = torch.empty(max(1, nb // 4), dtype=torch.float32, device=dev)
+    check(lib().dr_add_layernorm_bwd(ptr(a), a.stride(0), ptr(b), b.stride(0) if b is not None else 0, ptr(_c(gamma, torch.float32)),
+                                     ptr(stats), ptr(dy), dy.stride(0), M, D, ptr(d_s), d_s.stride(0), ptr(d_gamma), ptr(d_beta), ptr(ws),
+                                     ws.numel() * 4, stream_ptr()), "dr_add_layernorm_bwd")
+    return d_s, d_gamma, d_beta
+
+
+def token_embedding_fwd(ids, table, pos=None, rate=0.0, seed=0):
+    """out [B, L, D] = dropout(table[ids] * sqrt(D) + pos[l]); ids [B, L] int64, pos [L, D] or None"""
+    if ids.dtype != torch.int64 or ids.dim() != 2:
+        raise TypeError("ids must be a [B, L] int64 tensor")
+    ids = ids.contiguous()
+    B, L = ids.shape
+    table = _c(table, torch.float32)
+    V, D = table.shape
+    if pos is not None:
+        pos = _c(pos, torch.float32)
+        if pos.shape != (L, D):
+            raise ValueError("the position table must be [L, D]")
+    out = torch.empty((B, L, D), dtype=torch.float32, device=table.device)
+    if B * L > 0:
+        check(lib().dr_token_embedding_fwd(ptr(ids), B * L, L, ptr(table), V, D, ptr(pos), float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           ptr(out), D, stream_ptr()), "dr_token_embedding_fwd")
+    return out
+
+
+def token_embedding_bwd(ids, d_out, d_table, rate=0.0, seed=0):
+    """d_table [V, D] += sqrt(D) * (the kept d_out rows / (1 - rate)) summed per id in ascending position order (deterministic)"""
+    B, L = ids.shape
+    V, D = d_table.shape
+    assert d_table.is_contiguous() and d_table.dtype == torch.float32
+    d_out = _c(d_out.reshape(B * L, D), torch.float32)
+    if B * L == 0:
+        return d_table
+    sorted_ids, order = torch.sort(ids.reshape(-1), stable=True)     # plumbing: the order of the row owners' sums
+    check(lib().dr_token_embedding_bwd(ptr(sorted_ids), ptr(order), B * L, V, D, ptr(d_out), d_out.stride(0), float(rate),
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(d_table), stream_ptr()), "dr_token_embedding_bwd")
+    return d_table

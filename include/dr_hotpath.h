@@ -963,6 +963,54 @@ int dr_softmax_rows_bwd(const float* y, int64_t ld_y, const float* dy, int64_t l
 int dr_cce_prob_rows(const float* p, int64_t ld_p, const float* labels, int64_t ld_labels, int64_t B, int32_t C,
                      const float* sample_weight, float* row_loss, float* grad, int64_t ld_grad, dr_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * Transformer package (keras/models/nlp/ of the reference), csrc/attention.hip.
+ *
+ *   dr_attn_fwd   ScaledDotProductAttention of every (batch, head) (multi_head_attention.py:60-86 inside :122-149).  q [B, Lq, H*dh],
+ *                 k, v [B, Lk, H*dh] fp32 with row pitches ld_* >= H*dh; head h is the column block [h*dh, (h+1)*dh) -- the
+ *                 reference's split / concat copies do not exist.  s = (q . k) / sqrt(dh); key_mask (may be NULL) [B, Lk] bytes,
+ *                 1 = padded: s += -2^32 (the fp32 value of -2^32 + 1; an fp32 add, so it saturates only for |s| < 128..256);
+ *                 future != 0 (needs Lq == Lk): entries with key > query are REPLACED by -2^32.  p = softmax_k(s) -- a row whose
+ *                 scores are all equal is uniform over all Lk keys.  Dropout: element (b, h, i, j) is kept iff
+ *                 dr_mix32(seed, ((b*H + h)*Lq + i)*Lk + j) >= (uint32)min(4294967040, rate * 2^32)   [always when rate == 0], with
+ *                   dr_mix32(seed, idx): z = idx * 0x9E3779B97F4A7C15 + seed; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                                        z = (z ^ z >> 27) * 0x94D049BB133111EB; return (z ^ z >> 31) >> 32      (64-bit wrap-around)
+ *                 and kept probabilities are scaled by 1 / (1 - rate).  out [B, Lq, H*dh] = p_dropped . v.
+ *                 stats [B*H*Lq, 2] = (row maximum, sum of exp(s - maximum)) for the backward.  1 <= dh <= 128, any Lq, Lk >= 1.
+ *                 Products are fp32-input MFMA (exact fp32 products).  DR_ESHAPE: dh > 128, future with Lq != Lk; DR_EINVAL: rate
+ *                 outside [0, 1), a pitch below H*dh, a NULL tensor.
+ *   dr_attn_bwd   dq, dk, dv (same strided layout) from d_out; p is recomputed from q, k and stats, the dropout mask from the hash.
+ *                 The gradient passes through the additive padding mask and stops at entries the future mask replaced.
+ *                 delta: workspace of B*H*Lq floats (sum_j p_ij dp_ij, summed from the recomputed p and dp in a pass of its own).
+ *                 Bit-reproducible: no atomics, no inter-block waits.
+ *   dr_add_layernorm_fwd / _bwd   y = gamma * (s - mean) / sqrt(var + eps) + beta over the last axis, s = a + b (b may be NULL),
+ *                 population variance (transformer.py:109-113 after the residual adds of :212-219).  stats [M, 2] = (mean,
+ *                 1 / sqrt(var + eps)).  The backward writes d_s (the gradient of both addends), d_gamma and d_beta (overwritten;
+ *                 fixed-order column reduction through a workspace of dr_add_layernorm_bwd_workspace_bytes(M, D) bytes).
+ *   dr_token_embedding_fwd   out[n, :] = dropout(table[ids[n], :] * sqrt(D) + pos[n % L, :]) for n < N = B*L (transformer.py:195-204);
+ *                 pos [L, D] may be NULL; dropout as above on the element index n*D + c.  An id outside [0, V) reads as a zero row.
+ *   dr_token_embedding_bwd   d_table[v, :] += sqrt(D) * sum over the positions n with ids[n] == v, ascending, of the kept
+ *                 d_out[n, :] / (1 - rate).  sorted_ids / order: the ids sorted ascending by a STABLE sort and the permutation that
+ *                 sorts them (int64 [N]); every table row has one owner block: a fixed order, no atomics.
+ * ---------------------------------------------------------------------------------------- */
+int dr_attn_fwd(const float* q, int64_t ld_q, const float* k, int64_t ld_k, const float* v, int64_t ld_v, const uint8_t* key_mask,
+                int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t dh, int32_t future, float rate, uint64_t seed, float* out,
+                int64_t ld_o, float* stats, dr_stream_t stream);
+int dr_attn_bwd(const float* q, int64_t ld_q, const float* k, int64_t ld_k, const float* v, int64_t ld_v, const uint8_t* key_mask,
+                const float* d_out, int64_t ld_do, const float* stats, int32_t B, int32_t H,
+                int32_t Lq, int32_t Lk, int32_t dh, int32_t future, float rate, uint64_t seed, float* dq, int64_t ld_dq,
+                float* dk, int64_t ld_dk, float* dv, int64_t ld_dv, float* delta, dr_stream_t stream);
+int dr_add_layernorm_fwd(const float* a, int64_t ld_a, const float* b, int64_t ld_b, const float* gamma, const float* beta,
+                         int64_t M, int32_t D, float eps, float* y, int64_t ld_y, float* stats, dr_stream_t stream);
+int64_t dr_add_layernorm_bwd_workspace_bytes(int64_t M, int32_t D);
+int dr_add_layernorm_bwd(const float* a, int64_t ld_a, const float* b, int64_t ld_b, const float* gamma, const float* stats,
+                         const float* dy, int64_t ld_dy, int64_t M, int32_t D, float* d_s, int64_t ld_ds, float* d_gamma,
+                         float* d_beta, float* workspace, int64_t workspace_bytes, dr_stream_t stream);
+int dr_token_embedding_fwd(const int64_t* ids, int64_t N, int32_t L, const float* table, int64_t V, int32_t D, const float* pos,
+                           float rate, uint64_t seed, float* out, int64_t ld_out, dr_stream_t stream);
+int dr_token_embedding_bwd(const int64_t* sorted_ids, const int64_t* order, int64_t N, int64_t V, int32_t D, const float* d_out,
+                           int64_t ld_do, float rate, uint64_t seed, float* d_table, dr_stream_t stream);
+
 /* dr_clock_stamp: dst[0] = the device's constant-rate wall clock (100 MHz ticks) when a one-thread kernel reaches the head of
  * `stream`.  Measurement plumbing with no reference counterpart: bench.py brackets the sharded step's cross-stream waits with two
  * stamps to report the EXPOSED part of the exchange (HIP timing events around a wait serialise the step). */
