@@ -63,20 +63,6 @@ __device__ __forceinline__ void lds_dma16(const void* src, unsigned char* dst) {
     __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)dst, 16, 0, 0);
 }
 
-// the six products of one (A-fragment, B-fragment) pair, smallest terms first; the four accumulators of a wave are
-// interleaved so that back-to-back MFMAs are independent
-template <int TM, int TN>
-__device__ __forceinline__ void mma6(const bf16x8 (&af)[3][TM], const bf16x8 (&bf)[3][TN], f32x16 (&acc)[TM][TN]) {
-    constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};
-#pragma unroll
-    for (int term = 0; term < 6; ++term)
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int b = 0; b < TN; ++b)
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[term]][a], bf[PB[term]][b], acc[a][b], 0, 0, 0);
-}
-
 // =====================================================================================================================
 // NT:  C[m][n] = epilogue( sum_k A[m][k] B[n][k] )
 // =====================================================================================================================
@@ -89,172 +75,11 @@ struct NtArgs {
     const float* mask; int64_t ld_mask;          // optional: C = 0 where mask[m][n] <= 0   (ReLU' of the layer below)
 };
 
-// DBG (tools/exp/bf3_ablate.hip only; 0 in the library): 1 = no LDS-DMA after the first k-tile, 2 = no MFMAs,
-// 4 = LDS-DMA re-reads the first k-tile (cache hits)
-template <int WM, int WN, int DBG = 0>
-__global__ __launch_bounds__(NTHREADS, 2) void bf3_gemm_nt_kernel(NtArgs g) {
-    constexpr int BM = 64 * WM, BN = 64 * WN;
-    constexpr int A_PLANE = BM * 64, B_PLANE = BN * 64;                 // bytes: rows x 64-byte rows
-    constexpr int STAGE = 3 * (A_PLANE + B_PLANE);
-    constexpr int NKB = STAGE / 1024, KB_A = 3 * A_PLANE / 1024, PER_WAVE = NKB / NWAVES;
-    static_assert(WM * WN == NWAVES && NKB % NWAVES == 0, "tile / wave layout");
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int l31 = lane & 31, hi = lane >> 5;
-
-    const int tiles_n = (g.N + BN - 1) / BN;
-    const int tiles_m = (int)((g.M + BM - 1) / BM);
-    const int ntiles = tiles_m * tiles_n;
-    const int nk = g.K / BK;
-
-    // fragment read offsets (bytes within a stage): row = 64 wm + 32 t + l31, logical chunk = 2 ks + hi
-    const int sw = (l31 >> 2) & 3;
-    const int a_off = (wm * 64 + l31) * 64 + ((hi ^ sw) << 4);
-    const int b_off = 3 * A_PLANE + (wn * 64 + l31) * 64 + ((hi ^ sw) << 4);
-
-    const __bf16* src[PER_WAVE];
-    int64_t m0 = 0;
-    int n0 = 0;
-    auto setup = [&](int tile) {
-        const int lid = xcd_remap(tile, ntiles);
-        m0 = (int64_t)(lid / tiles_n) * BM;
-        n0 = (lid % tiles_n) * BN;
-#pragma unroll
-        for (int i = 0; i < PER_WAVE; ++i) {
-            const int j = wave + NWAVES * i;                            // 1-KB piece of the stage (wave-uniform)
-            const bool is_a = j < KB_A;
-            const int jj = is_a ? j : j - KB_A;
-            const int rows16 = is_a ? BM / 16 : BN / 16;
-            const int plane = jj / rows16, rb = jj % rows16;
-            const int row = rb * 16 + (lane >> 2);
-            const int c = (lane & 3) ^ ((row >> 2) & 3);
-            int64_t grow = (is_a ? m0 : (int64_t)n0) + row;
-            const int64_t lim = is_a ? g.M : (int64_t)g.N;
-            grow = grow < lim ? grow : lim - 1;                         // rows past the edge only feed unstored outputs
-            src[i] = is_a ? g.A + plane * g.a_ps + grow * g.a_ld + c * 8 : g.B + plane * g.b_ps + grow * g.b_ld + c * 8;
-        }
-    };
-    auto issue = [&](int stage) {
-#pragma unroll
-        for (int i = 0; i < PER_WAVE; ++i) {
-            unsigned char* dst = smem + stage * STAGE + (wave + NWAVES * i) * 1024;
-            lds_dma16(src[i], dst);
-            if constexpr (!(DBG & 4)) src[i] += BK;
-        }
-    };
-
-    f32x16 acc[2][2];
-    // One k-tile: all 24 fragment reads are issued up front (the first k-step's MFMAs start as soon as its 12 have landed, the
-    // second k-step's land under them), and the next k-tile's LDS-DMA pieces are issued one at a time BETWEEN MFMAs of the
-    // first k-step, where the ~60-cycle issue cost of a piece sits in the shadow of the matrix pipe instead of in front of it
-    // (issued as a block after the barrier, the 9 pieces kept both waves of a SIMD off the pipe for ~1300 cycles per k-tile).
-    auto compute = [&](int stage, bool prefetch) {
-        // offsets into the __shared__ array itself (not generic pointers: an XOR on a generic pointer makes hipcc emit
-        // flat_load, which also drags the LDS-DMA's vmcnt into every fragment wait)
-        const int sa = stage * STAGE + a_off, sb = stage * STAGE + b_off;
-        bf16x8 af[2][3][2], bf[2][3][2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    af[ks][p][t] = *reinterpret_cast<const bf16x8*>(&smem[(sa ^ (ks * 32)) + p * A_PLANE + t * 32 * 64]);
-                    bf[ks][p][t] = *reinterpret_cast<const bf16x8*>(&smem[(sb ^ (ks * 32)) + p * B_PLANE + t * 32 * 64]);
-                }
-        constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};
-        unsigned char* const dma_dst = smem + (stage ^ 1) * STAGE + wave * 1024;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int term = 0; term < 6; ++term) {
-                if constexpr (DBG & 2) {
-                    acc[0][0][term] += (float)af[ks][PA[term]][0][0] + (float)af[ks][PA[term]][1][0];
-                    acc[0][1][term] += (float)bf[ks][PB[term]][0][0] + (float)bf[ks][PB[term]][1][0];
-                } else {
-#pragma unroll
-                    for (int a = 0; a < 2; ++a)
-#pragma unroll
-                        for (int b = 0; b < 2; ++b)
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks][PA[term]][a], bf[ks][PB[term]][b], acc[a][b], 0, 0, 0);
-                }
-                if constexpr (!(DBG & 1)) {
-                    // pieces 0..8 of the next k-tile after MFMA groups 0..8 (of 12): every piece has at least a quarter of a
-                    // k-tile of matrix-pipe time to land before the barrier that publishes it
-                    const int piece = ks * 6 + term;
-                    if (piece < PER_WAVE) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (prefetch) {
-                            lds_dma16(src[piece], dma_dst + NWAVES * piece * 1024);
-                            if constexpr (!(DBG & 4)) src[piece] += BK;
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            }
-    };
-
-    int tile = blockIdx.x;
-    if (tile >= ntiles) return;
-    int buf = 0;
-    setup(tile);
-    issue(buf);
-    for (;;) {
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int k = 0; k < 16; ++k) acc[a][b][k] = 0.f;
-        const int64_t tm0 = m0;
-        const int tn0 = n0;
-        for (int kt = 0; kt < nk; ++kt) {
-            __syncthreads();              // this stage's DMA has landed (vmcnt(0) per wave, then the barrier); all waves are
-                                          // done reading the other stage
-            compute(buf, kt + 1 < nk);
-            buf ^= 1;
-        }
-        // every wave is past the last barrier, i.e. done with stage `buf` (read in iteration nk - 2): the next tile's first
-        // k-tile streams into it under this tile's epilogue
-        const int next = tile + gridDim.x;
-        if (next < ntiles) {
-            setup(next);
-            issue(buf);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) {
-                const int col = tn0 + wn * 64 + ni * 32 + l31;
-                const bool cv = col < g.N;
-                const int colc = cv ? col : g.N - 1;
-                const float bj = g.bias != nullptr ? g.bias[colc] : 0.f;
-                const int64_t row_b = tm0 + wm * 64 + mi * 32 + 4 * hi;
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int64_t row = row_b + (reg & 3) + 8 * (reg >> 2);
-                    if (!cv || row >= g.M) continue;
-                    float v = acc[mi][ni][reg] + bj;
-                    if (g.act == 1) v = fmaxf(v, 0.f);
-                    if (g.mask != nullptr && !(g.mask[row * g.ld_mask + col] > 0.f)) v = 0.f;
-                    g.C[row * g.ldc + col] = v;
-                }
-            }
-        if (next >= ntiles) break;
-        tile = next;
-    }
-}
-
 // =====================================================================================================================
 // NT, three-stage pipeline ("pipe"): the same product on 128 x 128 x 32 tiles with THREE LDS stages, so that the HBM stream
 // of the big operand runs one to two k-tiles ahead of the matrix pipe instead of in lock step with it.
 //
-// What the two-stage kernel above measured (tools/exp/bf3_ablate.hip, M = 65536, K = 1696, N = 256): 369 us, of which the
+// What the two-stage 128 x 256 kernel this one replaced measured (M = 65536, K = 1696, N = 256): 369 us, of which the
 // pieces -- A stream from HBM 132 us (667 MB at 5.05 TB/s), B tiles from L2 75 us, barrier + fragment reads 106 us, MFMAs
 // ~165 us at the clock the chip holds -- run essentially back to back: with two 72 KB stages a k-tile's LDS-DMA is issued one
 // k-tile before the barrier that needs it, every wave waits vmcnt(0) there, and the two waves of a SIMD read fragments and
@@ -276,9 +101,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void bf3_gemm_nt_kernel(NtArgs g) {
 // =====================================================================================================================
 #define BF3_DS_READ_B128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 
-// NW = 8 (2 x 4 waves of 64 x 32 outputs) or 16 (4 x 4 waves of 32 x 32, four per SIMD): an LDS-DMA piece costs its wave
-// 100 - 350 cycles of issue time (address coalescer queue), during which only OTHER waves of the SIMD can feed the matrix
-// pipe -- with two waves per SIMD the pipe idles about half of the time, with four the stalls overlap.
+// NW = 8 (2 x 4 waves of 64 x 32 outputs) or 16 (4 x 4 waves of 32 x 32, four per SIMD; the library launches only this one): an
+// LDS-DMA piece costs its wave 100 - 350 cycles of issue time (address coalescer queue), during which only OTHER waves of the SIMD
+// can feed the matrix pipe -- with two waves per SIMD the pipe idles about half of the time, with four the stalls overlap.
+// DBG (tools/exp/bf3_ablate.hip only; 0 in the library): 1 = no LDS-DMA after the first k-tile, 2 = no MFMAs,
+// 4 = LDS-DMA re-reads the first k-tile (cache hits)
 template <int NW, int DBG = 0>
 __global__ __launch_bounds__(64 * NW, NW / 4) void bf3_gemm_nt_pipe_kernel(NtArgs g) {
     constexpr int BM = 128, BN = 128, NS = 3;
@@ -577,19 +404,8 @@ __global__ __launch_bounds__(512 * CS / MS, MS == CS ? 2 : 1) void bf3_gemm_rs_k
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    // STG (DBG bit 16): STAGGERED wave groups.  Waves w and w + 4 share a SIMD; with one barrier per k-tile they run in phase, so the
-    // non-MFMA part of a step (waiting for and splitting the activation registers, issuing the next loads: ~1.5 us of a 5.1 us
-    // step) is paid by both at the same time with the matrix pipe idle.  Here waves 4..7 lag waves 0..3 by 6 of the 16 MFMA groups
-    // (one extra barrier before their first step, one extra for waves 0..3 after their last; a second barrier per step at group
-    // 6): while one group splits, the other multiplies.  The three-stage ring still suffices: stage s % 3 is refilled for step
-    // s + 3 only after the barrier at which the lagging group ends step s, which is the leading group's mid barrier of step s + 1
-    // -- so every wave issues its pieces in groups 6..11, behind its own mid barrier -- and a wave has its pieces of step t + 1
-    // landed before its mid barrier of step t (vmcnt(4): only this step's 4 activation loads are younger), which is the barrier
-    // in front of the leading group's first read of that stage.  Bit-identical results; no gain measured (see rs_launch).
-    constexpr bool STG = (DBG & 16) != 0 && MS == 1;
     const int rgi = CS == 1 ? wave : (wave & (RGW - 1));               // row group / column half of this wave
     const int chi = CS == 1 ? 0 : (wave / RGW);
-    const int grp = STG ? (wave >> 2) : 0;
 
     const int tiles_n = (g.N + BN - 1) / BN;
     const int tiles_m = (int)((g.M + BM - 1) / BM);
@@ -786,7 +602,6 @@ __global__ __launch_bounds__(512 * CS / MS, MS == CS ? 2 : 1) void bf3_gemm_rs_k
     if (total > 1) advance_b();
     __builtin_amdgcn_s_waitcnt(VM_WAIT_STEP);                           // vmcnt(4 MS + PW): step 0's pieces landed
     asm volatile("s_barrier" ::: "memory");
-    if (STG && grp) asm volatile("s_barrier" ::: "memory");             // the lagging group starts at the leading group's first mid barrier
     read_b(0, 0, 0);
     if constexpr (CS == 1) read_b(1, 0, 1);
 
@@ -866,10 +681,6 @@ __global__ __launch_bounds__(512 * CS / MS, MS == CS ? 2 : 1) void bf3_gemm_rs_k
         } else {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            if (STG && q == 6) {
-                __builtin_amdgcn_s_waitcnt(0x0F70 | 4);                // vmcnt(4): the pieces of step + 1 (issued a step ago) landed
-                asm volatile("s_barrier" ::: "memory");
-            }
             if (q < 14) {
                 wait_b(q & 3, false);
                 read_b((q + 2) & 3, stage, q + 2);
@@ -905,8 +716,8 @@ __global__ __launch_bounds__(512 * CS / MS, MS == CS ? 2 : 1) void bf3_gemm_rs_k
                 acc[0][q & 7][0] += (float)fa[0][q >> 3][0][0] + (float)fb[q & 3][0][0] + (float)fb[q & 3][1][0] + (H2 ? 0.f : (float)fb[q & 3][2][0]);
             }
             __builtin_amdgcn_sched_barrier(0);    // keeps the next group's lgkmcnt wait from being hoisted between these MFMAs
-            if (STG ? (q >= 6 && q < 6 + PW) : (MS == 2 ? q < PW : ((q & 1) == 1 && q < 2 * PW))) {
-                if constexpr (!(DBG & 1)) issue_b(STG ? q - 6 : (MS == 2 ? q : q >> 1));
+            if (MS == 2 ? q < PW : ((q & 1) == 1 && q < 2 * PW)) {
+                if constexpr (!(DBG & 1)) issue_b(MS == 2 ? q : q >> 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -1289,7 +1100,6 @@ __global__ __launch_bounds__(512 * CS / MS, MS == CS ? 2 : 1) void bf3_gemm_rs_k
             __builtin_amdgcn_s_waitcnt(0x0F70);
         }
     }
-    if (STG && !grp) asm volatile("s_barrier" ::: "memory");            // the leading group's extra barrier (see STG above)
     if constexpr (H2 && EPI != 4) {
         if (g.c_amax != nullptr) {                                      // (kernel-uniform) one load per wave, an atomic only if it raises the record
             uint32_t m = __float_as_uint(cmax);
@@ -2454,10 +2264,6 @@ int rs_launch(const RsArgs& g, hipStream_t stream) {
     const int64_t tiles = ((g.M + 255) / 256) * ((g.N + 255) / 256);
     if (tiles > 0x7fffffff) return DR_EINVAL;
     const int grid = (int)(tiles < 256 ? tiles : 256);                  // persistent: one block per CU
-    // staggered wave groups (see STG in bf3_gemm_rs_kernel): measured neutral to slightly negative (DeepFM step 1.628 vs 1.605 ms, DCN
-    // 26.93 vs 26.67 ms, same box, alternating) -- the kernel sits at the clock the power budget allows, keeping the pipe busier
-    // buys nothing -- so it is opt-in (DR_BF3_STAGGER=1)
-    static const bool stg = [] { const char* e = getenv("DR_BF3_STAGGER"); return e != nullptr && e[0] == '1'; }();
     if (g.mask != nullptr && g.accumulate) return DR_EINVAL;            // (no caller needs both)
     // the kernels address B's planes through ONE buffer resource with 32-bit offsets: planes further apart than that would be clamped
     // away and read as zeros without any error -- refuse instead
@@ -2480,10 +2286,9 @@ int rs_launch(const RsArgs& g, hipStream_t stream) {
         }
         if (g.tau != nullptr) {
             // the scan's reduction is short (K = the embedding width): resident activations (AR, see the kernel) when K is 128 or 64
-            // and the row tiles divide into the grid; DR_TOPK_RESIDENT=0: the streaming kernel (A/B, tools/exp/topk_xlane.sh)
-            static const bool resident = [] { const char* e = getenv("DR_TOPK_RESIDENT"); return e == nullptr || e[0] != '0'; }();
+            // and the row tiles divide into the grid; the streaming kernel otherwise
             const int tiles_m = (int)((g.M + 255) / 256);
-            if (resident && (g.K == 128 || g.K == 64) && tiles_m <= 256) {
+            if ((g.K == 128 || g.K == 64) && tiles_m <= 256) {
                 const int ar_grid = 256 / tiles_m * tiles_m;
                 if (g.K == 128) hipLaunchKernelGGL((bf3_gemm_rs_kernel<4, 0, 1, 1, 1, 4>), dim3(ar_grid), dim3(512), 0, stream, g);
                 else hipLaunchKernelGGL((bf3_gemm_rs_kernel<4, 0, 1, 1, 1, 2>), dim3(ar_grid), dim3(512), 0, stream, g);
@@ -2499,8 +2304,13 @@ int rs_launch(const RsArgs& g, hipStream_t stream) {
             DR_CHECK_LAUNCH();
             return DR_OK;
         }
-        {   // round 6: the 16-wave form (h2_occ.hip) for the plain epilogues; DR_H2_OCC=0 keeps the 8-wave kernel (A/B)
+        {   // round 6: the 16-wave form (h2_occ.hip) for the plain epilogues; the 8-wave kernel below takes what it declines
+#ifdef DR_OCC_ABLATE
+            // tools/exp/occ_bench.py, occ_ablate.py, fused_k4_bench.py: DR_H2_OCC=0 keeps the 8-wave kernel (A/B)
             static const bool occ = [] { const char* e = getenv("DR_H2_OCC"); return e == nullptr || e[0] != '0'; }();
+#else
+            constexpr bool occ = true;
+#endif
             if (occ) {
                 const int rc = occ_nt_launch(g, stream);
                 if (rc != 1) return rc;
@@ -2523,8 +2333,8 @@ int rs_launch(const RsArgs& g, hipStream_t stream) {
                 // 34 = no MFMA + no fragment reads, 3 = no MFMA + no weight DMA, 10 = no MFMA + A from cache, 98 = no MFMA + no reads + no split,
                 // 35 = no MFMA + no reads + no DMA, 43 = that + A from cache (what is left: the loop, the barrier, the epilogue stores)
                 RS_ABL2(34) RS_ABL2(3) RS_ABL2(10) RS_ABL2(98) RS_ABL2(35) RS_ABL2(43)
-                // round 5: WITH the MFMAs -- 8 = A from cache (its loads re-read k-tile 0), 4 = B always k-tile 0, 12 = both, 9 = no weight DMA + A from cache, 16 = staggered wave groups
-                RS_ABL2(8) RS_ABL2(4) RS_ABL2(12) RS_ABL2(9) RS_ABL2(16)
+                // round 5: WITH the MFMAs -- 8 = A from cache (its loads re-read k-tile 0), 4 = B always k-tile 0, 12 = both, 9 = no weight DMA + A from cache
+                RS_ABL2(8) RS_ABL2(4) RS_ABL2(12) RS_ABL2(9)
                 // 512 = no per-step barrier; 544 = that + no fragment reads; 521 = that + A from cache + no weight DMA
                 RS_ABL2(512) RS_ABL2(544) RS_ABL2(521)
 #undef RS_ABL2
@@ -2581,17 +2391,10 @@ int rs_launch(const RsArgs& g, hipStream_t stream) {
         DR_CHECK_LAUNCH();
         return DR_OK;
     }
-    if (stg) {
-        if (g.x0 != nullptr) hipLaunchKernelGGL((bf3_gemm_rs_kernel<2, 16>), dim3(grid), dim3(512), 0, stream, g);
-        else if (g.mask != nullptr) hipLaunchKernelGGL((bf3_gemm_rs_kernel<1, 16>), dim3(grid), dim3(512), 0, stream, g);
-        else if (g.accumulate) hipLaunchKernelGGL((bf3_gemm_rs_kernel<3, 16>), dim3(grid), dim3(512), 0, stream, g);
-        else hipLaunchKernelGGL((bf3_gemm_rs_kernel<0, 16>), dim3(grid), dim3(512), 0, stream, g);
-    } else {
-        if (g.x0 != nullptr) hipLaunchKernelGGL((bf3_gemm_rs_kernel<2>), dim3(grid), dim3(512), 0, stream, g);
-        else if (g.mask != nullptr) hipLaunchKernelGGL((bf3_gemm_rs_kernel<1>), dim3(grid), dim3(512), 0, stream, g);
-        else if (g.accumulate) hipLaunchKernelGGL((bf3_gemm_rs_kernel<3>), dim3(grid), dim3(512), 0, stream, g);
-        else hipLaunchKernelGGL((bf3_gemm_rs_kernel<0>), dim3(grid), dim3(512), 0, stream, g);
-    }
+    if (g.x0 != nullptr) hipLaunchKernelGGL((bf3_gemm_rs_kernel<2>), dim3(grid), dim3(512), 0, stream, g);
+    else if (g.mask != nullptr) hipLaunchKernelGGL((bf3_gemm_rs_kernel<1>), dim3(grid), dim3(512), 0, stream, g);
+    else if (g.accumulate) hipLaunchKernelGGL((bf3_gemm_rs_kernel<3>), dim3(grid), dim3(512), 0, stream, g);
+    else hipLaunchKernelGGL((bf3_gemm_rs_kernel<0>), dim3(grid), dim3(512), 0, stream, g);
     DR_CHECK_LAUNCH();
     return DR_OK;
 }
@@ -2649,23 +2452,11 @@ extern "C" int dr_bf3_gemm_nt(const void* a_planes, int64_t a_plane_stride, int6
     if (a_ld < K || b_ld < K || ldc < N || (mask != nullptr && ld_mask < N)) return DR_EINVAL;
     NtArgs g{static_cast<const __bf16*>(a_planes), a_plane_stride, a_ld, static_cast<const __bf16*>(b_planes), b_plane_stride, b_ld,
              M, N, K, C, ldc, bias, act, mask, ld_mask};
-    static const bool pipe = [] { const char* e = getenv("DR_BF3_PIPE"); return e == nullptr || e[0] != '0'; }();
-    if (pipe) {
-        // three-stage 128 x 128 x 32 pipeline; consecutive tiles share an A row-panel (same XCD, L2)
-        const int64_t tiles = ((M + 127) / 128) * ((N + 127) / 128);
-        if (tiles > 0x7fffffff) return DR_EINVAL;
-        const int grid = (int)(tiles < 256 ? tiles : 256);              // persistent: one block per CU
-        static const bool w16 = [] { const char* e = getenv("DR_BF3_WAVES"); return e == nullptr || atoi(e) != 8; }();
-        if (w16) hipLaunchKernelGGL((bf3_gemm_nt_pipe_kernel<16>), dim3(grid), dim3(1024), 0, dr_s(stream), g);
-        else hipLaunchKernelGGL((bf3_gemm_nt_pipe_kernel<8>), dim3(grid), dim3(512), 0, dr_s(stream), g);
-        DR_CHECK_LAUNCH();
-        return DR_OK;
-    }
-    // DR_BF3_PIPE=0: the two-stage 128 x 256 kernel (A/B reference)
-    const int64_t tiles = ((M + 127) / 128) * ((N + 255) / 256);
+    // three-stage 128 x 128 x 32 pipeline, 16 waves; consecutive tiles share an A row-panel (same XCD, L2)
+    const int64_t tiles = ((M + 127) / 128) * ((N + 127) / 128);
     if (tiles > 0x7fffffff) return DR_EINVAL;
     const int grid = (int)(tiles < 256 ? tiles : 256);                  // persistent: one block per CU
-    hipLaunchKernelGGL((bf3_gemm_nt_kernel<2, 4>), dim3(grid), dim3(NTHREADS), 0, dr_s(stream), g);
+    hipLaunchKernelGGL((bf3_gemm_nt_pipe_kernel<16>), dim3(grid), dim3(1024), 0, dr_s(stream), g);
     DR_CHECK_LAUNCH();
     return DR_OK;
 }

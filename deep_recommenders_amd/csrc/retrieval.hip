@@ -9,7 +9,6 @@
 // (2 entries per lane, k <= 128).  Only elements strictly greater than the current k-th score enter the list
 // (expected k*ln(N/k) insertions per row over the whole corpus), insertion = one rank count (wave sum) + a
 // lane shift (__shfl_up).  Ties resolve to the lower candidate index, as tf.math.top_k does.
-#include <cstdlib>
 #include "dr_common.h"
 #include "topk_list.h"
 #include <math.h>
@@ -255,13 +254,9 @@ static int64_t topk_hdr_bytes(int64_t Bq) { return (Bq * 8 + 8 + 255) / 256 * 25
 
 // corpus chunk of the scan: ~256 MB of [Bq, chunk] scores (1024 output tiles of the register-split GEMM at Bq = 8192: 4 per CU)
 constexpr int64_t TOPK_MAX_COLS = 32768;      // longest dense first chunk (the filtered chunks: TOPK_MAX_SCAN)
-static int64_t topk_env(const char* name, int64_t dflt) {
-    const char* e = getenv(name);
-    return e != nullptr && e[0] != 0 ? atoll(e) : dflt;
-}
+constexpr int64_t TOPK_FIRST_BYTES = (int64_t)256 << 20;
 static int64_t topk_chunk_for(int64_t Bq, int64_t N) {
-    static const int64_t first_bytes = topk_env("DR_TOPK_FIRST_MB", 256) << 20;     // (experiment knob)
-    int64_t chunk = first_bytes / (Bq > 0 ? Bq * 4 : 4);
+    int64_t chunk = TOPK_FIRST_BYTES / (Bq > 0 ? Bq * 4 : 4);
     chunk = chunk / 256 * 256;
     if (chunk < 256) chunk = 256;
     // bounded in COLUMNS too, whatever Bq: a small query batch over a large corpus (serving) used to get a chunk of 256 MB / (4 Bq)
@@ -289,9 +284,8 @@ constexpr int64_t TOPK_MAX_SCAN = 65536;
 static int64_t topk_scan_for(int64_t chunk, int64_t N) {
     if (N <= chunk) return chunk;
     int64_t rest = (N - chunk + 255) / 256 * 256;
-    static const int64_t scan_cols = topk_env("DR_TOPK_SCAN_COLS", 0);              // (experiment knob) 0: TOPK_SCAN_MULT x chunk
-    int64_t scan = scan_cols > 0 ? (scan_cols + 255) / 256 * 256 : chunk * TOPK_SCAN_MULT;
-    if (scan > TOPK_MAX_SCAN && scan_cols <= 0) scan = TOPK_MAX_SCAN;
+    int64_t scan = chunk * TOPK_SCAN_MULT;
+    if (scan > TOPK_MAX_SCAN) scan = TOPK_MAX_SCAN;
     if (scan > rest) scan = rest;
     return scan < chunk ? chunk : scan;
 }

@@ -33,7 +33,6 @@ class DCNDense:
     from one dr_h2_amax pass, every later one from the epilogue of the kernel that produces it -- or "bf16x3")."""
 
     def __init__(self, cross_W, cross_b, Ws, bs, batch, in_dim, ld, diag_scale, device, grads=None, k=None):
-        import os as _os
         self.cross_W, self.cross_b, self.Ws, self.bs = list(cross_W), list(cross_b), list(Ws), list(bs)
         self.B, self.in_dim, self.ld, self.diag = batch, in_dim, ld, diag_scale
         self.grads = grads
@@ -42,13 +41,12 @@ class DCNDense:
         units = [W.shape[1] for W in self.Ws]
         self.acts = [1] * (len(units) - 1) + [0]
         f32 = dict(dtype=torch.float32, device=device)
-        on = _os.environ.get("DR_PLANES", "1") == "1"
-        wide_cross = on and ops.planes_worthwhile(B, in_dim, in_dim)
+        wide_cross = ops.planes_worthwhile(B, in_dim, in_dim)
         self.h2 = wide_cross and ops.get_gemm_split() == "f16x2"
         self.h2_all_wide = self.h2                               # (bench.py: every planes GEMM of this engine is priced as f16x2)
         WP = ops.H2WeightPlanes if self.h2 else ops.WeightPlanes
         self.cross_planes = [WP(W) if wide_cross else None for W in self.cross_W]
-        self.wplanes = [WP(W) if on and u > 1 and ops.planes_worthwhile(B, W.shape[0], W.shape[1]) else None
+        self.wplanes = [WP(W) if u > 1 and ops.planes_worthwhile(B, W.shape[0], W.shape[1]) else None
                         for W, u in zip(self.Ws, units)]
         if self.h2:
             rec = lambda: ops.h2_record(device)
@@ -254,7 +252,7 @@ class DCNEngine:
         self._events = None
         # cross stack + MLP + loss and their backward, every SGD step fused into the wgrad kernels (see DCNDense): forward / dgrad GEMMs
         # on pre-split weights, in the "f16x2" operand split unless ops.set_gemm_split("bf16x3") / DR_GEMM_SPLIT=bf16x3 (read once, by
-        # the library) asks for the six-product one; DR_PLANES=0: the in-kernel-split GEMMs
+        # the library) asks for the six-product one
         self.dense = DCNDense(self.cross_W, self.cross_b, self.Ws, self.bs, B, self.in_dim, self.ld, diag_scale, device,
                               k=lambda name, bound, work, fn: self._k(name, bound, work, fn))
         self.row_base = torch.arange(F, device=device, dtype=torch.int64) * V

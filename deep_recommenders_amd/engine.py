@@ -9,6 +9,7 @@ DeepFM (keras/models/ranking/deepfm.py:36-47 of the reference): sigmoid(FM(first
 tf.losses.sigmoid_cross_entropy on the logits (examples/train_fm_on_movielens_estimator.py:46).
 """
 import math
+import os
 from typing import List, Optional, Sequence
 
 import torch
@@ -31,11 +32,6 @@ def _side_streams(device):
 
 def _pad4(n):
     return (n + 3) // 4 * 4
-
-
-def _os_env(name, default):
-    import os
-    return os.environ.get(name, default)
 
 
 class DeepFMEngine:
@@ -109,35 +105,27 @@ class DeepFMEngine:
             self.v_table = torch.zeros_like(self.table)
             # first-order moments interleaved in ONE [R, 2] array (m_lin, v_lin are its two columns; the kernels see v_lin == m_lin + 1
             # and stride by 2): a row's first-order Adam state is then one line to read and one to write instead of two each -- the
-            # fused Adam K4 is bound by line operations like the SGD one (round 4; DR_ADAM_LIN_PACKED=0: two arrays)
-            if _os_env("DR_ADAM_LIN_PACKED", "1") == "1":
-                self.mv_lin = torch.zeros((self.R, 2), dtype=torch.float32, device=device)
-                self.m_lin, self.v_lin = self.mv_lin[:, 0], self.mv_lin[:, 1]
-            else:
-                self.m_lin = torch.zeros_like(self.lin_w)
-                self.v_lin = torch.zeros_like(self.lin_w)
+            # fused Adam K4 is bound by line operations like the SGD one (round 4)
+            self.mv_lin = torch.zeros((self.R, 2), dtype=torch.float32, device=device)
+            self.m_lin, self.v_lin = self.mv_lin[:, 0], self.mv_lin[:, 1]
             self.row_step = torch.zeros(self.R, dtype=torch.int32, device=device) if self.adam_tf else None
-        import os as _os
         self.acts = [1] * len(dnn_units) + [0]
         # Wide layers: forward and dgrad on pre-split weights (dr_bf3_linear_nt: the activation operand stays fp32 and is split
         # in registers, only the weight is staged through the LDS): 360 -> 264 us forward, 400 -> 306 us dgrad at the first layer
-        # of config 3.  The planes are refreshed after every update of the weight.  DR_PLANES=0: the in-kernel-split GEMMs.
-        self.wplanes = [ops.WeightPlanes(W) if (_os.environ.get("DR_PLANES", "1") == "1" and u > 1
-                                                and ops.planes_worthwhile(B, W.shape[0], W.shape[1])) else None
+        # of config 3.  The planes are refreshed after every update of the weight.  Other layers: the in-kernel-split GEMMs.
+        self.wplanes = [ops.WeightPlanes(W) if (u > 1 and ops.planes_worthwhile(B, W.shape[0], W.shape[1])) else None
                         for W, u in zip(self.Ws, units)]
         self.dw_ws = [ops.linear_bwd_dw_workspace(B, W.shape[0], W.shape[1], device) for W in self.Ws]
         # wide layers: the register-split wgrad (dr_bf3_wgrad) on the same condition as the planes forward / dgrad
         self.wg_ws = [ops.bf3_wgrad_workspace(B, W.shape[0], W.shape[1], device) if wp is not None else None
                       for W, wp in zip(self.Ws, self.wplanes)]
-        # narrow layers (N <= 32, K in {128,256,512}) below the first: dx + dW + db fused in one pass over the activations
-        self.fuse_narrow = _os.environ.get("DR_FUSE_NARROW", "1") == "1"
         # last hidden layer (<= 32 units, relu) + Dense(1) + loss + Dense(1) backward fused into one GEMM epilogue
         nl = len(self.Ws)
-        self.fuse_head = (_os.environ.get("DR_FUSE_HEAD", "1") == "1" and nl >= 2 and self.Ws[-1].shape[1] == 1
-                          and self.Ws[-2].shape[1] <= 32 and self.acts[-2] == 1)
+        self.fuse_head = nl >= 2 and self.Ws[-1].shape[1] == 1 and self.Ws[-2].shape[1] <= 32 and self.acts[-2] == 1
         self.head_ws = ops.tower_head_workspace(B, device) if self.fuse_head else None
         self._head_done = False
         self._tail_done = False
+        # narrow layers (N <= 32, K in {128,256,512}) below the first: dx + dW + db fused in one pass over the activations
         self.narrow_ws = [ops.linear_bwd_narrow_workspace(B, W.shape[0], W.shape[1], device)
                           if (i > 0 and self.acts[i - 1] and ops.linear_bwd_narrow_supported(B, W.shape[0], W.shape[1])) else None
                           for i, W in enumerate(self.Ws)]
@@ -146,7 +134,7 @@ class DeepFMEngine:
         # kernel stages each 32-row chunk through the LDS once for the head's product and keeps it in registers for the backward.
         # Training steps only; needs the fused head, the narrow backward's shape domain (K in {128, 256}) and a ReLU layer below.
         # DR_FUSE_TAIL=0: the two launches of rounds 1-4.
-        self.fuse_tail = (_os.environ.get("DR_FUSE_TAIL", "1") == "1" and self.fuse_head and self.fuse_narrow and nl >= 3
+        self.fuse_tail = (os.environ.get("DR_FUSE_TAIL", "1") == "1" and self.fuse_head and nl >= 3
                           and self.narrow_ws[nl - 2] is not None and self.acts[nl - 3] == 1
                           and ops.tower_tail_supported(B, self.Ws[-2].shape[0], self.Ws[-2].shape[1]))
         self.tail_ws = ops.tower_tail_workspace(B, self.Ws[-2].shape[0], device) if self.fuse_tail else None
@@ -181,18 +169,12 @@ class DeepFMEngine:
         # ---- deterministic backward: slots sorted by table row on a side stream (depends only on ids) ----
         # Schedule experiments and their outcomes are recorded in DESIGN.md section 3 (sort started with K3 / in the backward /
         # on a high-priority stream, K4 overlapped with the first-layer wgrad, FM gradient folded into the dgrad epilogue):
-        # what remains here is the best measured schedule plus DR_SORT_INLINE=1 (sort on the training stream, for profiling).
+        # what remains here is the best measured schedule.
         self.sorted_bwd = sorted_bwd
-        self.sort_inline = _os.environ.get("DR_SORT_INLINE", "0") == "1"
-        # Where the side-stream sort starts.  Round 1: after K3, hidden under the in-kernel-split GEMMs (2 blocks / CU left room for
-        # it).  The register-split GEMMs are persistent 512-thread blocks that own their CU (144 KB of LDS, all registers): the
-        # sort only advances in the gaps between them (1.1 ms instead of 0.17) and K4 ends up waiting for it.  Started with K3 it
-        # shares HBM with the gather instead (round 1 measured +46 us on K3).  DR_SORT_WITH_K3=0 / 1 selects.
-        self.sort_with_k3 = _os.environ.get("DR_SORT_WITH_K3", "1") == "1"
         # K3 fused into the first layer's GEMM (dr_bf3_emb_linear_fwd: the register-split kernel gathers its activation rows from
         # the tables and produces concat / sum_x / fm_logit on the way).  Needs D == 64 and the planes path; DR_FUSE_K3=0: K3 as
         # its own kernel.
-        self.fuse_k3 = _os.environ.get("DR_FUSE_K3", "1") == "1" and D == 64 and self.Nd <= 32 and V <= (1 << 24)
+        self.fuse_k3 = os.environ.get("DR_FUSE_K3", "1") == "1" and D == 64 and self.Nd <= 32 and V <= (1 << 24)
         # (two buffers, indexed like the ids / plan buffers -- round 6: the next batch's dense features are placed with the early chain,
         # while this step's forward and wgrad still read the current buffer; see _prefetch_early)
         self._dense_pads = ([torch.zeros((B, 32), dtype=torch.float32, device=device) for _ in range(2)]
@@ -202,7 +184,7 @@ class DeepFMEngine:
         # ~70 us of the kernel) because nothing reads them any more -- the first layer's wgrad gathers its operand from the tables
         # itself (dr_bf3_wgrad_emb, from field-major int32 ids), and K4's duplicate pass takes x of the few slots that share rows
         # from a snapshot of those rows taken just before the update (dr_emb_snapshot_sorted_rows).  DR_NO_CONCAT=0: as round 2.
-        self.no_concat = (_os.environ.get("DR_NO_CONCAT", "1") == "1" and self.fuse_k3 and self.wplanes[0] is not None
+        self.no_concat = (os.environ.get("DR_NO_CONCAT", "1") == "1" and self.fuse_k3 and self.wplanes[0] is not None
                           and self.wg_ws[0] is not None and sorted_bwd and self.acts[0] in (0, 1) and len(dnn_units) >= 1
                           and not (self.fuse_head and len(self.Ws) == 2) and V < (1 << 24) - 1)
         if self.no_concat:
@@ -210,9 +192,9 @@ class DeepFMEngine:
             self.x_sorted = torch.empty((B * F, D), dtype=torch.float32, device=device)
         # The fused forward saves the first-order weight every slot read ([F, B], 6.8 MB at config 3); K4 then WRITES a unique row's
         # new weight (old + step) instead of read-modify-writing a line it would have to fetch from HBM again: K4 is bound by
-        # 128-byte line operations, 8 per slot, and this removes one (round 4; DR_K4_LINOLD=0: the read-modify-write).
+        # 128-byte line operations, 8 per slot, and this removes one (round 4).
         self.lin_old_t = (torch.empty((F, B), dtype=torch.float32, device=device)
-                          if (_os.environ.get("DR_K4_LINOLD", "1") == "1" and self.fuse_k3 and sorted_bwd) else None)
+                          if (self.fuse_k3 and sorted_bwd) else None)
         self._lin_old_valid = False
         # The first layer's three GEMMs in the "f16x2" operand mode (round 4; include/dr_hotpath.h dr_h2_*): every operand value as
         # two fp16 terms of x * s, three matrix instructions per fragment pair instead of the bf16x3 mode's six -- fused forward
@@ -223,7 +205,7 @@ class DeepFMEngine:
         # ops.set_gemm_split("bf16x3") / DR_GEMM_SPLIT=bf16x3 (read once, by the library) restores the six-product mode.  Needs the fused first layer, the gathering wgrad and the sorted K4;
         # "adam_tf" (whose catch-up kernel also writes table rows) stays on bf16x3.
         self.h2 = (ops.get_gemm_split() == "f16x2" and self.no_concat and self.wplanes[0] is not None
-                   and not self.adam_tf and _os.environ.get("DR_OVERLAP_DW", "0") != "1")
+                   and not self.adam_tf and os.environ.get("DR_OVERLAP_DW", "0") != "1")
         if self.h2:
             # (two W images: the fused dgrad + K4 of step s reads the old one while the refresh behind step s's wgrad writes the other)
             self.wplanes[0] = ops.H2WeightPlanes(self.Ws[0], double_buffer=True)
@@ -232,15 +214,12 @@ class DeepFMEngine:
             self._dense_amaxs = [ops.h2_record(device) for _ in range(2)] if self._dense_pads is not None else None
             self.dh0_amax = ops.h2_record(device)
             self._amax_scratch = ops.h2_record(device)
-        self._tighten_every = int(_os.environ.get("DR_AMAX_TIGHTEN_STEPS", "2048"))
+        self._tighten_every = int(os.environ.get("DR_AMAX_TIGHTEN_STEPS", "2048"))
         self._steps_since_tighten = 0
-        # (timing experiment only -- the record goes stale: K4 without the running maximum, to price the tracking)
-        self._exp_no_k4_amax = _os.environ.get("DR_EXP_K4_NO_AMAX", "0") == "1"
-        # The slot sort of batch s + 1 next to K4 of batch s (DR_PREFETCH_PLAN=0: every step hashes and sorts its own batch).  K4 is
+        # The slot sort of batch s + 1 next to K4 of batch s (a step called without next_keys hashes and sorts its own batch).  K4 is
         # the one long kernel of the step that is HBM-bound with small blocks, i.e. that shares the machine; beside the persistent
         # GEMMs (the fused first layer occupies all 160 KB of LDS on every CU) the sort chain's ~20 small launches only advance in
         # the gaps: 1.2 ms instead of 0.17, and K4 waited 74 us for it (round 2, rocprofv3: K4 305 us, its event 379 us).
-        self.prefetch_plan = _os.environ.get("DR_PREFETCH_PLAN", "1") == "1"
         # DR_PREFETCH_EARLY=1: the next batch's hash + slot plan start at the BEGINNING of this step (beside the
         # GEMMs, where they crawl but have a whole step of slack) instead of beside K4, which then has HBM to itself; the next batch's
         # dense features are still placed after this step's wgrad.
@@ -254,29 +233,25 @@ class DeepFMEngine:
         # (csrc/emb_plan.hip: the gated radix passes became one launch) the chain is short enough to profit: 0.975 - 0.978 ms against
         # 0.984 - 0.989 at the start of the step and 1.026 - 1.032 beside K4 (same call, alternating; before the slimmer plan the same
         # three read 1.056 - 1.061 / -- / 1.09).  Without the fused first layer "2" means "1".
-        _pe = _os.environ.get("DR_PREFETCH_EARLY", "2")
+        _pe = os.environ.get("DR_PREFETCH_EARLY", "2")
         self.prefetch_early = _pe in ("1", "2")
         self.prefetch_after_fwd = _pe == "2" and self.fuse_k3      # "2": behind the first GEMM, beside the tower tail
         # Fewer cross-stream packets in front of K4 (rocprofv3 showed a 31 us gap there against 11 - 13 us between the other
         # dependent kernels): the side chain is ordered behind the plane refresh instead of an event of its own, and the wait for
-        # a PREFETCHED plan -- long complete by then -- sits in front of the first-layer wgrad.  DR_LEAN_EVENTS=0: as before.
-        self.lean_events = _os.environ.get("DR_LEAN_EVENTS", "1") == "1"
-        # the early prefetch as ONE C call whose first kernel is K1 + field-major ids + composite keys + histogram (dr_hash_sort_slots);
-        # DR_FUSE_PLAN_FRONT=0: dr_hash_bucket_i64, dr_ids_transpose_i32, dr_emb_sort_slots one after the other (8 launches instead of 6)
-        self.fuse_plan_front = _os.environ.get("DR_FUSE_PLAN_FRONT", "1") == "1"
+        # a PREFETCHED plan -- long complete by then -- sits in front of the first-layer wgrad.
+        # The early prefetch is ONE C call whose first kernel is K1 + field-major ids + composite keys + histogram (dr_hash_sort_slots).
         self._plan_prefetched = False
         if sorted_bwd:
             self._plans = [ops.SortPlan(B * F, device) for _ in range(2)]
             # (round 5, measured and rejected: this stream restricted to a subset of the CUs -- hipExtStreamCreateWithCUMask, every 4th /
             # every 8th CU -- so that its ~25 small launches would not spread over the machine beside K4: the step went from 1.19 to
             # 1.75 - 1.85 ms, K4 itself unchanged; profiles/r05_ab_side_stream.log)
-            self.side, _side_r = _side_streams(device)
+            self.side, self.side_r = _side_streams(device)
             # Round 6: a stream of its own for what must be in place before the NEXT forward (the first layer's plane refresh behind its
             # wgrad, the next batch's dense features).  On `side` these five small launches queued behind the plan chain, whose kernels
             # only get CUs when a GEMM drains (a side kernel's blocks wait for the training stream's kernel to run out of blocks: the
             # chain advances about one kernel per kernel boundary of the step) -- rocprofv3 showed the refresh starting 17 us after the
-            # fused dgrad + K4 had ENDED and the next forward waiting 39 us for the dense features' record.  DR_SIDE_R=0: as before.
-            self.side_r = _side_r if _os.environ.get("DR_SIDE_R", "1") == "1" else self.side
+            # fused dgrad + K4 had ENDED and the next forward waiting 39 us for the dense features' record.
             self._refresh_stream = self.side
             self.ev_ids = torch.cuda.Event()
             self._ev_sorted = [torch.cuda.Event(), torch.cuda.Event()]
@@ -294,9 +269,9 @@ class DeepFMEngine:
         # First-order weights of the rows that are unique in the batch (99.4 % of the slots for uniform ids) updated by a kernel of
         # their own on the side stream, beside the tower tail, instead of inside K4: a random 4-byte read-modify-write fetches a
         # 128-byte line, 0.27 GB of K4's 1.64 GB.  DR_LIN_SIDE=1 (off by default: see DESIGN.md for the A/B).
-        self.lin_side = (sorted_bwd and optimizer == "sgd" and _os.environ.get("DR_LIN_SIDE", "0") == "1")
+        self.lin_side = (sorted_bwd and optimizer == "sgd" and os.environ.get("DR_LIN_SIDE", "0") == "1")
         # (the library reads the same variable once per process, with the same rule: off iff the value STARTS with '0')
-        self._k4_det = not _os.environ.get("DR_K4_DETERMINISTIC", "1").startswith("0")
+        self._k4_det = not os.environ.get("DR_K4_DETERMINISTIC", "1").startswith("0")
         # Round 6: K4's unique-row pass as the EPILOGUE of the first layer's dgrad (dr_h2_dgrad_emb_sgd, csrc/h2_occ.hip).  The dgrad's
         # output tile for (example m, field f) IS the gradient row of slot (m, f); the separate K4 read it back from d_concat 0.2 ms
         # after the dgrad had written it -- 0.88 GB of the step's HBM traffic for nothing.  Fused, a slot whose table row no other slot
@@ -304,16 +279,16 @@ class DeepFMEngine:
         # tests/test_gpu_fused_k4.py); the few shared rows go through d_concat and K4's duplicate pass as before.  The first-layer
         # wgrad, which gathers x from the tables, moves IN FRONT of the dgrad.  Needs the f16x2 split, SGD, the sorted plan, no
         # concat, D == 64 and the forward's saved first-order weights.  DR_FUSE_K4=0: dgrad, wgrad, K4 as in round 5.
-        self.fuse_k4 = (_os.environ.get("DR_FUSE_K4", "1") != "0" and self.h2 and optimizer == "sgd" and sorted_bwd and self.no_concat
-                        and D == 64 and not self.lin_side and not self.sort_inline and self.lin_old_t is not None
+        self.fuse_k4 = (os.environ.get("DR_FUSE_K4", "1") != "0" and self.h2 and optimizer == "sgd" and sorted_bwd and self.no_concat
+                        and D == 64 and not self.lin_side and self.lin_old_t is not None
                         and self.Ws[0].shape[0] >= F * D)
         # The step's three small reduce kernels -- the fused head's finish (partials -> Dense(1) step + loss), the narrow backward's
         # reduce (partials -> its weight step) and the first-layer wgrad's split-K reduce -- on the SIDE stream (round 4;
         # DR_REDUCE_SIDE=0: on the training stream as before).  Nothing in the rest of the step reads what they write; on the training
         # stream each cost its own 6 - 19 us plus a dependent-launch boundary (a build that skips them: 1.408 -> 1.37 ms).  SGD only
         # (Adam's dense step consumes the gradient bucket they fill).
-        _rs = _os.environ.get("DR_REDUCE_SIDE", "0")
-        self.reduce_side = (sorted_bwd and optimizer == "sgd" and _rs in ("1", "2") and _os.environ.get("DR_SORT_INLINE", "0") != "1")
+        _rs = os.environ.get("DR_REDUCE_SIDE", "0")
+        self.reduce_side = sorted_bwd and optimizer == "sgd" and _rs in ("1", "2")
         # "2": the head's and the narrow backward's only.  The wgrad's reduce is never deferred in the f16x2 mode: its part 2 divides
         # by the scales part 1 multiplied with, both derived from the table's amax record at launch time -- on the side stream it
         # would run beside K4, which raises that record (a power-of-two crossing between the two parts = W0 off by 2^k)
@@ -329,7 +304,7 @@ class DeepFMEngine:
         # (one 512-thread block per CU holding all its registers and 96 KB of LDS) the two kernels only time-slice the CUs: the
         # pair takes 740 - 750 us against 340 + 310 back to back, the step 1.764 vs 1.746 ms (round 2, A/B on one box).  So it
         # is OFF unless DR_OVERLAP_DW=1 asks for it.
-        _ov = _os.environ.get("DR_OVERLAP_DW", "0")
+        _ov = os.environ.get("DR_OVERLAP_DW", "0")
         self.overlap_dw = _ov == "1"
         if self.overlap_dw:
             self.no_concat = False       # the gathering wgrad would read the tables while K4 updates them on the other stream
@@ -369,12 +344,12 @@ class DeepFMEngine:
         """First half of the next batch's prefetch, BEFORE K4 is launched: the point on the training stream the side chain may
         start behind (K4's own start).  Returns the token _prefetch_issue needs, or None when nothing is to be prefetched."""
         nk = self._next_keys
-        if nk is None or not (self.sorted_bwd and not self.sort_inline and self.prefetch_plan):
+        if nk is None or not self.sorted_bwd:
             return None
         # the side stream already waits for the LAYER-0 wgrad (the last reader of concat's dense columns) iff the plane refresh
         # queued last was layer 0's; with e.g. dnn_units [64, 256] layer 0 has no planes and the last refresh waited only for
         # layer 1's wgrad (ADVICE r2): then the side chain takes its own event behind everything on the training stream
-        ordered = self._planes_pending and self._planes_pending_l0 and self.lean_events
+        ordered = self._planes_pending and self._planes_pending_l0
         if not ordered:
             self.ev_k4.record()
         return (ordered,)
@@ -434,19 +409,11 @@ class DeepFMEngine:
         """DR_PREFETCH_EARLY=1: hash + field-major ids + slot plan of the NEXT batch, issued at the start of this step's forward."""
         nk = self._next_keys
         self._early_issued = False
-        if nk is None or not (self.prefetch_early and self.sorted_bwd and not self.sort_inline and self.prefetch_plan):
+        if nk is None or not (self.prefetch_early and self.sorted_bwd):
             return
         nxt = self.cur ^ 1
         self.ev_fwd0.record()                   # behind the previous step's K4 (the last user of buffer `nxt`)
         nk.record_stream(self.side)
-        self._exp_n = getattr(self, "_exp_n", 0) + 1
-        if _os_env("DR_EXP_SKIP_PLAN", "") and self._exp_n > 8:      # EXPERIMENT (tools/exp/exp_plan.sh, timing only): buffers keep an older batch's ids + plan
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(self.ev_fwd0)
-                self._ev_hashed[nxt].record(self.side)
-                self._ev_sorted[nxt].record(self.side)
-            self._early_issued = True
-            return
         nd = self._next_dense
         self._dense_early = (nd is not None and self.Nd and self.no_concat and self._dense_pads is not None and not self.overlap_dw)
         if self._dense_early:
@@ -463,20 +430,11 @@ class DeepFMEngine:
                 self._ev_dense[nxt].record(self.side_r)
         with torch.cuda.stream(self.side):
             self.side.wait_event(self.ev_fwd0)
-            if self.fuse_plan_front:
-                # K1, the field-major ids and the plan as one chain of 6 launches (round 6: dr_hash_sort_slots; rounds 3 - 5: 27)
-                self._k("next_batch: hash_sort_slots(side stream, overlapped)", "overlap", self.B * self.F * 52,
-                        lambda: ops.hash_sort_slots(nk, self.col_buckets, self.row_base, self.R, self._ids[nxt],
-                                                    self._ids_t[nxt] if self.no_concat else None, self._plans[nxt]))
-                self._ev_hashed[nxt].record(self.side)
-            else:
-                self._k("next_batch: hash_bucket_i64(side stream, overlapped)", "overlap", self.B * self.F * 16,
-                        lambda: ops.hash_bucket_i64(nk, self.col_buckets, out=self._ids[nxt]))
-                if self.no_concat:
-                    ops.ids_transpose_i32(self._ids[nxt], out=self._ids_t[nxt])
-                self._ev_hashed[nxt].record(self.side)
-                self._k("next_batch: emb_sort_slots(side stream, overlapped)", "overlap", self.B * self.F * 36,
-                        lambda: ops.emb_sort_slots(self._ids[nxt], self.row_base, self.R, self._plans[nxt]))
+            # K1, the field-major ids and the plan as one chain of 6 launches (round 6: dr_hash_sort_slots; rounds 3 - 5: 27)
+            self._k("next_batch: hash_sort_slots(side stream, overlapped)", "overlap", self.B * self.F * 52,
+                    lambda: ops.hash_sort_slots(nk, self.col_buckets, self.row_base, self.R, self._ids[nxt],
+                                                self._ids_t[nxt] if self.no_concat else None, self._plans[nxt]))
+            self._ev_hashed[nxt].record(self.side)
             self._ev_sorted[nxt].record(self.side)
         self._early_issued = True
 
@@ -543,8 +501,7 @@ class DeepFMEngine:
 
     def _wgrad_reduce_deferred(self, i):
         """layer 0's gathering wgrad with its reduce on the side stream, in front of the plane refresh that lives there already"""
-        return (self.reduce_side_wgrad and i == 0 and self.no_concat and self.wplanes[0] is not None and not self.sort_inline
-                and not self.overlap_dw)
+        return self.reduce_side_wgrad and i == 0 and self.no_concat and self.wplanes[0] is not None and not self.overlap_dw
 
     def _side_part2(self, fn):
         """second half of a two-part call on the side stream, behind the first half (just launched on the training stream)"""
@@ -608,11 +565,7 @@ class DeepFMEngine:
                 ops.ids_transpose_i32(self.ids, out=self._ids_t[self.cur])
         if self._in_train_step and not self.prefetch_after_fwd:
             self._prefetch_early()
-        if self.sorted_bwd and self.sort_inline:
-            self._k("emb_sort_slots", "hbm", B * F * 36,
-                    lambda: ops.emb_sort_slots(self.ids, self.row_base, self.R, self.plan))
-            self.ev_sorted.record()
-        if self.sorted_bwd and not self.sort_inline and self.sort_with_k3 and not prefetched:
+        if self.sorted_bwd and not prefetched:
             self._launch_sort()              # next to K3 (both HBM-bound, small blocks: they do share the machine)
         if self.adam_tf:
             # (the catch-up stamps the looked-up rows with step t + 1 BEFORE that step's update exists: a forward that is not followed
@@ -631,8 +584,6 @@ class DeepFMEngine:
                     lambda: ops.emb_pool_fwd(self.ids, F, None, self.row_base, self.table, self.lin_w, self.lin_bias,
                                              ld_concat=self.ld, concat=self.concat, sum_x=self.sum_x,
                                              fm_logit=self.fm_logit))
-        if self.sorted_bwd and not self.sort_inline and not self.sort_with_k3 and not prefetched:
-            self._launch_sort()              # after K3: under the first GEMM and the tower tail
         if self.Nd and not (prefetched and self._pref_dense is not None and self._pref_dense == self._token(dense)):
             if not self.no_concat:
                 self.concat[:, F * D:F * D + self.Nd].copy_(dense)                     # layout: append dense feats
@@ -719,7 +670,7 @@ class DeepFMEngine:
     def backward_and_update(self):
         F, D, lr = self.F, self.D, self.lr
         adam = self.optimizer == "adam"
-        lin_side = self.lin_side and not adam and not self.sort_inline
+        lin_side = self.lin_side and not adam
         if lin_side:
             # d_logit is final (fused head or K11 above); the plan of this batch was produced on the side stream itself
             self.ev_dlogit.record()
@@ -749,7 +700,7 @@ class DeepFMEngine:
             else:
                 dx = self.d_concat[:, :self.in_dim]
                 rs = None
-            if i > 0 and self.fuse_narrow and self.narrow_ws[i] is not None:
+            if i > 0 and self.narrow_ws[i] is not None:
                 def narrow(parts, x=x, dy=dy, W=W, dx=dx, i=i, dstW=dstW, dstb=dstb):
                     return ops.linear_bwd_narrow(x, dy, W, sc, dstW, dstb, dx, relu_mask=True, workspace=self.narrow_ws[i], parts=parts,
                                                  dx_amax=self.dh0_amax if (i == 1 and self.h2 and (parts & 1)) else None)
@@ -761,14 +712,14 @@ class DeepFMEngine:
                 dy = dx
                 continue
             if i == 0 and self.fuse_k4 and self._lin_old_valid and not adam and not self.overlap_dw:
-                if self.h2 and not (n > 1 and self.fuse_narrow and self.narrow_ws[1] is not None):
+                if self.h2 and not (n > 1 and self.narrow_ws[1] is not None):
                     ops.h2_amax(dy, self.dh0_amax)       # (as below: no narrow layer-1 kernel left the record the wgrad and dgrad read)
                 self._backward_l0_fused_k4(x, dy, sc, dstW, dstb, fl)
                 dy = None
                 continue
             # dx first (uses the pre-update W), then the wgrad (with the fused SGD step unless Adam)
             if i == 0 and self.h2:
-                if not (n > 1 and self.fuse_narrow and self.narrow_ws[1] is not None):
+                if not (n > 1 and self.narrow_ws[1] is not None):
                     ops.h2_amax(dy, self.dh0_amax)       # (layer 1's backward was not the narrow kernel that leaves the record)
                 self._k("linear_bwd_dx_L%d" % i, "mfma", fl,
                         lambda dy=dy, rs=rs, dx=dx, i=i: ops.h2_linear_nt(dy, self.dh0_amax, self.wplanes[i].w, mask=rs, out=dx))
@@ -778,8 +729,9 @@ class DeepFMEngine:
             else:
                 self._k("linear_bwd_dx_L%d" % i, "mfma", fl,
                         lambda dy=dy, W=W, rs=rs, dx=dx: ops.linear_bwd_dx(dy, W, relu_src=rs, out=dx))
-            if i == 0 and self.sorted_bwd and self._plan_prefetched and self.lean_events:
-                torch.cuda.current_stream().wait_event(self.ev_sorted)     # (see lean_events)
+            if i == 0 and self.sorted_bwd and self._plan_prefetched:
+                # the wait for a prefetched plan, long complete by now, goes here: no cross-stream packet in front of K4
+                torch.cuda.current_stream().wait_event(self.ev_sorted)
             if i == 0 and self.overlap_dw:
                 # first-layer wgrad on the second stream; K4 follows on this one as soon as dx is out
                 self.ev_dx.record()
@@ -795,7 +747,7 @@ class DeepFMEngine:
             self._k("linear_bwd_dw_L%d" % i, "mfma", fl,
                     lambda x=x, dy=dy, i=i, dstW=dstW, dstb=dstb: self._wgrad(i, x, dy, sc, dstW, dstb))
             if self.wplanes[i] is not None and not adam:
-                if self.sorted_bwd and not self.sort_inline:
+                if self.sorted_bwd:
                     # the weight just moved: its planes follow -- on the side stream, beside whatever comes next on this one (the
                     # two split launches are needed only by the next step's forward / dgrad, which wait for ev_planes)
                     self.ev_dw_done.record()
@@ -821,7 +773,7 @@ class DeepFMEngine:
         elif self._k4_fused_done:
             self._k4_fused_done = False
         elif self.sorted_bwd:
-            if not (self._plan_prefetched and self.lean_events):
+            if not self._plan_prefetched:
                 torch.cuda.current_stream().wait_event(self.ev_sorted)
             if self.no_concat and not self._k4_det:
                 # x of the slots that share rows, before the atomic pieces of hot rows touch them (DR_K4_DETERMINISTIC=0 only: the
@@ -833,7 +785,7 @@ class DeepFMEngine:
                                                        concat=None if self.no_concat else self.concat, sum_x=self.sum_x,
                                                        x_sorted=self.x_sorted if self.no_concat else None, parts=parts,
                                                        lin_old_t=self.lin_old_t if (self._lin_old_valid and not lin_side) else None,
-                                                       table_amax=self.tab_amax if (self.h2 and not self._exp_no_k4_amax) else None)
+                                                       table_amax=self.tab_amax if self.h2 else None)
             sk = 4 if lin_side else 0
             self._k("emb_pool_bwd", "hbm", self.alg_bytes_bwd() - (self.B * self.F * 8 if lin_side else 0),   # K4 (sorted)
                     lambda: k4(1 | sk))
@@ -881,15 +833,14 @@ class DeepFMEngine:
             self._prefetch_issue(mark)
         if not self._k4_det:
             ops.emb_snapshot_sorted_rows(self.plan, self.table, self.R, self.x_sorted)
-        tab_amax = self.tab_amax if not self._exp_no_k4_amax else None
         # bytes this kernel must move: SURVEY 8(d)'s K4 figure minus the 4FD read of d_concat that no longer exists, plus the dgrad's dy
         work = self.alg_bytes_bwd() - 4.0 * self.B * self.F * self.D + 4.0 * self.B * dy.shape[1]
         self._k("emb_pool_bwd_fused_dgrad_L0", "hbm", work,
                 lambda: ops.h2_dgrad_emb_sgd(dy, self.dh0_amax, w_old, self._ids_t[self.cur], self.plan, self.row_base, self.table,
-                                             self.lin_w, self.lin_old_t, self.sum_x, self.d_logit, -lr, self.d_concat, table_amax=tab_amax))
+                                             self.lin_w, self.lin_old_t, self.sum_x, self.d_logit, -lr, self.d_concat, table_amax=self.tab_amax))
         k4 = lambda parts: ops.emb_pool_bwd_sorted(self.ids, self.row_base, self.plan, self.D, self.R, self.d_concat, self.d_logit, -lr,
                                                    self.table, self.lin_w, self.lin_bias, sum_x=self.sum_x, x_sorted=self.x_sorted,
-                                                   parts=parts | 8, lin_old_t=self.lin_old_t, table_amax=tab_amax)
+                                                   parts=parts | 8, lin_old_t=self.lin_old_t, table_amax=self.tab_amax)
         self._k("emb_pool_bwd_dups", "hbm", 0, lambda: k4(1))
         self._k("emb_hot_rows_apply", "hbm", 0, lambda: k4(2))
         if not early:
@@ -897,9 +848,9 @@ class DeepFMEngine:
         self._k4_fused_done = True
 
     def _launch_sort(self):
-        """The slot sort depends only on ids and is needed only by K4: it runs on a side stream.  It is HBM-bound like K3 and,
-        squeezed next to a GEMM, long (~660 us vs 167 us alone): started with K3 it stretched K3; started before the first-layer
-        dgrad it crawled to 1.17 ms and K4 waited for it; started after K3 it hides under the first GEMM and the tower tail."""
+        """The slot sort of a batch that was not prefetched.  It depends only on ids and is needed only by K4: it runs on the side
+        stream and starts with K3 (both HBM-bound with small blocks, they share the machine).  Started later it only advances in the
+        gaps between the persistent register-split GEMMs, which own their CUs, and K4 ends up waiting for it."""
         self.ev_ids.record()
         with torch.cuda.stream(self.side):
             self.side.wait_event(self.ev_ids)
@@ -911,7 +862,7 @@ class DeepFMEngine:
         """Adam mode: fused row-wise Adam K4, first-order bias gradient, one dense Adam step over the flat parameters."""
         self.t += 1
         lr_t = ops.adam_lr_t(self.lr, self.beta1, self.beta2, self.t)
-        if not (self._plan_prefetched and self.lean_events):
+        if not self._plan_prefetched:
             torch.cuda.current_stream().wait_event(self.ev_sorted)
         if self.no_concat:
             ops.emb_snapshot_sorted_rows(self.plan, self.table, self.R, self.x_sorted)

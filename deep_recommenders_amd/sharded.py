@@ -21,6 +21,7 @@ here) — the world_size-2 gloo tests substitute an oracle-backed implementation
 on CPU, where the kernels cannot run.
 """
 import math
+import os
 from typing import Sequence
 
 import torch
@@ -180,8 +181,7 @@ class CApiTransport:
 
 def default_transport(world, rank, group=None):
     """torch.distributed unless DR_TRANSPORT=capi asks for the C-ABI exchange library."""
-    import os as _os
-    if _os.environ.get("DR_TRANSPORT", "torch") == "capi":
+    if os.environ.get("DR_TRANSPORT", "torch") == "capi":
         return CApiTransport(world, rank, group)
     return TorchDistTransport(group)
 
@@ -219,8 +219,7 @@ class ShardedEmbeddingExchange:
         # keras/models/ranking/fm.py:57-61 of the reference).  Uniform ids over 10 M rows: nothing to save (99.8 % of a micro-batch's
         # slots are distinct rows); Zipf(1.05) keys: 1.6 x fewer bytes on the wire, for a slot plan + a representative map per
         # micro-batch on the routing stream and fp32 atomics in the pack for the shared rows (their summation order is then not fixed).
-        import os as _os
-        self.dedup = (_os.environ.get("DR_SH_DEDUP", "0") == "1") if dedup is None else bool(dedup)
+        self.dedup = (os.environ.get("DR_SH_DEDUP", "0") == "1") if dedup is None else bool(dedup)
         self.world, self.rank, self.dev = world, rank, device
         self.rows_per_shard = (vocab_per_field + world - 1) // world
         self.local_rows = num_fields * self.rows_per_shard
@@ -603,8 +602,7 @@ class ShardedDeepFMEngine:
         Bm = B // mb
         # the tower tail of a micro-batch in ONE pass over its h (round 5: dr_tower_tail_fused, as engine.DeepFMEngine; DR_FUSE_TAIL=0: the
         # head and the narrow backward as two launches).  HipPrims only: the oracle-backed primitives of the gloo tests have no such call.
-        import os as _os0
-        self.fuse_tail = (self._cuda and hasattr(self.p, "tower_tail_fused") and _os0.environ.get("DR_FUSE_TAIL", "1") == "1"
+        self.fuse_tail = (self._cuda and hasattr(self.p, "tower_tail_fused") and os.environ.get("DR_FUSE_TAIL", "1") == "1"
                           and self.fuse_head and nl >= 3 and self.acts[nl - 3] == 1
                           and self.p.tower_tail_supported(Bm, self.Ws[-2].shape[0], self.Ws[-2].shape[1]))
         self.tail_ws = ops.tower_tail_workspace(Bm, self.Ws[-2].shape[0], device) if self.fuse_tail else None
@@ -614,8 +612,7 @@ class ShardedDeepFMEngine:
         # Wide layers on the register-split GEMMs of engine.DeepFMEngine (weights kept as bf16 planes, refreshed after the update):
         # the dgrad of a micro-batch and the wgrad over the whole rank batch.  The forward stays on the in-kernel-split GEMM below
         # 65 536 rows: its 256-row tiles number 128 at a 32 768-row micro-batch, half a machine (267 us either way, measured).
-        import os as _os
-        use_planes = self._cuda and self.p is HipPrims and _os.environ.get("DR_PLANES", "1") == "1"
+        use_planes = self._cuda and self.p is HipPrims
         self.wplanes = [ops.WeightPlanes(Wt) if (use_planes and ops.planes_worthwhile(Bm, Wt.shape[0], Wt.shape[1])) else None
                         for Wt in self.Ws]
         self.wg_ws = [ops.bf3_wgrad_workspace(B, Wt.shape[0], Wt.shape[1], device) if self.wplanes[i] is not None else None
@@ -624,7 +621,7 @@ class ShardedDeepFMEngine:
         # K3 inside the first layer's GEMM, over the RECEIVED rows: the register-split kernel gathers its activation operand by
         # LDS-DMA and does not care where the rows live -- table := the receive buffer, ids := each slot's position in it, one
         # "field" of n rows (engine.DeepFMEngine's fused first layer; DR_FUSE_K3=0: K3 + a separate GEMM as in round 2).
-        self.fuse_k3 = (use_planes and _os.environ.get("DR_FUSE_K3", "1") == "1" and D == 64 and self.Nd <= 32
+        self.fuse_k3 = (use_planes and os.environ.get("DR_FUSE_K3", "1") == "1" and D == 64 and self.Nd <= 32
                         and self.wplanes[0] is not None and B * F <= (1 << 24) and self.acts[0] in (0, 1))
         self.dense_pad = torch.zeros((B, 32), **f32) if (self.fuse_k3 and self.Nd) else None
         # first-layer dgrad and the gradient pack in one launch (dr_h2_linear_nt_pack / dr_bf3_linear_nt_pack): d_concat is never
@@ -633,11 +630,10 @@ class ShardedDeepFMEngine:
         # 16 rows) lost to dgrad + pack (400 us against 173 + 143 per half batch); round 5's, in the f16x2 split, turns each
         # accumulator block through the LDS and moves float4s with 8 lanes on a row.  DR_FUSE_PACK=0 / 1 (default: see _fuse_pack_default).
         _will_h2 = (self.fuse_k3 and ops.get_gemm_split() == "f16x2" and not (self.fuse_head and len(self.Ws) - 2 == 0))     # (= self.h2 below)
-        self.fuse_pack = (use_planes and _os.environ.get("DR_FUSE_PACK", _fuse_pack_default(_will_h2)) == "1" and D == 64
+        self.fuse_pack = (use_planes and os.environ.get("DR_FUSE_PACK", _fuse_pack_default(_will_h2)) == "1" and D == 64
                           and num_fields <= 64 and not self.ex.dedup)
-        # streams for the later micro-batches' fused first layers (see train_step); DR_FWD_STREAMS=0: all on the training stream
-        self.fwd_streams = ([torch.cuda.Stream(device=device) for _ in range(max(0, min(mb - 1, 3)))]
-                            if (self.fuse_k3 and _os.environ.get("DR_FWD_STREAMS", "1") == "1") else [])
+        # streams for the later micro-batches' fused first layers (see train_step)
+        self.fwd_streams = [torch.cuda.Stream(device=device) for _ in range(max(0, min(mb - 1, 3)))] if self.fuse_k3 else []
         # The first layer's three GEMMs in the "f16x2" operand mode (round 4; see engine.DeepFMEngine / include/dr_hotpath.h dr_h2_*).  The
         # activation scale of the forward and the wgrad comes from the amax record of the TABLES: every rank keeps a running record of
         # its own shard (K4 raises it) and, with real peers, one 4-byte all-reduce(MAX) behind the step's last owner-side update makes
@@ -663,7 +659,7 @@ class ShardedDeepFMEngine:
         # owner-side update, the two-buffer swap -- WITHOUT the f16x2 kernels, so that the N > 1 control flow of the mode runs wherever
         # the engine runs (world-size-2 gloo on CPU with the oracle-backed primitives: the record is recomputed from the shard with
         # torch after every owner-side update instead of being raised by K4).
-        self.track_amax = self.h2 or _os.environ.get("DR_SH_TRACK_AMAX", "0") == "1"
+        self.track_amax = self.h2 or os.environ.get("DR_SH_TRACK_AMAX", "0") == "1"
         if self.track_amax and not self.h2:
             self.tab_amax_local = self._amax_of(self.table)
             self._tab_bufs = None if self.ex.local else [self.tab_amax_local.clone(), self.tab_amax_local.clone()]
@@ -672,8 +668,6 @@ class ShardedDeepFMEngine:
             if not self.ex.local:
                 self.tr.allreduce(self.tab_amax, op=dist.ReduceOp.MAX)
         self._ev_every, self._ev_step, self._ev_live = 1, 0, False
-        self.k4_first = _os.environ.get("DR_SH_K4_FIRST", "0") == "1"
-        self.wgrad_split = _os.environ.get("DR_SH_WGRAD_SPLIT", "0") == "1"
         self._events = None
         self._stamps = None
         self._route = None
@@ -1081,24 +1075,6 @@ class ShardedDeepFMEngine:
             if cuda:
                 ev_p = torch.cuda.Event()
                 ev_p.record()
-                if self.wgrad_split:
-                    # this micro-batch's share of the wide layers' wgrads right here (dW accumulates over the micro-batches): the
-                    # exchange + owner-side K4 of micro-batch m then run beside a HALF-length wgrad, and the last K4 -- which the
-                    # next step's first row fetch waits for -- beside wgrad(M - 1) only, not beside the whole batch's
-                    for i in (dw_todo if m > 0 else list(dw_todo)):
-                        xin = x_in[sl] if i == 0 else self.hs[i - 1][sl]
-                        dyi = self.dhs[i][sl] if i < n_layers - 1 else self.d_logit[sl].reshape(-1, 1)
-                        if i == 0 and h2:
-                            self._x_record()
-                            self._k("linear_bwd_dw_L%d" % i, "mfma", 2.0 * Bm * self.Ws[i].shape[0] * self.Ws[i].shape[1],
-                                    lambda xin=xin, dyi=dyi, i=i, m=m: ops.h2_wgrad(xin, self.x_amax_all, dyi, self.dh0_amax[m], 1.0, self.gWs[i],
-                                                                                    self.gbs[i], workspace=self.wg_ws[i]))
-                        elif self.wg_ws[i] is not None:
-                            self._k("linear_bwd_dw_L%d" % i, "mfma", 2.0 * Bm * self.Ws[i].shape[0] * self.Ws[i].shape[1],
-                                    lambda xin=xin, dyi=dyi, i=i: ops.bf3_wgrad(xin, dyi, 1.0, self.gWs[i], self.gbs[i], workspace=self.wg_ws[i]))
-                        else:
-                            self._k("linear_bwd_dw_L%d" % i, "mfma", 2.0 * Bm * self.Ws[i].shape[0] * self.Ws[i].shape[1],
-                                    lambda xin=xin, dyi=dyi, i=i: p.linear_bwd_dw(xin, dyi, 1.0, self.gWs[i], self.gbs[i], workspace=self.dw_ws[i]))
                 with torch.cuda.stream(self.comm):
                     self.comm.wait_event(ev_p)
                     self._k("emb_grads(a2a+sorted K4)", "xgmi", Bm * F * (4 * D + 4),
@@ -1118,16 +1094,10 @@ class ShardedDeepFMEngine:
                     if m == M - 1:
                         self._publish_table_bound()
         # ---- wgrads over the WHOLE rank batch (activations of all micro-batches are contiguous) --------------------------------
-        # DR_SH_K4_FIRST=1 (measured, not adopted): the wgrad WAITS for the last owner-side update.  A persistent GEMM block owns its
-        # CU, so the last K4 crawls beside the wgrad (469 us instead of 170, rocprofv3 timeline of the world-1 step) and the next
-        # step's row fetches -- which must see that update -- queue behind it: K4 -> gather -> forward is a serial 180 us hole on
-        # the training stream.  With K4 first the NEXT step's fetches run beside the wgrad and both forwards find their rows
-        # waiting (322 us for the pair instead of 436) -- but the wgrad stretches by as much beside the gathers (309 -> 413 us) and
-        # the last K4 is fully exposed: 1.97 ms against 1.94 (same call, alternating, three rounds).
-        if cuda and self.k4_first and ev_last_apply is not None:
-            self._stall("stall_apply(training stream waits for C3 + owner-side update)", main, ev_last_apply)
+        # They run BESIDE the last owner-side update on the communication stream; the step waits for that update at its end (the wgrad
+        # behind the update, and a per-micro-batch wgrad, were measured and not adopted: docs/DESIGN_HISTORY.md).
         dys[0] = self.dhs[0] if n_layers > 1 else self.d_logit.reshape(-1, 1)
-        for i in ([] if (cuda and self.wgrad_split) else dw_todo):
+        for i in dw_todo:
             xin = x_in if i == 0 else self.hs[i - 1]
             dyi = self.dhs[i] if i < n_layers - 1 else self.d_logit.reshape(-1, 1)
             if i == 0 and h2:
@@ -1171,8 +1141,7 @@ class ShardedDeepFMEngine:
         if adam and self.fuse_head:
             self.loss.mul_(W)          # loss_parts were normalised by the global batch: report the rank's mean like the SGD mode
         if cuda:
-            if not self.k4_first:
-                self._stall("stall_apply(training stream waits for C3 + owner-side update)", main, ev_last_apply)   # the step ends when every owner has applied its updates
+            self._stall("stall_apply(training stream waits for C3 + owner-side update)", main, ev_last_apply)   # the step ends when every owner has applied its updates
             ev = torch.cuda.Event()
             ev.record()
             self._done.append(ev)
@@ -1260,10 +1229,9 @@ class ShardedDCNEngine:
         # runs (round 5): wide GEMMs on pre-split weights in the operand split the library reports ("f16x2" by default; x0's amax record
         # comes from a pass over the rows this rank received, so no record has to travel with the exchange), gradients accumulated
         # into the all-reduce bucket instead of applied in place.  The generic in-kernel-split path below remains for primitives other
-        # than HipPrims (the oracle-backed ones of the gloo tests) and DR_SH_DCN_CORE=0.
-        import os as _os
+        # than HipPrims (the oracle-backed ones of the gloo tests).
         self.core = None
-        if self._cuda and self.p is HipPrims and _os.environ.get("DR_SH_DCN_CORE", "1") == "1":
+        if self._cuda and self.p is HipPrims:
             from .dcn_engine import DCNDense
             self.core = DCNDense(self.cross_W, self.cross_b, self.Ws, self.bs, B, self.in_dim, ld, diag_scale, device,
                                  grads=(self.g_cross_W, self.g_cross_b, self.gWs, self.gbs))

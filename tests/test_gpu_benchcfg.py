@@ -273,7 +273,7 @@ def _run_deepfm(V, optimizer, kind, lr, steps=2):
         # train_step without them)
         nk, nd = (batches[i + 1][0], batches[i + 1][1]) if i + 1 < len(batches) else (None, None)
         loss = float(eng.train_step(keys, dense, labels, next_keys=nk, next_dense=nd).item())
-        assert eng._plan_prefetched == (i > 0 and eng.prefetch_plan), "the prefetched plan was not picked up"
+        assert eng._plan_prefetched == (i > 0), "the prefetched plan was not picked up"
         np.testing.assert_array_equal(eng.ids.cpu().numpy(), ids_list[i])                     # integer path: bit-exact
         want = orc.step(i, dense.cpu(), labels.cpu(), relu_masks=_device_relu_masks(eng))
         T.check_ties(orc.ties, max_frac=1e-5 if optimizer == "sgd" else 1e-4)

@@ -323,6 +323,7 @@ def test_engine_next_batch_prefetch_is_bit_identical(optimizer, D, V):
     engs = [DeepFMEngine(F, V, D, [256, 16], B, num_dense=Nd, lr=0.05 if optimizer == "sgd" else 0.01, seed=3, lin_init_std=0.1,
                          optimizer=optimizer) for _ in range(2)]
     order = [0, 1, 2, 3, 1, 0]
+    picked_up = []
     for n, i in enumerate(order):
         engs[0].train_step(*batches[i])
         nxt = order[n + 1] if n + 1 < len(order) else None
@@ -330,11 +331,14 @@ def test_engine_next_batch_prefetch_is_bit_identical(optimizer, D, V):
             nxt = 0                                     # announced batch 0, batch 1 comes: the prefetched plan must be dropped
         engs[1].train_step(*batches[i], next_keys=None if nxt is None else batches[nxt][0],
                            next_dense=None if nxt is None else batches[nxt][1])
+        picked_up.append(engs[1]._plan_prefetched)
         if n == 0:
             # the announced tensor is modified before it is used: its version changes, the prefetched ids are stale
             batches[1][0].add_(1)
     torch.cuda.synchronize()
-    assert engs[1].prefetch_plan
+    # a prefetched plan was in fact picked up wherever the announced batch came next unmodified (steps 2, 4, 5), and only there: step 0
+    # had no announcement, step 1's keys were modified after they were announced, step 3 was announced as batch 0
+    assert picked_up == [False, False, True, False, True, True], picked_up
     assert torch.equal(engs[0].table, engs[1].table) and torch.equal(engs[0].lin_w, engs[1].lin_w)
     assert torch.equal(engs[0].flat_params, engs[1].flat_params)
     assert engs[0].loss.item() == engs[1].loss.item()

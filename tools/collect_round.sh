@@ -21,22 +21,19 @@ timeout -s KILL 200 python bench.py --full --ids zipf --no-cpu-baseline > $OUT/l
 timeout -s KILL 200 python bench.py --full --preset c2 --no-cpu-baseline > $OUT/line_c2.log 2>&1
 timeout -s KILL 400 python bench.py --full --model dcn > $OUT/line_dcn.log 2>&1
 timeout -s KILL 400 python bench.py --full --model dssm > $OUT/line_dssm.log 2>&1
-DR_FUSE_K3=0 DR_PREFETCH_PLAN=0 timeout -s KILL 200 python bench.py --full --no-cpu-baseline > $OUT/line_unfused.log 2>&1
+DR_FUSE_K3=0 timeout -s KILL 200 python bench.py --full --no-cpu-baseline > $OUT/line_unfused.log 2>&1
 DR_NO_CONCAT=0 timeout -s KILL 200 python bench.py --full --no-cpu-baseline > $OUT/line_concat.log 2>&1
 DR_FORCE_SHARDED=1 timeout -s KILL 200 python bench.py --full --no-cpu-baseline > $OUT/line_sharded_world1.log 2>&1
 DR_FORCE_SHARDED=1 timeout -s KILL 300 python bench.py --full --model dcn --no-cpu-baseline > $OUT/line_dcn_sharded_world1.log 2>&1
 DR_PREFETCH_EARLY=0 timeout -s KILL 200 python bench.py --full --no-cpu-baseline > $OUT/line_plan_beside_k4.log 2>&1
-# round 6 (second half): the prefetch chain as rounds 3 - 5 scheduled it (start of the step, K1 / transpose / plan as three calls, one side stream)
-DR_PREFETCH_EARLY=1 DR_FUSE_PLAN_FRONT=0 DR_SIDE_R=0 DR_BENCH_STRICT=0 timeout -s KILL 200 python bench.py --full --no-cpu-baseline > $OUT/line_chain_r5_schedule.log 2>&1
-# what the chain costs the step (tools/exp/exp_plan.sh: the chain not launched at all, timing only), and one step as a timeline
-bash tools/exp/exp_plan.sh > $OUT/plan_cost.log 2>&1
+# one step as a timeline
 bash tools/exp/timeline_call.sh default bf3_emb_linear_kernel -- > /dev/null 2>&1
 bash tools/exp/timeline_call.sh sharded bf3_gemm_tn_rs_kernel DR_FORCE_SHARDED=1 -- > /dev/null 2>&1
 cd $R
-# round 6: the three-kernel backward of round 5 (dgrad, wgrad, K4) beside the fused default; the 8-wave GEMM kernel everywhere
+# round 6: the three-kernel backward of round 5 (dgrad, wgrad, K4) beside the fused default
 DR_FUSE_K4=0 DR_BENCH_STRICT=0 timeout -s KILL 200 python bench.py --full --no-cpu-baseline > $OUT/line_k4_unfused.log 2>&1
-DR_H2_OCC=0 DR_BENCH_STRICT=0 timeout -s KILL 300 python bench.py --full --model dcn --no-cpu-baseline > $OUT/line_dcn_8wave.log 2>&1
-# round 6 experiment drivers: the 16-wave kernel against the 8-wave one (bit-identity + times), the fused dgrad + K4 against dgrad + K4
+# round 6 experiment drivers: the 16-wave kernel against the 8-wave one (bit-identity + times; the 8-wave leg needs a library built with
+# DR_HIPCC_EXTRA=-DDR_OCC_ABLATE, see occ_bench.py), the fused dgrad + K4 against dgrad + K4
 timeout -s KILL 300 python tools/exp/occ_bench.py 2>&1 | grep "OCC=" > $OUT/occ_bench.log
 timeout -s KILL 300 python tools/exp/fused_k4_bench.py 2>&1 | grep FUSEDK4 > $OUT/fused_k4_bench.log
 timeout -s KILL 300 python tools/exp/fused_k4_bench.py 2000000 zipf 2>&1 | grep FUSEDK4 >> $OUT/fused_k4_bench.log
@@ -45,7 +42,7 @@ DR_GEMM_SPLIT=bf16x3 timeout -s KILL 200 python bench.py --full --no-cpu-baselin
 DR_GEMM_SPLIT=bf16x3 timeout -s KILL 300 python bench.py --full --model dcn --no-cpu-baseline > $OUT/line_dcn_bf16x3.log 2>&1
 DR_GEMM_SPLIT=bf16x3 DR_FORCE_SHARDED=1 timeout -s KILL 200 python bench.py --full --no-cpu-baseline > $OUT/line_sharded_world1_bf16x3.log 2>&1
 timeout -s KILL 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-for f in default adam zipf c2 dcn dssm unfused concat sharded_world1 dcn_sharded_world1 plan_beside_k4 chain_r5_schedule k4_unfused dcn_8wave bf16x3 dcn_bf16x3 sharded_world1_bf16x3; do
+for f in default adam zipf c2 dcn dssm unfused concat sharded_world1 dcn_sharded_world1 plan_beside_k4 k4_unfused bf16x3 dcn_bf16x3 sharded_world1_bf16x3; do
   python - $f <<'PY'
 import json, os, sys
 try:

@@ -1,6 +1,7 @@
-// GPU experiment (not product): where does a k-tile of the planes NT GEMM go?  Ablations of bf3_gemm_nt_kernel at the first
-// tower layer's forward shape (M = 65536, K = 1696, N = 256) on random operands.
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics tools/exp/bf3_ablate.hip -o /tmp/bf3_ablate
+// GPU experiment (not product): where does a k-tile of the planes NT GEMM go?  Ablations of bf3_gemm_nt_pipe_kernel<16> and
+// bf3_gemm_rs_kernel at the first tower layer's forward shape (M = 65536, K = 1696, N = 256) on random operands.
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -mllvm -pragma-unroll-threshold=131072 \
+//            tools/exp/bf3_ablate.hip deep_recommenders_amd/csrc/h2_occ.hip -o tools/exp/bf3_ablate   (h2_occ.hip: rs_launch links against it)
 #include "../../deep_recommenders_amd/csrc/bf3_gemm.hip"
 #include <cstdio>
 #include <vector>
@@ -41,20 +42,6 @@ static float run_rs(const RsArgs& g, int grid, int reps) {
     return ms / reps * 1e3f;
 }
 
-template <int DBG>
-static float run(const NtArgs& g, int grid, int reps) {
-    hipEvent_t a, b;
-    (void)hipEventCreate(&a); (void)hipEventCreate(&b);
-    for (int i = 0; i < 2; ++i) hipLaunchKernelGGL((bf3_gemm_nt_kernel<2, 4, DBG>), dim3(grid), dim3(NTHREADS), 0, 0, g);
-    (void)hipEventRecord(a, 0);
-    for (int i = 0; i < reps; ++i) hipLaunchKernelGGL((bf3_gemm_nt_kernel<2, 4, DBG>), dim3(grid), dim3(NTHREADS), 0, 0, g);
-    (void)hipEventRecord(b, 0);
-    (void)hipEventSynchronize(b);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms / reps * 1e3f;
-}
-
 int main(int argc, char** argv) {
     const int64_t M = 65536; const int K = 1696;
     for (int N : {256, 1024}) {
@@ -63,19 +50,10 @@ int main(int argc, char** argv) {
         hipLaunchKernelGGL(fill_kernel, dim3(2048), dim3(256), 0, 0, (uint16_t*)A, 3 * M * K, 1u);
         hipLaunchKernelGGL(fill_kernel, dim3(2048), dim3(256), 0, 0, (uint16_t*)B, 3 * (int64_t)N * K, 7u);
         NtArgs g{A, M * K, K, B, (int64_t)N * K, K, M, N, K, C, N, nullptr, 0, nullptr, 0};
-        const int64_t tiles = ((M + 127) / 128) * ((N + 255) / 256);
-        const int grid = tiles < 256 ? (int)tiles : 256;
         const double fl = 2.0 * M * 1677 * N;
         float t;
-        t = run<0>(g, grid, 10); printf("N=%4d base            %8.1f us %6.1f TF/s\n", N, t, fl / t / 1e6);
-        t = run<1>(g, grid, 10); printf("N=%4d no DMA          %8.1f us %6.1f TF/s\n", N, t, fl / t / 1e6);
-        t = run<2>(g, grid, 10); printf("N=%4d no MFMA         %8.1f us %6.1f TF/s\n", N, t, fl / t / 1e6);
-        t = run<4>(g, grid, 10); printf("N=%4d DMA cache hits  %8.1f us %6.1f TF/s\n", N, t, fl / t / 1e6);
-        t = run<3>(g, grid, 10); printf("N=%4d no DMA no MFMA  %8.1f us %6.1f TF/s\n", N, t, fl / t / 1e6);
-        t = run<6>(g, grid, 10); printf("N=%4d hits, no MFMA   %8.1f us %6.1f TF/s\n", N, t, fl / t / 1e6);
         const int64_t ptiles = ((M + 127) / 128) * ((N + 127) / 128);
         const int pgrid = ptiles < 256 ? (int)ptiles : 256;
-        t = run_pipe<8, 0>(g, pgrid, 10); printf("N=%4d PIPE8 base            %8.1f us %6.1f TF/s\n", N, t, fl / t / 1e6);
         t = run_pipe<16, 0>(g, pgrid, 10); printf("N=%4d PIPE16 base           %8.1f us %6.1f TF/s\n", N, t, fl / t / 1e6);
         t = run_pipe<16, 1>(g, pgrid, 10); printf("N=%4d PIPE16 no DMA         %8.1f us %6.1f TF/s\n", N, t, fl / t / 1e6);
         t = run_pipe<16, 2>(g, pgrid, 10); printf("N=%4d PIPE16 no MFMA        %8.1f us %6.1f TF/s\n", N, t, fl / t / 1e6);

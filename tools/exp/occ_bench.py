@@ -1,6 +1,8 @@
 """EXPERIMENT driver (not product): the 16-wave f16x2 NT GEMM (csrc/h2_occ.hip) against the 8-wave register-split kernel.
 One setting per process (DR_H2_OCC=0 / 1 is read once by the library); `python tools/exp/occ_bench.py` runs both as subprocesses,
-compares their outputs bit for bit and prints the times."""
+compares their outputs bit for bit and prints the times.
+The library reads DR_H2_OCC only when it was built with DR_HIPCC_EXTRA=-DDR_OCC_ABLATE (as for occ_ablate.py and fused_k4_bench.py):
+the default build has no such switch and always takes the 16-wave kernel, so without that build both legs run the same kernel."""
 import os, sys, subprocess, hashlib
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 
