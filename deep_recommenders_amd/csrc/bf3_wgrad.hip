@@ -1,0 +1,420 @@
+// =====================================================================================================================
+// TN, "register split" wgrad:  dst[f][n] += scale * sum_r X[r][f] Y[r][n],  dstb[n] += scale * sum_r Y[r][n]
+// Both operands are fp32 ACTIVATIONS, reduction-major (x [R, F] and dy [R, N] as their producers write them); nothing is
+// pre-split.  A block owns a 256 (f) x 256 (n) tile of one reduction slice; each of its 8 waves owns 32 f x all 256 n.
+//   A (x):  every lane loads the 16 reduction elements of ITS column f for a k-tile with 16 dword loads (the 32 lanes of a half
+//           wave cover 128 contiguous bytes of one row) and splits them in registers -- the transposition MFMA's A operand
+//           needs ("8 consecutive k per lane") is free because the lane index runs along f.
+//   B (dy): the same loads with the lane index along n give every lane 8 consecutive r of its column, i.e. exactly one
+//           16-byte fragment chunk per plane: wave w splits the 32 columns 32 w .. 32 w + 31 of the tile once and writes the
+//           three planes as ds_write_b128 into the [n][32 r] image the fragment reads of the NT kernels use; the 8 waves'
+//           pieces make the tile that all of them read.  Two LDS stages: step g's MFMAs read stage g while stage g + 1 is
+//           written from registers loaded during step g - 1.
+// The in-kernel-split wgrad of dense.hip re-stages BOTH operands through the LDS per 128 x 128 tile; here x never touches
+// it and each dy element is split once per 256 rows of x.
+// Partials go to a padded workspace [split][tiles_f * 256][tiles_n * 256] (+ [split][tiles_n * 256] column sums): every store of
+// the epilogue is unconditional; a fixed-order reduce applies them (deterministic).
+// =====================================================================================================================
+// Cache-policy experiment (round 4): a stream that is read / written ONCE marked nontemporal so that it does not wash the weight
+// planes (and, in K4, the first-order lines) out of the L2 / Infinity Cache.  0 = default policy, 1 = nontemporal.
+#ifndef DR_NT_WGRAD_GATHER
+#define DR_NT_WGRAD_GATHER 0
+#endif
+#include "bf3_rs_core.h"
+
+namespace {
+
+using namespace drrs;
+
+struct TnRsArgs {
+    const float* X; int64_t ldx;
+    const float* Y; int64_t ldy;
+    int64_t R; int32_t F; int32_t N;
+    int64_t per; int32_t split;                  // reduction rows per slice (multiple of 32), number of slices
+    float* partial; float* colsum;               // [split][Fp][Np], [split][Np] (colsum may be null)
+    // GATHER form (the first layer of the DeepFM / DCN tower): X is never materialised -- column c < 64 nf of reduction row r is
+    // element (c & 63) of table row row_base[c >> 6] + ids_t[c >> 6][r] (zero for a missing id), columns [64 nf, F) come from
+    // dense_pad[r][c - 64 nf]
+    const int32_t* ids_t; const int64_t* row_base; const float* table; int32_t nf; const float* dense_pad;
+    // f16x2 mode: amax records of x (GATHER: the table's; x2 = the dense features', may be null) and of dy
+    const uint32_t* x_amax; const uint32_t* x2_amax; const uint32_t* y_amax;
+};
+
+// H2: the f16x2 operand mode (h2_split8): both operands split into two fp16 terms with their tensors' scales; the partials carry
+// s_x s_y and the reduce kernel divides it out.
+template <int GATHER, int H2 = 0>
+__global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
+    constexpr int NW = 8, BMF = 32 * NW, BN = 256, NT = BN / 32;
+    constexpr int NPL = RS_NPL<H2>, B_PLANE = RS_B_PLANE, STAGE = RS_STAGE<H2>;    // the dy image's two stages (bf3_rs_core.h)
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, hi = lane >> 5;
+    const int tiles_n = (g.N + BN - 1) / BN, tiles_f = (g.F + BMF - 1) / BMF;
+    const int per_slice = tiles_f * tiles_n;
+    const int Fp = tiles_f * BMF, Np = tiles_n * BN;
+    const int lid = xcd_remap(blockIdx.x, per_slice * g.split);         // consecutive logical ids share a reduction slice
+    const int slice = lid / per_slice, t = lid % per_slice;
+    const int f0 = (t / tiles_n) * BMF, n0 = (t % tiles_n) * BN;
+    const int64_t r_begin = (int64_t)slice * g.per;
+    int64_t r_end = r_begin + g.per;
+    if (r_end > g.R) r_end = g.R;
+    const int nk = (int)((r_end - r_begin + BK - 1) / BK);              // >= 1 by construction of split
+    const bool want_cs = g.colsum != nullptr && f0 == 0;
+    float h2_sx = 1.f, h2_sy = 1.f;
+    if constexpr (H2) {
+        float inv;
+        h2_prologue(g.x_amax, g.x2_amax, g.y_amax, h2_sx, h2_sy, inv);
+    }
+
+    // this lane's columns (clamped: columns past the edge only feed outputs nobody reads)
+    const int fcol = min(f0 + wave * 32 + l31, g.F - 1);
+    const int ncol = min(n0 + wave * 32 + l31, g.N - 1);
+    // fragment read addresses as in bf3_gemm_rs_kernel (bf3_gemm.hip): B row = 32 nt + l31, chunk (2 hi + s) ^ ((row >> 2) & 3)
+    const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)smem;
+    const int sw = rs_swizzle(l31);
+    unsigned b_addr[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) b_addr[s] = rs_frag_addr(lds0, l31, hi, sw, s);
+    // where this lane writes its own column's chunks: row 32 wave + l31 of the image, same swizzle
+    unsigned char* const wrow = smem + (wave * 32 + l31) * 64;
+
+    // raw operand values of one k-tile: element e = 8 s + j  <->  reduction row r0 + 16 hi + 8 s + j   (the k permutation of
+    // the RS kernels: lane half hi holds k = 16 hi .. 16 hi + 15, k-step s uses 16 hi + 8 s .. + 7 = chunk 2 hi + s)
+    float xa[16], yb[16];
+    // per-lane byte offset inside a k-tile's rows (32-bit) + a wave-uniform row pointer per load: one address register, the
+    // row stepping stays on the scalar unit
+    const unsigned xoff = (unsigned)((16 * hi * g.ldx + fcol) * 4), yoff = (unsigned)((16 * hi * g.ldy + ncol) * 4);
+    auto load_raw = [&](float (&dst)[16], const float* base, int64_t ld, unsigned voff, int64_t r0) {
+        if (r0 + BK <= r_end) {                                         // (wave-uniform) a full k-tile: no checks
+            const char* rowp = reinterpret_cast<const char*>(base + r0 * ld);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) dst[e] = *reinterpret_cast<const float*>(rowp + (int64_t)e * ld * 4 + voff);
+        } else {                                                        // the slice's last, partial k-tile (or past its end)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int64_t r = r0 + 16 * hi + e;
+                const bool ok = r < r_end;
+                const float v = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base + (ok ? r : r_end - 1) * ld) +
+                                                                (voff - (unsigned)(16 * hi * ld * 4)));
+                dst[e] = ok ? v : 0.f;
+            }
+        }
+    };
+    // GATHER: where this wave's 32 columns live.  A wave covers half a field's row (32 of its 64 dims: one 128-byte line per
+    // reduction row and lane half, exactly the lines the forward's gather fetched), or the dense features, or nothing (columns
+    // past F: a valid dummy source, the outputs are never read).  Every load stays unconditional.
+    const int c0w = f0 + wave * 32;
+    const bool w_field = GATHER && c0w < 64 * g.nf;
+    const bool w_dense = GATHER && !w_field && g.dense_pad != nullptr && c0w < 64 * g.nf + 32;
+    // One raw buffer resource per wave (its field's rows / the dense features / a dummy): the address of a load is then ONE 32-bit
+    // VALU operation, id * 256 + column (a field is below 2^24 rows = 4 GB, as in the fused forward), instead of 64-bit pointer
+    // arithmetic per lane and load.  The resource's range check does the masking: a missing id (-1) becomes offset 0xFFFFFF00 +
+    // column >= num_records and the hardware returns 0 -- no clamp, no select.  The 32 ids of a k-tile sit in the lanes so that
+    // DPP row_share:e hands every lane the id of ITS row e (lanes 0-31: rows 0-15 twice, lanes 32-63: rows 16-31 twice) -- one
+    // VALU move per load, no LDS shuffle.  (First cut: 64-bit pointers + ds_bpermute + clamp + select: +53 us on the kernel.)
+    const float* gptr = g.table;
+    unsigned gpitch = 0;                                                // bytes per source row
+    const int32_t* idrow = nullptr;
+    if (GATHER) {
+        if (w_field) {
+            const int fld = c0w >> 6;
+            gptr = g.table + g.row_base[fld] * 64 + (c0w & 32);
+            gpitch = 256;
+            idrow = g.ids_t + (int64_t)fld * g.R;
+        } else if (w_dense) {
+            gptr = g.dense_pad;
+            gpitch = 128;
+        }
+    }
+    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gptr), 0, (int)0xFFFFFF00u, 0x00020000);
+    const unsigned gcol = (unsigned)l31 * 4u;
+    const int id_lane = (lane & 15) + 16 * hi;                          // the row of the k-tile whose id this lane keeps
+    int idv = 0;                                                        // ids of the k-tile whose rows are fetched next
+    int xmask = -1;                                                     // validity of xa[e] (partial k-tiles only)
+    auto load_ids = [&](int64_t r0) -> int {
+        if (!w_field) return 0;                                         // (wave-uniform)
+        const int64_t r = r0 + id_lane < g.R ? r0 + id_lane : g.R - 1;
+        return idrow[r];
+    };
+    auto load_gather = [&](float (&dst)[16], int ids_of_tile, int64_t r0) {
+        const bool full = r0 + BK <= r_end;                             // (wave-uniform) all but a slice's last k-tile
+        int vm = -1;
+#define GATHER_ONE(E)                                                                                                   \
+        {                                                                                                                \
+            const int64_t r = r0 + 16 * hi + E;                                                                          \
+            unsigned idx;                                                                                                \
+            if (w_field) idx = (unsigned)__builtin_amdgcn_update_dpp(0, ids_of_tile, 0x150 + E, 0xf, 0xf, false);        \
+            else idx = (unsigned)(r < r_end ? r : r_end - 1);                                                            \
+            if (!full && !(r < r_end)) { idx = w_field ? 0x00FFFFFFu : idx; vm &= ~(1 << E); }                           \
+            dst[E] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(grsrc, (int)(idx * gpitch + gcol), 0, DR_NT_WGRAD_GATHER ? 2 : 0)); \
+        }
+        GATHER_ONE(0) GATHER_ONE(1) GATHER_ONE(2) GATHER_ONE(3) GATHER_ONE(4) GATHER_ONE(5) GATHER_ONE(6) GATHER_ONE(7)
+        GATHER_ONE(8) GATHER_ONE(9) GATHER_ONE(10) GATHER_ONE(11) GATHER_ONE(12) GATHER_ONE(13) GATHER_ONE(14) GATHER_ONE(15)
+#undef GATHER_ONE
+        if (!(w_field || w_dense)) vm = 0;                              // columns past F: zeros (their outputs are never read)
+        xmask = vm;
+    };
+    bf16x8 fa[2][3];
+    bf16x8 fb[4][3];                                                    // group q uses buffer q & 3, read two groups ahead
+    float cs = 0.f;
+    auto stage_b = [&](int stage) {                                     // yb -> three planes of this lane's column
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            bf16x8 p0, p1, p2;
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { v[j] = yb[8 * s + j]; cs += v[j]; }
+            if constexpr (H2) h2_split8v(v, h2_sy, p0, p1);
+            else rs_split8v(v, p0, p1, p2);
+            unsigned char* w = wrow + stage * STAGE + rs_chunk_off(hi, sw, s);
+            *reinterpret_cast<bf16x8*>(w) = p0;
+            *reinterpret_cast<bf16x8*>(w + B_PLANE) = p1;
+            if constexpr (!H2) *reinterpret_cast<bf16x8*>(w + 2 * B_PLANE) = p2;
+        }
+    };
+    auto read_b = [&](int buf, int stage, int q) {
+        const unsigned bb = b_addr[q >> 3] + stage * STAGE;
+        rs_read_frag<NPL>(fb[buf], bb, q & 7);
+    };
+    f32x16 acc[NT];
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc[tt][k] = 0.f;
+
+    // ---- prologue: B(0) into stage 0, A(0) and B(1) into registers -------------------------------------------------------------
+    load_raw(yb, g.Y, g.ldy, yoff, r_begin);
+    stage_b(0);
+    if (GATHER) {
+        idv = load_ids(r_begin);
+        load_gather(xa, idv, r_begin);
+        idv = load_ids(r_begin + BK);
+    } else {
+        load_raw(xa, g.X, g.ldx, xoff, r_begin);
+    }
+    load_raw(yb, g.Y, g.ldy, yoff, r_begin + BK);                       // (all zeros when nk == 1)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    read_b(0, 0, 0);
+    read_b(1, 0, 1);
+
+    for (int kt = 0; kt < nk; ++kt) {
+        const int stage = kt & 1;
+        // A of this k-tile -> bf16 terms; B of the next k-tile -> the other stage (its readers passed the barrier at the end of
+        // the previous step); the loads of the k-tile after that go into flight
+        {
+            float v[8];
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = (!GATHER || xmask == -1 || ((xmask >> (8 * s + j)) & 1)) ? xa[8 * s + j] : 0.f;
+                if constexpr (H2) h2_split8v(v, h2_sx, fa[s][0], fa[s][1]);
+                else rs_split8v(v, fa[s][0], fa[s][1], fa[s][2]);
+            }
+        }
+        if (kt + 1 < nk) stage_b(stage ^ 1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (GATHER) {
+            // (the 16 id shuffles are LDS operations: they and the loads they address stay between these two scheduling
+            // barriers, i.e. in front of every fragment read the counted lgkmcnt waits of the MFMA loop reckon with)
+            load_gather(xa, idv, r_begin + (int64_t)(kt + 1) * BK);
+            idv = load_ids(r_begin + (int64_t)(kt + 2) * BK);
+        } else {
+            load_raw(xa, g.X, g.ldx, xoff, r_begin + (int64_t)(kt + 1) * BK);
+        }
+        load_raw(yb, g.Y, g.ldy, yoff, r_begin + (int64_t)(kt + 2) * BK);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            if (q < 14) {
+                rs_wait_frag<NPL, NPL>(fb[q & 3]);                     // the next group's NPL reads may fly
+                read_b((q + 2) & 3, stage, q + 2);
+            } else if (q == 14) {
+                // groups 14 and 15 are in registers, this wave is done reading this stage and its ds_writes of the next one
+                // have retired (lgkmcnt(0) covers both): publish
+                rs_wait_frag<NPL, 0>(fb[2]);
+                asm volatile("s_barrier" ::: "memory");
+                if (kt + 1 < nk) read_b(0, stage ^ 1, 0);
+            } else {
+                if (kt + 1 < nk) read_b(1, stage ^ 1, 1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int term = 0; term < RS_TERMS<H2>; ++term) acc[q & 7] = rs_mma_term<H2>(term, fa[q >> 3], fb[q & 3], acc[q & 7]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    // ---- epilogue: partial tile (padded workspace: unconditional stores); C/D layout: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 hi
+    float* out = g.partial + ((int64_t)slice * Fp + f0 + wave * 32 + 4 * hi) * Np + n0 + l31;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) out[(int64_t)((reg & 3) + 8 * (reg >> 2)) * Np + nt * 32] = acc[nt][reg];
+    if (want_cs) {
+        cs += __shfl_xor(cs, 32, 64);
+        if (hi == 0) g.colsum[(int64_t)slice * Np + n0 + wave * 32 + l31] = cs;
+    }
+}
+
+// dst[f][n] += scale * sum_s partial[s][f][n]  (fixed order);  dstb[n] += scale * sum_s colsum[s][n]
+__global__ __launch_bounds__(256) void bf3_tn_rs_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ colsum,
+                                                               int32_t split, int32_t F, int32_t N, int32_t Fp, int32_t Np,
+                                                               float scale, float* __restrict__ dst, int64_t ld,
+                                                               float* __restrict__ dstb, const uint32_t* __restrict__ x_amax = nullptr,
+                                                               const uint32_t* __restrict__ x2_amax = nullptr,
+                                                               const uint32_t* __restrict__ y_amax = nullptr) {
+    const int64_t total = (int64_t)F * N, stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t ps = (int64_t)Fp * Np;
+    float wscale = scale;                                               // f16x2 partials carry s_x s_y (powers of two: exact)
+    if (x_amax != nullptr) {
+        float sx, ix, sy, iy;
+        h2_scale_of(max(x_amax[0], x2_amax != nullptr ? x2_amax[0] : 0u), sx, ix);
+        h2_scale_of(y_amax[0], sy, iy);
+        wscale = scale * (ix * iy);
+    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int64_t f = i / N;
+        const int n = (int)(i - f * N);
+        const float* p = partial + f * Np + n;
+        float acc = 0.f;
+        int s = 0;
+        for (; s + 4 <= split; s += 4) {             // four loads in flight, summed in slice order
+            const float v0 = p[s * ps], v1 = p[(s + 1) * ps], v2 = p[(s + 2) * ps], v3 = p[(s + 3) * ps];
+            acc = (((acc + v0) + v1) + v2) + v3;
+        }
+        for (; s < split; ++s) acc += p[s * ps];
+        dst[f * ld + n] = fmaf(wscale, acc, dst[f * ld + n]);
+    }
+    if (blockIdx.x == 0 && colsum != nullptr && dstb != nullptr)
+        for (int n = threadIdx.x; n < N; n += blockDim.x) {
+            float acc = 0.f;
+            for (int s = 0; s < split; ++s) acc += colsum[(int64_t)s * Np + n];
+            dstb[n] = fmaf(scale, acc, dstb[n]);
+        }
+}
+
+void tn_rs_plan(int64_t R, int32_t F, int32_t N, int& split, int64_t& per, int& Fp, int& Np) {
+    const int tf = (F + 255) / 256, tn = (N + 255) / 256;
+    Fp = tf * 256;
+    Np = tn * 256;
+    int64_t sp = 256 / ((int64_t)tf * tn);                              // about one block per CU
+    const int64_t max_split = (R + 16 * BK - 1) / (16 * BK);            // at least 16 k-tiles per slice
+    if (sp > max_split) sp = max_split;
+    if (sp < 1) sp = 1;
+    per = ((R + sp - 1) / sp + BK - 1) / BK * BK;
+    split = (int)((R + per - 1) / per);                                 // every slice non-empty
+}
+}  // namespace
+
+extern "C" int64_t dr_bf3_wgrad_workspace_bytes(int64_t R, int32_t F, int32_t N) {
+    if (R <= 0 || F <= 0 || N <= 0) return 0;
+    int split, Fp, Np;
+    int64_t per;
+    tn_rs_plan(R, F, N, split, per, Fp, Np);
+    return ((int64_t)split * Fp * Np + (int64_t)split * Np) * (int64_t)sizeof(float);
+}
+
+// dstW[f][n] += scale * sum_r x[r][f] dy[r][n];  dstb[n] += scale * sum_r dy[r][n] (dstb may be NULL).  x [R, F], dy [R, N] fp32
+// row-major; the bf16x3 product mode, deterministic (fixed-order reduce over the reduction slices).
+static int wgrad_impl(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, int64_t R, int32_t F, int32_t N,
+                      float scale, float* dstW, int64_t ld_w, float* dstb, void* workspace, int64_t workspace_bytes,
+                      dr_stream_t stream, const uint32_t* x_amax = nullptr, const uint32_t* dy_amax = nullptr) {
+    if (R <= 0 || F <= 0 || N <= 0) return DR_EINVAL;
+    if (!x || !dy || !dstW || !workspace || ld_x < F || ld_dy < N || ld_w < N) return DR_EINVAL;
+    if (workspace_bytes < dr_bf3_wgrad_workspace_bytes(R, F, N)) return DR_EINVAL;
+    int split, Fp, Np;
+    int64_t per;
+    tn_rs_plan(R, F, N, split, per, Fp, Np);
+    float* partial = static_cast<float*>(workspace);
+    float* colsum = partial + (int64_t)split * Fp * Np;
+    TnRsArgs g{x, ld_x, dy, ld_dy, R, F, N, per, split, partial, dstb != nullptr ? colsum : nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+               x_amax, nullptr, dy_amax};
+    const int grid = (Fp / 256) * (Np / 256) * split;
+    if (x_amax != nullptr) hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<0, 1>), dim3(grid), dim3(512), 0, dr_s(stream), g);
+    else hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<0, 0>), dim3(grid), dim3(512), 0, dr_s(stream), g);
+    hipLaunchKernelGGL(bf3_tn_rs_reduce_kernel, dim3(dr_grid_for((int64_t)F * N, 256)), dim3(256), 0, dr_s(stream), partial,
+                       dstb != nullptr ? colsum : nullptr, split, F, N, Fp, Np, scale, dstW, ld_w, dstb, x_amax,
+                       static_cast<const uint32_t*>(nullptr), dy_amax);
+    DR_CHECK_LAUNCH();
+    return DR_OK;
+}
+
+extern "C" int dr_bf3_wgrad(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, int64_t R, int32_t F, int32_t N,
+                            float scale, float* dstW, int64_t ld_w, float* dstb, void* workspace, int64_t workspace_bytes,
+                            dr_stream_t stream) {
+    return wgrad_impl(x, ld_x, dy, ld_dy, R, F, N, scale, dstW, ld_w, dstb, workspace, workspace_bytes, stream);
+}
+
+// dr_bf3_wgrad in the f16x2 operand mode (h2_split8): x_amax / dy_amax are the operands' amax records (dr_h2_amax, or a producer's).
+// Same workspace, same fixed-order reduce.
+extern "C" int dr_h2_wgrad(const float* x, int64_t ld_x, const uint32_t* x_amax, const float* dy, int64_t ld_dy, const uint32_t* dy_amax,
+                           int64_t R, int32_t F, int32_t N, float scale, float* dstW, int64_t ld_w, float* dstb, void* workspace,
+                           int64_t workspace_bytes, dr_stream_t stream) {
+    if (!x_amax || !dy_amax) return DR_EINVAL;
+    return wgrad_impl(x, ld_x, dy, ld_dy, R, F, N, scale, dstW, ld_w, dstb, workspace, workspace_bytes, stream, x_amax, dy_amax);
+}
+
+// The same wgrad for the FIRST tower layer, whose x = concat(field embeddings, dense features) is never read from a buffer: the
+// kernel gathers it from the tables (GATHER form of TnRsArgs; D = 64).  ids_t [nf][R] int32: the batch's bucket ids, field-major
+// (dr_ids_transpose_i32), -1 = missing; dense_pad [R, 32] zero-padded dense features (NULL iff F == 64 nf).  With this the forward
+// need not store `concat` at all (keras/models/ranking/deepfm.py:44-45: stack / concat become pure fiction).
+static int wgrad_emb_impl(const int32_t* ids_t, int64_t R, int32_t nf, const int64_t* row_base, const float* table, int32_t D,
+                          const float* dense_pad, const float* dy, int64_t ld_dy, int32_t F, int32_t N, float scale, float* dstW,
+                          int64_t ld_w, float* dstb, void* workspace, int64_t workspace_bytes, int32_t parts, dr_stream_t stream,
+                          const uint32_t* table_amax = nullptr, const uint32_t* dense_amax = nullptr, const uint32_t* dy_amax = nullptr) {
+    if (R <= 0 || F <= 0 || N <= 0 || nf <= 0) return DR_EINVAL;
+    if (table_amax != nullptr && (!dy_amax || (F > 64 * nf && !dense_amax))) return DR_EINVAL;
+    if (D != 64 || F < 64 * nf || F > 64 * nf + 32) return DR_ESHAPE;
+    if (!ids_t || !row_base || !table || !dy || !dstW || !workspace || ld_dy < N || ld_w < N) return DR_EINVAL;
+    if (F > 64 * nf && !dense_pad) return DR_EINVAL;
+    if (workspace_bytes < dr_bf3_wgrad_workspace_bytes(R, F, N)) return DR_EINVAL;
+    int split, Fp, Np;
+    int64_t per;
+    tn_rs_plan(R, F, N, split, per, Fp, Np);
+    float* partial = static_cast<float*>(workspace);
+    float* colsum = partial + (int64_t)split * Fp * Np;
+    TnRsArgs g{nullptr, 0, dy, ld_dy, R, F, N, per, split, partial, dstb != nullptr ? colsum : nullptr, ids_t, row_base, table, nf,
+               F > 64 * nf ? dense_pad : nullptr, table_amax, F > 64 * nf ? dense_amax : nullptr, dy_amax};
+    const int grid = (Fp / 256) * (Np / 256) * split;
+    if (parts & 1) {
+        if (table_amax != nullptr) hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<1, 1>), dim3(grid), dim3(512), 0, dr_s(stream), g);
+        else hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<1, 0>), dim3(grid), dim3(512), 0, dr_s(stream), g);
+    }
+    if (parts & 2)
+        hipLaunchKernelGGL(bf3_tn_rs_reduce_kernel, dim3(dr_grid_for((int64_t)F * N, 256)), dim3(256), 0, dr_s(stream), partial,
+                           dstb != nullptr ? colsum : nullptr, split, F, N, Fp, Np, scale, dstW, ld_w, dstb, table_amax,
+                           F > 64 * nf ? dense_amax : static_cast<const uint32_t*>(nullptr), dy_amax);
+    DR_CHECK_LAUNCH();
+    return DR_OK;
+}
+
+extern "C" int dr_bf3_wgrad_emb(const int32_t* ids_t, int64_t R, int32_t nf, const int64_t* row_base, const float* table, int32_t D,
+                                const float* dense_pad, const float* dy, int64_t ld_dy, int32_t F, int32_t N, float scale, float* dstW,
+                                int64_t ld_w, float* dstb, void* workspace, int64_t workspace_bytes, dr_stream_t stream) {
+    return wgrad_emb_impl(ids_t, R, nf, row_base, table, D, dense_pad, dy, ld_dy, F, N, scale, dstW, ld_w, dstb, workspace, workspace_bytes,
+                          3, stream);
+}
+
+// In two halves: parts = 1 the split-K GEMM into the workspace, parts = 2 the fixed-order reduce that applies it (dstW += scale * sum,
+// dstb likewise), 3 = both.  Part 2 may run on another stream (the engine puts it in front of the weight-plane refresh, which lives
+// there already); it must finish before anything reads dstW / dstb and before the next part 1 over the same workspace.
+extern "C" int dr_bf3_wgrad_emb_parts(const int32_t* ids_t, int64_t R, int32_t nf, const int64_t* row_base, const float* table, int32_t D,
+                                      const float* dense_pad, const float* dy, int64_t ld_dy, int32_t F, int32_t N, float scale,
+                                      float* dstW, int64_t ld_w, float* dstb, void* workspace, int64_t workspace_bytes, int32_t parts,
+                                      dr_stream_t stream) {
+    if (parts < 1 || parts > 3) return DR_EINVAL;
+    return wgrad_emb_impl(ids_t, R, nf, row_base, table, D, dense_pad, dy, ld_dy, F, N, scale, dstW, ld_w, dstb, workspace, workspace_bytes,
+                          parts, stream);
+}
+
+// dr_bf3_wgrad_emb_parts in the f16x2 operand mode: table_amax as in dr_h2_emb_linear_fwd, dense_amax the record of dense_pad (required
+// iff F > 64 nf), dy_amax the record of dy.  The records must be the same for part 1 and part 2 of one product.
+extern "C" int dr_h2_wgrad_emb(const int32_t* ids_t, int64_t R, int32_t nf, const int64_t* row_base, const float* table, int32_t D,
+                               const uint32_t* table_amax, const float* dense_pad, const uint32_t* dense_amax, const float* dy, int64_t ld_dy,
+                               const uint32_t* dy_amax, int32_t F, int32_t N, float scale, float* dstW, int64_t ld_w, float* dstb,
+                               void* workspace, int64_t workspace_bytes, int32_t parts, dr_stream_t stream) {
+    if (parts < 1 || parts > 3 || !table_amax || !dy_amax) return DR_EINVAL;
+    return wgrad_emb_impl(ids_t, R, nf, row_base, table, D, dense_pad, dy, ld_dy, F, N, scale, dstW, ld_w, dstb, workspace, workspace_bytes,
+                          parts, stream, table_amax, dense_amax, dy_amax);
+}

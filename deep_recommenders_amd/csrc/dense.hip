@@ -25,6 +25,7 @@
 // Consecutive workgroup ids are remapped so that the tiles sharing an A row-panel run on the same XCD
 // (same L2): dispatch places block b on XCD b % 8.
 #include "dr_common.h"
+#include "rs_args.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 #include <atomic>
 #include <cstdlib>
@@ -1561,18 +1562,8 @@ __global__ __launch_bounds__(256) void sum_blocks_kernel(const float* __restrict
     if (threadIdx.x == 0) out[0] = (float)((red[0] + red[1]) + (red[2] + red[3]));
 }
 
-// f16x2 path of the two score passes (round 5): bf3_gemm.hip's register-split kernel with the LSE / softmax-gradient epilogues; the
+// f16x2 path of the two score passes (round 5): bf3_gemm.hip's register-split kernel with the LSE / softmax-gradient epilogues (rs_args.h); the
 // candidates' two fp16 planes and both amax records live behind the partials in the workspace.
-int dr_h2_inbatch_lse(const float* q, int64_t ldq, const uint32_t* q_amax, const void* c_planes, int64_t c_ps, int64_t c_ld,
-                      const uint32_t* c_amax, int64_t B, int32_t D, const float* cand_prob, const int64_t* cand_ids, float inv_t,
-                      float* part_m, float* part_l, float* pos, dr_stream_t stream);
-int dr_h2_inbatch_smgrad(const float* q, int64_t ldq, const uint32_t* q_amax, const void* c_planes, int64_t c_ps, int64_t c_ld,
-                         const uint32_t* c_amax, int64_t B, int32_t D, const float* cand_prob, const int64_t* cand_ids, float inv_t,
-                         const float* row_lse, const float* sample_weight, float d_loss, float* G, int64_t ld_g, dr_stream_t stream);
-extern "C" int dr_h2_amax(const float* src, int64_t ld, int64_t R, int32_t C, uint32_t* amax, int32_t reset, dr_stream_t stream);
-extern "C" int dr_h2_split(const float* src, int64_t ld_src, int64_t R, int32_t C, void* planes, int64_t plane_stride, int64_t ld_planes,
-                           int64_t row_offset, int64_t col_offset, int32_t transpose, const uint32_t* amax, dr_stream_t stream);
-
 constexpr int IB_H2_MAX_D = 512;                        // the workspace is sized without knowing D: planes budgeted for D <= 512
 static int64_t ib_parts_floats(int64_t B) {
     const int64_t tiles_n = (B + BN - 1) / BN;

@@ -10,6 +10,7 @@
 // (expected k*ln(N/k) insertions per row over the whole corpus), insertion = one rank count (wave sum) + a
 // lane shift (__shfl_up).  Ties resolve to the lower candidate index, as tf.math.top_k does.
 #include "dr_common.h"
+#include "rs_args.h"
 #include "topk_list.h"
 #include <math.h>
 
@@ -296,31 +297,6 @@ extern "C" int64_t dr_topk_workspace_bytes(int64_t Bq, int64_t N, int32_t k) {
     const int64_t scan = topk_scan_for(chunk, N);
     return topk_hdr_bytes(Bq) + Bq * scan * 8 + topk_planes_bytes(scan);
 }
-
-int dr_scores_nt_filter(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t M, int32_t N, int32_t D,
-                        const float* tau, float* cand_s, int32_t* cand_c, int32_t* cand_cnt, int64_t cand_cap,
-                        dr_stream_t stream);        // dense.hip
-int dr_bf3_scores_filter(const float* a, int64_t lda, const void* b_planes, int64_t b_plane_stride, int64_t b_ld, int64_t M, int32_t N,
-                         int32_t K, const float* tau, float* cand_s, int32_t* cand_c, int32_t* cand_cnt, int64_t cand_cap,
-                         dr_stream_t stream);       // bf3_gemm.hip
-extern "C" int dr_bf3_split(const float* src, int64_t ld_src, int64_t R, int32_t C, void* planes, int64_t plane_stride, int64_t ld_planes,
-                            int64_t row_offset, int64_t col_offset, int32_t transpose, dr_stream_t stream);
-extern "C" int dr_bf3_linear_nt(const float* A, int64_t lda, const void* b_planes, int64_t b_plane_stride, int64_t b_ld, int64_t M,
-                                int32_t N, int32_t K, const float* bias, int32_t act, const float* mask, int64_t ld_mask,
-                                int32_t accumulate, float* C, int64_t ldc, dr_stream_t stream);
-extern "C" int32_t dr_get_gemm_mode(void);
-extern "C" int32_t dr_get_gemm_split(void);
-// the same three in the f16x2 operand mode (bf3_gemm.hip; include/dr_hotpath.h "f16x2 operand mode")
-int dr_h2_scores_filter(const float* a, int64_t lda, const uint32_t* a_amax, const void* b_planes, int64_t b_plane_stride, int64_t b_ld,
-                        const uint32_t* b_amax, int64_t M, int32_t N, int32_t K, const float* tau, float* cand_s, int32_t* cand_c,
-                        int32_t* cand_cnt, int64_t cand_cap, dr_stream_t stream);
-extern "C" int dr_h2_amax(const float* src, int64_t ld, int64_t R, int32_t C, uint32_t* amax, int32_t reset, dr_stream_t stream);
-extern "C" int dr_h2_split(const float* src, int64_t ld_src, int64_t R, int32_t C, void* planes, int64_t plane_stride, int64_t ld_planes,
-                           int64_t row_offset, int64_t col_offset, int32_t transpose, const uint32_t* amax, dr_stream_t stream);
-extern "C" int dr_h2_linear_nt(const float* A, int64_t lda, const uint32_t* a_amax, const void* b_planes, int64_t b_plane_stride,
-                               int64_t b_ld, const uint32_t* b_amax, int64_t M, int32_t N, int32_t K, const float* bias, int32_t act,
-                               const float* mask, int64_t ld_mask, int32_t accumulate, float* C, int64_t ldc, uint32_t* c_amax,
-                               dr_stream_t stream);
 
 __global__ __launch_bounds__(256) void zero_i32_kernel(int32_t* __restrict__ p, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,8 +1,8 @@
-// Argument block of the register-split / occupancy GEMM kernels and the f16x2 operand format's helpers, shared by bf3_gemm.hip (the
-// 8-wave register-split kernels) and h2_occ.hip (the 16-wave kernels of round 6).
+// Argument block of the register-split / occupancy GEMM kernels and the f16x2 operand format's helpers, shared by bf3_gemm.hip, bf3_emb_linear.hip and
+// bf3_wgrad.hip (the 8-wave register-split kernels) and h2_occ.hip (the 16-wave kernels of round 6); and the library's internal cross-file entry
+// points (C++ linkage: not part of include/dr_hotpath.h), declared here once for their definers and their callers.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "dr_common.h"
 
 namespace drrs {
 
@@ -71,3 +71,23 @@ __device__ __forceinline__ void h2_mode_on() { __builtin_amdgcn_s_setreg(1 | (23
 int occ_nt_launch(const RsArgs& g, hipStream_t stream);
 
 }  // namespace drrs
+
+// ---- internal cross-file entry points ---------------------------------------------------------------------------------------
+// dense.hip: scores = a @ b^T for two reduction-contiguous fp32 operands, filtered against tau into per-row candidate lists
+int dr_scores_nt_filter(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t M, int32_t N, int32_t D,
+                        const float* tau, float* cand_s, int32_t* cand_c, int32_t* cand_cnt, int64_t cand_cap,
+                        dr_stream_t stream);
+// bf3_gemm.hip: the same filter on the register-split kernel, B = a corpus chunk as planes (bf16x3, f16x2); retrieval.hip's top-K scan
+int dr_bf3_scores_filter(const float* a, int64_t lda, const void* b_planes, int64_t b_plane_stride, int64_t b_ld, int64_t M, int32_t N,
+                         int32_t K, const float* tau, float* cand_s, int32_t* cand_c, int32_t* cand_cnt, int64_t cand_cap,
+                         dr_stream_t stream);
+int dr_h2_scores_filter(const float* a, int64_t lda, const uint32_t* a_amax, const void* b_planes, int64_t b_plane_stride, int64_t b_ld,
+                        const uint32_t* b_amax, int64_t M, int32_t N, int32_t K, const float* tau, float* cand_s, int32_t* cand_c,
+                        int32_t* cand_cnt, int64_t cand_cap, dr_stream_t stream);
+// bf3_gemm.hip: the in-batch softmax's two score passes on the register-split f16x2 kernel; dense.hip's dr_inbatch_softmax_*
+int dr_h2_inbatch_lse(const float* q, int64_t ldq, const uint32_t* q_amax, const void* c_planes, int64_t c_ps, int64_t c_ld,
+                      const uint32_t* c_amax, int64_t B, int32_t D, const float* cand_prob, const int64_t* cand_ids, float inv_t,
+                      float* part_m, float* part_l, float* pos, dr_stream_t stream);
+int dr_h2_inbatch_smgrad(const float* q, int64_t ldq, const uint32_t* q_amax, const void* c_planes, int64_t c_ps, int64_t c_ld,
+                         const uint32_t* c_amax, int64_t B, int32_t D, const float* cand_prob, const int64_t* cand_ids, float inv_t,
+                         const float* row_lse, const float* sample_weight, float d_loss, float* G, int64_t ld_g, dr_stream_t stream);

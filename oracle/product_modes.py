@@ -6,7 +6,7 @@ fp64 product within a tolerance.  This file restates how the kernels FORM an fp3
 tolerances the GPU tests use are pinned by a CPU test that runs everywhere (tests/test_product_modes_model.py):
 
   bf16x3  x = x0 + x1 + x2 exactly (three bf16 terms), a b ~ a0b2 + a1b1 + a2b0 + a0b1 + a1b0 + a0b0      (csrc/bf3_split.h)
-  f16x2   x s = h + l (two fp16 terms, 22 bits), s = 2^(140 - e) from the tensor's amax record,             (csrc/bf3_gemm.hip:
+  f16x2   x s = h + l (two fp16 terms, 22 bits), s = 2^(140 - e) from the tensor's amax record,             (csrc/rs_args.h, bf3_rs_core.h:
           a b ~ (h_a l_b + l_a h_b + h_a h_b) / (s_a s_b)                                                     h2_scale_of / h2_split8)
 
 Accumulation is modelled as fp32 adds of 16-deep blocks of exact products (one MFMA's reduction depth), terms in the kernels' order.
@@ -23,7 +23,7 @@ def amax_bits(x):
 
 
 def h2_scale_of(bits):
-    """(s, 1/s) exactly as the kernels derive them from a record (bf3_gemm.hip: h2_scale_of)."""
+    """(s, 1/s) exactly as the kernels derive them from a record (rs_args.h: h2_scale_of)."""
     e = (int(bits) >> 23) & 0xFF                      # max |x| < 2^(e - 126)
     e = min(max(e, 20), 250)
     s = np.array((267 - e) << 23, dtype=np.uint32).view(np.float32)

@@ -2,6 +2,7 @@
 // bf3_gemm_rs_kernel at the first tower layer's forward shape (M = 65536, K = 1696, N = 256) on random operands.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -mllvm -pragma-unroll-threshold=131072 \
 //            tools/exp/bf3_ablate.hip deep_recommenders_amd/csrc/h2_occ.hip -o tools/exp/bf3_ablate   (h2_occ.hip: rs_launch links against it)
+#include "../../deep_recommenders_amd/csrc/bf3_planes.hip"
 #include "../../deep_recommenders_amd/csrc/bf3_gemm.hip"
 #include <cstdio>
 #include <vector>

@@ -5,7 +5,7 @@
 //   stream_dwordx4     plain coalesced global_load_dwordx4 of the whole buffer                (the guide's reference pattern)
 //   gather_ldsdma      struct buffer_load ... lds, 16 B / lane, lane -> (row = lane >> 3, chunk = lane & 7) of a random
 //                      permutation of 256-byte rows, half row h of every row -- the fused kernel's instruction and mapping
-//                      (csrc/bf3_gemm.hip issue_gather)
+//                      (csrc/bf3_emb_linear.hip issue_gather)
 //   gather_ldsdma_both the same with both half rows fetched by consecutive instructions
 // Run under `rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv`; tools/exp/ldsdma_fetch_calib.sh prints
 // FETCH_SIZE * 1024 / known bytes per kernel (1.0 = tallied in full, 0.5 = needs the x2).
