@@ -881,7 +881,7 @@ __global__ __launch_bounds__(256) void adam_catchup_rows_kernel(const int64_t* _
 extern "C" int dr_adam_catchup_rows(const int64_t* ids, int64_t n, int32_t F, const int64_t* row_base, int32_t D, float* table,
                                     float* m_table, float* v_table, float* lin_w, float* m_lin, float* v_lin, int32_t* row_step,
                                     int32_t upto, int32_t stamp, float lr, float beta1, float beta2, float eps, dr_stream_t stream) {
-    if (n < 0 || F <= 0 || D < 4 || (D & 3) || upto < 0 || stamp < upto) return DR_EINVAL;
+    if (n < 0 || F <= 0 || D < 4 || D > 256 || (D & 3) || upto < 0 || stamp < upto) return DR_EINVAL;      // (D: as every embedding kernel)
     if (n == 0) return DR_OK;
     if (!ids || !row_base || !table || !m_table || !v_table || !row_step) return DR_EINVAL;
     if (lin_w != nullptr && (!m_lin || !v_lin)) return DR_EINVAL;

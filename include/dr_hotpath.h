@@ -289,7 +289,8 @@ int dr_emb_pool_bwd_sorted_adam_ex(const int64_t* ids, const int64_t* row_base, 
  * missing) to `upto` steps by replaying their missed decay-only steps  m *= b1 ; v *= b2 ; w -= lr_s m / (sqrt(v) + eps)
  * (lr_s = lr sqrt(1 - b2^s) / (1 - b1^s)) in order, and stamps them `stamp`.  Before the forward of step t: upto = t - 1,
  * stamp = t, then dr_emb_pool_bwd_sorted_adam applies step t -- every value the model reads equals TF's dense update.  To
- * export the tables: upto = stamp = steps taken, over all rows.  One replayer per row and call (atomic exchange of the stamp). */
+ * export the tables: upto = stamp = steps taken, over all rows.  One replayer per row and call (atomic exchange of the stamp).
+ * D: 4 .. 256, a multiple of 4, as for the kernels that share the tables (DR_EINVAL otherwise). */
 int dr_adam_catchup_rows(const int64_t* ids, int64_t n, int32_t F, const int64_t* row_base, int32_t D, float* table,
                          float* m_table, float* v_table, float* lin_w, float* m_lin, float* v_lin, int32_t* row_step,
                          int32_t upto, int32_t stamp, float lr, float beta1, float beta2, float eps, dr_stream_t stream);
