@@ -173,6 +173,13 @@ SIGNATURES = {
     "dr_add_layernorm_bwd": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _i64, _p],
     "dr_token_embedding_fwd": [_p, _i64, _i32, _p, _i64, _i32, _p, _f32, _u64, _p, _i64, _p],
     "dr_token_embedding_bwd": [_p, _p, _i64, _i64, _i32, _p, _i64, _f32, _u64, _p, _p],
+    "dr_dice_fwd": [_p, _i64, _p, _i64, _i32, _f32, _p, _i64, _p],
+    "dr_dice_bwd_workspace_bytes": [_i64, _i32],
+    "dr_dice_bwd": [_p, _i64, _p, _p, _i64, _i64, _i32, _f32, _p, _i64, _p, _p, _i64, _p],
+    "dr_din_pool_fwd": [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _p, _i64, _p, _p],
+    "dr_din_pool_bwd_workspace_bytes": [_i64, _i32, _i32, _i32],
+    "dr_din_pool_bwd": [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _i32, _f32,
+                        _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p],
     "dr_version": [],
     "dr_set_gemm_mode": [_i32],
     "dr_get_gemm_mode": [],
@@ -192,7 +199,8 @@ _RESTYPE = {"dr_version": ctypes.c_char_p, "dr_shard_bucket_workspace_bytes": ct
             "dr_linear_bwd_dw_grouped_workspace_bytes": ctypes.c_int64, "dr_mse_workspace_bytes": ctypes.c_int64,
             "dr_csr_plan_bytes": ctypes.c_int64, "dr_csr_plan_workspace_bytes": ctypes.c_int64,
             "dr_csr_spmm_workspace_bytes": ctypes.c_int64, "dr_csr_transpose_workspace_bytes": ctypes.c_int64,
-            "dr_add_layernorm_bwd_workspace_bytes": ctypes.c_int64}
+            "dr_add_layernorm_bwd_workspace_bytes": ctypes.c_int64,
+            "dr_dice_bwd_workspace_bytes": ctypes.c_int64, "dr_din_pool_bwd_workspace_bytes": ctypes.c_int64}
 
 DR_OK, DR_EINVAL, DR_ELAUNCH, DR_ESHAPE = 0, -1, -2, -3
 _ERR = {DR_EINVAL: "DR_EINVAL (bad argument)", DR_ELAUNCH: "DR_ELAUNCH (HIP launch error)",

@@ -769,3 +769,50 @@ def global_average_pooling_1d(x):
         _POOL_CACHE.clear()
         _POOL_CACHE[key] = SparseAdjacency._from_device(row_ptr, col, val, (B, B * L))
     return aggregate(_POOL_CACHE[key], x.reshape(B * L, C))
+
+
+# ---- DIN: Dice and the fused interest pooling (csrc/din.hip) ----------------------------------------------------------------------------
+class _DiceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, alpha, eps):
+        ctx.eps = eps
+        ctx.save_for_backward(x, alpha)
+        return ops.dice_fwd(x, alpha, eps)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, alpha = ctx.saved_tensors
+        dx, dalpha = ops.dice_bwd(x, alpha, dy, ctx.eps)
+        return dx, dalpha, None
+
+
+def dice(x, alpha, eps=1e-8):
+    """Dice over the rows of x [M, N] with the per-feature PReLU parameter alpha [N] (din.py:88-130 of the reference, literally: the
+    standard deviation gets a second square root).  Where a row is constant (always for N == 1) the gradient's term through the
+    standard deviation is taken as zero; TensorFlow returns NaN there."""
+    return _DiceFn.apply(x, alpha, float(eps))
+
+
+class _DinPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, query, keys, mask, W, b, w_out, b_out, mode, act, alpha, eps):
+        out, scores = ops.din_pool_fwd(query, keys, mask, W, b, w_out, b_out, mode, act, alpha, eps)
+        ctx.cfg = (mode, act, eps, w_out.shape)
+        ctx.save_for_backward(query, keys, mask, W, b, w_out, b_out, alpha)
+        return out, scores
+
+    @staticmethod
+    def backward(ctx, d_out, d_scores):
+        query, keys, mask, W, b, w_out, b_out, alpha = ctx.saved_tensors
+        mode, act, eps, wo_shape = ctx.cfg
+        d_q, d_k, dW, db, d_wo, d_bo, dalpha = ops.din_pool_bwd(query, keys, mask, W, b, w_out, b_out, mode, act, d_out, d_scores, alpha, eps)
+        return d_q, d_k, None, dW, db, d_wo.reshape(wo_shape), d_bo, None, None, (dalpha if alpha is not None else None), None
+
+
+def din_interest_pooling(query, keys, mask, W, b, w_out, b_out, mode, act, alpha=None, eps=1e-8):
+    """(out [B, D], scores [B, T]): DIN's local activation unit Dense(1)(act(concat([q, k, inter(q, k)]) W + b)) scored for every key
+    keys[b, t] against query[b], zero where mask[b, t] == 0 (mask None: all valid), and out[b] = sum_t scores[b, t] keys[b, t] -- no
+    softmax, as in the paper.  mode 0 / 1 / 2: no interacter / q - k / q * k; act 0..3 as in mlp, 4 = Dice over the hidden units with
+    alpha [U] and eps.  Masked keys are skipped, not multiplied by zero: what they hold reaches no result and their gradient is exactly
+    0.  One kernel forward; the backward recomputes the hidden layer and keeps only its [B * T, U] gradient."""
+    return _DinPoolFn.apply(query, keys, mask, W, b, w_out, b_out, int(mode), int(act), alpha, float(eps))

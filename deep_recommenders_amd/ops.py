@@ -1914,3 +1914,108 @@ def token_embedding_bwd(ids, d_out, d_table, rate=0.0, seed=0):
     check(lib().dr_token_embedding_bwd(ptr(sorted_ids), ptr(order), B * L, V, D, ptr(d_out), d_out.stride(0), float(rate),
                                        int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(d_table), stream_ptr()), "dr_token_embedding_bwd")
     return d_table
+
+
+# ---- DIN (csrc/din.hip) ----------------------------------------------------------------------------------------------------------------
+def dice_fwd(x, alpha, eps=1e-8):
+    """y [M, N] of dr_dice_fwd: the reference's Dice over the rows of x (a view with a row pitch is read in place)"""
+    x = _rows_f32(x, "x")
+    M, N = x.shape
+    if N < 1 or alpha.shape != (N,):
+        raise ValueError("dice: alpha must be [N] with N >= 1 (x is %s)" % (tuple(x.shape),))
+    y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    check(lib().dr_dice_fwd(ptr(x), x.stride(0) if M else N, ptr(_c(alpha, torch.float32)), M, N, float(eps), ptr(y), N, stream_ptr()),
+          "dr_dice_fwd")
+    return y
+
+
+def dice_bwd(x, alpha, dy, eps=1e-8):
+    """(dx [M, N], dalpha [N]) of dr_dice_bwd; dalpha is summed over the rows in a fixed order"""
+    x = _rows_f32(x, "x")
+    dy = _rows_f32(dy, "dy")
+    M, N = x.shape
+    if N < 1 or alpha.shape != (N,) or dy.shape != (M, N):
+        raise ValueError("dice backward: shapes do not agree")
+    dev = x.device
+    dx = torch.empty((M, N), dtype=torch.float32, device=dev)
+    dalpha = torch.empty(N, dtype=torch.float32, device=dev)
+    nb = lib().dr_dice_bwd_workspace_bytes(M, N)
+    ws = torch.empty(max(1, nb // 4), dtype=torch.float32, device=dev)
+    check(lib().dr_dice_bwd(ptr(x), x.stride(0) if M else N, ptr(_c(alpha, torch.float32)), ptr(dy), dy.stride(0) if M else N, M, N,
+                            float(eps), ptr(dx), N, ptr(dalpha), ptr(ws), ws.numel() * 4, stream_ptr()), "dr_dice_bwd")
+    return dx, dalpha
+
+
+DIN_POOL_DOMAIN = "D % 4 == 0, 4 <= D <= 128, 1 <= U <= 128, T >= 1"
+
+
+def _din_pool_args(query, keys, mask, W, b, w_out, b_out, mode, act, alpha):
+    if query.dtype != torch.float32 or keys.dtype != torch.float32 or query.dim() != 2 or keys.dim() != 3:
+        raise TypeError("din_pool: query must be [B, D] and keys [B, T, D], fp32")
+    B, T, D = keys.shape
+    mode, act = int(mode), int(act)
+    if mode not in (0, 1, 2) or act not in (0, 1, 2, 3, 4):
+        raise ValueError("din_pool: mode must be 0 (none) / 1 (q - k) / 2 (q * k) and act 0..4 (linear, relu, sigmoid, tanh, Dice)")
+    n_in = 2 if mode == 0 else 3
+    U = W.shape[1] if W.dim() == 2 else -1
+    if query.shape != (B, D) or W.dim() != 2 or W.shape[0] != n_in * D:
+        raise ValueError("din_pool: query %s, keys %s and W %s do not agree (W is [%d * D, U] for mode %d)"
+                         % (tuple(query.shape), tuple(keys.shape), tuple(W.shape), n_in, mode))
+    if not (D % 4 == 0 and 4 <= D <= 128 and 1 <= U <= 128 and T >= 1):
+        raise ValueError("din_pool: D = %d, U = %d, T = %d is outside the kernels' domain (%s); there is no composed fallback"
+                         % (D, U, T, DIN_POOL_DOMAIN))
+    if w_out.numel() != U or (b is not None and b.shape != (U,)) or (b_out is not None and b_out.numel() != 1):
+        raise ValueError("din_pool: b must be [U], w_out [U] or [U, 1], b_out [1]")
+    if act == 4 and (alpha is None or alpha.shape != (U,)):
+        raise ValueError("din_pool: Dice (act 4) needs alpha [U]")
+    query = _rows_f32(query, "query")
+    if B * T > 0 and not (keys.stride(2) == 1 and keys.stride(1) >= D and keys.stride(1) % 4 == 0 and keys.stride(0) == T * keys.stride(1)
+                          and keys.data_ptr() % 16 == 0):
+        keys = keys.contiguous()
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.contiguous().view(torch.uint8)
+        if mask.dtype != torch.uint8 or mask.shape != (B, T):
+            raise TypeError("din_pool: mask must be a [B, T] bool / uint8 tensor (nonzero = valid)")
+        mask = mask.contiguous()
+    f32 = torch.float32
+    return (query, keys, mask, _c(W, f32), None if b is None else _c(b, f32), _c(w_out, f32).reshape(-1), None if b_out is None else _c(b_out, f32),
+            None if alpha is None else _c(alpha, f32), B, T, D, U, mode, act)
+
+
+def din_pool_fwd(query, keys, mask, W, b, w_out, b_out, mode, act, alpha=None, eps=1e-8):
+    """(out [B, D], scores [B, T]) of dr_din_pool_fwd: DIN's activation unit scored for every key against the example's query and the
+    keys summed with those scores; masked keys (mask == 0) are never read.  A shape outside the domain raises ValueError."""
+    query, keys, mask, W, b, w_out, b_out, alpha, B, T, D, U, mode, act = _din_pool_args(query, keys, mask, W, b, w_out, b_out, mode, act, alpha)
+    out = torch.empty((B, D), dtype=torch.float32, device=keys.device)
+    scores = torch.empty((B, T), dtype=torch.float32, device=keys.device)
+    check(lib().dr_din_pool_fwd(ptr(query), query.stride(0) if B else D, ptr(keys), keys.stride(1) if B else D, ptr(mask), ptr(W), ptr(b),
+                                ptr(w_out), ptr(b_out), ptr(alpha), B, T, D, U, mode, act, float(eps), ptr(out), D, ptr(scores),
+                                stream_ptr()), "dr_din_pool_fwd")
+    return out, scores
+
+
+def din_pool_bwd(query, keys, mask, W, b, w_out, b_out, mode, act, d_out, d_scores=None, alpha=None, eps=1e-8):
+    """(d_query, d_keys, dW, db, d_w_out, d_b_out, dalpha) of dr_din_pool_bwd; db / d_b_out / dalpha are None where the forward had no
+    such parameter.  Every reduction over examples runs in a fixed order."""
+    query, keys, mask, W, b, w_out, b_out, alpha, B, T, D, U, mode, act = _din_pool_args(query, keys, mask, W, b, w_out, b_out, mode, act, alpha)
+    dev = keys.device
+    d_out = _c(d_out, torch.float32)
+    if d_out.shape != (B, D) or (d_scores is not None and d_scores.shape != (B, T)):
+        raise ValueError("din_pool backward: d_out must be [B, D] and d_scores [B, T]")
+    if d_scores is not None:
+        d_scores = _c(d_scores, torch.float32)
+    d_query = torch.empty((B, D), dtype=torch.float32, device=dev)
+    d_keys = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+    dW = torch.empty_like(W)
+    db = torch.empty(U, dtype=torch.float32, device=dev) if b is not None else None
+    d_w_out = torch.empty(U, dtype=torch.float32, device=dev)
+    d_b_out = torch.empty(1, dtype=torch.float32, device=dev) if b_out is not None else None
+    dalpha = torch.empty(U, dtype=torch.float32, device=dev) if act == 4 else None
+    nb = lib().dr_din_pool_bwd_workspace_bytes(B, T, D, U)
+    ws = torch.empty(max(4, nb // 4), dtype=torch.float32, device=dev)
+    check(lib().dr_din_pool_bwd(ptr(query), query.stride(0) if B else D, ptr(keys), keys.stride(1) if B else D, ptr(mask), ptr(W), ptr(b),
+                                ptr(w_out), ptr(b_out), ptr(alpha), ptr(d_out), D, ptr(d_scores), B, T, D, U, mode, act, float(eps),
+                                ptr(d_query), D, ptr(d_keys), D, ptr(dW), ptr(db), ptr(d_w_out), ptr(d_b_out), ptr(dalpha), ptr(ws),
+                                ws.numel() * 4, stream_ptr()), "dr_din_pool_bwd")
+    return d_query, d_keys, dW, db, d_w_out, d_b_out, dalpha

@@ -1012,6 +1012,49 @@ int dr_token_embedding_fwd(const int64_t* ids, int64_t N, int32_t L, const float
 int dr_token_embedding_bwd(const int64_t* sorted_ids, const int64_t* order, int64_t N, int64_t V, int32_t D, const float* d_out,
                            int64_t ld_do, float rate, uint64_t seed, float* d_table, dr_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * DIN (keras/models/ranking/din.py of the reference), csrc/din.hip.
+ *
+ *   dr_dice_fwd   Dice (din.py:88-130) over the rows of x [M, N] fp32 (row pitch ld_x), alpha [N] = Keras PReLU's parameter:
+ *                   m = mean_j x_j;  s = sqrt(mean_j (x_j - m)^2);  r = 1 / sqrt(s + eps)     (the reference's second square root)
+ *                   p_j = sigmoid((x_j - m) r);  pre_j = max(x_j, 0) - alpha_j max(-x_j, 0);  y_j = pre_j > 0 ? p_j pre_j : (1 - p_j) pre_j
+ *                 Any M >= 0 and N >= 1 (DR_ESHAPE otherwise).
+ *   dr_dice_bwd   dx [M, N] and dalpha [N] (overwritten) from dy:
+ *                   dpre_j = dy_j (pre_j > 0 ? p_j : 1 - p_j);   c_j = dy_j pre_j (pre_j > 0 ? 1 : -1) p_j (1 - p_j)
+ *                   dx_i = dpre_i (x_i > 0 ? 1 : x_i < 0 ? alpha_i : 0) + r (c_i - mean_j c_j)
+ *                          - 0.5 r^3 (sum_j c_j (x_j - m)) (x_i - m) / (N s)            [this term is ZERO where s == 0]
+ *                   dalpha_j = sum over rows of dpre_j min(x_j, 0)
+ *                 s == 0 (a constant row, always for N == 1): TensorFlow's gradient is NaN there; this returns the finite rest.
+ *                 dalpha is reduced in a fixed order in two stages through a workspace of dr_dice_bwd_workspace_bytes(M, N) bytes
+ *                 (no float atomics: bit-reproducible).
+ *   dr_din_pool_fwd   score[b, t] = mask[b, t] ? Dense(1)(act(concat([q_b, k_bt, inter(q_b, k_bt)]) W + b)) : 0   (scores [B, T], dense)
+ *                     out[b, :]   = sum over the valid t of score[b, t] keys[b, t, :]                               (no softmax)
+ *                 query [B, D] (pitch ld_q), keys [B, T, D] with key (b, t) at keys + (b T + t) ld_k (ld_k % 4 == 0, 16-byte aligned),
+ *                 mask [B, T] bytes, nonzero = valid, NULL = all valid.  W [(2 or 3) D, U] dense row-major in the concat's order
+ *                 [q | k | inter]; mode 0: no interacter (W is [2D, U]), 1: q - k, 2: q * k.  b [U], b_out [1] may be NULL (no bias);
+ *                 w_out [U].  act 0 linear, 1 relu, 2 sigmoid, 3 tanh, 4 Dice over the U hidden units with alpha [U] and eps.
+ *                 Masked keys are never read.  One launch, fp32-input MFMA products, nothing of size B T except scores is written.
+ *                 Domain: D % 4 == 0, 4 <= D <= 128, 1 <= U <= 128, T >= 1, B >= 0 -- DR_ESHAPE outside it.
+ *   dr_din_pool_bwd   d_query [B, D], d_keys [B, T, D] (exactly 0 at masked keys), dW, db, d_w_out, d_b_out, dalpha (all overwritten;
+ *                 db / d_b_out / dalpha may be NULL when the forward had none) from d_out [B, D] (pitch ld_do % 4 == 0) and d_scores
+ *                 [B, T] dense (may be NULL).  The hidden layer is recomputed; the workspace (dr_din_pool_bwd_workspace_bytes) holds its
+ *                 gradient [B T, U] and the fixed-order partial sums of the parameter gradients.  Bit-reproducible.
+ * ---------------------------------------------------------------------------------------- */
+int dr_dice_fwd(const float* x, int64_t ld_x, const float* alpha, int64_t M, int32_t N, float eps, float* y, int64_t ld_y,
+                dr_stream_t stream);
+int64_t dr_dice_bwd_workspace_bytes(int64_t M, int32_t N);
+int dr_dice_bwd(const float* x, int64_t ld_x, const float* alpha, const float* dy, int64_t ld_dy, int64_t M, int32_t N, float eps,
+                float* dx, int64_t ld_dx, float* dalpha, void* workspace, int64_t workspace_bytes, dr_stream_t stream);
+int dr_din_pool_fwd(const float* query, int64_t ld_q, const float* keys, int64_t ld_k, const uint8_t* mask, const float* W,
+                    const float* b, const float* w_out, const float* b_out, const float* alpha, int64_t B, int32_t T, int32_t D,
+                    int32_t U, int32_t mode, int32_t act, float eps, float* out, int64_t ld_out, float* scores, dr_stream_t stream);
+int64_t dr_din_pool_bwd_workspace_bytes(int64_t B, int32_t T, int32_t D, int32_t U);
+int dr_din_pool_bwd(const float* query, int64_t ld_q, const float* keys, int64_t ld_k, const uint8_t* mask, const float* W,
+                    const float* b, const float* w_out, const float* b_out, const float* alpha, const float* d_out, int64_t ld_do,
+                    const float* d_scores, int64_t B, int32_t T, int32_t D, int32_t U, int32_t mode, int32_t act, float eps,
+                    float* d_query, int64_t ld_dq, float* d_keys, int64_t ld_dk, float* dW, float* db, float* d_w_out,
+                    float* d_b_out, float* dalpha, void* workspace, int64_t workspace_bytes, dr_stream_t stream);
+
 /* dr_clock_stamp: dst[0] = the device's constant-rate wall clock (100 MHz ticks) when a one-thread kernel reaches the head of
  * `stream`.  Measurement plumbing with no reference counterpart: bench.py brackets the sharded step's cross-stream waits with two
  * stamps to report the EXPOSED part of the exchange (HIP timing events around a wait serialise the step). */
