@@ -40,6 +40,9 @@ __host__ __device__ __forceinline__ uint32_t dr_drop_thresh(float rate) {
     return (uint32_t)fminf(4294967040.f, rate * 4294967296.f);
 }
 
+// The sigmoid of dr_sigmoid_fwd; dr_confusion_hist_update(from_logits = 1) must bin exactly the probability that kernel stores.
+__device__ __forceinline__ float dr_sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
+
 // Binary cross-entropy terms of one example, logit x, label z (shared by the stand-alone loss kernel and the fused tower
 // head).  mode 0: [TF] sigmoid_cross_entropy_with_logits  max(x,0) - x z + log1p(exp(-|x|)) ; mode 1: tf.losses.log_loss
 // on p = sigmoid(x) (eps 1e-7) ; mode 2: keras binary_crossentropy (p clipped to [eps, 1-eps] first).  Outputs the

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void fm2_bwd_kernel(const float* __restrict__ 
 // ---- K11 ---------------------------------------------------------------------------------
 constexpr int BCE_BLOCKS = 512;   // partial sums; stage 2 is one block
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+__device__ __forceinline__ float sigmoidf_(float x) { return dr_sigmoidf(x); }
 
 __global__ __launch_bounds__(256) void bce_stage1(const float* __restrict__ logits, const float* __restrict__ logits_b,
                                                   int64_t ldb, const float* __restrict__ labels,

@@ -1538,6 +1538,34 @@ def copy_nt(src, dst):
     return dst
 
 
+CONFUSION_HIST_MAX_THRESHOLDS = 4096
+
+
+def confusion_hist_workspace(n, num_thresholds, device="cuda"):
+    """The scratch buffer dr_confusion_hist_update needs for up to n examples (the per-block partial histograms)."""
+    nbytes = lib().dr_confusion_hist_workspace_bytes(int(n), int(num_thresholds))
+    return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
+
+
+def confusion_hist_update(pred, labels, thresholds, hist, weights=None, from_logits=False, workspace=None):
+    """hist[label != 0][#{t : pred > thresholds[t]}] += weight over flat fp32 pred / labels (/ weights) of equal length
+    (dr_confusion_hist_update).  thresholds: ascending fp32 [T] on the device; hist: fp64 [2, T + 1], accumulated into.  Enqueues on
+    the current stream and returns hist; nothing here waits for the device."""
+    pred, labels, thresholds = _c(pred, torch.float32), _c(labels, torch.float32), _c(thresholds, torch.float32)
+    n, T = pred.numel(), thresholds.numel()
+    if labels.numel() != n or (weights is not None and weights.numel() != n):
+        raise ValueError("pred, labels and weights must hold the same number of elements")
+    if hist.dtype != torch.float64 or not hist.is_contiguous() or hist.numel() != 2 * (T + 1):
+        raise ValueError("hist must be a contiguous fp64 tensor of 2 * (T + 1) elements")
+    if weights is not None:
+        weights = _c(weights, torch.float32)
+    if workspace is None or workspace.numel() * workspace.element_size() < lib().dr_confusion_hist_workspace_bytes(n, T):
+        workspace = confusion_hist_workspace(n, T, pred.device)
+    check(lib().dr_confusion_hist_update(ptr(pred), ptr(labels), ptr(weights), n, ptr(thresholds), T, int(bool(from_logits)),
+                                         ptr(hist), ptr(workspace), stream_ptr()), "dr_confusion_hist_update")
+    return hist
+
+
 def clock_stamp(buf, index):
     """buf[index] (int64 device tensor) = the device wall clock (100 MHz ticks) when the current stream reaches this point
     (dr_clock_stamp: a one-thread kernel; measurement plumbing for bench.py's exposed-wait report)."""

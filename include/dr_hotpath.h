@@ -1055,6 +1055,30 @@ int dr_din_pool_bwd(const float* query, int64_t ld_q, const float* keys, int64_t
                     float* d_query, int64_t ld_dq, float* d_keys, int64_t ld_dk, float* dW, float* db, float* d_w_out,
                     float* d_b_out, float* dalpha, void* workspace, int64_t workspace_bytes, dr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Streaming evaluation metrics (deep_recommenders_amd/csrc/metrics.hip): the confusion counters of tf.metrics.auc
+ * (examples/train_fm_on_movielens_estimator.py:47, train_fnn_..:48, train_deepfm_..:48, train_wdl_..:61) and of
+ * tf.keras.metrics.AUC / Precision / Recall
+ * (examples/train_deepfm_on_movielens_keras.py:45-47), kept on the device as one histogram.
+ *
+ * bucket(p) = the number of t in 0 .. T-1 with p > thresholds[t], every comparison in fp32 against the array passed (device memory,
+ * ASCENDING, T floats), as TensorFlow compares.  A NaN compares false everywhere: bucket 0.  Predictions outside [0, 1] fall into
+ * the end buckets a threshold array that brackets [0, 1] gives them; nothing on the device asserts the range.
+ * hist[(labels[i] != 0) * (T + 1) + bucket(pred[i])] += weights[i] (1 when weights is NULL) for i < n; hist is [2][T + 1] fp64 and is
+ * ACCUMULATED INTO (zero it to reset).  tp[t] = sum_{b > t} hist[1][b], fp[t] = sum_{b > t} hist[0][b], fn = sum hist[1] - tp,
+ * tn = sum hist[0] - fp.  from_logits != 0: pred holds logits and bucket(sigmoid(pred[i])) is taken, with dr_sigmoid_fwd's arithmetic
+ * (the state equals, bit for bit, an update with that kernel's output).
+ * Without weights the per-block partial counts are integers combined in a fixed order: the state is exact up to 2^53 and
+ * bit-identical from run to run.  With weights the sums are fp64 end to end (the order of the adds inside a block is not fixed).
+ * Two launches on `stream`, no host synchronisation.  workspace: dr_confusion_hist_workspace_bytes(n, T) bytes (0 for arguments
+ * the update refuses), contents unspecified before and after.
+ * n == 0: nothing is done, DR_OK.  T < 1, n < 0 or (n > 0) a NULL pred / labels / thresholds / hist / workspace: DR_EINVAL.
+ * T > 4096 (the supported maximum: the histogram and the thresholds live in LDS) or n > 2^40: DR_ESHAPE.
+ * ---------------------------------------------------------------------------------------- */
+int64_t dr_confusion_hist_workspace_bytes(int64_t n, int32_t num_thresholds);
+int dr_confusion_hist_update(const float* pred, const float* labels, const float* weights, int64_t n, const float* thresholds,
+                             int32_t T, int32_t from_logits, double* hist, void* workspace, dr_stream_t stream);
+
 /* dr_clock_stamp: dst[0] = the device's constant-rate wall clock (100 MHz ticks) when a one-thread kernel reaches the head of
  * `stream`.  Measurement plumbing with no reference counterpart: bench.py brackets the sharded step's cross-stream waits with two
  * stamps to report the EXPOSED part of the exchange (HIP timing events around a wait serialise the step). */
