@@ -16,9 +16,12 @@
 //   * So the rows are fetched by LDS-DMA, 8 lanes x 16 bytes per 128-byte line (8 requests per instruction, 32 per wave and
 //     k-tile), two k-tiles ahead, into a wave-private 2 x 4 KB LDS image -- no destination VGPRs, which is what allows the
 //     two-step lead.  Each field is addressed as a STRUCTURED buffer (base = its first row, index = bucket id, stride 256 B;
-//     buffer offsets are 32 bits wide, so a field may have 2^24 rows).  The image is XOR-swizzled by the choice of which (row, chunk) each DMA lane fetches, so that
-//     both readers are conflict-free: the MFMA-operand read (lane = row, 4 x ds_read_b128) and the position-wise read that
-//     feeds the COALESCED concat stores (8 lanes per 128-byte line again).
+//     buffer offsets are 32 bits wide, so a field may have 2^24 rows).  The image is XOR-swizzled by the choice of which (row, chunk) each DMA lane fetches
+//     (chunk c of row r at position c ^ (r & 7) ^ ((r >> 4) & 1), emb_a_swizzle in bf3_rs_core.h), so that both readers are
+//     conflict-free: the MFMA-operand read (lane = row, 4 x ds_read_b128, served in the lane groups {0-3, 12-15, 20-27} and
+//     {4-11, 16-19, 28-31} of each half wave: the eight rows of one parity in a group need eight distinct swizzle values, which
+//     r & 7 alone does not give -- rows 12 and 20 share it; bf3_rs_core.h proves the image at compile time) and the position-wise
+//     read that feeds the COALESCED concat stores (8 lanes per 128-byte line again; lane-linear).
 //   * LDS: 2 x 48 KB weight stages + 2 x 32 KB activation stages = all 160 KB.  The weight pieces of k-tile s + 1 are issued first
 //     in step s, the gather of s + 2 and the id / weight loads after them, so the one counted wait per step (vmcnt(10) in front
 //     of the barrier) covers exactly the pieces and leaves the younger gather in flight.
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(512, 2) void bf3_emb_linear_kernel(RsArgs g, EmbArg
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
     const int grow = lane >> 3;                                         // gather layout: DMA i of this lane fetches row 8 i + grow,
-    const int gchunk = (lane & 7) ^ grow;                               // 16-byte chunk gchunk (image slot lane & 7: XOR swizzle)
+    const int gchunk = (lane & 7) ^ grow;                               // 16-byte chunk gchunk ^ (i >> 1) (image slot lane & 7: emb_a_swizzle)
 
     const int tiles_n = (g.N + BN - 1) / BN;
     const int tiles_m = (int)((g.M + BM - 1) / BM);
@@ -89,8 +92,8 @@ __global__ __launch_bounds__(512, 2) void bf3_emb_linear_kernel(RsArgs g, EmbArg
     unsigned b_addr[2];                                                 // B fragment reads, one per k-step
 #pragma unroll
     for (int s = 0; s < 2; ++s) b_addr[s] = rs_frag_addr(lds0, l31, hi, sw, s);
-    // A image of this wave: position p = 8 row + (chunk ^ (row & 7)), 16 bytes each
-    const unsigned a_rd = lds0 + A_BASE + wave * A_WAVE + l31 * 128 + (((4 * hi) ^ (l31 & 7)) << 4);    // own row, chunk 4 hi (^ c << 4)
+    // A image of this wave: position p = 8 row + (chunk ^ emb_a_swizzle(row)), 16 bytes each
+    const unsigned a_rd = lds0 + A_BASE + wave * A_WAVE + emb_a_read_off(l31, hi, 0);                   // own row, chunk 4 hi (^ c << 4)
     const unsigned a_st = lds0 + A_BASE + wave * A_WAVE + lane * 16;                                    // position 64 i + lane
 
     const __amdgpu_buffer_rsrc_t brsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(512, 2) void bf3_emb_linear_kernel(RsArgs g, EmbArg
             const int idx = dense ? grow_row(M0, i) : max(IDS[i], 0);                                                                \
             unsigned char* dst = smem + A_BASE + (AST) * A_STAGE + wave * A_WAVE + i * 1024;                                         \
             __builtin_amdgcn_struct_ptr_buffer_load_lds(dense ? drsrc : trsrc, (lds_ptr_t)dst, 16, idx,                              \
-                                                        gchunk * 16 + (dense ? 0 : ((KT) & 1) * 128), 0, 0, DR_NT_FWD_GATHER ? 2 : 0); \
+                                                        (gchunk ^ (i >> 1)) * 16 + (dense ? 0 : ((KT) & 1) * 128), 0, 0, DR_NT_FWD_GATHER ? 2 : 0); \
         }                                                                                                                            \
     }
     auto issue_gather = [&](int kt, int m0, int rb, int ast) -> int {  // ... from the ids in idg; returns the 4 missing bits
@@ -238,7 +241,7 @@ __global__ __launch_bounds__(512, 2) void bf3_emb_linear_kernel(RsArgs g, EmbArg
             for (int i = 0; i < 4; ++i) {
                 const int row = m0c + wave * 32 + 8 * i + grow;
                 if (row < g.M) {
-                    float* dst = e.concat + (int64_t)row * e.ld_concat + kt * BK + 4 * gchunk;
+                    float* dst = e.concat + (int64_t)row * e.ld_concat + kt * BK + 4 * (gchunk ^ (i >> 1));
                     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
                     const f32x4 v = ((m4q >> i) & 1) ? z : st[i];
                     // inline asm on purpose: stores the compiler can see make it treat vmcnt as unordered (loads + stores

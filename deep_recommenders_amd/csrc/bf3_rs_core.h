@@ -96,11 +96,70 @@ constexpr int RS_B_PLANE = 256 * 64;                                    // bytes
 template <int H2> constexpr int RS_NPL = H2 ? 2 : 3;                    // operand planes
 template <int H2> constexpr int RS_STAGE = RS_NPL<H2> * RS_B_PLANE;     // 48 KB (32 KB)
 
-// the image's swizzle: k-step s's chunk 2 hi + s of row r (a reader's 32 nt + l31, a writer's own row) sits at chunk ^ rs_swizzle(r)
-__device__ __forceinline__ int rs_swizzle(int row) { return (row >> 2) & 3; }
-__device__ __forceinline__ int rs_chunk_off(int hi, int sw, int s) { return ((2 * hi + s) ^ sw) << 4; }
+// the image's swizzle: k-step s's chunk 2 hi + s of row r (a reader's 32 nt + l31, a writer's own row) sits at chunk ^ rs_swizzle(r).
+// rs_swizzle belongs to the images LDS-DMA fills (bf3_gemm_rs_kernel, bf3_emb_linear_kernel, h2_occ.hip): their writes are lane-linear,
+// only the fragment reads have to be spread.  bf3_gemm_tn_rs_kernel fills its dy image with ds_write_b128 from registers, 8 consecutive
+// rows per lane group, and needs a swizzle that spreads those as well: tn_img_swizzle.
+__host__ __device__ constexpr int rs_swizzle(int row) { return (row >> 2) & 3; }
+__host__ __device__ constexpr int tn_img_swizzle(int row) { return ((row >> 1) & 3) ^ ((row >> 4) & 1); }
+__host__ __device__ constexpr int rs_chunk_off(int hi, int sw, int s) { return ((2 * hi + s) ^ sw) << 4; }
 // fragment read address of k-step s: stage 0, plane 0, column tile 0
-__device__ __forceinline__ unsigned rs_frag_addr(unsigned lds0, int l31, int hi, int sw, int s) { return lds0 + l31 * 64 + rs_chunk_off(hi, sw, s); }
+__host__ __device__ constexpr unsigned rs_frag_addr(unsigned lds0, int l31, int hi, int sw, int s) { return lds0 + l31 * 64 + rs_chunk_off(hi, sw, s); }
+// the fused forward's activation image (bf3_emb_linear_kernel): per wave [32 rows][8 chunks of 16 bytes]; chunk c of row r sits at
+// position c ^ emb_a_swizzle(r).  The MFMA-operand read of lane (l31, hi) takes chunks 4 hi .. 4 hi + 3 of row l31.
+__host__ __device__ constexpr int emb_a_swizzle(int row) { return (row & 7) ^ ((row >> 4) & 1); }
+__host__ __device__ constexpr unsigned emb_a_read_off(int l31, int hi, int c) { return l31 * 128 + (((4 * hi + c) ^ emb_a_swizzle(l31)) << 4); }
+
+// ---- bank model of the two 16-byte LDS instructions (CDNA4) -----------------------------------------------------------------------
+// A wave's access is served in fixed lane groups, one LDS cycle per group when no two lanes of a group ask one bank for different
+// addresses (equal addresses are one broadcast):
+//   16-byte read:  4 groups of 16 lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32; bank of byte a = (a / 4) % 64
+//   16-byte write: 8 groups of 8 consecutive lanes;                                                  bank of byte a = (a / 4) % 32
+// lds_b128_ways = 1 + the largest number of lanes that collide with one lane of their group: 1 means conflict-free.  Address
+// arithmetic only; the static_asserts below evaluate it over every wave, k-step and column tile of the images above, so a swizzle that
+// brings a conflict back does not compile.
+constexpr int LDS_RD128_HALF[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
+                                       {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
+constexpr int lds_rd128_lane(int group, int i) { return LDS_RD128_HALF[group & 1][i] + 32 * (group >> 1); }
+constexpr int lds_wr128_lane(int group, int i) { return 8 * group + i; }
+typedef unsigned (*lds_addr_fn)(int lane, int p0, int p1);              // byte address of a lane's 16-byte access; p0, p1: the case
+constexpr int lds_b128_ways(bool write, lds_addr_fn addr, int p0, int p1) {
+    const int groups = write ? 8 : 4, lanes = write ? 8 : 16, banks = write ? 32 : 64;
+    int worst = 1;
+    for (int gq = 0; gq < groups; ++gq)
+        for (int i = 0; i < lanes; ++i) {
+            const unsigned ai = addr(write ? lds_wr128_lane(gq, i) : lds_rd128_lane(gq, i), p0, p1);
+            int n = 1;
+            for (int j = 0; j < lanes; ++j) {
+                const unsigned aj = addr(write ? lds_wr128_lane(gq, j) : lds_rd128_lane(gq, j), p0, p1);
+                if (aj != ai && (aj / 4) % banks == (ai / 4) % banks) ++n;
+            }
+            if (n > worst) worst = n;
+        }
+    return worst;
+}
+template <int SWZ> constexpr int img_swizzle(int row) { return SWZ ? tn_img_swizzle(row) : rs_swizzle(row); }
+// the [256 rows][64 bytes] image: fragment read of k-step s, column tile nt; the TN kernel's write of k-step s by wave w
+template <int SWZ> constexpr unsigned img_read_addr(int lane, int s, int nt) {
+    return rs_frag_addr(0, lane & 31, lane >> 5, img_swizzle<SWZ>(lane & 31), s) + nt * 2048;
+}
+template <int SWZ> constexpr unsigned img_write_addr(int lane, int s, int w) {
+    return (32 * w + (lane & 31)) * 64 + rs_chunk_off(lane >> 5, img_swizzle<SWZ>(32 * w + (lane & 31)), s);
+}
+constexpr unsigned emb_a_read_addr(int lane, int c, int w) { return w * 4096 + emb_a_read_off(lane & 31, lane >> 5, c); }
+constexpr int lds_b128_worst(bool write, lds_addr_fn addr, int n0, int n1) {
+    int worst = 1;
+    for (int p0 = 0; p0 < n0; ++p0)
+        for (int p1 = 0; p1 < n1; ++p1) {
+            const int w = lds_b128_ways(write, addr, p0, p1);
+            if (w > worst) worst = w;
+        }
+    return worst;
+}
+static_assert(lds_b128_worst(false, img_read_addr<0>, 2, 8) == 1, "NT weight image: fragment reads conflict");
+static_assert(lds_b128_worst(false, img_read_addr<1>, 2, 8) == 1, "TN dy image: fragment reads conflict");
+static_assert(lds_b128_worst(true, img_write_addr<1>, 2, 8) == 1, "TN dy image: ds_write_b128 conflicts");
+static_assert(lds_b128_worst(false, emb_a_read_addr, 4, 8) == 1, "fused forward's activation image: operand reads conflict");
 
 // the NP planes' fragments of column tile nt (bb: rs_frag_addr + the stage's offset).  Immediates must be literal: dispatch on nt
 template <int NP>

@@ -7,8 +7,9 @@
 //           needs ("8 consecutive k per lane") is free because the lane index runs along f.
 //   B (dy): the same loads with the lane index along n give every lane 8 consecutive r of its column, i.e. exactly one
 //           16-byte fragment chunk per plane: wave w splits the 32 columns 32 w .. 32 w + 31 of the tile once and writes the
-//           three planes as ds_write_b128 into the [n][32 r] image the fragment reads of the NT kernels use; the 8 waves'
-//           pieces make the tile that all of them read.  Two LDS stages: step g's MFMAs read stage g while stage g + 1 is
+//           three planes as ds_write_b128 into the [n][32 r] image the fragment reads of the NT kernels use (with a swizzle of
+//           its own, tn_img_swizzle: the 8 consecutive rows of a store's lane group must be spread too); the 8 waves' pieces
+//           make the tile that all of them read.  Two LDS stages: step g's MFMAs read stage g while stage g + 1 is
 //           written from registers loaded during step g - 1.
 // The in-kernel-split wgrad of dense.hip re-stages BOTH operands through the LDS per 128 x 128 tile; here x never touches
 // it and each dy element is split once per 256 rows of x.
@@ -71,9 +72,10 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
     // this lane's columns (clamped: columns past the edge only feed outputs nobody reads)
     const int fcol = min(f0 + wave * 32 + l31, g.F - 1);
     const int ncol = min(n0 + wave * 32 + l31, g.N - 1);
-    // fragment read addresses as in bf3_gemm_rs_kernel (bf3_gemm.hip): B row = 32 nt + l31, chunk (2 hi + s) ^ ((row >> 2) & 3)
+    // fragment read addresses as in bf3_gemm_rs_kernel (bf3_gemm.hip): B row = 32 nt + l31, chunk (2 hi + s) ^ tn_img_swizzle(row)
+    // (rows 32 nt + l31 and 32 wave + l31 have the swizzle of l31)
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)smem;
-    const int sw = rs_swizzle(l31);
+    const int sw = tn_img_swizzle(l31);
     unsigned b_addr[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) b_addr[s] = rs_frag_addr(lds0, l31, hi, sw, s);
@@ -104,23 +106,31 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
     };
     // GATHER: where this wave's 32 columns live.  A wave covers half a field's row (32 of its 64 dims: one 128-byte line per
     // reduction row and lane half, exactly the lines the forward's gather fetched), or the dense features, or nothing (columns
-    // past F: a valid dummy source, the outputs are never read).  Every load stays unconditional.
+    // past F: an empty buffer, every load returns 0; the outputs are never read).  Every load stays unconditional.
     const int c0w = f0 + wave * 32;
     const bool w_field = GATHER && c0w < 64 * g.nf;
     const bool w_dense = GATHER && !w_field && g.dense_pad != nullptr && c0w < 64 * g.nf + 32;
     // One raw buffer resource per wave (its field's rows / the dense features / a dummy): the address of a load is then ONE 32-bit
     // VALU operation, id * 256 + column (a field is below 2^24 rows = 4 GB, as in the fused forward), instead of 64-bit pointer
-    // arithmetic per lane and load.  The resource's range check does the masking: a missing id (-1) becomes offset 0xFFFFFF00 +
-    // column >= num_records and the hardware returns 0 -- no clamp, no select.  The 32 ids of a k-tile sit in the lanes so that
-    // DPP row_share:e hands every lane the id of ITS row e (lanes 0-31: rows 0-15 twice, lanes 32-63: rows 16-31 twice) -- one
-    // VALU move per load, no LDS shuffle.  (First cut: 64-bit pointers + ds_bpermute + clamp + select: +53 us on the kernel.)
+    // arithmetic per lane and load.  The resource's range check does ALL the masking: a missing id (-1) becomes offset 0xFFFFFF00 +
+    // column >= num_records and the hardware returns 0 -- no clamp, no select; a row past the slice's end (its last, partial k-tile
+    // only) is given that offset, and a wave without columns has num_records = 0.  So xa needs no validity mask and the main loop
+    // no selects; the partial k-tile's offset fix-up is VALU only, under a wave-uniform branch.  The 32 ids of a k-tile sit in the
+    // lanes so that DPP row_share:e hands every lane the id of ITS row e (lanes 0-31: rows 0-15 twice, lanes 32-63: rows 16-31
+    // twice) -- one VALU move per load, no LDS shuffle.  (First cut: 64-bit pointers + ds_bpermute + clamp + select: +53 us on
+    // the kernel.)
     const float* gptr = g.table;
     unsigned gpitch = 0;                                                // bytes per source row
     const int32_t* idrow = nullptr;
     if (GATHER) {
         if (w_field) {
             const int fld = c0w >> 6;
-            gptr = g.table + g.row_base[fld] * 64 + (c0w & 32);
+            // (readfirstlane: the load through the argument struct's generic pointer counts as divergent, and a resource that may
+            // differ from lane to lane puts every buffer load of the main loop into a loop over the distinct resources)
+            const int64_t rbv = g.row_base[fld];
+            const int64_t rb = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(rbv >> 32)) << 32) |
+                                         (uint32_t)__builtin_amdgcn_readfirstlane((int)rbv));
+            gptr = g.table + rb * 64 + (c0w & 32);
             gpitch = 256;
             idrow = g.ids_t + (int64_t)fld * g.R;
         } else if (w_dense) {
@@ -128,11 +138,20 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
             gpitch = 128;
         }
     }
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gptr), 0, (int)0xFFFFFF00u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t grsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gptr), 0, (w_field || w_dense) ? (int)0xFFFFFF00u : 0, 0x00020000);
     const unsigned gcol = (unsigned)l31 * 4u;
     const int id_lane = (lane & 15) + 16 * hi;                          // the row of the k-tile whose id this lane keeps
     int idv = 0;                                                        // ids of the k-tile whose rows are fetched next
-    int xmask = -1;                                                     // validity of xa[e] (partial k-tiles only)
+    auto gather_id = [&](int ids_of_tile, int e) -> int {              // DPP row_share:e (the control word must be a literal)
+        switch (e) {
+#define GATHER_ID(E) case E: return __builtin_amdgcn_update_dpp(0, ids_of_tile, 0x150 + E, 0xf, 0xf, false);
+            GATHER_ID(0) GATHER_ID(1) GATHER_ID(2) GATHER_ID(3) GATHER_ID(4) GATHER_ID(5) GATHER_ID(6) GATHER_ID(7)
+            GATHER_ID(8) GATHER_ID(9) GATHER_ID(10) GATHER_ID(11) GATHER_ID(12) GATHER_ID(13) GATHER_ID(14)
+#undef GATHER_ID
+            default: return __builtin_amdgcn_update_dpp(0, ids_of_tile, 0x15f, 0xf, 0xf, false);
+        }
+    };
     auto load_ids = [&](int64_t r0) -> int {
         if (!w_field) return 0;                                         // (wave-uniform)
         const int64_t r = r0 + id_lane < g.R ? r0 + id_lane : g.R - 1;
@@ -140,32 +159,38 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
     };
     auto load_gather = [&](float (&dst)[16], int ids_of_tile, int64_t r0) {
         const bool full = r0 + BK <= r_end;                             // (wave-uniform) all but a slice's last k-tile
-        int vm = -1;
-#define GATHER_ONE(E)                                                                                                   \
-        {                                                                                                                \
-            const int64_t r = r0 + 16 * hi + E;                                                                          \
-            unsigned idx;                                                                                                \
-            if (w_field) idx = (unsigned)__builtin_amdgcn_update_dpp(0, ids_of_tile, 0x150 + E, 0xf, 0xf, false);        \
-            else idx = (unsigned)(r < r_end ? r : r_end - 1);                                                            \
-            if (!full && !(r < r_end)) { idx = w_field ? 0x00FFFFFFu : idx; vm &= ~(1 << E); }                           \
-            dst[E] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(grsrc, (int)(idx * gpitch + gcol), 0, DR_NT_WGRAD_GATHER ? 2 : 0)); \
+        unsigned off[16];
+        if (w_field) {                                                  // (wave-uniform; ONE branch, not one per load)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) off[e] = (unsigned)gather_id(ids_of_tile, e) * gpitch;
+        } else {                                                        // dense_pad: R rows of 128 bytes, below 4 GB; no columns: 0
+            const unsigned o0 = (unsigned)(r0 + 16 * hi) * gpitch;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) off[e] = o0 + (unsigned)e * gpitch;
         }
-        GATHER_ONE(0) GATHER_ONE(1) GATHER_ONE(2) GATHER_ONE(3) GATHER_ONE(4) GATHER_ONE(5) GATHER_ONE(6) GATHER_ONE(7)
-        GATHER_ONE(8) GATHER_ONE(9) GATHER_ONE(10) GATHER_ONE(11) GATHER_ONE(12) GATHER_ONE(13) GATHER_ONE(14) GATHER_ONE(15)
-#undef GATHER_ONE
-        if (!(w_field || w_dense)) vm = 0;                              // columns past F: zeros (their outputs are never read)
-        xmask = vm;
+        if (!full) {
+            const int nv = (int)(r_end - r0 < BK ? r_end - r0 : BK) - 16 * hi;     // this lane half's rows inside the slice (<= 0: none)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) off[e] = e < nv ? off[e] : 0xFFFFFF00u;
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+            dst[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(grsrc, (int)(off[e] + gcol), 0, DR_NT_WGRAD_GATHER ? 2 : 0));
     };
     bf16x8 fa[2][3];
     bf16x8 fb[4][3];                                                    // group q uses buffer q & 3, read two groups ahead
     float cs = 0.f;
     auto stage_b = [&](int stage) {                                     // yb -> three planes of this lane's column
+        if (want_cs) {                                                  // (block-uniform) only the f0 == 0 blocks store the column sum
+#pragma unroll
+            for (int e = 0; e < 16; ++e) cs += yb[e];
+        }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             bf16x8 p0, p1, p2;
             float v[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { v[j] = yb[8 * s + j]; cs += v[j]; }
+            for (int j = 0; j < 8; ++j) v[j] = yb[8 * s + j];
             if constexpr (H2) h2_split8v(v, h2_sy, p0, p1);
             else rs_split8v(v, p0, p1, p2);
             unsigned char* w = wrow + stage * STAGE + rs_chunk_off(hi, sw, s);
@@ -208,7 +233,7 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = (!GATHER || xmask == -1 || ((xmask >> (8 * s + j)) & 1)) ? xa[8 * s + j] : 0.f;
+                for (int j = 0; j < 8; ++j) v[j] = xa[8 * s + j];
                 if constexpr (H2) h2_split8v(v, h2_sx, fa[s][0], fa[s][1]);
                 else rs_split8v(v, fa[s][0], fa[s][1], fa[s][2]);
             }
@@ -216,8 +241,7 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
         if (kt + 1 < nk) stage_b(stage ^ 1);
         __builtin_amdgcn_sched_barrier(0);
         if (GATHER) {
-            // (the 16 id shuffles are LDS operations: they and the loads they address stay between these two scheduling
-            // barriers, i.e. in front of every fragment read the counted lgkmcnt waits of the MFMA loop reckon with)
+            // (the loads stay between these two scheduling barriers, in front of the MFMA loop's fragment reads)
             load_gather(xa, idv, r_begin + (int64_t)(kt + 1) * BK);
             idv = load_ids(r_begin + (int64_t)(kt + 2) * BK);
         } else {
@@ -258,13 +282,21 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
 }
 
 // dst[f][n] += scale * sum_s partial[s][f][n]  (fixed order);  dstb[n] += scale * sum_s colsum[s][n]
-__global__ __launch_bounds__(256) void bf3_tn_rs_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ colsum,
-                                                               int32_t split, int32_t F, int32_t N, int32_t Fp, int32_t Np,
-                                                               float scale, float* __restrict__ dst, int64_t ld,
-                                                               float* __restrict__ dstb, const uint32_t* __restrict__ x_amax = nullptr,
-                                                               const uint32_t* __restrict__ x2_amax = nullptr,
-                                                               const uint32_t* __restrict__ y_amax = nullptr) {
-    const int64_t total = (int64_t)F * N, stride = (int64_t)gridDim.x * blockDim.x;
+// A streaming kernel: 2-D index (blockIdx.x = row f, a thread = V consecutive columns: no division), V = 4 (16-byte loads and stores)
+// where the pointers and `ld` allow it, eight slices' loads in flight per thread.  The additions of an element run in slice order,
+// one after the other from 0.f, and fmaf(wscale, sum, dst) comes last: any unrolling gives the same bits.  The blocks of row 0 also
+// apply the column sums, each column in slice order.
+template <int V>
+__global__ __launch_bounds__(64) void bf3_tn_rs_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ colsum,
+                                                              int32_t split, int32_t F, int32_t N, int32_t Fp, int32_t Np,
+                                                              float scale, float* __restrict__ dst, int64_t ld,
+                                                              float* __restrict__ dstb, const uint32_t* __restrict__ x_amax = nullptr,
+                                                              const uint32_t* __restrict__ x2_amax = nullptr,
+                                                              const uint32_t* __restrict__ y_amax = nullptr) {
+    typedef float vec_t __attribute__((ext_vector_type(V)));
+    const int f = blockIdx.x;
+    const int n = ((int)blockIdx.y * 64 + (int)threadIdx.x) * V;        // < Np: the padded workspace holds all V columns
+    if (n >= N) return;
     const int64_t ps = (int64_t)Fp * Np;
     float wscale = scale;                                               // f16x2 partials carry s_x s_y (powers of two: exact)
     if (x_amax != nullptr) {
@@ -273,25 +305,49 @@ __global__ __launch_bounds__(256) void bf3_tn_rs_reduce_kernel(const float* __re
         h2_scale_of(y_amax[0], sy, iy);
         wscale = scale * (ix * iy);
     }
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const int64_t f = i / N;
-        const int n = (int)(i - f * N);
-        const float* p = partial + f * Np + n;
-        float acc = 0.f;
+    auto sum_slices = [&](const float* p, int64_t stride) -> vec_t {   // sum_s p[s * stride], V columns each, in slice order
+        vec_t acc = 0.f;
         int s = 0;
-        for (; s + 4 <= split; s += 4) {             // four loads in flight, summed in slice order
-            const float v0 = p[s * ps], v1 = p[(s + 1) * ps], v2 = p[(s + 2) * ps], v3 = p[(s + 3) * ps];
-            acc = (((acc + v0) + v1) + v2) + v3;
+        for (; s + 8 <= split; s += 8) {
+            vec_t v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const vec_t*>(p + (s + u) * stride);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc += v[u];
         }
-        for (; s < split; ++s) acc += p[s * ps];
-        dst[f * ld + n] = fmaf(wscale, acc, dst[f * ld + n]);
+        for (; s < split; ++s) acc += *reinterpret_cast<const vec_t*>(p + s * stride);
+        return acc;
+    };
+    const vec_t acc = sum_slices(partial + (int64_t)f * Np + n, ps);
+    float* d = dst + (int64_t)f * ld + n;
+    if (V == 1 || n + V <= N) {
+        vec_t o = *reinterpret_cast<vec_t*>(d);
+#pragma unroll
+        for (int c = 0; c < V; ++c) o[c] = fmaf(wscale, acc[c], o[c]);
+        *reinterpret_cast<vec_t*>(d) = o;
+    } else {                                                            // the row's last, partial group of columns
+#pragma unroll
+        for (int c = 0; c < V; ++c)
+            if (n + c < N) d[c] = fmaf(wscale, acc[c], d[c]);
     }
-    if (blockIdx.x == 0 && colsum != nullptr && dstb != nullptr)
-        for (int n = threadIdx.x; n < N; n += blockDim.x) {
-            float acc = 0.f;
-            for (int s = 0; s < split; ++s) acc += colsum[(int64_t)s * Np + n];
-            dstb[n] = fmaf(scale, acc, dstb[n]);
-        }
+    if (f == 0 && colsum != nullptr && dstb != nullptr) {
+        const vec_t cacc = sum_slices(colsum + n, Np);
+#pragma unroll
+        for (int c = 0; c < V; ++c)
+            if (n + c < N) dstb[n + c] = fmaf(scale, cacc[c], dstb[n + c]);
+    }
+}
+
+void launch_tn_rs_reduce(const float* partial, const float* colsum, int split, int32_t F, int32_t N, int Fp, int Np, float scale,
+                         float* dst, int64_t ld, float* dstb, const uint32_t* x_amax, const uint32_t* x2_amax, const uint32_t* y_amax,
+                         dr_stream_t stream) {
+    const bool vec = ((reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 && (ld & 3) == 0;
+    if (vec)
+        hipLaunchKernelGGL(bf3_tn_rs_reduce_kernel<4>, dim3(F, (N + 255) / 256), dim3(64), 0, dr_s(stream), partial, colsum, split, F, N,
+                           Fp, Np, scale, dst, ld, dstb, x_amax, x2_amax, y_amax);
+    else
+        hipLaunchKernelGGL(bf3_tn_rs_reduce_kernel<1>, dim3(F, (N + 63) / 64), dim3(64), 0, dr_s(stream), partial, colsum, split, F, N,
+                           Fp, Np, scale, dst, ld, dstb, x_amax, x2_amax, y_amax);
 }
 
 void tn_rs_plan(int64_t R, int32_t F, int32_t N, int& split, int64_t& per, int& Fp, int& Np) {
@@ -333,9 +389,8 @@ static int wgrad_impl(const float* x, int64_t ld_x, const float* dy, int64_t ld_
     const int grid = (Fp / 256) * (Np / 256) * split;
     if (x_amax != nullptr) hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<0, 1>), dim3(grid), dim3(512), 0, dr_s(stream), g);
     else hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<0, 0>), dim3(grid), dim3(512), 0, dr_s(stream), g);
-    hipLaunchKernelGGL(bf3_tn_rs_reduce_kernel, dim3(dr_grid_for((int64_t)F * N, 256)), dim3(256), 0, dr_s(stream), partial,
-                       dstb != nullptr ? colsum : nullptr, split, F, N, Fp, Np, scale, dstW, ld_w, dstb, x_amax,
-                       static_cast<const uint32_t*>(nullptr), dy_amax);
+    launch_tn_rs_reduce(partial, dstb != nullptr ? colsum : nullptr, split, F, N, Fp, Np, scale, dstW, ld_w, dstb, x_amax, nullptr, dy_amax,
+                        stream);
     DR_CHECK_LAUNCH();
     return DR_OK;
 }
@@ -382,9 +437,8 @@ static int wgrad_emb_impl(const int32_t* ids_t, int64_t R, int32_t nf, const int
         else hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<1, 0>), dim3(grid), dim3(512), 0, dr_s(stream), g);
     }
     if (parts & 2)
-        hipLaunchKernelGGL(bf3_tn_rs_reduce_kernel, dim3(dr_grid_for((int64_t)F * N, 256)), dim3(256), 0, dr_s(stream), partial,
-                           dstb != nullptr ? colsum : nullptr, split, F, N, Fp, Np, scale, dstW, ld_w, dstb, table_amax,
-                           F > 64 * nf ? dense_amax : static_cast<const uint32_t*>(nullptr), dy_amax);
+        launch_tn_rs_reduce(partial, dstb != nullptr ? colsum : nullptr, split, F, N, Fp, Np, scale, dstW, ld_w, dstb, table_amax,
+                            F > 64 * nf ? dense_amax : nullptr, dy_amax, stream);
     DR_CHECK_LAUNCH();
     return DR_OK;
 }
