@@ -129,6 +129,9 @@ SIGNATURES = {
     "dr_h2_wgrad_emb": [_p, _i64, _i32, _p, _p, _i32, _p, _p, _p, _p, _i64, _p, _i32, _i32, _f32, _p, _i64, _p, _p, _i64, _i32, _p],
     "dr_cin_fwd": [_p, _p, _i64, _i32, _i32, _i32, _p, _i32, _p, _i32, _p, _p],
     "dr_cin_bwd": [_p, _p, _i64, _i32, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p],
+    "dr_cin_pool_fwd": [_p, _p, _i64, _i32, _i32, _i32, _p, _i32, _p, _i32, _p, _p, _p],
+    "dr_cin_pool_bwd_workspace_bytes": [_i64, _i32, _i32, _i32, _i32],
+    "dr_cin_pool_bwd": [_p, _p, _i64, _i32, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _i64, _p],
     "dr_din_concat_fwd": [_p, _p, _i64, _i32, _i32, _p, _i64, _p],
     "dr_din_concat_bwd": [_p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p],
     "dr_act_fwd": [_p, _i64, _i32, _i64, _i32, _p],
@@ -203,7 +206,7 @@ _RESTYPE = {"dr_version": ctypes.c_char_p, "dr_shard_bucket_workspace_bytes": ct
             "dr_csr_spmm_workspace_bytes": ctypes.c_int64, "dr_csr_transpose_workspace_bytes": ctypes.c_int64,
             "dr_add_layernorm_bwd_workspace_bytes": ctypes.c_int64,
             "dr_dice_bwd_workspace_bytes": ctypes.c_int64, "dr_din_pool_bwd_workspace_bytes": ctypes.c_int64,
-            "dr_confusion_hist_workspace_bytes": ctypes.c_int64}
+            "dr_confusion_hist_workspace_bytes": ctypes.c_int64, "dr_cin_pool_bwd_workspace_bytes": ctypes.c_int64}
 
 DR_OK, DR_EINVAL, DR_ELAUNCH, DR_ESHAPE = 0, -1, -2, -3
 _ERR = {DR_EINVAL: "DR_EINVAL (bad argument)", DR_ELAUNCH: "DR_ELAUNCH (HIP launch error)",

@@ -15,6 +15,7 @@
 // as straightforward fp32 kernels (one thread per output element, W broadcast across the lanes of a wave; dW as a block
 // reduction per (i, j)): correct and coalesced, not tuned -- CIN is outside BASELINE.json's configurations.
 #include "dr_common.h"
+#include "dr_cin_act.h"             // cin_act / cin_act_grad (shared with cin_pool.hip)
 
 namespace {
 
@@ -22,20 +23,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CIN_ROWS = 64;        // (b, d) rows per block
 constexpr int CIN_PITCH = 65;       // LDS pitch of a field's row values (bank-conflict-free for the per-field reads)
-
-__device__ __forceinline__ float cin_act(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.f);
-    if (act == 2) return 1.f / (1.f + expf(-v));
-    if (act == 3) return tanhf(v);
-    return v;
-}
-// activation'(pre) expressed through out = activation(pre)
-__device__ __forceinline__ float cin_act_grad(float out, int act) {
-    if (act == 1) return out > 0.f ? 1.f : 0.f;
-    if (act == 2) return out * (1.f - out);
-    if (act == 3) return 1.f - out * out;
-    return 1.f;
-}
 
 // grid.x: blocks of 64 (b, d) rows; grid.y: groups of 64 feature maps.  4 waves: wave = (row half, f half): 32 f x 32 rows each.
 __global__ __launch_bounds__(256) void cin_fwd_kernel(const float* __restrict__ x0, const float* __restrict__ x, int64_t B,

@@ -2,3 +2,5 @@
 from deep_recommenders_amd.keras.models.ranking.fm import FM
 from deep_recommenders_amd.keras.models.ranking.fm import FactorizationMachine
 from deep_recommenders_amd.keras.models.ranking.deepfm import DeepFM
+from deep_recommenders_amd.keras.models.ranking.xdeepfm import CINNetwork
+from deep_recommenders_amd.keras.models.ranking.xdeepfm import XDeepFM

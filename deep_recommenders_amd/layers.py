@@ -816,3 +816,78 @@ def din_interest_pooling(query, keys, mask, W, b, w_out, b_out, mode, act, alpha
     alpha [U] and eps.  Masked keys are skipped, not multiplied by zero: what they hold reaches no result and their gradient is exactly
     0.  One kernel forward; the backward recomputes the hidden layer and keeps only its [B * T, U] gradient."""
     return _DinPoolFn.apply(query, keys, mask, W, b, w_out, b_out, int(mode), int(act), alpha, float(eps))
+
+
+# ---- xDeepFM: the CIN layer with its sum pooling, and a stack of them (csrc/cin_pool.hip) -------------------------------------------------
+class _CinPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x0, x, W, bias, act, want_out):
+        out, pooled = ops.cin_pool_fwd(x0, x, W, bias, act, want_out=want_out or act != 0)
+        ctx.act, ctx.has_bias = act, bias is not None
+        ctx.save_for_backward(x0, x, W, out)
+        if not want_out:
+            return None, pooled
+        return out, pooled
+
+    @staticmethod
+    def backward(ctx, d_out, d_pooled):
+        x0, x, W, out = ctx.saved_tensors
+        if d_out is None and d_pooled is None:
+            return None, None, None, None, None, None
+        # one layer cannot know what else feeds x0: d_x0 is returned and autograd adds (cin_stack below is where accumulate_x0 is used)
+        d_x0, d_x, dW, dbias = ops.cin_pool_bwd(x0, x, W, ctx.act, out, d_out, d_pooled, want_bias=ctx.has_bias)
+        return d_x0, d_x, dW, dbias, None, None
+
+
+def cin_pool(x0, x, W, bias=None, act=0, want_out=True):
+    """(out [B, Fm, D] | None, pooled [B, Fm]) of one CIN layer: out = act(conv1d(x0 (x) x, W) + bias), pooled = out.sum(-1), one kernel.
+    want_out=False returns no out (a stack's last layer is only read through its pooling); with a non-linear act it is still computed
+    and kept for the backward.  The backward takes either gradient being absent and returns d_x0 for autograd to add."""
+    return _CinPoolFn.apply(x0, x, W, bias, int(act), bool(want_out))
+
+
+class _CinStackFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x0, act, n, *params):
+        Ws, biases = params[:n], params[n:]
+        outs, pooled = [], []
+        x = x0
+        for k in range(n):
+            last = k == n - 1
+            out, p = ops.cin_pool_fwd(x0, x, Ws[k], biases[k], act, want_out=not last or act != 0)
+            outs.append(out)
+            pooled.append(p)
+            x = out
+        ctx.act, ctx.n = act, n
+        ctx.has_bias = [b is not None for b in biases]
+        ctx.last_out = outs[-1] is not None
+        ctx.save_for_backward(x0, *Ws, *[o for o in outs if o is not None])
+        return torch.cat(pooled, dim=1) if n > 1 else pooled[0]
+
+    @staticmethod
+    def backward(ctx, d_res):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        x0, Ws = saved[0], saved[1:1 + n]
+        outs = list(saved[1 + n:]) + ([] if ctx.last_out else [None])
+        sizes = [W.shape[1] for W in Ws]
+        offs = [sum(sizes[:k]) for k in range(n)]
+        # every layer sends a gradient to the same x0: the last layer's call writes d_x0 and the others add to it in the kernel
+        # (accumulate_x0); only the first layer's d_x, whose x IS x0, costs an elementwise add
+        d_x0, d_next = None, None
+        dWs, dbs = [None] * n, [None] * n
+        for k in reversed(range(n)):
+            xk = x0 if k == 0 else outs[k - 1]
+            d_x0, d_next, dWs[k], dbs[k] = ops.cin_pool_bwd(x0, xk, Ws[k], ctx.act, outs[k], d_next, d_res[:, offs[k]:offs[k] + sizes[k]],
+                                                            want_bias=ctx.has_bias[k], d_x0=d_x0)
+        d_x0 += d_next
+        return (d_x0, None, None) + tuple(dWs) + tuple(dbs)
+
+
+def cin_stack(x0, Ws, biases, act=0):
+    """[B, sum Fm_k]: the pooled outputs of x_k = CIN(x0, x_{k-1}; Ws[k], biases[k]), x_0 = x0, concatenated (xDeepFM's direct connection).
+    The last layer's out is not written when act is linear.  One autograd node, so the backward accumulates d_x0 inside the kernels."""
+    n = len(Ws)
+    if n == 0 or len(biases) != n:
+        raise ValueError("cin_stack: one W and one bias (or None) per layer, at least one layer")
+    return _CinStackFn.apply(x0, int(act), n, *Ws, *biases)

@@ -1467,6 +1467,61 @@ def cin_bwd(x0, x, W, act, out, d_out, want_bias=False):
     return d_x0, d_x, dW, dbias
 
 
+def _cin_pool_dims(x0, x, W):
+    if x0.dim() != 3 or x.dim() != 3 or W.dim() != 2:
+        raise ValueError("cin_pool: x0 [B, H0, D], x [B, Hk, D], W [H0 * Hk, Fm] (got %s, %s, %s)"
+                         % (tuple(x0.shape), tuple(x.shape), tuple(W.shape)))
+    B, H0, D = x0.shape
+    Hk, Fm = x.shape[1], W.shape[1]
+    if x.shape != (B, Hk, D) or W.shape[0] != H0 * Hk:
+        raise ValueError("cin_pool: shapes do not agree (x0 %s, x %s, W %s)" % (tuple(x0.shape), tuple(x.shape), tuple(W.shape)))
+    return B, H0, Hk, D, Fm
+
+
+def cin_pool_fwd(x0, x, W, bias=None, act=0, want_out=True, want_pooled=True):
+    """(out [B, Fm, D] | None, pooled [B, Fm] | None) of dr_cin_pool_fwd: cin_fwd's out and pooled = out.sum(-1) in one launch."""
+    x0, x, W = _c(x0, torch.float32), _c(x, torch.float32), _c(W, torch.float32)
+    B, H0, Hk, D, Fm = _cin_pool_dims(x0, x, W)
+    out = torch.empty((B, Fm, D), dtype=torch.float32, device=x0.device) if want_out else None
+    pooled = torch.empty((B, Fm), dtype=torch.float32, device=x0.device) if want_pooled else None
+    check(lib().dr_cin_pool_fwd(ptr(x0), ptr(x), B, H0, Hk, D, ptr(W), Fm, ptr(None if bias is None else _c(bias, torch.float32)), int(act),
+                                ptr(out), ptr(pooled), stream_ptr()), "dr_cin_pool_fwd")
+    return out, pooled
+
+
+def cin_pool_bwd_partials(B, H0, Hk, D, Fm):
+    """how many per-chunk partials of dW dr_cin_pool_bwd adds for these sizes, from the workspace size (include/dr_hotpath.h's formula)"""
+    nb = lib().dr_cin_pool_bwd_workspace_bytes(B, H0, Hk, D, Fm)
+    packed = H0 * ((Hk + 31) // 32) * ((Fm + 7) // 8) * 256
+    return (nb // 4 - packed) // (H0 * Hk * Fm + Fm)
+
+
+def cin_pool_bwd(x0, x, W, act, out, d_out, d_pooled, want_bias=False, d_x0=None, workspace=None):
+    """(d_x0, d_x, dW, dbias | None) of dr_cin_pool_bwd.  d_out [B, Fm, D] or d_pooled [B, Fm] may be None; out may be None for act 0.
+    d_x0 given: the gradient is added to it in place (accumulate_x0) and it is returned.  workspace: an fp32 tensor to use instead of
+    allocating dr_cin_pool_bwd_workspace_bytes."""
+    x0, x, W = _c(x0, torch.float32), _c(x, torch.float32), _c(W, torch.float32)
+    B, H0, Hk, D, Fm = _cin_pool_dims(x0, x, W)
+    d_out = None if d_out is None else _c(d_out, torch.float32)
+    d_pooled = None if d_pooled is None else _c(d_pooled, torch.float32)
+    if (d_out is not None and d_out.shape != (B, Fm, D)) or (d_pooled is not None and d_pooled.shape != (B, Fm)) or \
+            (out is not None and out.shape != (B, Fm, D)):
+        raise ValueError("cin_pool backward: shapes do not agree")
+    accumulate = d_x0 is not None
+    if accumulate and (d_x0.shape != x0.shape or d_x0.dtype != torch.float32 or not d_x0.is_contiguous()):
+        raise ValueError("cin_pool backward: d_x0 to accumulate into must be a contiguous fp32 tensor shaped like x0")
+    if not accumulate:
+        d_x0 = torch.empty_like(x0)
+    d_x, dW = torch.empty_like(x), torch.empty_like(W)
+    dbias = torch.empty(Fm, dtype=torch.float32, device=x0.device) if want_bias else None
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(max(lib().dr_cin_pool_bwd_workspace_bytes(B, H0, Hk, D, Fm) // 4, 4), dtype=torch.float32, device=x0.device)
+    check(lib().dr_cin_pool_bwd(ptr(x0), ptr(x), B, H0, Hk, D, ptr(W), Fm, int(act), ptr(out), ptr(d_out), ptr(d_pooled), ptr(d_x0),
+                                int(accumulate), ptr(d_x), ptr(dW), ptr(dbias), ptr(ws), ws.numel() * 4, stream_ptr()), "dr_cin_pool_bwd")
+    return d_x0, d_x, dW, dbias
+
+
 def din_concat_fwd(x, y, mode):
     x, y = _c(x, torch.float32), _c(y, torch.float32)
     B, D = x.shape

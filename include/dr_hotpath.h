@@ -842,6 +842,31 @@ int dr_cin_bwd(const float* x0, const float* x, int64_t B, int32_t H0, int32_t H
                float* dbias, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CIN with its sum pooling, for stacks (xDeepFM's CINNetwork), csrc/cin_pool.hip.  Same tensors and act codes as above.
+ *   dr_cin_pool_fwd   out [B, Fm, D] as dr_cin_fwd and pooled[b, f] = sum_d out[b, f, d] ([B, Fm]) in one launch.  A block owns whole
+ *                     examples, so pooled is summed in a fixed order (no atomics) and no example's result depends on its neighbours.
+ *                     out or pooled may be NULL (then it is not written); both NULL is DR_EINVAL.
+ *                     DR_ESHAPE when (H0 + Hk + 64) * 65 floats exceed the 160 KB LDS.
+ *   dr_cin_pool_bwd   with g = (d_out + d_pooled[:, :, None]) * act'(out): d_x0 [B, H0, D], d_x [B, Hk, D], dW [H0 * Hk, Fm] and
+ *                     dbias [Fm] (may be NULL), all three products on the fp32-input MFMA; bit-reproducible (no float atomics).
+ *                     d_out or d_pooled may be NULL (contributes zero; both NULL is DR_EINVAL); out may be NULL only for act 0.
+ *                     accumulate_x0 != 0: the gradient is ADDED to what d_x0 holds (every layer of a stack feeds the same x0).
+ *                     workspace: 16-byte aligned, at least dr_cin_pool_bwd_workspace_bytes(B, H0, Hk, D, Fm) bytes
+ *                       = 4 * (H0 * ceil(Hk / 32) * ceil(Fm / 8) * 256  [W packed for the MFMA's A operand]
+ *                              + chunks * (H0 * Hk * Fm + Fm))          [per-chunk partials of dW and dbias, added in chunk order]
+ *                     where the B * D rows are split into `chunks` <= 64 runs of whole 64-row tiles.
+ *                     DR_ESHAPE when (8 * ceil(Fm / 8) + 3 * H0 + 32 * ceil(Hk / 32)) * 65 floats exceed the 160 KB LDS.
+ *   Both: DR_EINVAL for a NULL required pointer, a negative or zero size, act outside 0..3 or a short workspace; B == 0 is DR_OK and
+ *   launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+int dr_cin_pool_fwd(const float* x0, const float* x, int64_t B, int32_t H0, int32_t Hk, int32_t D, const float* W, int32_t Fm,
+                    const float* bias, int32_t act, float* out, float* pooled, dr_stream_t stream);
+int64_t dr_cin_pool_bwd_workspace_bytes(int64_t B, int32_t H0, int32_t Hk, int32_t D, int32_t Fm);
+int dr_cin_pool_bwd(const float* x0, const float* x, int64_t B, int32_t H0, int32_t Hk, int32_t D, const float* W, int32_t Fm,
+                    int32_t act, const float* out, const float* d_out, const float* d_pooled, float* d_x0, int32_t accumulate_x0,
+                    float* d_x, float* dW, float* dbias, void* ws, int64_t ws_bytes, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * DIN ActivationUnit input (keras/models/ranking/din.py:59-67): out[b, :] = concat(x[b], y[b], interacter(x, y)[b])
  * mode 0: no interacter (2 D columns), 1: x - y (keras Subtract, the reference test's interacter), 2: x * y (Multiply).
  * The two Dense layers that follow (:69-70) are dr_linear_fwd / dr_linear_bwd_*.
