@@ -125,6 +125,11 @@ SIGNATURES = {
     "dr_cross_combine_bwd_amax": [_p, _p, _p, _i64, _i32, _i64, _f32, _p, _p, _p, _p, _p],
     "dr_h2_emb_linear_fwd": [_p, _i64, _i32, _p, _i64, _p, _i32, _p, _p, _p, _p, _p, _p, _i64, _i32, _p, _i64, _i64, _p, _i32, _p, _i32,
                              _p, _p, _p, _i64, _p, _p],
+    "dr_h2_emb_linear_tail_fwd_workspace_bytes": [_i64],
+    "dr_h2_emb_linear_tail_fwd": [_p, _i64, _i32, _p, _i64, _p, _i32, _p, _p, _p, _p, _p, _p, _i64, _i32, _p, _i64, _i64, _p, _i32, _p, _i32,
+                                  _p, _p, _p, _i64, _p,
+                                  _p, _i64, _p, _i32, _p, _i64, _p, _p, _i32, _f32, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64,
+                                  _p, _p, _i64, _i32, _p, _p],
     "dr_h2_wgrad": [_p, _i64, _p, _p, _i64, _p, _i64, _i32, _i32, _f32, _p, _i64, _p, _p, _i64, _p],
     "dr_h2_wgrad_emb": [_p, _i64, _i32, _p, _p, _i32, _p, _p, _p, _p, _i64, _p, _i32, _i32, _f32, _p, _i64, _p, _p, _i64, _i32, _p],
     "dr_cin_fwd": [_p, _p, _i64, _i32, _i32, _i32, _p, _i32, _p, _i32, _p, _p],
@@ -192,7 +197,7 @@ SIGNATURES = {
     "dr_get_gemm_split": [],
 }
 _RESTYPE = {"dr_version": ctypes.c_char_p, "dr_shard_bucket_workspace_bytes": ctypes.c_int64,
-            "dr_emb_sort_workspace_bytes": ctypes.c_int64, "dr_tower_tail_workspace_bytes": ctypes.c_int64, "dr_ivf_build_workspace_bytes": ctypes.c_int64,
+            "dr_emb_sort_workspace_bytes": ctypes.c_int64, "dr_tower_tail_workspace_bytes": ctypes.c_int64, "dr_h2_emb_linear_tail_fwd_workspace_bytes": ctypes.c_int64, "dr_ivf_build_workspace_bytes": ctypes.c_int64,
             "dr_linear_bwd_dw_workspace_bytes": ctypes.c_int64,
             "dr_linear_fwd_splitk_workspace_bytes": ctypes.c_int64,
             "dr_bf3_gemm_tn_workspace_bytes": ctypes.c_int64,

@@ -17,14 +17,11 @@
 // s_waitcnt vmcnt(0) each (see emb_pool.hip).
 //
 // Bounded by HBM: algorithmic bytes = 4 M (2 K + N).
-#include "dr_common.h"
+#include "tower_tail_core.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int TT_ROWS = 32;     // rows per chunk (one MFMA tile)
-constexpr int TT_P = 33;        // LDS pitch of the dy chunk
+using namespace drtail;
 
 template <int KT> struct VecT;
 template <> struct VecT<1> { typedef float type; };
@@ -43,13 +40,6 @@ template <> __device__ __forceinline__ void vset<2>(float2& v, int i, float x) {
 template <> __device__ __forceinline__ void vset<4>(float4& v, int i, float x) {
     if (i == 0) v.x = x; else if (i == 1) v.y = x; else if (i == 2) v.z = x; else v.w = x;
 }
-
-// s_barrier behind the wave's own LDS traffic only.  __syncthreads() also waits vmcnt(0): with it every barrier of the loop below would
-// sit out the NEXT chunk's prefetch (and this chunk's dx stores) -- three times per chunk.  The hazards the barriers order are all
-// LDS ones; registers loaded from HBM are waited for by the compiler where they are used.
-__device__ __forceinline__ void tail_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ int tt_row(int j, int h) { return (j & 3) + 8 * (j >> 2) + 4 * h; }
 
 // KT = K / 128: every wave owns 32*KT columns; lane c holds the KT adjacent columns  col0 + KT*c + t  (one KT-wide
 // vector load per row), so "tile t" is the column set { col0 + KT*c + t : c < 32 }.
@@ -249,7 +239,8 @@ __global__ __launch_bounds__(256) void linear_bwd_narrow_reduce_kernel(const flo
 #ifndef DR_TAIL_DBG
 #define DR_TAIL_DBG 0
 #endif
-constexpr int TAIL_HEAD_PART = 34;          // == HEAD_PART of dense.hip: dw2[32], db2, loss
+// (the stage bodies -- head product, head epilogue of a row, narrow backward of a tile -- live in tower_tail_core.h: the fused
+// first-layer forward runs the same steps as its epilogue)
 
 struct TailArgs {
     const float* x; int64_t ldx;
@@ -346,14 +337,7 @@ __global__ __launch_bounds__(64 * NWV, (DR_TAIL_DBG & 1) ? 4 : 2) void tower_tai
 #pragma unroll
             for (int j = 0; j < 16; ++j) acc1[j] = 0.f;
             const float* xr = &xs[c * XP + cb];               // row m = c, this wave-half's 16 columns
-#pragma unroll
-            for (int q = 0; q < ((DR_TAIL_DBG & 16) ? 1 : 4); ++q) {
-                const float4 v = *reinterpret_cast<const float4*>(xr + 4 * q);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v.x, w1f[4 * q + 0], acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v.y, w1f[4 * q + 1], acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v.z, w1f[4 * q + 2], acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v.w, w1f[4 * q + 3], acc1, 0, 0, 0);
-            }
+            DR_TAIL_HEAD_MFMA((DR_TAIL_DBG & 16) ? 1 : 4, acc1, xr, w1f)
             // this wave's partial [32 rows][32 n] -> LDS (C/D layout: column n = c, row = tt_row(reg, h))
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) red[wave][tt_row(reg, h) * TT_P + c] = acc1[reg];
@@ -369,18 +353,7 @@ __global__ __launch_bounds__(64 * NWV, (DR_TAIL_DBG & 1) ? 4 : 2) void tower_tai
             float v = 0.f;
 #pragma unroll
             for (int w = 0; w < NWV; ++w) v += red[w][li];   // fixed order
-            v = fmaxf(v + b1j, 0.f);
-            if (!cv) v = 0.f;
-            float dot = v * w2j;
-#pragma unroll
-            for (int o = 1; o < 32; o <<= 1) dot += __shfl_xor(dot, o, 64);
-            const float lg = (dot + b2v) + extv[rr];
-            float p, l, gr;
-            if constexpr (DR_TAIL_DBG & 32) { p = lg; l = lg; gr = lg - labv[rr]; }
-            else dr_bce_terms(lg, labv[rr], a.loss_mode, p, l, gr);
-            float gs = gr * a.inv_n;
-            if (!live_block) { l = 0.f; gs = 0.f; }
-            const float dh = !(v > 0.f) ? 0.f : gs * w2j;
+            DR_TAIL_HEAD_ROW(!(DR_TAIL_DBG & 32), v, b1j, cv, w2j, b2v, extv[rr], labv[rr], a.loss_mode, a.inv_n, live_block, p, l, gs, dh)
             dys[li] = dh;
             if (live_block) {
                 if (c == 0) {
@@ -404,22 +377,7 @@ __global__ __launch_bounds__(64 * NWV, (DR_TAIL_DBG & 1) ? 4 : 2) void tower_tai
 #pragma unroll 8
             for (int r = 0; r < TT_ROWS; ++r) bias_acc += dys[r * TT_P + c];
         }
-#pragma unroll
-        for (int s = 0; s < ((DR_TAIL_DBG & 64) ? 1 : 16); ++s) accw = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[s], dwb[s], accw, 0, 0, 0);
-        {
-            f32x16 acc;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-#pragma unroll
-            for (int s = 0; s < ((DR_TAIL_DBG & 64) ? 1 : 16); ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(dxa[s], wf[s], acc, 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                float v = acc[j];
-                if (!(xv[j] > 0.f)) v = 0.f;
-                dx_max = fmaxf(dx_max, fabsf(v));
-                xv[j] = v;
-            }
-        }
+        DR_TAIL_BWD_TILE((DR_TAIL_DBG & 64) ? 1 : 16, xv, dxa, dwb, wf, accw, dx_max)
         if (live_block && (!(DR_TAIL_DBG & 128) || chunk < 0)) {
             float* base = a.dx + chunk * TT_ROWS * lddx;                      // wave-uniform
 #pragma unroll
@@ -555,6 +513,15 @@ int tt_grid(int64_t M) {
 
 }  // namespace
 
+int drtail::launch_reduce(const float* partial, const float* head_partial, int32_t nparts, int32_t K, int32_t H, float scale, float inv_n,
+                          float* dst_w1, int64_t ld_dst_w1, float* dst_b1, float* dst_w2, int64_t ld_dst_w2, float* dst_b2,
+                          float* loss_out, const uint32_t* amax_part, uint32_t* dx_amax, dr_stream_t stream) {
+    hipLaunchKernelGGL(tower_tail_reduce_kernel, dim3(K + 2), dim3(256), 0, dr_s(stream), partial, head_partial, nparts, K, H, scale, inv_n,
+                       dst_w1, ld_dst_w1, dst_b1, dst_w2, ld_dst_w2, dst_b2, loss_out, amax_part, dx_amax);
+    DR_CHECK_LAUNCH();
+    return DR_OK;
+}
+
 extern "C" int64_t dr_linear_bwd_narrow_workspace_bytes(int64_t M, int32_t K, int32_t N) {
     (void)N;
     if (M < TT_ROWS) return 256;
@@ -664,10 +631,9 @@ extern "C" int dr_tower_tail_fused(const float* x, int64_t ld_x, const float* W1
         if (K == 128) hipLaunchKernelGGL((tower_tail_fused_kernel<4>), dim3(grid), dim3(256), 0, dr_s(stream), a);
         else hipLaunchKernelGGL((tower_tail_fused_kernel<8>), dim3(grid), dim3(512), 0, dr_s(stream), a);
     }
-    if (parts & 2) {
-        hipLaunchKernelGGL(tower_tail_reduce_kernel, dim3(K + 2), dim3(256), 0, dr_s(stream), partial, head_partial, grid, K, H, scale, inv_n,
-                           dst_w1, ld_dst_w1, dst_b1, dst_w2, ld_dst_w2, dst_b2, loss_out, amax_part, dx_amax);
-    }
     DR_CHECK_LAUNCH();
+    if (parts & 2)
+        return launch_reduce(partial, head_partial, grid, K, H, scale, inv_n, dst_w1, ld_dst_w1, dst_b1, dst_w2, ld_dst_w2, dst_b2, loss_out,
+                             amax_part, dx_amax, stream);
     return DR_OK;
 }

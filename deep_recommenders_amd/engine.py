@@ -214,6 +214,16 @@ class DeepFMEngine:
             self._dense_amaxs = [ops.h2_record(device) for _ in range(2)] if self._dense_pads is not None else None
             self.dh0_amax = ops.h2_record(device)
             self._amax_scratch = ops.h2_record(device)
+        # The tower tail as the EPILOGUE of the fused first layer (dr_h2_emb_linear_tail_fwd): with a [256, H <= 32] tower a wave of that
+        # GEMM ends its main loop holding complete rows of h0, so the 256 -> H -> 1 forward, the loss and the backward down to d h0 run
+        # on the accumulators -- h0 (67 MB at config 3) is not read back, and the tail's launch and its dependent boundary are gone.
+        # Row-wise results are bit-identical to the two launches (tests/test_gpu_fwd_tail.py).  Training steps, SGD, the f16x2 mode.
+        # DR_TAIL_IN_FWD=0: the fused forward and the one-pass tail as two launches.
+        self.tail_in_fwd = (os.environ.get("DR_TAIL_IN_FWD", "1") != "0" and self.h2 and self.fuse_k3 and self.fuse_tail and nl == 3
+                            and optimizer == "sgd"
+                            and ops.h2_emb_linear_tail_supported(B, self.Ws[0].shape[1], self.Ws[1].shape[1]))
+        self.fwd_tail_ws = ops.h2_emb_linear_tail_workspace(B, device) if self.tail_in_fwd else None
+        self._tail_in_fwd_ran = False            # (what the last forward did)
         self._tighten_every = int(os.environ.get("DR_AMAX_TIGHTEN_STEPS", "2048"))
         self._steps_since_tighten = 0
         # The slot sort of batch s + 1 next to K4 of batch s (a step called without next_keys hashes and sorts its own batch).  K4 is
@@ -596,6 +606,35 @@ class DeepFMEngine:
         head = self.fuse_head and labels is not None
         nl = len(self.Ws)
         self._lin_old_valid = False
+        self._tail_in_fwd_ran = False
+        if self.tail_in_fwd and head and fused_l0 and self._in_train_step:
+            # K3 + first Dense + the whole tower tail in one launch (+ the tail's reduce): prob, loss, d_logit, d_h, d h0 and the SGD steps
+            # of the two small layers.  h0 is still stored (hs[0]: the engine's activations stay observable, and the full-size oracle
+            # tests read the ReLU decisions off them) but nothing reads it back
+            W0, W1, W2 = self.Ws
+            work = 2.0 * B * W0.shape[0] * W0.shape[1] + 3 * 2.0 * B * W1.shape[0] * 32
+            def fwd_tail(parts):
+                return ops.h2_emb_linear_tail_fwd(self.ids, self.row_base, self.V, self.table, self.tab_amax, self.lin_w, self.lin_bias,
+                                                  self.dense_pad, self.dense_amax, None, self.in_dim, self.wplanes[0].wt, self.bs[0],
+                                                  self.acts[0], self.sum_x, self.fm_logit, self.hs[0], W1, self.bs[1], W2, self.bs[2], labels,
+                                                  loss_mode, -self.lr, self.dhs[0], lin_vals_t=self.lin_old_t, prob=self.prob,
+                                                  d_logit=self.d_logit, d_h=self.dhs[-1], loss=self.loss, workspace=self.fwd_tail_ws,
+                                                  parts=parts, dx_amax=self.dh0_amax if (parts & 1) else None)
+            if self.reduce_side:                 # (the tail's reduce on the side stream, as with the tail as a kernel of its own)
+                self._k("emb_linear_fwd_L0", "mfma", work, lambda: fwd_tail(1))
+                self._side_part2(lambda: fwd_tail(2))
+            else:
+                self._k("emb_linear_fwd_L0", "mfma", work, lambda: fwd_tail(3))
+            self._lin_old_valid = self.lin_old_t is not None
+            # the next batch's prefetch chain keeps its start behind this launch: it now runs beside the wgrad.  Measured against a start
+            # behind the wgrad's main kernel and behind the fused dgrad + K4 (same call, alternating, three runs each, before this kernel
+            # stored h0): 0.892 - 0.898 ms against 0.900 - 0.905 and 0.916 - 0.922 (profiles/r08_tail_in_fwd_ab.log)
+            if self.prefetch_after_fwd:
+                self._prefetch_early()
+            self._head_done = True
+            self._tail_done = True
+            self._tail_in_fwd_ran = True
+            return self.prob
         for i, (W, b) in enumerate(zip(self.Ws, self.bs)):                             # K7
             if head and i == nl - 2:
                 break

@@ -1356,6 +1356,50 @@ def h2_emb_linear_fwd(ids, row_base, field_rows_max, table, table_amax, lin_w, l
     return out
 
 
+def h2_emb_linear_tail_supported(M, N, H):
+    """Shape domain of the fused first layer with the tower tail as its epilogue (dr_h2_emb_linear_tail_fwd)."""
+    return N == 256 and 0 < H <= 32 and M > 0 and M % 32 == 0
+
+
+def h2_emb_linear_tail_workspace(M, device):
+    return torch.empty(max(128, lib().dr_h2_emb_linear_tail_fwd_workspace_bytes(int(M)) // 4), dtype=torch.float32, device=device)
+
+
+def h2_emb_linear_tail_fwd(ids, row_base, field_rows_max, table, table_amax, lin_w, lin_bias, dense_pad, dense_amax, concat, K, wt: H2Planes, bias,
+                           act, sum_x, fm_logit, out, W1, b1, W2, b2, labels, loss_mode, scale, dx, lin_vals_t=None, dst_W1="inplace",
+                           dst_b1="inplace", dst_W2="inplace", dst_b2="inplace", prob=None, d_logit=None, d_h=None, loss=None, workspace=None,
+                           parts=3, dx_amax=None):
+    """h2_emb_linear_fwd + tower_tail_fused (extra_logit = fm_logit) in one kernel and the tail's reduce (dr_h2_emb_linear_tail_fwd): the
+    tail runs on the forward GEMM's accumulators.  out (h0) may be None: it is then not written.  Returns (loss, prob, d_logit, dx)."""
+    ids = _c(ids, torch.int64)
+    M, F = ids.shape
+    N, H = wt.rows, W1.shape[1]
+    dev = table.device
+    dst_W1 = W1 if isinstance(dst_W1, str) else dst_W1
+    dst_b1 = b1 if isinstance(dst_b1, str) else dst_b1
+    dst_W2 = W2 if isinstance(dst_W2, str) else dst_W2
+    dst_b2 = b2 if isinstance(dst_b2, str) else dst_b2
+    assert (concat is None or concat.stride(1) == 1) and wt.cols == K and (out is None or (out.stride(1) == 1 and out.shape == (M, N)))
+    assert dense_pad is None or (dense_pad.shape == (M, 32) and dense_pad.is_contiguous())
+    assert lin_vals_t is None or (lin_vals_t.shape == (F, M) and lin_vals_t.is_contiguous() and lin_vals_t.dtype == torch.float32)
+    assert W1.shape[0] == N and W1.stride(1) == 1 and dst_W1.stride(1) == 1 and W2.shape == (H, 1) and dx.shape == (M, N) and dx.stride(1) == 1
+    assert labels.numel() == M and labels.is_contiguous() and labels.dtype == torch.float32
+    prob = prob if prob is not None else torch.empty(M, dtype=torch.float32, device=dev)
+    d_logit = d_logit if d_logit is not None else torch.empty(M, dtype=torch.float32, device=dev)
+    loss = loss if loss is not None else torch.empty(1, dtype=torch.float32, device=dev)
+    if workspace is None:
+        workspace = h2_emb_linear_tail_workspace(M, dev)
+    check(lib().dr_h2_emb_linear_tail_fwd(
+        ptr(ids), M, F, ptr(row_base), int(field_rows_max), ptr(table), table.shape[1], ptr(table_amax), ptr(lin_w), ptr(lin_bias),
+        ptr(dense_pad), ptr(dense_amax), ptr(concat), concat.stride(0) if concat is not None else 0, int(K), ptr(wt.buf), wt.plane_stride,
+        wt.ld, ptr(wt.amax), N, ptr(bias), int(act), ptr(sum_x), ptr(fm_logit), ptr(out), out.stride(0) if out is not None else 0,
+        ptr(lin_vals_t), ptr(W1), W1.stride(0), ptr(b1), H, ptr(W2), W2.stride(0), ptr(b2), ptr(labels), int(loss_mode), float(scale),
+        ptr(dst_W1), dst_W1.stride(0), ptr(dst_b1), ptr(dst_W2), dst_W2.stride(0) if dst_W2 is not None else 0, ptr(dst_b2), ptr(prob),
+        ptr(d_logit), ptr(d_h), d_h.stride(0) if d_h is not None else 0, ptr(dx), dx.stride(0), ptr(loss), ptr(workspace),
+        workspace.numel() * 4, int(parts), ptr(dx_amax), stream_ptr()), "dr_h2_emb_linear_tail_fwd")
+    return loss, prob, d_logit, dx
+
+
 def h2_wgrad(x, x_amax, dy, dy_amax, scale, dstW, dstb=None, workspace=None):
     """bf3_wgrad in the f16x2 mode."""
     R, F = x.shape

@@ -818,6 +818,24 @@ int dr_h2_emb_linear_fwd(const int64_t* ids, int64_t M, int32_t F, const int64_t
                          const uint32_t* dense_amax, float* concat, int64_t ld_concat, int32_t K, const void* wt_planes,
                          int64_t plane_stride, int64_t ld_planes, const uint32_t* w_amax, int32_t N, const float* bias, int32_t act,
                          float* sum_x, float* fm_logit, float* out, int64_t ld_out, float* lin_vals_t, dr_stream_t stream);
+/* dr_h2_emb_linear_fwd followed by dr_tower_tail_fused (extra_logit = fm_logit, n_total = M) on its output h0, as ONE kernel plus the
+ * tail's reduce: the tail runs as the forward GEMM's epilogue, on the accumulators.  `out` (h0) may be NULL: it is then never written.
+ * prob, d_logit, d_h (may be NULL), dx = d h0 [M, N] and the record dx_amax (may be NULL; parts == 3: stored by the reduce, parts == 1:
+ * reset in front of the kernel and raised by it, parts == 2: ignored) are the bits the two calls give; dst_* += scale * gradient and loss_out are the same fixed-order fp32 sums, grouped by this kernel's blocks (one per 256
+ * rows).  parts: 1 = the kernel, 2 = the reduce (dr_tower_tail_fused's), 3 = both.
+ * Domain: N == 256, H <= 32, M a positive multiple of 32, and dr_h2_emb_linear_fwd's (D == 64, K <= 64 F + 32, field_rows_max <= 2^24);
+ * outside it: DR_ESHAPE, nothing launched. */
+int64_t dr_h2_emb_linear_tail_fwd_workspace_bytes(int64_t M);
+int dr_h2_emb_linear_tail_fwd(const int64_t* ids, int64_t M, int32_t F, const int64_t* row_base, int64_t field_rows_max,
+                              const float* table, int32_t D, const uint32_t* table_amax, const float* lin_w, const float* lin_bias,
+                              const float* dense_pad, const uint32_t* dense_amax, float* concat, int64_t ld_concat, int32_t K,
+                              const void* wt_planes, int64_t plane_stride, int64_t ld_planes, const uint32_t* w_amax, int32_t N,
+                              const float* bias, int32_t act, float* sum_x, float* fm_logit, float* out, int64_t ld_out,
+                              float* lin_vals_t, const float* W1, int64_t ld_w1, const float* b1, int32_t H, const float* w2,
+                              int64_t ld_w2, const float* b2, const float* labels, int32_t loss_mode, float scale, float* dst_w1,
+                              int64_t ld_dst_w1, float* dst_b1, float* dst_w2, int64_t ld_dst_w2, float* dst_b2, float* prob,
+                              float* d_logit, float* d_h, int64_t ld_dh, float* dx, int64_t ld_dx, float* loss_out, void* workspace,
+                              int64_t workspace_bytes, int32_t parts, uint32_t* dx_amax, dr_stream_t stream);
 int dr_h2_wgrad(const float* x, int64_t ld_x, const uint32_t* x_amax, const float* dy, int64_t ld_dy, const uint32_t* dy_amax, int64_t R,
                 int32_t F, int32_t N, float scale, float* dstW, int64_t ld_w, float* dstb, void* workspace, int64_t workspace_bytes,
                 dr_stream_t stream);
