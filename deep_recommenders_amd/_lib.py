@@ -137,6 +137,8 @@ SIGNATURES = {
     "dr_cin_pool_fwd": [_p, _p, _i64, _i32, _i32, _i32, _p, _i32, _p, _i32, _p, _p, _p],
     "dr_cin_pool_bwd_workspace_bytes": [_i64, _i32, _i32, _i32, _i32],
     "dr_cin_pool_bwd": [_p, _p, _i64, _i32, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _i64, _p],
+    "dr_dot_interact_fwd": [_p, _i64, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _p],
+    "dr_dot_interact_bwd": [_p, _i64, _p, _i64, _p, _i64, _i64, _i32, _i32, _i32, _p, _i64, _p, _i64, _p],
     "dr_din_concat_fwd": [_p, _p, _i64, _i32, _i32, _p, _i64, _p],
     "dr_din_concat_bwd": [_p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p],
     "dr_act_fwd": [_p, _i64, _i32, _i64, _i32, _p],

@@ -4,3 +4,5 @@ from deep_recommenders_amd.keras.models.ranking.fm import FactorizationMachine
 from deep_recommenders_amd.keras.models.ranking.deepfm import DeepFM
 from deep_recommenders_amd.keras.models.ranking.xdeepfm import CINNetwork
 from deep_recommenders_amd.keras.models.ranking.xdeepfm import XDeepFM
+from deep_recommenders_amd.keras.models.ranking.dlrm import DotInteraction
+from deep_recommenders_amd.keras.models.ranking.dlrm import DLRM

@@ -891,3 +891,39 @@ def cin_stack(x0, Ws, biases, act=0):
     if n == 0 or len(biases) != n:
         raise ValueError("cin_stack: one W and one bias (or None) per layer, at least one layer")
     return _CinStackFn.apply(x0, int(act), n, *Ws, *biases)
+
+
+# ---- DLRM: the pairwise dot interaction (csrc/dot_interact.hip) ------------------------------------------------------------------------
+class _DotInteractFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dense, emb, F, D, self_interaction):
+        ctx.F, ctx.D, ctx.self_interaction = F, D, self_interaction
+        ctx.emb_shape = emb.shape
+        ctx.save_for_backward(dense, emb)
+        return ops.dot_interact_fwd(dense, emb, F, D, self_interaction)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        dense, emb = ctx.saved_tensors
+        if d_out.dim() != 2 or (d_out.shape[0] > 1 and (d_out.stride(1) != 1 or d_out.stride(0) % 4 != 0 or d_out.stride(0) < d_out.shape[1])):
+            buf = torch.empty((d_out.shape[0], _pad4(d_out.shape[1])), dtype=torch.float32, device=d_out.device)[:, :d_out.shape[1]]
+            buf.copy_(d_out)                                   # layout only: the kernel reads rows at a pitch that is a multiple of 4
+            d_out = buf
+        d_dense, d_emb = ops.dot_interact_bwd(dense, emb, ctx.F, ctx.D, d_out, ctx.self_interaction)
+        return d_dense, d_emb.reshape(ctx.emb_shape), None, None, None
+
+
+def dot_interaction(dense, emb, self_interaction=False):
+    """[B, c0 + P]: DLRM's interaction of the vectors T = [dense; emb's fields] of every example -- dense [B, D] (or None) copied to the
+    first c0 = D columns (c0 = 0 without it), then the row-major lower triangle of T T^T (the diagonal included only with
+    self_interaction), P = N (N -+ 1) / 2 columns.  emb: [B, F, D] contiguous; a [B, F * D] matrix (a column-strided view of the slab's
+    concat is read in place) needs dense to tell D, or else pass it as [B, F, D].  One kernel each way; no [B, N, N] matrix."""
+    if emb.dim() == 3:
+        F, D = int(emb.shape[1]), int(emb.shape[2])
+    elif emb.dim() == 2 and dense is not None and dense.dim() == 2 and dense.shape[1] > 0 and emb.shape[1] % dense.shape[1] == 0:
+        D = int(dense.shape[1])
+        F = int(emb.shape[1]) // D
+    else:
+        raise ValueError("dot_interaction: emb must be [B, F, D], or [B, F * D] next to a dense [B, D]; got emb %s, dense %s"
+                         % (tuple(emb.shape), None if dense is None else tuple(dense.shape)))
+    return _DotInteractFn.apply(dense, emb, F, D, bool(self_interaction))

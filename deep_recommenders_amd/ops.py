@@ -1566,6 +1566,95 @@ def cin_pool_bwd(x0, x, W, act, out, d_out, d_pooled, want_bias=False, d_x0=None
     return d_x0, d_x, dW, dbias
 
 
+# ---- DLRM: the pairwise dot interaction (csrc/dot_interact.hip) ------------------------------------------------------------------------
+def _di_rows(t, cols, what, written_to_pitch=False):
+    """row stride of a [B, cols] fp32 device matrix with unit column stride; ValueError unless it is a multiple of 4 and >= cols.
+    A single row has no pitch to speak of, except where the kernel writes up to it (written_to_pitch: the forward's zero padding)."""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError("dot_interact: %s must be fp32 [B, %d], got %s %s" % (what, cols, t.dtype, tuple(t.shape)))
+    ok = t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= cols
+    if not ok and t.shape[0] <= 1 and t.stride(1) == 1 and (cols % 4 == 0 or not written_to_pitch):
+        return _pad4(cols)
+    if not ok:
+        raise ValueError("dot_interact: %s needs unit column stride and a row stride that is a multiple of 4 and >= %d, got strides %s"
+                         % (what, cols, tuple(t.stride())))
+    return t.stride(0)
+
+
+def _di_dims(dense, emb, F, D, self_interaction):
+    """validates the domain of dr_dot_interact_*; returns (emb as [B, F * D], B, N, c0, P)"""
+    F, D = int(F), int(D)
+    if D % 4 != 0 or not 4 <= D <= 256:
+        raise ValueError("dot_interact: D must be a multiple of 4 in [4, 256], got %d" % D)
+    N = F + (0 if dense is None else 1)
+    if F < 1 or not 2 <= N <= 64:
+        raise ValueError("dot_interact: needs 2 <= N <= 64 vectors per example (F fields + the dense vector), got F = %d, N = %d" % (F, N))
+    if emb.dim() == 3:
+        if emb.shape[1:] != (F, D) or not emb.is_contiguous():
+            raise ValueError("dot_interact: a 3-d emb must be contiguous [B, %d, %d], got %s" % (F, D, tuple(emb.shape)))
+        emb = emb.reshape(emb.shape[0], F * D)
+    B = emb.shape[0]
+    if dense is not None and dense.shape[0] != B:
+        raise ValueError("dot_interact: dense and emb disagree on the batch size")
+    c0 = 0 if dense is None else D
+    P = N * (N + 1) // 2 if self_interaction else N * (N - 1) // 2
+    return emb, B, N, c0, P
+
+
+def dot_interact_width(F, D, dense=True, self_interaction=False):
+    """columns of the interaction output: c0 + P"""
+    N = F + (1 if dense else 0)
+    return (D if dense else 0) + (N * (N + 1) // 2 if self_interaction else N * (N - 1) // 2)
+
+
+def dot_interact_fwd(dense, emb, F, D, self_interaction=False, out=None, ld_out=None):
+    """out [B, c0 + P] (a view of a [B, ld_out] buffer, zero beyond c0 + P) of dr_dot_interact_fwd: dense [B, D] (or None) copied to the
+    first D columns, then the row-major lower triangle of T T^T for T = [dense; emb's F rows].  emb: [B, F, D] contiguous, or
+    [B, F * D] with any row stride that is a multiple of 4.  out: a [B, c0 + P] view to write into (its row stride is ld_out)."""
+    emb, B, N, c0, P = _di_dims(dense, emb, F, D, self_interaction)
+    ld_emb = _di_rows(emb, F * D, "emb")
+    ld_dense = 0 if dense is None else _di_rows(dense, D, "dense")
+    if out is None:
+        ld_out = _pad4(c0 + P) if ld_out is None else int(ld_out)
+        if ld_out % 4 != 0 or ld_out < c0 + P:
+            raise ValueError("dot_interact: ld_out must be a multiple of 4 and >= %d, got %d" % (c0 + P, ld_out))
+        out = torch.empty((B, ld_out), dtype=torch.float32, device=emb.device)[:, :c0 + P]
+    else:
+        ld_out = _di_rows(out, c0 + P, "out", written_to_pitch=True)
+    if B == 0:
+        return out
+    st = lib().dr_dot_interact_fwd(ptr(dense), ld_dense, ptr(emb), ld_emb, B, int(F), int(D), int(bool(self_interaction)), ptr(out),
+                                   ld_out, stream_ptr())
+    if st == _lib.DR_EINVAL:
+        raise ValueError("dr_dot_interact_fwd: DR_EINVAL (outside the kernel's domain, or a base address that is not 16-byte aligned)")
+    check(st, "dr_dot_interact_fwd")
+    return out
+
+
+def dot_interact_bwd(dense, emb, F, D, d_out, self_interaction=False, d_dense=None, d_emb=None):
+    """(d_dense [B, D] | None, d_emb [B, F * D]) of dr_dot_interact_bwd from d_out [B, c0 + P] (row stride a multiple of 4; columns
+    beyond c0 + P are not read).  d_dense / d_emb: buffers to overwrite (only their first D / F * D columns are written)."""
+    emb, B, N, c0, P = _di_dims(dense, emb, F, D, self_interaction)
+    ld_emb = _di_rows(emb, F * D, "emb")
+    ld_dense = 0 if dense is None else _di_rows(dense, D, "dense")
+    ld_dout = _di_rows(d_out, c0 + P, "d_out")
+    if d_emb is None:
+        d_emb = torch.empty((B, F * D), dtype=torch.float32, device=emb.device)
+    if dense is not None and d_dense is None:
+        d_dense = torch.empty((B, D), dtype=torch.float32, device=emb.device)
+    ld_demb = _di_rows(d_emb, F * D, "d_emb")
+    ld_ddense = 0 if dense is None else _di_rows(d_dense, D, "d_dense")
+    if B == 0:
+        return (d_dense if dense is not None else None), d_emb
+    st = lib().dr_dot_interact_bwd(ptr(dense), ld_dense, ptr(emb), ld_emb, ptr(d_out), ld_dout, B, int(F), int(D),
+                                   int(bool(self_interaction)), ptr(d_dense) if dense is not None else None, ld_ddense, ptr(d_emb), ld_demb,
+                                   stream_ptr())
+    if st == _lib.DR_EINVAL:
+        raise ValueError("dr_dot_interact_bwd: DR_EINVAL (outside the kernel's domain, or a base address that is not 16-byte aligned)")
+    check(st, "dr_dot_interact_bwd")
+    return (d_dense if dense is not None else None), d_emb
+
+
 def din_concat_fwd(x, y, mode):
     x, y = _c(x, torch.float32), _c(y, torch.float32)
     B, D = x.shape

@@ -885,6 +885,29 @@ int dr_cin_pool_bwd(const float* x0, const float* x, int64_t B, int32_t H0, int3
                     float* d_x, float* dW, float* dbias, void* ws, int64_t ws_bytes, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DLRM's pairwise dot interaction (Naumov et al. 2019; the reference's README lists DLRM among the models it plans and ships no code
+ * for it), csrc/dot_interact.hip.  Per example, T [N, D] = the row dense[b] (when dense != NULL) followed by the F rows of
+ * emb[b] ([F * D], field-major: the slab's concat, read in place); N = F + (dense != NULL), c0 = dense != NULL ? D : 0.
+ *   dr_dot_interact_fwd   out[b, 0:c0] = dense[b];  the row-major lower triangle of T T^T after it:
+ *                           self_interaction 0: out[b, c0 + i (i - 1) / 2 + j] = <t_i, t_j>, 0 <= j <  i < N   (P = N (N - 1) / 2)
+ *                           self_interaction 1: out[b, c0 + i (i + 1) / 2 + j] = <t_i, t_j>, 0 <= j <= i < N   (P = N (N + 1) / 2)
+ *                         and zeros in columns [c0 + P, ld_out); nothing is written beyond ld_out.
+ *   dr_dot_interact_bwd   with G the lower-triangular matrix of d_out's triangle and S = G + G^T (the diagonal doubled):
+ *                         dT = S T, dT_0 += d_out[b, 0:D];  d_dense [B, D] = dT_0, d_emb [B, F * D] = the other rows.  Reads the first
+ *                         c0 + P columns of d_out only; overwrites D columns of d_dense and F * D columns of d_emb, nothing else.
+ *   Products on the fp32-input MFMA (an fmaf chain in a fixed order); one wave owns one example: no atomics, bit-reproducible, an
+ *   example's bits do not depend on its batch; the [B, N, N] matrix is never written.  One launch each, no workspace.
+ *   Domain: D % 4 == 0, 4 <= D <= 256, 2 <= N <= 64, self_interaction 0 or 1, every ld a multiple of 4 and at least the width it covers
+ *   (ld_dense, ld_ddense >= D; ld_emb, ld_demb >= F * D; ld_out, ld_dout >= c0 + P), dense, emb, d_dense and d_emb 16-byte aligned,
+ *   d_dense given exactly when dense is.  Anything else is DR_EINVAL.  B == 0 is DR_OK and launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+int dr_dot_interact_fwd(const float* dense, int64_t ld_dense, const float* emb, int64_t ld_emb, int64_t B, int32_t F, int32_t D,
+                        int32_t self_interaction, float* out, int64_t ld_out, dr_stream_t stream);
+int dr_dot_interact_bwd(const float* dense, int64_t ld_dense, const float* emb, int64_t ld_emb, const float* d_out, int64_t ld_dout,
+                        int64_t B, int32_t F, int32_t D, int32_t self_interaction, float* d_dense, int64_t ld_ddense, float* d_emb,
+                        int64_t ld_demb, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * DIN ActivationUnit input (keras/models/ranking/din.py:59-67): out[b, :] = concat(x[b], y[b], interacter(x, y)[b])
  * mode 0: no interacter (2 D columns), 1: x - y (keras Subtract, the reference test's interacter), 2: x * y (Multiply).
  * The two Dense layers that follow (:69-70) are dr_linear_fwd / dr_linear_bwd_*.
