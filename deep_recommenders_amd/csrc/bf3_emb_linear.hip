@@ -142,28 +142,19 @@ static int emb_linear_fwd_impl(const int64_t* ids, int64_t M, int32_t F, const i
     return DR_OK;
 }
 
-extern "C" int dr_bf3_emb_linear_fwd(const int64_t* ids, int64_t M, int32_t F, const int64_t* row_base, int64_t field_rows_max,
-                                     const float* table, int32_t D, const float* lin_w, const float* lin_bias, const float* dense_pad, float* concat,
-                                     int64_t ld_concat, int32_t K, const void* wt_planes, int64_t plane_stride, int64_t ld_planes, int32_t N,
-                                     const float* bias, int32_t act, float* sum_x, float* fm_logit, float* out, int64_t ld_out,
-                                     dr_stream_t stream) {
-    return emb_linear_fwd_impl(ids, M, F, row_base, field_rows_max, table, D, lin_w, lin_bias, dense_pad, concat, ld_concat, K, wt_planes,
-                               plane_stride, ld_planes, N, bias, act, sum_x, fm_logit, out, ld_out, nullptr, stream);
-}
-
-// The same, also saving the first-order weight of every slot as it was read: lin_vals_t [F, M] field-major (lin_vals_t[f * M + m] =
-// lin_w[row_base[f] + ids[m, f]]; undefined for a missing id).  dr_emb_pool_bwd_sorted_ex takes it as `lin_old_t`: the backward then
+// lin_vals_t [F, M] field-major (may be NULL): also saves the first-order weight of every slot as it was read (lin_vals_t[f * M + m] =
+// lin_w[row_base[f] + ids[m, f]]; undefined for a missing id).  dr_emb_pool_bwd_sorted takes it as `lin_old_t`: the backward then
 // updates a unique row's first-order weight with ONE write instead of a read-modify-write of a line it would have to fetch again.
-extern "C" int dr_bf3_emb_linear_fwd_lv(const int64_t* ids, int64_t M, int32_t F, const int64_t* row_base, int64_t field_rows_max,
-                                        const float* table, int32_t D, const float* lin_w, const float* lin_bias, const float* dense_pad,
-                                        float* concat, int64_t ld_concat, int32_t K, const void* wt_planes, int64_t plane_stride,
-                                        int64_t ld_planes, int32_t N, const float* bias, int32_t act, float* sum_x, float* fm_logit,
-                                        float* out, int64_t ld_out, float* lin_vals_t, dr_stream_t stream) {
+extern "C" int dr_bf3_emb_linear_fwd(const int64_t* ids, int64_t M, int32_t F, const int64_t* row_base, int64_t field_rows_max,
+                                     const float* table, int32_t D, const float* lin_w, const float* lin_bias, const float* dense_pad,
+                                     float* concat, int64_t ld_concat, int32_t K, const void* wt_planes, int64_t plane_stride,
+                                     int64_t ld_planes, int32_t N, const float* bias, int32_t act, float* sum_x, float* fm_logit,
+                                     float* out, int64_t ld_out, float* lin_vals_t, dr_stream_t stream) {
     return emb_linear_fwd_impl(ids, M, F, row_base, field_rows_max, table, D, lin_w, lin_bias, dense_pad, concat, ld_concat, K, wt_planes,
                                plane_stride, ld_planes, N, bias, act, sum_x, fm_logit, out, ld_out, lin_vals_t, stream);
 }
 
-// dr_bf3_emb_linear_fwd_lv in the f16x2 operand mode: wt_planes = two fp16 planes (dr_h2_split with w_amax); table_amax >= the largest
+// dr_bf3_emb_linear_fwd in the f16x2 operand mode: wt_planes = two fp16 planes (dr_h2_split with w_amax); table_amax >= the largest
 // magnitude in `table` (the engine keeps it as a running maximum: dr_h2_amax over the table once, K4 afterwards); dense_amax = the
 // record of dense_pad (required iff K > 64 F).  lin_vals_t may be NULL.
 extern "C" int dr_h2_emb_linear_fwd(const int64_t* ids, int64_t M, int32_t F, const int64_t* row_base, int64_t field_rows_max,

@@ -1143,12 +1143,17 @@ extern "C" int64_t dr_tower_head_workspace_bytes(int64_t M) {
     return (tiles > 0 ? tiles : 1) * HEAD_PART * (int64_t)sizeof(float);
 }
 
-static int tower_head_impl(const float* x, int64_t ld_x, const float* W1, int64_t ld_w1, const float* b1,
-                           int64_t M, int64_t n_total, int32_t K, int32_t H, int32_t act, const float* w2,
-                           int64_t ld_w2, const float* b2, const float* extra_logit, const float* labels,
-                           int32_t loss_mode, float scale, float* dst_w2, int64_t ld_dst_w2, float* dst_b2,
-                           float* h_out, int64_t ld_h, float* prob, float* d_logit, float* d_h, int64_t ld_dh,
-                           float* loss_out, void* workspace, int64_t workspace_bytes, int32_t parts, dr_stream_t stream) {
+// In two halves (parts = 1: the GEMM + head kernel -- prob, d_logit, d_h and the per-block partials; parts = 2: the small finish kernel
+// that sums the partials into dst_w2 / dst_b2 / loss_out; 3 = both).  Nothing the rest of the step reads comes out of part 2, so a
+// caller may run it on another stream (it must finish before the NEXT call's part 1: w2 / b2 and the workspace).  Round 4: the three
+// small reduce kernels of the step off the training stream.
+extern "C" int dr_tower_head_fwd_bwd(const float* x, int64_t ld_x, const float* W1, int64_t ld_w1, const float* b1,
+                                     int64_t M, int64_t n_total, int32_t K, int32_t H, int32_t act, const float* w2,
+                                     int64_t ld_w2, const float* b2, const float* extra_logit, const float* labels,
+                                     int32_t loss_mode, float scale, float* dst_w2, int64_t ld_dst_w2, float* dst_b2,
+                                     float* h_out, int64_t ld_h, float* prob, float* d_logit, float* d_h, int64_t ld_dh,
+                                     float* loss_out, void* workspace, int64_t workspace_bytes, int32_t parts, dr_stream_t stream) {
+    if (parts < 1 || parts > 3) return DR_EINVAL;
     if (M <= 0 || K <= 0 || H <= 0) return DR_EINVAL;
     if (H > 32) return DR_ESHAPE;
     if (!x || !W1 || !w2 || !labels || !workspace || loss_mode < 0 || loss_mode > 2) return DR_EINVAL;
@@ -1174,32 +1179,6 @@ static int tower_head_impl(const float* x, int64_t ld_x, const float* W1, int64_
     }
     DR_CHECK_LAUNCH();
     return DR_OK;
-}
-
-extern "C" int dr_tower_head_fwd_bwd(const float* x, int64_t ld_x, const float* W1, int64_t ld_w1, const float* b1,
-                                     int64_t M, int64_t n_total, int32_t K, int32_t H, int32_t act, const float* w2,
-                                     int64_t ld_w2, const float* b2, const float* extra_logit, const float* labels,
-                                     int32_t loss_mode, float scale, float* dst_w2, int64_t ld_dst_w2, float* dst_b2,
-                                     float* h_out, int64_t ld_h, float* prob, float* d_logit, float* d_h, int64_t ld_dh,
-                                     float* loss_out, void* workspace, int64_t workspace_bytes, dr_stream_t stream) {
-    return tower_head_impl(x, ld_x, W1, ld_w1, b1, M, n_total, K, H, act, w2, ld_w2, b2, extra_logit, labels, loss_mode, scale, dst_w2,
-                           ld_dst_w2, dst_b2, h_out, ld_h, prob, d_logit, d_h, ld_dh, loss_out, workspace, workspace_bytes, 3, stream);
-}
-
-// The same call in two halves (parts = 1: the GEMM + head kernel -- prob, d_logit, d_h and the per-block partials; parts = 2: the small
-// finish kernel that sums the partials into dst_w2 / dst_b2 / loss_out; 3 = both = the call above).  Nothing the rest of the step
-// reads comes out of part 2, so a caller may run it on another stream (it must finish before the NEXT call's part 1: w2 / b2 and the
-// workspace).  Round 4: the three small reduce kernels of the step off the training stream.
-extern "C" int dr_tower_head_fwd_bwd_parts(const float* x, int64_t ld_x, const float* W1, int64_t ld_w1, const float* b1,
-                                           int64_t M, int64_t n_total, int32_t K, int32_t H, int32_t act, const float* w2,
-                                           int64_t ld_w2, const float* b2, const float* extra_logit, const float* labels,
-                                           int32_t loss_mode, float scale, float* dst_w2, int64_t ld_dst_w2, float* dst_b2,
-                                           float* h_out, int64_t ld_h, float* prob, float* d_logit, float* d_h, int64_t ld_dh,
-                                           float* loss_out, void* workspace, int64_t workspace_bytes, int32_t parts,
-                                           dr_stream_t stream) {
-    if (parts < 1 || parts > 3) return DR_EINVAL;
-    return tower_head_impl(x, ld_x, W1, ld_w1, b1, M, n_total, K, H, act, w2, ld_w2, b2, extra_logit, labels, loss_mode, scale, dst_w2,
-                           ld_dst_w2, dst_b2, h_out, ld_h, prob, d_logit, d_h, ld_dh, loss_out, workspace, workspace_bytes, parts, stream);
 }
 
 extern "C" int dr_linear_fwd(const float* x, int64_t ld_x, const float* W, int64_t ld_w, const float* b, int64_t M,
@@ -1499,25 +1478,13 @@ extern "C" int dr_cross_fwd(const float* x0, const float* x, int64_t ld, const f
     return launch<true, false, EPI_CROSS>(g, dr_s(stream));
 }
 
+// d_prod_amax (may be NULL): also leaves max |d_prod| (float bits) in d_prod_amax[0] (reset first): the amax record of d_prod for the
+// f16x2 GEMMs that take it as an operand (dr_h2_linear_nt, dr_h2_wgrad)
 extern "C" int dr_cross_combine_bwd(const float* x0, const float* prod, const float* d_out, int64_t M, int32_t Dm,
                                     int64_t ld, float diag_scale, float* d_prod, float* d_x0_accum, float* d_x_accum,
-                                    dr_stream_t stream) {
+                                    uint32_t* d_prod_amax, dr_stream_t stream) {
     if (M < 0 || Dm <= 0) return DR_EINVAL;
-    if (M == 0) return DR_OK;
-    if (!x0 || !prod || !d_out || !d_prod || ld < Dm) return DR_EINVAL;
-    hipLaunchKernelGGL(cross_combine_bwd_kernel, dim3(dr_grid_for(M * Dm, 256)), dim3(256), 0, dr_s(stream), x0, prod,
-                       d_out, M, Dm, ld, diag_scale, d_prod, d_x0_accum, d_x_accum, static_cast<uint32_t*>(nullptr));
-    DR_CHECK_LAUNCH();
-    return DR_OK;
-}
-
-// ... that also leaves max |d_prod| (float bits) in d_prod_amax[0] (reset first): the amax record of d_prod for the f16x2 GEMMs that
-// take it as an operand (dr_h2_linear_nt, dr_h2_wgrad)
-extern "C" int dr_cross_combine_bwd_amax(const float* x0, const float* prod, const float* d_out, int64_t M, int32_t Dm,
-                                         int64_t ld, float diag_scale, float* d_prod, float* d_x0_accum, float* d_x_accum,
-                                         uint32_t* d_prod_amax, dr_stream_t stream) {
-    if (M < 0 || Dm <= 0 || !d_prod_amax) return DR_EINVAL;
-    if (hipMemsetAsync(d_prod_amax, 0, sizeof(uint32_t), dr_s(stream)) != hipSuccess) return DR_ELAUNCH;
+    if (d_prod_amax != nullptr && hipMemsetAsync(d_prod_amax, 0, sizeof(uint32_t), dr_s(stream)) != hipSuccess) return DR_ELAUNCH;
     if (M == 0) return DR_OK;
     if (!x0 || !prod || !d_out || !d_prod || ld < Dm) return DR_EINVAL;
     hipLaunchKernelGGL(cross_combine_bwd_kernel, dim3(dr_grid_for(M * Dm, 256)), dim3(256), 0, dr_s(stream), x0, prod,
@@ -1527,9 +1494,6 @@ extern "C" int dr_cross_combine_bwd_amax(const float* x0, const float* prod, con
 }
 
 // ---- K9: in-batch sampled softmax (Retrieval.call, keras/models/retrieval/sbcnm.py:120-151 of the reference) ----------
-extern "C" int dr_inbatch_softmax_grad_scores(const float* q, const float* c, int64_t B, int32_t D, const float* cand_prob,
-                                              const int64_t* cand_ids, const float* sample_weight, float inv_temperature,
-                                              const float* row_lse, float d_loss, float* G, int64_t ld_g, dr_stream_t stream);
 __global__ __launch_bounds__(256) void lse_finalize_kernel(const float* __restrict__ part_m, const float* __restrict__ part_l,
                                                            int32_t nparts, int64_t B, const float* __restrict__ pos,
                                                            const float* __restrict__ w, float* __restrict__ row_lse,
@@ -1633,13 +1597,13 @@ extern "C" int dr_inbatch_softmax_fwd(const float* q, const float* c, int64_t B,
 
 // G[i][j] = d_loss * w_i * (softmax_ij - delta_ij) * inv_t  (the gradient of the loss wrt the raw q.c^T scores);
 // the caller finishes with two plain GEMMs: dq = G @ c (dr_linear_fwd), dc = G^T @ q (dr_linear_bwd_dw).
-// ... with a workspace (dr_inbatch_softmax_workspace_bytes(B); the forward's may be reused, its contents are not needed): lets the
-// pass run on the f16x2 register-split kernel, which wants the candidates as fp16 planes.  workspace NULL / too small, or a split /
-// shape the f16x2 path does not take: the fp32 kernel, as dr_inbatch_softmax_grad_scores.
-extern "C" int dr_inbatch_softmax_grad_scores_ws(const float* q, const float* c, int64_t B, int32_t D, const float* cand_prob,
-                                                 const int64_t* cand_ids, const float* sample_weight, float inv_temperature,
-                                                 const float* row_lse, float d_loss, float* G, int64_t ld_g, float* workspace,
-                                                 int64_t workspace_bytes, dr_stream_t stream) {
+// workspace (may be NULL; dr_inbatch_softmax_workspace_bytes(B) bytes; the forward's may be reused, its contents are not needed): lets
+// the pass run on the f16x2 register-split kernel, which wants the candidates as fp16 planes.  workspace NULL / too small, or a split /
+// shape the f16x2 path does not take: the fp32 kernel.
+extern "C" int dr_inbatch_softmax_grad_scores(const float* q, const float* c, int64_t B, int32_t D, const float* cand_prob,
+                                              const int64_t* cand_ids, const float* sample_weight, float inv_temperature,
+                                              const float* row_lse, float d_loss, float* G, int64_t ld_g, float* workspace,
+                                              int64_t workspace_bytes, dr_stream_t stream) {
     if (B <= 0 || D < 4 || B > 0x7fffffff || ld_g < B) return DR_EINVAL;
     if (!q || !c || !row_lse || !G) return DR_EINVAL;
     uint32_t* rec = nullptr;
@@ -1651,15 +1615,6 @@ extern "C" int dr_inbatch_softmax_grad_scores_ws(const float* q, const float* c,
         return dr_h2_inbatch_smgrad(q, D, rec, planes, ps, ld, rec + 1, B, D, cand_prob, cand_ids, inv_temperature, row_lse, sample_weight,
                                     d_loss, G, ld_g, stream);
     }
-    return dr_inbatch_softmax_grad_scores(q, c, B, D, cand_prob, cand_ids, sample_weight, inv_temperature, row_lse, d_loss, G, ld_g, stream);
-}
-
-extern "C" int dr_inbatch_softmax_grad_scores(const float* q, const float* c, int64_t B, int32_t D, const float* cand_prob,
-                                              const int64_t* cand_ids, const float* sample_weight, float inv_temperature,
-                                              const float* row_lse, float d_loss, float* G, int64_t ld_g,
-                                              dr_stream_t stream) {
-    if (B <= 0 || D < 4 || B > 0x7fffffff || ld_g < B) return DR_EINVAL;
-    if (!q || !c || !row_lse || !G) return DR_EINVAL;
     GemmArgs g{};
     g.A = q; g.lda = D; g.B = c; g.ldb = D; g.M = B; g.N = (int32_t)B; g.R = D; g.C = G; g.ldc = ld_g;
     g.cand_prob = cand_prob; g.cand_ids = cand_ids; g.inv_t = inv_temperature; g.lse = row_lse; g.vec = sample_weight;

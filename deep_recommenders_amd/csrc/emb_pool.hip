@@ -273,10 +273,10 @@ int lpr_for(int D) {
         default: return DR_EINVAL;            \
     }
 
-extern "C" int dr_emb_pool_fwd_ex(const int64_t* ids, int64_t B, int32_t F, int32_t C, const int32_t* col_start,
-                                  const int64_t* row_base, const float* table, int32_t D, const float* lin_w,
-                                  const float* lin_bias, float* concat, int64_t ld_concat, float* sum_x, float* fm_logit,
-                                  int32_t flags, dr_stream_t stream) {
+extern "C" int dr_emb_pool_fwd(const int64_t* ids, int64_t B, int32_t F, int32_t C, const int32_t* col_start,
+                               const int64_t* row_base, const float* table, int32_t D, const float* lin_w,
+                               const float* lin_bias, float* concat, int64_t ld_concat, float* sum_x, float* fm_logit,
+                               int32_t flags, dr_stream_t stream) {
     const float so = (flags & 1) ? 0.f : 0.5f;          // DR_POOL_FIRST_ORDER_ONLY: fm_logit = bias + sum w (the "wide" logit)
     if (B < 0 || F <= 0 || C < F || D < 4 || D > 256 || (D & 3) || ld_concat < (int64_t)F * D || (ld_concat & 3))
         return DR_EINVAL;
@@ -305,14 +305,6 @@ extern "C" int dr_emb_pool_fwd_ex(const int64_t* ids, int64_t B, int32_t F, int3
     }
     DR_CHECK_LAUNCH();
     return DR_OK;
-}
-
-extern "C" int dr_emb_pool_fwd(const int64_t* ids, int64_t B, int32_t F, int32_t C, const int32_t* col_start,
-                               const int64_t* row_base, const float* table, int32_t D, const float* lin_w,
-                               const float* lin_bias, float* concat, int64_t ld_concat, float* sum_x, float* fm_logit,
-                               dr_stream_t stream) {
-    return dr_emb_pool_fwd_ex(ids, B, F, C, col_start, row_base, table, D, lin_w, lin_bias, concat, ld_concat, sum_x, fm_logit,
-                              0, stream);
 }
 
 // ---- per-field first-order outputs (FNN, estimator/models/ranking/fnn.py:53-64 of the reference: one Dense(1, no bias)

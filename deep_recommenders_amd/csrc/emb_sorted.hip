@@ -102,10 +102,10 @@ __device__ __forceinline__ void emb_bwd_unique_body(const int bid, const int nbl
     const int lane = threadIdx.x & 63, slot = lane / LPR, sub = lane % LPR;
     const int nq = D >> 2;
     const bool dvalid = sub < nq;
-    // lin_old_t [F, B] (may be NULL; SGD only): the first-order weight every slot READ in the forward (dr_bf3_emb_linear_fwd_lv).  A
-    // unique row's weight has not changed since, so its update is one WRITE of old + scale * g -- not a read-modify-write whose line
-    // has to come back from HBM first.  K4 is bound by 128-byte line operations (8 per slot with the RMW: gradient 2, row 2 + 2,
-    // first-order 1 + 1): this removes one of them (measured: 281 -> 264 us, tools/exp/k4_ladder.py LINW).
+    // lin_old_t [F, B] (may be NULL; SGD only): the first-order weight every slot READ in the forward (lin_vals_t of
+    // dr_bf3_emb_linear_fwd).  A unique row's weight has not changed since, so its update is one WRITE of old + scale * g -- not a
+    // read-modify-write whose line has to come back from HBM first.  K4 is bound by 128-byte line operations (8 per slot with the RMW:
+    // gradient 2, row 2 + 2, first-order 1 + 1): this removes one of them (measured: 281 -> 264 us, tools/exp/k4_ladder.py LINW).
     const bool lold = lin_old_t != nullptr && lin_w != nullptr;
     const int subc = dvalid ? sub : nq - 1;
     const bool fm = sum_x != nullptr && d_fm_logit != nullptr;      // (a unique row's own value IS x: concat is never read here)
@@ -538,7 +538,7 @@ static int bwd_sorted_impl(const int64_t* ids, const int64_t* row_base, const in
                            int64_t ld_grad, const float* concat, int64_t ld_concat, const float* sum_x,
                            const float* d_fm_logit, const float* slot_lin_grad, float scale, float* dst_table,
                            float* dst_lin, float* dst_bias, const AdamArgs* adam, float* x_sorted, dr_stream_t stream,
-                           int parts = 3, const float* lin_old_t = nullptr, uint32_t* table_amax = nullptr) {
+                           int parts, const float* lin_old_t, uint32_t* table_amax) {
     if (B < 0 || F <= 0 || F > 64 || D < 4 || D > 256 || (D & 3) || num_rows <= 0) return DR_EINVAL;
     const int64_t n = B * F;
     if (n == 0) return DR_OK;
@@ -611,6 +611,19 @@ static int bwd_sorted_impl(const int64_t* ids, const int64_t* row_base, const in
     return DR_OK;
 }
 
+// parts: 1 = the update kernel, 2 = the ordered combination of hot rows' parked pieces (a no-op without x_sorted or with
+// DR_K4_DETERMINISTIC=0), 3 = both (the whole update); for callers that time (or overlap) the halves separately.  A caller that runs
+// part 1 MUST run part 2 on the same stream before anything reads the tables.
+// parts | 4: the first-order weights of rows that are UNIQUE in the batch are left alone -- the caller updates them with
+// dr_emb_lin_update_unique (same values, any stream, any time between the head's backward and the next forward): a random 4-byte
+// read-modify-write costs a 128-byte fetch, 0.27 GB of K4's 1.64 GB at config 3, and next to a GEMM it costs nothing.
+// parts | 8: the slots whose row is unique in the batch were updated elsewhere (dr_h2_dgrad_emb_sgd) -- only the duplicate pass, the hot
+// rows and the first-order bias run here; `grad` need hold the rows of the non-unique slots only.
+// lin_old_t [F, B] (field-major; may be NULL): the first-order weight every slot read in the forward of THIS step (lin_vals_t of
+// dr_bf3_emb_linear_fwd).  Rows unique in the batch then get dst_lin[row] = lin_old + scale * g as ONE write -- valid only if nothing
+// has written dst_lin since that forward.  Shared rows are summed and updated as before.
+// table_amax (may be NULL): running amax record of dst_table -- raised to the largest |value| this call writes into the table (the
+// f16x2 GEMMs, dr_h2_emb_linear_fwd / dr_h2_wgrad_emb, scale the table rows by it).
 extern "C" int dr_emb_pool_bwd_sorted(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
                                       const int32_t* sorted_slots, const uint8_t* unique_flags,
                                       const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
@@ -618,47 +631,7 @@ extern "C" int dr_emb_pool_bwd_sorted(const int64_t* ids, const int64_t* row_bas
                                       const float* concat, int64_t ld_concat, const float* sum_x,
                                       const float* d_fm_logit, const float* slot_lin_grad, float scale,
                                       float* dst_table, float* dst_lin, float* dst_bias, float* x_sorted,
-                                      dr_stream_t stream) {
-    return bwd_sorted_impl(ids, row_base, sorted_rows, sorted_slots, unique_flags, dup_heads, dup_count, B, F, D, num_rows,
-                           grad, ld_grad, concat, ld_concat, sum_x, d_fm_logit, slot_lin_grad, scale, dst_table, dst_lin,
-                           dst_bias, nullptr, x_sorted, stream);
-}
-
-// The same call in two halves, for callers that time (or overlap) them separately: parts = 1 the update kernel, parts = 2 the ordered
-// combination of hot rows' parked pieces (a no-op without x_sorted or with DR_K4_DETERMINISTIC=0), parts = 3 both = the call above.
-// A caller that runs part 1 MUST run part 2 on the same stream before anything reads the tables.
-// parts | 4: the first-order weights of rows that are UNIQUE in the batch are left alone -- the caller updates them with
-// dr_emb_lin_update_unique (same values, any stream, any time between the head's backward and the next forward): a random 4-byte
-// read-modify-write costs a 128-byte fetch, 0.27 GB of K4's 1.64 GB at config 3, and next to a GEMM it costs nothing.
-extern "C" int dr_emb_pool_bwd_sorted_parts(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
-                                            const int32_t* sorted_slots, const uint8_t* unique_flags,
-                                            const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
-                                            int32_t D, int64_t num_rows, const float* grad, int64_t ld_grad,
-                                            const float* concat, int64_t ld_concat, const float* sum_x,
-                                            const float* d_fm_logit, const float* slot_lin_grad, float scale,
-                                            float* dst_table, float* dst_lin, float* dst_bias, float* x_sorted,
-                                            int32_t parts, dr_stream_t stream) {
-    if (parts < 1 || parts > 7 || (parts & 3) == 0) return DR_EINVAL;
-    return bwd_sorted_impl(ids, row_base, sorted_rows, sorted_slots, unique_flags, dup_heads, dup_count, B, F, D, num_rows,
-                           grad, ld_grad, concat, ld_concat, sum_x, d_fm_logit, slot_lin_grad, scale, dst_table, dst_lin,
-                           dst_bias, nullptr, x_sorted, stream, parts);
-}
-
-// dr_emb_pool_bwd_sorted_parts with `lin_old_t` [F, B] (field-major; may be NULL = as above): the first-order weight every slot read in
-// the forward of THIS step (dr_bf3_emb_linear_fwd_lv).  Rows unique in the batch then get dst_lin[row] = lin_old + scale * g as ONE
-// write -- valid only if nothing has written dst_lin since that forward.  Shared rows are summed and updated as before.
-// table_amax (may be NULL): running amax record of dst_table -- raised to the largest |value| this call writes into the table (the
-// f16x2 GEMMs, dr_h2_emb_linear_fwd / dr_h2_wgrad_emb, scale the table rows by it).
-extern "C" int dr_emb_pool_bwd_sorted_ex(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
-                                         const int32_t* sorted_slots, const uint8_t* unique_flags,
-                                         const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
-                                         int32_t D, int64_t num_rows, const float* grad, int64_t ld_grad,
-                                         const float* concat, int64_t ld_concat, const float* sum_x,
-                                         const float* d_fm_logit, const float* slot_lin_grad, float scale,
-                                         float* dst_table, float* dst_lin, float* dst_bias, float* x_sorted,
-                                         const float* lin_old_t, int32_t parts, uint32_t* table_amax, dr_stream_t stream) {
-    // parts | 8 (SGD form only): the slots whose row is unique in the batch were updated elsewhere (dr_h2_dgrad_emb_sgd) -- only the
-    // duplicate pass, the hot rows and the first-order bias run here; `grad` need hold the rows of the non-unique slots only
+                                      const float* lin_old_t, int32_t parts, uint32_t* table_amax, dr_stream_t stream) {
     if (parts < 1 || parts > 15 || (parts & 3) == 0) return DR_EINVAL;
     return bwd_sorted_impl(ids, row_base, sorted_rows, sorted_slots, unique_flags, dup_heads, dup_count, B, F, D, num_rows,
                            grad, ld_grad, concat, ld_concat, sum_x, d_fm_logit, slot_lin_grad, scale, dst_table, dst_lin,
@@ -666,7 +639,7 @@ extern "C" int dr_emb_pool_bwd_sorted_ex(const int64_t* ids, const int64_t* row_
 }
 
 // dst_lin[row_base[f] + ids[b, f]] += scale * (slot_lin_grad ? slot_lin_grad[b, f] : d_fm_logit[b])  for every slot whose row no other
-// slot of the batch shares (unique_flags of the slot plan) -- the part of K4's first-order update that dr_emb_pool_bwd_sorted_parts
+// slot of the batch shares (unique_flags of the slot plan) -- the part of K4's first-order update that dr_emb_pool_bwd_sorted
 // (parts | 4) leaves out.  One thread per slot, plain read-modify-write (a unique row has one writer): deterministic.
 namespace {
 __global__ __launch_bounds__(256) void lin_update_unique_kernel(const int64_t* __restrict__ ids, const uint8_t* __restrict__ flags,
@@ -740,6 +713,8 @@ extern "C" int dr_emb_snapshot_sorted_rows(const int64_t* sorted_rows, const int
 // caller.  Untouched rows keep their moments ("lazy" Adam): identical to tf.train.AdamOptimizer on the first step,
 // and on every step for rows that are touched every step; TF itself decays m/v of the whole variable each step.
 // The bias of the first-order term is a dense parameter: update it with dr_adam_step on its own gradient.
+// lin_old_t [F, B] (may be NULL) as in dr_emb_pool_bwd_sorted: the first-order weight of a row unique in the batch is written from the
+// value the forward of this step saved instead of being read again.  table_amax (may be NULL): as above.
 extern "C" int dr_emb_pool_bwd_sorted_adam(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
                                            const int32_t* sorted_slots, const uint8_t* unique_flags,
                                            const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
@@ -747,29 +722,11 @@ extern "C" int dr_emb_pool_bwd_sorted_adam(const int64_t* ids, const int64_t* ro
                                            const float* concat, int64_t ld_concat, const float* sum_x,
                                            const float* d_fm_logit, const float* slot_lin_grad, float lr_t, float beta1,
                                            float beta2, float eps, float* table, float* m_table, float* v_table,
-                                           float* lin_w, float* m_lin, float* v_lin, float* x_sorted, dr_stream_t stream) {
+                                           float* lin_w, float* m_lin, float* v_lin, float* x_sorted, const float* lin_old_t,
+                                           uint32_t* table_amax, dr_stream_t stream) {
     if (!m_table || !v_table) return DR_EINVAL;
     if (lin_w != nullptr && (!m_lin || !v_lin)) return DR_EINVAL;
     // m_lin / v_lin as the two columns of one [R, 2] array (v_lin == m_lin + 1): row stride 2
-    AdamArgs ad{m_table, v_table, m_lin, v_lin, (m_lin != nullptr && v_lin == m_lin + 1) ? 2 : 1, lr_t, beta1, beta2, eps};
-    return bwd_sorted_impl(ids, row_base, sorted_rows, sorted_slots, unique_flags, dup_heads, dup_count, B, F, D, num_rows,
-                           grad, ld_grad, concat, ld_concat, sum_x, d_fm_logit, slot_lin_grad, 0.f, table, lin_w, nullptr,
-                           &ad, x_sorted, stream);
-}
-
-// ... with lin_old_t [F, B] (may be NULL) as in dr_emb_pool_bwd_sorted_ex: the first-order weight of a row unique in the batch is
-// written from the value the forward of this step saved instead of being read again.  table_amax (may be NULL): as above.
-extern "C" int dr_emb_pool_bwd_sorted_adam_ex(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
-                                              const int32_t* sorted_slots, const uint8_t* unique_flags,
-                                              const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
-                                              int32_t D, int64_t num_rows, const float* grad, int64_t ld_grad,
-                                              const float* concat, int64_t ld_concat, const float* sum_x,
-                                              const float* d_fm_logit, const float* slot_lin_grad, float lr_t, float beta1,
-                                              float beta2, float eps, float* table, float* m_table, float* v_table,
-                                              float* lin_w, float* m_lin, float* v_lin, float* x_sorted, const float* lin_old_t,
-                                              uint32_t* table_amax, dr_stream_t stream) {
-    if (!m_table || !v_table) return DR_EINVAL;
-    if (lin_w != nullptr && (!m_lin || !v_lin)) return DR_EINVAL;
     AdamArgs ad{m_table, v_table, m_lin, v_lin, (m_lin != nullptr && v_lin == m_lin + 1) ? 2 : 1, lr_t, beta1, beta2, eps};
     return bwd_sorted_impl(ids, row_base, sorted_rows, sorted_slots, unique_flags, dup_heads, dup_count, B, F, D, num_rows,
                            grad, ld_grad, concat, ld_concat, sum_x, d_fm_logit, slot_lin_grad, 0.f, table, lin_w, nullptr,

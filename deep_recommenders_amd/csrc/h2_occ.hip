@@ -51,7 +51,7 @@ constexpr int A_OFF = 0, B_OFF = 2 * PLANE, STAGE = 4 * PLANE;          // a sta
 //     table[row] = x + scale g ;  lin_w[row] = lin_old[f, m] + scale d_fm_logit[m]
 // -- the arithmetic of emb_bwd_unique_body (emb_sorted.hip), operation for operation, so the tables end up bit-identical to
 // dgrad + K4.  Slots that share a row (or are missing) get their dx stored to d_concat as before: K4's duplicate pass
-// (dr_emb_pool_bwd_sorted_ex, parts | 8) reads it there.  0.88 GB of d_concat traffic per step disappears at config 3.
+// (dr_emb_pool_bwd_sorted, parts | 8) reads it there.  0.88 GB of d_concat traffic per step disappears at config 3.
 struct K4Args {
     const int32_t* ids_t;                        // [F, M] field-major bucket ids (-1 = missing)
     const uint8_t* flags;                        // [M, F] 1 = the slot's row is unique in the batch (slot plan)
@@ -912,7 +912,7 @@ int occ_nt_launch(const RsArgs& g, hipStream_t stream) {
 // First-layer dgrad of the DeepFM tower + K4's unique-row pass in one launch (EPI 8 above):  dx = dy W^T  (W as fp16 planes [2][>= 64 F
 // rows][ld >= roundup(K, 32)], the layer's kernel rows = input columns), never stored for slots whose table row is unique in the batch --
 // those rows and their first-order weights receive K4's SGD update on the spot -- and stored to d_concat [M, ld_dc] for the others.
-// Follow with dr_emb_pool_bwd_sorted_ex(parts | 8) (the duplicate pass + the first-order bias) on the same stream.
+// Follow with dr_emb_pool_bwd_sorted(parts | 8) (the duplicate pass + the first-order bias) on the same stream.
 // Autodiff of keras/models/ranking/deepfm.py:30-34 w.r.t. the concatenated embeddings + of fm.py:23-37 / safe_embedding_lookup_sparse
 // w.r.t. the tables (reference root), with the SGD step of examples/train_fm_on_movielens_estimator.py:51-52 fused (SGD instead of Adam).
 extern "C" int dr_h2_dgrad_emb_sgd(const float* dy, int64_t ld_dy, const uint32_t* dy_amax, const void* w_planes, int64_t w_ps,

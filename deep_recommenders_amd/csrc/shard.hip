@@ -368,8 +368,12 @@ extern "C" int64_t dr_shard_bucket_workspace_bytes(int64_t n, int32_t world) {
     return (nblk * world + 16) * (int64_t)sizeof(int64_t);
 }
 
-static int bucket_ids_impl(const int64_t* ids, const int64_t* rep, int64_t n, int32_t C, int64_t rows_per_shard, int32_t world,
-                           int64_t* counts, int64_t* send_rows, int64_t* pos, int64_t* workspace, dr_stream_t stream) {
+// rep (may be NULL): the representative map of dr_shard_dedup_slots -- only slots that are their own representative then get a send slot
+// (counts then sum to the number of DISTINCT rows of the micro-batch, missing ids included one by one); pos[p] of every other slot =
+// pos of its representative.
+extern "C" int dr_shard_bucket_ids(const int64_t* ids, const int64_t* rep, int64_t n, int32_t C, int64_t rows_per_shard,
+                                   int32_t world, int64_t* counts, int64_t* send_rows, int64_t* pos, int64_t* workspace,
+                                   dr_stream_t stream) {
     if (n < 0 || C <= 0 || world <= 0 || world > MAXW || rows_per_shard <= 0) return DR_EINVAL;
     if (!counts) return DR_EINVAL;
     if (n == 0) {
@@ -386,22 +390,6 @@ static int bucket_ids_impl(const int64_t* ids, const int64_t* rep, int64_t n, in
         hipLaunchKernelGGL(dedup_pos_kernel, dim3(dr_grid_for(n, 256)), dim3(256), 0, dr_s(stream), rep, n, pos);
     DR_CHECK_LAUNCH();
     return DR_OK;
-}
-
-extern "C" int dr_shard_bucket_ids(const int64_t* ids, int64_t n, int32_t C, int64_t rows_per_shard, int32_t world,
-                                   int64_t* counts, int64_t* send_rows, int64_t* pos, int64_t* workspace,
-                                   dr_stream_t stream) {
-    return bucket_ids_impl(ids, nullptr, n, C, rows_per_shard, world, counts, send_rows, pos, workspace, stream);
-}
-
-// The same with the representative map of dr_shard_dedup_slots: only slots that are their own representative get a send slot
-// (counts then sum to the number of DISTINCT rows of the micro-batch, missing ids included one by one); pos[p] of every other slot =
-// pos of its representative.
-extern "C" int dr_shard_bucket_ids_dedup(const int64_t* ids, const int64_t* rep, int64_t n, int32_t C, int64_t rows_per_shard,
-                                         int32_t world, int64_t* counts, int64_t* send_rows, int64_t* pos, int64_t* workspace,
-                                         dr_stream_t stream) {
-    if (!rep) return DR_EINVAL;
-    return bucket_ids_impl(ids, rep, n, C, rows_per_shard, world, counts, send_rows, pos, workspace, stream);
 }
 
 // rep[p] = lowest slot of the micro-batch that looks up the same row as slot p (p itself for a row no other slot shares, and for a
@@ -469,9 +457,14 @@ extern "C" int dr_axpy(int64_t n, float alpha, const float* x, float* y, dr_stre
     return DR_OK;
 }
 
-static int pack_grads_impl(const int64_t* pos, const uint8_t* uniq, int64_t B, int32_t F, int32_t D, const float* d_concat, int64_t ld_dconcat,
-                           const float* concat, int64_t ld_concat, const float* sum_x, const float* d_fm_logit,
-                           float* out_rows, float* out_lin, float* bias_sum, dr_stream_t stream) {
+// De-duplicated form (unique_flags given; may be NULL): pos maps several slots to one destination (dr_shard_bucket_ids with rep);
+// unique_flags [B * F] = the slot plan's flags of the same micro-batch.  Slots whose row is unique store, the others ADD (fp32 atomics:
+// the order in which a shared row's slots arrive is not fixed) -- out_rows / out_lin must be zero where shared rows land (the caller
+// zero-fills the buffers).
+extern "C" int dr_emb_pack_grads(const int64_t* pos, const uint8_t* unique_flags, int64_t B, int32_t F, int32_t D,
+                                 const float* d_concat, int64_t ld_dconcat, const float* concat, int64_t ld_concat,
+                                 const float* sum_x, const float* d_fm_logit, float* out_rows, float* out_lin, float* bias_sum,
+                                 dr_stream_t stream) {
     if (B < 0 || F <= 0 || D < 4 || D > 256 || (D & 3)) return DR_EINVAL;
     if (B == 0) return DR_OK;
     if (!pos || !d_concat || !out_rows || ld_dconcat < (int64_t)F * D || (ld_dconcat & 3)) return DR_EINVAL;
@@ -479,33 +472,14 @@ static int pack_grads_impl(const int64_t* pos, const uint8_t* uniq, int64_t B, i
     const int lpr = lpr_for_d(D);
     const int grid = dr_grid_for(B, 4, 8192);
 #define CALL(L)                                                                                                                       \
-    if (uniq != nullptr)                                                                                                              \
+    if (unique_flags != nullptr)                                                                                                      \
         hipLaunchKernelGGL((pack_grads_kernel<L, (64 / L >= 16 ? 2 : 4), true>), dim3(grid), dim3(256), 0, dr_s(stream), pos, B, F, D, \
-                           d_concat, ld_dconcat, concat, ld_concat, sum_x, d_fm_logit, out_rows, out_lin, bias_sum, uniq);             \
+                           d_concat, ld_dconcat, concat, ld_concat, sum_x, d_fm_logit, out_rows, out_lin, bias_sum, unique_flags);     \
     else                                                                                                                              \
         hipLaunchKernelGGL((pack_grads_kernel<L, (64 / L >= 16 ? 2 : 4), false>), dim3(grid), dim3(256), 0, dr_s(stream), pos, B, F, D, \
-                           d_concat, ld_dconcat, concat, ld_concat, sum_x, d_fm_logit, out_rows, out_lin, bias_sum, uniq)
+                           d_concat, ld_dconcat, concat, ld_concat, sum_x, d_fm_logit, out_rows, out_lin, bias_sum, unique_flags)
     DR_LPR_SWITCH(lpr, CALL)
 #undef CALL
     DR_CHECK_LAUNCH();
     return DR_OK;
-}
-
-extern "C" int dr_emb_pack_grads(const int64_t* pos, int64_t B, int32_t F, int32_t D, const float* d_concat, int64_t ld_dconcat,
-                                 const float* concat, int64_t ld_concat, const float* sum_x, const float* d_fm_logit,
-                                 float* out_rows, float* out_lin, float* bias_sum, dr_stream_t stream) {
-    return pack_grads_impl(pos, nullptr, B, F, D, d_concat, ld_dconcat, concat, ld_concat, sum_x, d_fm_logit, out_rows, out_lin, bias_sum,
-                           stream);
-}
-
-// De-duplicated form: pos maps several slots to one destination (dr_shard_bucket_ids_dedup); unique_flags [B * F] = the slot plan's
-// flags of the same micro-batch.  Slots whose row is unique store, the others ADD (fp32 atomics: the order in which a shared row's
-// slots arrive is not fixed) -- out_rows / out_lin must be zero where shared rows land (the caller zero-fills the buffers).
-extern "C" int dr_emb_pack_grads_dedup(const int64_t* pos, const uint8_t* unique_flags, int64_t B, int32_t F, int32_t D,
-                                       const float* d_concat, int64_t ld_dconcat, const float* concat, int64_t ld_concat,
-                                       const float* sum_x, const float* d_fm_logit, float* out_rows, float* out_lin, float* bias_sum,
-                                       dr_stream_t stream) {
-    if (!unique_flags) return DR_EINVAL;
-    return pack_grads_impl(pos, unique_flags, B, F, D, d_concat, ld_dconcat, concat, ld_concat, sum_x, d_fm_logit, out_rows, out_lin,
-                           bias_sum, stream);
 }

@@ -530,10 +530,16 @@ extern "C" int64_t dr_linear_bwd_narrow_workspace_bytes(int64_t M, int32_t K, in
 
 // Returns DR_ESHAPE when the shape is outside the fused kernel's domain (the caller then uses dr_linear_bwd_dx +
 // dr_linear_bwd_dw): needs N <= 32, K in {128, 256, 512}, M a positive multiple of 32, 4*KT-byte aligned rows.
-static int bwd_narrow_impl(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, const float* W,
-                           int64_t ld_w, int64_t M, int32_t K, int32_t N, int32_t relu_mask, float scale,
-                           float* dstW, int64_t ld_dstw, float* dstb, float* dx, int64_t ld_dx, void* workspace,
-                           int64_t workspace_bytes, int32_t parts, dr_stream_t stream, uint32_t* dx_amax = nullptr) {
+// In two halves: parts = 1 the one-pass kernel (dx and the per-block partials of dW / db), parts = 2 the reduce that applies them
+// (dstW += scale * sum, dstb likewise), 3 = both.  Part 2 may run on another stream; it must finish before anything reads dstW / dstb
+// and before the next part 1 over the same workspace.
+// dx_amax (may be NULL): also leaves max |dx| (float bits) in dx_amax[0] -- the amax record the f16x2 GEMMs (dr_h2_linear_nt,
+// dr_h2_wgrad_emb) want for dx as their operand; the record is reset and rebuilt by part 1.
+extern "C" int dr_linear_bwd_narrow(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, const float* W,
+                                    int64_t ld_w, int64_t M, int32_t K, int32_t N, int32_t relu_mask, float scale,
+                                    float* dstW, int64_t ld_dstw, float* dstb, float* dx, int64_t ld_dx, void* workspace,
+                                    int64_t workspace_bytes, int32_t parts, uint32_t* dx_amax, dr_stream_t stream) {
+    if (parts < 1 || parts > 3) return DR_EINVAL;
     if (M <= 0 || K <= 0 || N <= 0) return DR_EINVAL;
     if (!x || !dy || !W || !dstW || !dx || !workspace) return DR_EINVAL;
     if (N > 32 || (K != 128 && K != 256 && K != 512) || (M % TT_ROWS) != 0) return DR_ESHAPE;
@@ -561,37 +567,6 @@ static int bwd_narrow_impl(const float* x, int64_t ld_x, const float* dy, int64_
                            dstW, ld_dstw, dstb);
     DR_CHECK_LAUNCH();
     return DR_OK;
-}
-
-extern "C" int dr_linear_bwd_narrow(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, const float* W,
-                                    int64_t ld_w, int64_t M, int32_t K, int32_t N, int32_t relu_mask, float scale,
-                                    float* dstW, int64_t ld_dstw, float* dstb, float* dx, int64_t ld_dx, void* workspace,
-                                    int64_t workspace_bytes, dr_stream_t stream) {
-    return bwd_narrow_impl(x, ld_x, dy, ld_dy, W, ld_w, M, K, N, relu_mask, scale, dstW, ld_dstw, dstb, dx, ld_dx, workspace,
-                           workspace_bytes, 3, stream);
-}
-
-// In two halves: parts = 1 the one-pass kernel (dx and the per-block partials of dW / db), parts = 2 the reduce that applies them
-// (dstW += scale * sum, dstb likewise), 3 = both.  Part 2 may run on another stream; it must finish before anything reads dstW / dstb
-// and before the next part 1 over the same workspace.
-extern "C" int dr_linear_bwd_narrow_parts(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, const float* W,
-                                          int64_t ld_w, int64_t M, int32_t K, int32_t N, int32_t relu_mask, float scale,
-                                          float* dstW, int64_t ld_dstw, float* dstb, float* dx, int64_t ld_dx, void* workspace,
-                                          int64_t workspace_bytes, int32_t parts, dr_stream_t stream) {
-    if (parts < 1 || parts > 3) return DR_EINVAL;
-    return bwd_narrow_impl(x, ld_x, dy, ld_dy, W, ld_w, M, K, N, relu_mask, scale, dstW, ld_dstw, dstb, dx, ld_dx, workspace,
-                           workspace_bytes, parts, stream);
-}
-
-// dr_linear_bwd_narrow_parts that also leaves max |dx| (float bits) in dx_amax[0] -- the amax record the f16x2 GEMMs (dr_h2_linear_nt,
-// dr_h2_wgrad_emb) want for dx as their operand; the record is reset and rebuilt by part 1.
-extern "C" int dr_linear_bwd_narrow_amax(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, const float* W,
-                                         int64_t ld_w, int64_t M, int32_t K, int32_t N, int32_t relu_mask, float scale,
-                                         float* dstW, int64_t ld_dstw, float* dstb, float* dx, int64_t ld_dx, void* workspace,
-                                         int64_t workspace_bytes, int32_t parts, uint32_t* dx_amax, dr_stream_t stream) {
-    if (parts < 1 || parts > 3 || !dx_amax) return DR_EINVAL;
-    return bwd_narrow_impl(x, ld_x, dy, ld_dy, W, ld_w, M, K, N, relu_mask, scale, dstW, ld_dstw, dstb, dx, ld_dx, workspace,
-                           workspace_bytes, parts, stream, dx_amax);
 }
 
 extern "C" int64_t dr_tower_tail_workspace_bytes(int64_t M, int32_t K) {

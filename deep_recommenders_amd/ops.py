@@ -89,10 +89,10 @@ def emb_pool_fwd(ids, F, col_start, row_base, table, lin_w=None, lin_bias=None, 
         sum_x = torch.empty((B, D), dtype=torch.float32, device=dev)
     if want_fm and fm_logit is None:
         fm_logit = torch.empty((B,), dtype=torch.float32, device=dev)
-    check(lib().dr_emb_pool_fwd_ex(ptr(ids), B, F, C, ptr(col_start), ptr(row_base), ptr(table), D, ptr(lin_w),
-                                   ptr(lin_bias), ptr(concat), ld, ptr(sum_x) if want_sum_x else None,
-                                   ptr(fm_logit) if want_fm else None, 0 if second_order else 1, stream_ptr()),
-          "dr_emb_pool_fwd_ex")
+    check(lib().dr_emb_pool_fwd(ptr(ids), B, F, C, ptr(col_start), ptr(row_base), ptr(table), D, ptr(lin_w),
+                                ptr(lin_bias), ptr(concat), ld, ptr(sum_x) if want_sum_x else None,
+                                ptr(fm_logit) if want_fm else None, 0 if second_order else 1, stream_ptr()),
+          "dr_emb_pool_fwd")
     return concat, sum_x, fm_logit
 
 
@@ -248,21 +248,11 @@ def linear_bwd_narrow(x, dy, W, scale, dstW, dstb, dx, relu_mask=True, workspace
     assert W.shape == (K, N) and dstW.shape == (K, N) and dx.shape == (M, K)
     if workspace is None:
         workspace = linear_bwd_narrow_workspace(M, K, N, x.device)
-    if dx_amax is not None:  # also leave max |dx| in the record (the f16x2 GEMMs that take dx as an operand want it)
-        check(lib().dr_linear_bwd_narrow_amax(ptr(x), x.stride(0), ptr(dy), dy.stride(0), ptr(W), W.stride(0), M, K, N,
-                                              1 if relu_mask else 0, float(scale), ptr(dstW), dstW.stride(0), ptr(dstb), ptr(dx),
-                                              dx.stride(0), ptr(workspace), workspace.numel() * 4, int(parts), ptr(dx_amax), stream_ptr()),
-              "dr_linear_bwd_narrow_amax")
-        return dx
-    if parts != 3:          # 1: the one-pass kernel, 2: the reduce that applies the partials (may run on another stream)
-        check(lib().dr_linear_bwd_narrow_parts(ptr(x), x.stride(0), ptr(dy), dy.stride(0), ptr(W), W.stride(0), M, K, N,
-                                               1 if relu_mask else 0, float(scale), ptr(dstW), dstW.stride(0), ptr(dstb), ptr(dx),
-                                               dx.stride(0), ptr(workspace), workspace.numel() * 4, int(parts), stream_ptr()),
-              "dr_linear_bwd_narrow_parts")
-        return dx
+    # parts 1: the one-pass kernel, 2: the reduce that applies the partials (may run on another stream); dx_amax: also leave max |dx| in
+    # the record (the f16x2 GEMMs that take dx as an operand want it)
     check(lib().dr_linear_bwd_narrow(ptr(x), x.stride(0), ptr(dy), dy.stride(0), ptr(W), W.stride(0), M, K, N,
                                      1 if relu_mask else 0, float(scale), ptr(dstW), dstW.stride(0), ptr(dstb), ptr(dx),
-                                     dx.stride(0), ptr(workspace), workspace.numel() * 4, stream_ptr()),
+                                     dx.stride(0), ptr(workspace), workspace.numel() * 4, int(parts), ptr(dx_amax), stream_ptr()),
           "dr_linear_bwd_narrow")
     return dx
 
@@ -327,19 +317,12 @@ def tower_head_fwd_bwd(x, W1, b1, W2, b2, extra_logit, labels, loss_mode, scale,
     loss = loss if loss is not None else torch.empty(1, dtype=torch.float32, device=dev)
     if workspace is None:
         workspace = tower_head_workspace(M, dev)
-    if parts != 3:          # 1: GEMM + head kernel, 2: the finish kernel (partials -> dst_W2 / dst_b2 / loss; may run on another stream)
-        check(lib().dr_tower_head_fwd_bwd_parts(ptr(x), x.stride(0), ptr(W1), W1.stride(0), ptr(b1), M, int(n_total), K, H, int(act), ptr(W2),
-                                                W2.stride(0), ptr(b2), ptr(extra_logit), ptr(labels), int(loss_mode), float(scale),
-                                                ptr(dst_W2), dst_W2.stride(0) if dst_W2 is not None else 0, ptr(dst_b2),
-                                                ptr(h_out), h_out.stride(0) if h_out is not None else 0, ptr(prob), ptr(d_logit),
-                                                ptr(d_h), d_h.stride(0), ptr(loss), ptr(workspace), workspace.numel() * 4, int(parts),
-                                                stream_ptr()), "dr_tower_head_fwd_bwd_parts")
-        return loss, prob, d_logit, d_h
+    # parts 1: GEMM + head kernel, 2: the finish kernel (partials -> dst_W2 / dst_b2 / loss; may run on another stream)
     check(lib().dr_tower_head_fwd_bwd(ptr(x), x.stride(0), ptr(W1), W1.stride(0), ptr(b1), M, int(n_total), K, H, int(act), ptr(W2),
                                       W2.stride(0), ptr(b2), ptr(extra_logit), ptr(labels), int(loss_mode), float(scale),
                                       ptr(dst_W2), dst_W2.stride(0) if dst_W2 is not None else 0, ptr(dst_b2),
                                       ptr(h_out), h_out.stride(0) if h_out is not None else 0, ptr(prob), ptr(d_logit),
-                                      ptr(d_h), d_h.stride(0), ptr(loss), ptr(workspace), workspace.numel() * 4,
+                                      ptr(d_h), d_h.stride(0), ptr(loss), ptr(workspace), workspace.numel() * 4, int(parts),
                                       stream_ptr()), "dr_tower_head_fwd_bwd")
     return loss, prob, d_logit, d_h
 
@@ -373,12 +356,9 @@ def cross_combine_bwd(x0, prod, d_out, diag_scale, d_x0_accum, d_x_accum, d_prod
     for t in (x0, prod, d_x0_accum, d_x_accum):
         assert t is None or t.stride(0) == ld, "cross tensors must share one leading dimension"
     d_prod = torch.empty((M, ld), dtype=torch.float32, device=d_out.device)[:, :Dm]
-    if d_prod_amax is not None:     # also the amax record of d_prod (operand of the cross layer's f16x2 dgrad / wgrad)
-        check(lib().dr_cross_combine_bwd_amax(ptr(x0), ptr(prod), ptr(d_out), M, Dm, ld, float(diag_scale), ptr(d_prod),
-                                              ptr(d_x0_accum), ptr(d_x_accum), ptr(d_prod_amax), stream_ptr()), "dr_cross_combine_bwd_amax")
-        return d_prod
+    # d_prod_amax: also the amax record of d_prod (operand of the cross layer's f16x2 dgrad / wgrad)
     check(lib().dr_cross_combine_bwd(ptr(x0), ptr(prod), ptr(d_out), M, Dm, ld, float(diag_scale), ptr(d_prod),
-                                     ptr(d_x0_accum), ptr(d_x_accum), stream_ptr()), "dr_cross_combine_bwd")
+                                     ptr(d_x0_accum), ptr(d_x_accum), ptr(d_prod_amax), stream_ptr()), "dr_cross_combine_bwd")
     return d_prod
 
 
@@ -468,11 +448,7 @@ def shard_bucket_ids(ids, rows_per_shard, world, counts=None, send_rows=None, po
     if workspace is None:
         nbytes = lib().dr_shard_bucket_workspace_bytes(n, world)
         workspace = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
-    if rep is not None:
-        check(lib().dr_shard_bucket_ids_dedup(ptr(ids), ptr(rep), n, C, int(rows_per_shard), int(world), ptr(counts), ptr(send_rows),
-                                              ptr(pos), ptr(workspace), stream_ptr()), "dr_shard_bucket_ids_dedup")
-        return counts, send_rows, pos
-    check(lib().dr_shard_bucket_ids(ptr(ids), n, C, int(rows_per_shard), int(world), ptr(counts), ptr(send_rows),
+    check(lib().dr_shard_bucket_ids(ptr(ids), ptr(rep), n, C, int(rows_per_shard), int(world), ptr(counts), ptr(send_rows),
                                     ptr(pos), ptr(workspace), stream_ptr()), "dr_shard_bucket_ids")
     return counts, send_rows, pos
 
@@ -583,24 +559,19 @@ def emb_pool_bwd_sorted(ids, row_base, plan, D, num_rows, grad, d_fm_logit, scal
                         concat=None, sum_x=None, slot_lin_grad=None, x_sorted=None, parts=3, lin_old_t=None, table_amax=None):
     """K4 on the slot plan.  x_sorted ([B * F, D] scratch; with the FM term and no `concat` it must hold the snapshot of
     emb_snapshot_sorted_rows) also makes the update of rows hit more than 32 times deterministic: it is clobbered.  parts: 1 = the
-    update kernel, 2 = the ordered combination of hot rows' parked pieces, 3 = both (dr_emb_pool_bwd_sorted[_parts])."""
+    update kernel, 2 = the ordered combination of hot rows' parked pieces, 3 = both (dr_emb_pool_bwd_sorted).
+    lin_old_t: first-order weights as this step's forward read them, [F, B]: unique rows get one write, no RMW.
+    table_amax: running amax record of dst_table (ops.h2_record), raised to the largest magnitude written."""
     ids = _c(ids, torch.int64)
     B, F = ids.shape
     assert grad.stride(1) == 1
-    args = (ptr(ids), ptr(row_base), ptr(plan.rows), ptr(plan.slots), ptr(plan.flags),
-            ptr(plan.dup_heads), ptr(plan.dup_count), B, F, D, int(num_rows), ptr(grad),
-            grad.stride(0), ptr(concat), concat.stride(0) if concat is not None else 0,
-            ptr(sum_x), ptr(d_fm_logit), ptr(slot_lin_grad), float(scale), ptr(dst_table), ptr(dst_lin),
-            ptr(dst_bias), ptr(x_sorted))
-    if lin_old_t is not None or table_amax is not None:
-        # lin_old_t: first-order weights as this step's forward read them, [F, B]: unique rows get one write, no RMW
-        # table_amax: running amax record of dst_table (ops.h2_record), raised to the largest magnitude written
-        assert lin_old_t is None or (lin_old_t.shape == (F, B) and lin_old_t.is_contiguous() and lin_old_t.dtype == torch.float32)
-        check(lib().dr_emb_pool_bwd_sorted_ex(*args, ptr(lin_old_t), int(parts), ptr(table_amax), stream_ptr()), "dr_emb_pool_bwd_sorted_ex")
-    elif parts == 3:
-        check(lib().dr_emb_pool_bwd_sorted(*args, stream_ptr()), "dr_emb_pool_bwd_sorted")
-    else:
-        check(lib().dr_emb_pool_bwd_sorted_parts(*args, int(parts), stream_ptr()), "dr_emb_pool_bwd_sorted_parts")
+    assert lin_old_t is None or (lin_old_t.shape == (F, B) and lin_old_t.is_contiguous() and lin_old_t.dtype == torch.float32)
+    check(lib().dr_emb_pool_bwd_sorted(ptr(ids), ptr(row_base), ptr(plan.rows), ptr(plan.slots), ptr(plan.flags),
+                                       ptr(plan.dup_heads), ptr(plan.dup_count), B, F, D, int(num_rows), ptr(grad),
+                                       grad.stride(0), ptr(concat), concat.stride(0) if concat is not None else 0,
+                                       ptr(sum_x), ptr(d_fm_logit), ptr(slot_lin_grad), float(scale), ptr(dst_table), ptr(dst_lin),
+                                       ptr(dst_bias), ptr(x_sorted), ptr(lin_old_t), int(parts), ptr(table_amax), stream_ptr()),
+          "dr_emb_pool_bwd_sorted")
 
 
 def h2_dgrad_emb_sgd(dy, dy_amax, w: "H2Planes", ids_t, plan, row_base, table, lin_w, lin_old_t, sum_x, d_fm_logit, scale, d_concat,
@@ -641,21 +612,14 @@ def emb_pool_bwd_sorted_adam(ids, row_base, plan, D, num_rows, grad, d_fm_logit,
     ids = _c(ids, torch.int64)
     B, F = ids.shape
     assert grad.stride(1) == 1
-    if lin_old_t is not None or table_amax is not None:
-        assert lin_old_t is None or (lin_old_t.shape == (F, B) and lin_old_t.is_contiguous())
-        check(lib().dr_emb_pool_bwd_sorted_adam_ex(ptr(ids), ptr(row_base), ptr(plan.rows), ptr(plan.slots), ptr(plan.flags),
-                                            ptr(plan.dup_heads), ptr(plan.dup_count), B, F, D, int(num_rows), ptr(grad),
-                                            grad.stride(0), ptr(concat), concat.stride(0) if concat is not None else 0,
-                                            ptr(sum_x), ptr(d_fm_logit), ptr(slot_lin_grad), float(lr_t), float(beta1),
-                                            float(beta2), float(eps), ptr(table), ptr(m_table), ptr(v_table), ptr(lin_w),
-                                            ptr(m_lin), ptr(v_lin), ptr(x_sorted), ptr(lin_old_t), ptr(table_amax), stream_ptr()), "dr_emb_pool_bwd_sorted_adam_ex")
-        return
+    assert lin_old_t is None or (lin_old_t.shape == (F, B) and lin_old_t.is_contiguous())
     check(lib().dr_emb_pool_bwd_sorted_adam(ptr(ids), ptr(row_base), ptr(plan.rows), ptr(plan.slots), ptr(plan.flags),
                                             ptr(plan.dup_heads), ptr(plan.dup_count), B, F, D, int(num_rows), ptr(grad),
                                             grad.stride(0), ptr(concat), concat.stride(0) if concat is not None else 0,
                                             ptr(sum_x), ptr(d_fm_logit), ptr(slot_lin_grad), float(lr_t), float(beta1),
                                             float(beta2), float(eps), ptr(table), ptr(m_table), ptr(v_table), ptr(lin_w),
-                                            ptr(m_lin), ptr(v_lin), ptr(x_sorted), stream_ptr()), "dr_emb_pool_bwd_sorted_adam")
+                                            ptr(m_lin), ptr(v_lin), ptr(x_sorted), ptr(lin_old_t), ptr(table_amax), stream_ptr()),
+          "dr_emb_pool_bwd_sorted_adam")
 
 
 def adam_catchup_rows(ids, row_base, table, m_table, v_table, lin_w, m_lin, v_lin, row_step, upto, stamp, lr, beta1=0.9,
@@ -741,9 +705,9 @@ def inbatch_softmax_grad_scores(q, c, row_lse, d_loss, cand_prob=None, cand_ids=
     # with a workspace the pass may run on the f16x2 register-split kernel (it needs the candidates as fp16 planes)
     nbytes = lib().dr_inbatch_softmax_workspace_bytes(B)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
-    check(lib().dr_inbatch_softmax_grad_scores_ws(ptr(q), ptr(c), B, D, ptr(cand_prob), ptr(cand_ids), ptr(sample_weight),
-                                                  float(inv_temperature), ptr(row_lse), float(d_loss), ptr(G), G.stride(0),
-                                                  ptr(ws), nbytes, stream_ptr()), "dr_inbatch_softmax_grad_scores_ws")
+    check(lib().dr_inbatch_softmax_grad_scores(ptr(q), ptr(c), B, D, ptr(cand_prob), ptr(cand_ids), ptr(sample_weight),
+                                               float(inv_temperature), ptr(row_lse), float(d_loss), ptr(G), G.stride(0),
+                                               ptr(ws), nbytes, stream_ptr()), "dr_inbatch_softmax_grad_scores")
     return G
 
 
@@ -1014,12 +978,8 @@ def softmax_ce_rows_bwd(logits, labels, inv_temperature, sample_weight, d_loss, 
 def emb_pack_grads(pos, D, d_concat, concat, sum_x, d_fm_logit, out_rows, out_lin=None, bias_sum=None, unique_flags=None):
     pos = _c(pos, torch.int64)
     B, F = pos.shape
-    if unique_flags is not None:          # de-duplicated exchange: several slots per destination, shared rows accumulate (zero-filled buffers)
-        check(lib().dr_emb_pack_grads_dedup(ptr(pos), ptr(unique_flags), B, F, D, ptr(d_concat), d_concat.stride(0), ptr(concat),
-                                            concat.stride(0) if concat is not None else 0, ptr(sum_x), ptr(d_fm_logit), ptr(out_rows),
-                                            ptr(out_lin), ptr(bias_sum), stream_ptr()), "dr_emb_pack_grads_dedup")
-        return
-    check(lib().dr_emb_pack_grads(ptr(pos), B, F, D, ptr(d_concat), d_concat.stride(0), ptr(concat),
+    # unique_flags: de-duplicated exchange -- several slots per destination, shared rows accumulate (zero-filled buffers)
+    check(lib().dr_emb_pack_grads(ptr(pos), ptr(unique_flags), B, F, D, ptr(d_concat), d_concat.stride(0), ptr(concat),
                                   concat.stride(0) if concat is not None else 0, ptr(sum_x), ptr(d_fm_logit), ptr(out_rows),
                                   ptr(out_lin), ptr(bias_sum), stream_ptr()), "dr_emb_pack_grads")
 
@@ -1183,17 +1143,12 @@ def bf3_emb_linear_fwd(ids, row_base, field_rows_max, table, lin_w, lin_bias, de
     M, F = ids.shape
     assert (concat is None or concat.stride(1) == 1) and out.stride(1) == 1 and wt.cols == K and out.shape == (M, wt.rows)
     assert dense_pad is None or (dense_pad.shape == (M, 32) and dense_pad.is_contiguous())
-    if lin_vals_t is not None:      # also save every slot's first-order weight, field-major [F, M] (emb_pool_bwd_sorted's lin_old_t)
-        assert lin_vals_t.shape == (F, M) and lin_vals_t.is_contiguous() and lin_vals_t.dtype == torch.float32
-        check(lib().dr_bf3_emb_linear_fwd_lv(ptr(ids), M, F, ptr(row_base), int(field_rows_max), ptr(table), table.shape[1], ptr(lin_w), ptr(lin_bias),
-                                             ptr(dense_pad), ptr(concat), concat.stride(0) if concat is not None else 0, int(K), ptr(wt.buf),
-                                             wt.plane_stride, wt.ld, wt.rows, ptr(bias), int(act), ptr(sum_x), ptr(fm_logit), ptr(out), out.stride(0),
-                                             ptr(lin_vals_t), stream_ptr()), "dr_bf3_emb_linear_fwd_lv")
-        return out
+    # lin_vals_t: also save every slot's first-order weight, field-major [F, M] (emb_pool_bwd_sorted's lin_old_t)
+    assert lin_vals_t is None or (lin_vals_t.shape == (F, M) and lin_vals_t.is_contiguous() and lin_vals_t.dtype == torch.float32)
     check(lib().dr_bf3_emb_linear_fwd(ptr(ids), M, F, ptr(row_base), int(field_rows_max), ptr(table), table.shape[1], ptr(lin_w), ptr(lin_bias),
                                       ptr(dense_pad), ptr(concat), concat.stride(0) if concat is not None else 0, int(K), ptr(wt.buf), wt.plane_stride, wt.ld,
-                                      wt.rows, ptr(bias), int(act), ptr(sum_x), ptr(fm_logit), ptr(out), out.stride(0), stream_ptr()),
-          "dr_bf3_emb_linear_fwd")
+                                      wt.rows, ptr(bias), int(act), ptr(sum_x), ptr(fm_logit), ptr(out), out.stride(0), ptr(lin_vals_t),
+                                      stream_ptr()), "dr_bf3_emb_linear_fwd")
     return out
 
 
@@ -1210,14 +1165,10 @@ def bf3_wgrad_emb(ids_t, row_base, table, dense_pad, dy, scale, dstW, dstb=None,
     assert dense_pad is None or (dense_pad.shape == (R, 32) and dense_pad.is_contiguous())
     if workspace is None:
         workspace = bf3_wgrad_workspace(R, F, N, dy.device)
-    if parts != 3:          # 1: the split-K GEMM into the workspace, 2: the reduce that applies it (may run on another stream)
-        check(lib().dr_bf3_wgrad_emb_parts(ptr(ids_t), R, nf, ptr(row_base), ptr(table), table.shape[1], ptr(dense_pad), ptr(dy), dy.stride(0),
-                                           F, N, float(scale), ptr(dstW), dstW.stride(0), ptr(dstb), ptr(workspace), workspace.numel() * 4,
-                                           int(parts), stream_ptr()), "dr_bf3_wgrad_emb_parts")
-        return dstW
+    # parts 1: the split-K GEMM into the workspace, 2: the reduce that applies it (may run on another stream)
     check(lib().dr_bf3_wgrad_emb(ptr(ids_t), R, nf, ptr(row_base), ptr(table), table.shape[1], ptr(dense_pad), ptr(dy), dy.stride(0),
                                  F, N, float(scale), ptr(dstW), dstW.stride(0), ptr(dstb), ptr(workspace), workspace.numel() * 4,
-                                 stream_ptr()), "dr_bf3_wgrad_emb")
+                                 int(parts), stream_ptr()), "dr_bf3_wgrad_emb")
     return dstW
 
 

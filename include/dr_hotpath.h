@@ -116,20 +116,15 @@ int dr_vocab_lookup_bytes(const uint8_t* bytes, const int64_t* offsets, int64_t 
  * lin_w may be NULL (no first-order term); lin_bias is a 1-element device array (the trained bias) or
  * NULL; sum_x / fm_logit may be NULL (pure lookup).
  * D must be a multiple of 4, 4 <= D <= 256.
+ * flags: 0, or DR_POOL_FIRST_ORDER_ONLY: fm_logit = lin_bias + sum w (no second-order term) -- the "wide" logit of
+ * WDL (`tf.feature_column.linear_model`, estimator/models/ranking/wide_and_deep.py:30-32 of the reference).
  * ---------------------------------------------------------------------------------------- */
+#define DR_POOL_FIRST_ORDER_ONLY 1
 int dr_emb_pool_fwd(const int64_t* ids, int64_t B, int32_t F, int32_t C, const int32_t* col_start,
                     const int64_t* row_base, const float* table, int32_t D,
                     const float* lin_w, const float* lin_bias,
                     float* concat, int64_t ld_concat, float* sum_x, float* fm_logit,
-                    dr_stream_t stream);
-
-/* Same, with flags.  DR_POOL_FIRST_ORDER_ONLY: fm_logit = lin_bias + sum w (no second-order term) -- the "wide" logit of
- * WDL (`tf.feature_column.linear_model`, estimator/models/ranking/wide_and_deep.py:30-32 of the reference). */
-#define DR_POOL_FIRST_ORDER_ONLY 1
-int dr_emb_pool_fwd_ex(const int64_t* ids, int64_t B, int32_t F, int32_t C, const int32_t* col_start,
-                       const int64_t* row_base, const float* table, int32_t D, const float* lin_w,
-                       const float* lin_bias, float* concat, int64_t ld_concat, float* sum_x,
-                       float* fm_logit, int32_t flags, dr_stream_t stream);
+                    int32_t flags, dr_stream_t stream);
 /* Per-field first-order outputs (FNN, estimator/models/ranking/fnn.py:53-64: a bias-free Dense(1) over every indicator
  * column's multi-hot input, concatenated):  out[b][f] = sum over the bag of field f of lin_w[row_base[f] + id]  (ids < 0
  * skipped).  bwd: dst_lin[row] += scale * d_out[b][f] for every id of the bag (fp32 atomics). */
@@ -208,7 +203,8 @@ int dr_emb_pool_bwd_sorted(const int64_t* ids, const int64_t* row_base, const in
                            int32_t D, int64_t num_rows, const float* grad, int64_t ld_grad,
                            const float* concat, int64_t ld_concat, const float* sum_x,
                            const float* d_fm_logit, const float* slot_lin_grad, float scale,
-                           float* dst_table, float* dst_lin, float* dst_bias, float* x_sorted, dr_stream_t stream);
+                           float* dst_table, float* dst_lin, float* dst_bias, float* x_sorted,
+                           const float* lin_old_t, int32_t parts, uint32_t* table_amax, dr_stream_t stream);
 /* The FM term (sum_x, d_fm_logit given) needs x[b, f, :] of every slot: for a slot that owns its row it is the row's own value
  * (read by the update anyway); for slots that SHARE a row it comes from `concat` if the forward stored it, else from
  * x_sorted [B * F, D], where dr_emb_snapshot_sorted_rows has placed -- before the update starts -- the row of every work-list
@@ -221,35 +217,24 @@ int dr_emb_pool_bwd_sorted(const int64_t* ids, const int64_t* row_base, const in
  * piece parks its sum in its own row of x_sorted (overwriting the snapshot it has consumed) and a second small launch inside
  * the call adds a row's pieces in sorted order and updates the row once -- the same batch then gives the same bits, whatever
  * the id distribution.  (The Adam variant always sums a row's slots in one lane group and never used atomics.) */
-/* dr_emb_pool_bwd_sorted in two halves (parts: 1 = the update kernel, 2 = the ordered combination of hot rows' parked pieces, 3 =
- * both = dr_emb_pool_bwd_sorted): for callers that time or overlap the halves separately.  Part 2 must follow part 1 on the same
- * stream before the tables are read; it is a no-op without x_sorted. */
-int dr_emb_pool_bwd_sorted_parts(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
-                                 const int32_t* sorted_slots, const uint8_t* unique_flags,
-                                 const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
-                                 int32_t D, int64_t num_rows, const float* grad, int64_t ld_grad,
-                                 const float* concat, int64_t ld_concat, const float* sum_x,
-                                 const float* d_fm_logit, const float* slot_lin_grad, float scale,
-                                 float* dst_table, float* dst_lin, float* dst_bias, float* x_sorted, int32_t parts,
-                                 dr_stream_t stream);
+/* parts -- the call in two halves, for callers that time or overlap them separately: 1 = the update kernel, 2 = the ordered combination
+ * of hot rows' parked pieces, 3 = both (the whole update).  Part 2 must follow part 1 on the same stream before the tables are read;
+ * it is a no-op without x_sorted.  Two more bits select what part 1 covers; parts must lie in 1..15 with (parts & 3) != 0 (DR_EINVAL
+ * otherwise). */
+/* parts | 8: the slots whose row is unique in the batch were updated elsewhere (dr_h2_dgrad_emb_sgd) -- only the duplicate pass, the
+ * hot rows and the first-order bias run here; `grad` need hold the rows of the non-unique slots only.
+ * lin_old_t [F, B] (field-major, may be NULL): the first-order weights as the forward of THIS step read them (lin_vals_t of
+ * dr_bf3_emb_linear_fwd).  A row unique in the batch then gets dst_lin[row] = lin_old + scale * g as ONE write instead of a
+ * read-modify-write (K4 is bound by 128-byte line operations; this removes one of eight per slot).  Valid only if nothing wrote
+ * dst_lin since that forward; ignored with slot_lin_grad.
+ * table_amax (may be NULL): running amax record of dst_table -- raised to the largest |value| this call writes into the table (the
+ * f16x2 GEMMs, dr_h2_emb_linear_fwd / dr_h2_wgrad_emb, scale the table rows by it). */
 /* parts | 4: first-order weights of rows unique in the batch are NOT updated by the call; dr_emb_lin_update_unique applies exactly that
  * part (dst_lin[row] += scale * gradient for every slot whose unique flag is set), on any stream between the head's backward and
  * the next forward.  Why: a random 4-byte read-modify-write fetches a 128-byte line -- 0.27 GB of K4's 1.64 GB at config 3 -- and
  * beside a matrix-bound GEMM that traffic is free. */
 int dr_emb_lin_update_unique(const int64_t* ids, const uint8_t* unique_flags, int64_t B, int32_t F, const int64_t* row_base,
                              const float* d_fm_logit, const float* slot_lin_grad, float scale, float* dst_lin, dr_stream_t stream);
-/* dr_emb_pool_bwd_sorted_parts with lin_old_t [F, B] (field-major, may be NULL): the first-order weights as the forward of THIS step
- * read them (dr_bf3_emb_linear_fwd_lv).  A row unique in the batch then gets dst_lin[row] = lin_old + scale * g as ONE write instead
- * of a read-modify-write (K4 is bound by 128-byte line operations; this removes one of eight per slot).  Valid only if nothing
- * wrote dst_lin since that forward; ignored with slot_lin_grad. */
-int dr_emb_pool_bwd_sorted_ex(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
-                              const int32_t* sorted_slots, const uint8_t* unique_flags,
-                              const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
-                              int32_t D, int64_t num_rows, const float* grad, int64_t ld_grad,
-                              const float* concat, int64_t ld_concat, const float* sum_x,
-                              const float* d_fm_logit, const float* slot_lin_grad, float scale,
-                              float* dst_table, float* dst_lin, float* dst_bias, float* x_sorted,
-                              const float* lin_old_t, int32_t parts, uint32_t* table_amax, dr_stream_t stream);
 int dr_emb_snapshot_sorted_rows(const int64_t* sorted_rows, const int32_t* dup_heads, const int32_t* dup_count,
                                 const float* table, int32_t D, int64_t num_rows, float* x_sorted, dr_stream_t stream);
 
@@ -264,7 +249,8 @@ int dr_emb_snapshot_sorted_rows(const int64_t* sorted_rows, const int32_t* dup_h
  * dr_adam_step.  Deterministic (a row's slots are summed by one lane group in sorted order). */
 /* (round 4) m_lin / v_lin may be the two columns of ONE [R, 2] array -- pass v_lin == m_lin + 1 -- and are then addressed with a row
  * stride of 2: a row's first-order moments share a cache line (one line operation to read, one to write, instead of two each).  The
- * same convention holds for dr_adam_catchup_rows. */
+ * same convention holds for dr_adam_catchup_rows.
+ * lin_old_t (may be NULL) and table_amax (may be NULL): as in dr_emb_pool_bwd_sorted. */
 int dr_emb_pool_bwd_sorted_adam(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
                                 const int32_t* sorted_slots, const uint8_t* unique_flags,
                                 const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
@@ -272,16 +258,8 @@ int dr_emb_pool_bwd_sorted_adam(const int64_t* ids, const int64_t* row_base, con
                                 const float* concat, int64_t ld_concat, const float* sum_x,
                                 const float* d_fm_logit, const float* slot_lin_grad, float lr_t, float beta1,
                                 float beta2, float eps, float* table, float* m_table, float* v_table,
-                                float* lin_w, float* m_lin, float* v_lin, float* x_sorted, dr_stream_t stream);
-/* ... with lin_old_t as in dr_emb_pool_bwd_sorted_ex */
-int dr_emb_pool_bwd_sorted_adam_ex(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
-                                const int32_t* sorted_slots, const uint8_t* unique_flags,
-                                const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
-                                int32_t D, int64_t num_rows, const float* grad, int64_t ld_grad,
-                                const float* concat, int64_t ld_concat, const float* sum_x,
-                                const float* d_fm_logit, const float* slot_lin_grad, float lr_t, float beta1,
-                                float beta2, float eps, float* table, float* m_table, float* v_table,
-                                float* lin_w, float* m_lin, float* v_lin, float* x_sorted, const float* lin_old_t, uint32_t* table_amax, dr_stream_t stream);
+                                float* lin_w, float* m_lin, float* v_lin, float* x_sorted, const float* lin_old_t,
+                                uint32_t* table_amax, dr_stream_t stream);
 /* Dense Adam step (same formula) over a flat parameter buffer; grad is multiplied by grad_scale first. */
 /* TF's NON-lazy sparse Adam, evaluated lazily (examples/train_fm_on_movielens_estimator.py:51-52: tf.train.AdamOptimizer decays
  * m / v of the WHOLE variable and moves every row on every step).  row_step[R] int32 (zero-initialised) counts
@@ -366,12 +344,13 @@ int dr_linear_bwd_dw(const float* x, int64_t ld_x, const float* dy, int64_t ld_d
  * produces  dx = (dy @ W^T) * (x > 0 if relu_mask)  and the fused SGD step  dstW += scale * x^T dy,
  * dstb += scale * colsum(dy)  (dx uses the pre-update W even when dstW == W).  Deterministic.
  * Domain: N <= 32, K in {128, 256, 512}, M a multiple of 32, x/dx rows 4*(K/128)-byte aligned; anything else returns
- * DR_ESHAPE and the caller uses dr_linear_bwd_dx + dr_linear_bwd_dw. */
+ * DR_ESHAPE and the caller uses dr_linear_bwd_dx + dr_linear_bwd_dw.
+ * parts (1..3) and dx_amax (may be NULL): see "in two halves" below. */
 int64_t dr_linear_bwd_narrow_workspace_bytes(int64_t M, int32_t K, int32_t N);
 int dr_linear_bwd_narrow(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, const float* W,
                          int64_t ld_w, int64_t M, int32_t K, int32_t N, int32_t relu_mask, float scale,
                          float* dstW, int64_t ld_dstw, float* dstb, float* dx, int64_t ld_dx,
-                         void* workspace, int64_t workspace_bytes, dr_stream_t stream);
+                         void* workspace, int64_t workspace_bytes, int32_t parts, uint32_t* dx_amax, dr_stream_t stream);
 
 /* Fused tower head: the last hidden layer (H <= 32 units), the Dense(1) output that follows it, the FM logit, the loss,
  * and the backward of the Dense(1) -- i.e. keras/models/ranking/deepfm.py:30-34,41-47 `Dense(32, relu)`, `Dense(1)`,
@@ -386,13 +365,15 @@ int dr_linear_bwd_narrow(const float* x, int64_t ld_x, const float* dy, int64_t 
  *            gradient buffers with scale = 1 (data-parallel: all-reduce, then apply); NULL / scale = 0: skipped
  * n_total (0 = M): the number of examples the loss is a mean over, when these M rows are one slice of a larger batch
  * (micro-batches): loss_out = sum(l) / n_total, d_logit = dl/dlogit / n_total.
- * Deterministic.  H > 32 returns DR_ESHAPE (use dr_linear_fwd x2 + dr_bce_fwd_bwd + dr_linear_bwd_*). */
+ * Deterministic.  H > 32 returns DR_ESHAPE (use dr_linear_fwd x2 + dr_bce_fwd_bwd + dr_linear_bwd_*).
+ * parts (1..3): see "in two halves" below. */
 int64_t dr_tower_head_workspace_bytes(int64_t M);
 int dr_tower_head_fwd_bwd(const float* x, int64_t ld_x, const float* W1, int64_t ld_w1, const float* b1,
                           int64_t M, int64_t n_total, int32_t K, int32_t H, int32_t act, const float* w2,
                           int64_t ld_w2, const float* b2, const float* extra_logit, const float* labels,
-                          int32_t loss_mode, float scale, float* dst_w2, int64_t ld_dst_w2, float* dst_b2, float* h_out, int64_t ld_h, float* prob, float* d_logit, float* d_h, int64_t ld_dh,
-                          float* loss_out, void* workspace, int64_t workspace_bytes, dr_stream_t stream);
+                          int32_t loss_mode, float scale, float* dst_w2, int64_t ld_dst_w2, float* dst_b2, float* h_out, int64_t ld_h,
+                          float* prob, float* d_logit, float* d_h, int64_t ld_dh, float* loss_out, void* workspace,
+                          int64_t workspace_bytes, int32_t parts, dr_stream_t stream);
 /* The whole tower tail in ONE pass over x (round 5): dr_tower_head_fwd_bwd (act = relu) and dr_linear_bwd_narrow (relu_mask = 1) of the
  * SAME layer W1 [K, H] -- in the reference's towers the last hidden layer, Dense(H <= 32, relu), is at once the head's first factor and
  * the layer whose backward follows (keras/models/ranking/deepfm.py:30-34,41-47; estimator/models/feature_interaction/dnn.py:17-29):
@@ -415,24 +396,11 @@ int dr_tower_tail_fused(const float* x, int64_t ld_x, const float* W1, int64_t l
 
 /* dr_linear_bwd_narrow / dr_tower_head_fwd_bwd in two halves (round 4): parts = 1 the main kernel (everything the rest of the step
  * reads: dx; prob, d_logit, d_h), parts = 2 the small reduce that applies the per-block partials to the weights (and writes the
- * loss), 3 = both.  Part 2 may run on ANOTHER stream -- the engine keeps the three reduce kernels of a step off its training stream;
- * it must finish before anything reads the updated weights and before the next part 1 over the same workspace. */
-int dr_linear_bwd_narrow_parts(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, const float* W,
-                               int64_t ld_w, int64_t M, int32_t K, int32_t N, int32_t relu_mask, float scale,
-                               float* dstW, int64_t ld_dstw, float* dstb, float* dx, int64_t ld_dx,
-                               void* workspace, int64_t workspace_bytes, int32_t parts, dr_stream_t stream);
-/* ... that also leaves max |dx| as float bits in dx_amax[0] (reset and rebuilt by part 1): the amax record of dx for the f16x2 GEMMs
- * (dr_h2_linear_nt / dr_h2_wgrad_emb below) */
-int dr_linear_bwd_narrow_amax(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, const float* W, int64_t ld_w, int64_t M,
-                              int32_t K, int32_t N, int32_t relu_mask, float scale, float* dstW, int64_t ld_dstw, float* dstb, float* dx,
-                              int64_t ld_dx, void* workspace, int64_t workspace_bytes, int32_t parts, uint32_t* dx_amax,
-                              dr_stream_t stream);
-int dr_tower_head_fwd_bwd_parts(const float* x, int64_t ld_x, const float* W1, int64_t ld_w1, const float* b1,
-                                int64_t M, int64_t n_total, int32_t K, int32_t H, int32_t act, const float* w2,
-                                int64_t ld_w2, const float* b2, const float* extra_logit, const float* labels,
-                                int32_t loss_mode, float scale, float* dst_w2, int64_t ld_dst_w2, float* dst_b2, float* h_out, int64_t ld_h,
-                                float* prob, float* d_logit, float* d_h, int64_t ld_dh, float* loss_out, void* workspace,
-                                int64_t workspace_bytes, int32_t parts, dr_stream_t stream);
+ * loss), 3 = both (the whole call); any other value is DR_EINVAL.  Part 2 may run on ANOTHER stream -- the engine keeps the three
+ * reduce kernels of a step off its training stream; it must finish before anything reads the updated weights and before the next
+ * part 1 over the same workspace.
+ * dx_amax of dr_linear_bwd_narrow (may be NULL): the call also leaves max |dx| as float bits in dx_amax[0] (reset and rebuilt by
+ * part 1): the amax record of dx for the f16x2 GEMMs (dr_h2_linear_nt / dr_h2_wgrad_emb below). */
 
 /* ------------------------------------------------------------------------------------------
  * K8  DCN cross layer (keras/models/ranking/dcn.py:70-88):
@@ -442,13 +410,16 @@ int dr_tower_head_fwd_bwd_parts(const float* x, int64_t ld_x, const float* W1, i
  * then this with W NULL adds bias-free combine).  x0, x, out, prod share leading dimension ld.
  * bwd (elementwise part): d_prod = d_out * x0 ; d_x0 += d_out * prod ; d_x += d_out + diag_scale*d_prod;
  * the GEMM parts are dr_linear_bwd_dx(d_prod, W, accumulate=1 -> d_x) and dr_linear_bwd_dw(x, d_prod).
+ * d_prod_amax (may be NULL): dr_cross_combine_bwd also leaves max |d_prod| as float bits in d_prod_amax[0] (reset first, also
+ * when M == 0): the amax record of d_prod for the f16x2 GEMMs that take it as an operand (the cross layer's dgrad
+ * and wgrad: dr_h2_linear_nt, dr_h2_wgrad).
  * ---------------------------------------------------------------------------------------- */
 int dr_cross_fwd(const float* x0, const float* x, int64_t ld, const float* W, int64_t ld_w,
                  const float* b, float diag_scale, int64_t M, int32_t Dm, float* out,
                  float* prod_out, dr_stream_t stream);
 int dr_cross_combine_bwd(const float* x0, const float* prod, const float* d_out, int64_t M,
                          int32_t Dm, int64_t ld, float diag_scale, float* d_prod, float* d_x0_accum,
-                         float* d_x_accum, dr_stream_t stream);
+                         float* d_x_accum, uint32_t* d_prod_amax, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * K11  fused sigmoid + binary cross-entropy (+ gradient wrt the logit).
@@ -491,17 +462,13 @@ int dr_inbatch_softmax_fwd(const float* q, const float* c, int64_t B, int32_t D,
 int dr_inbatch_softmax_grad_scores(const float* q, const float* c, int64_t B, int32_t D,
                                    const float* cand_prob, const int64_t* cand_ids,
                                    const float* sample_weight, float inv_temperature, const float* row_lse,
-                                   float d_loss, float* G, int64_t ld_g, dr_stream_t stream);
+                                   float d_loss, float* G, int64_t ld_g, float* workspace,
+                                   int64_t workspace_bytes, dr_stream_t stream);
 /* Round 5: in the f16x2 operand split (dr_get_gemm_split) both score passes run on the register-split kernel with the LSE /
  * softmax-gradient epilogues (three fp16 products per fp32 product, scores never leave the tile) whenever D % 4 == 0, D <= 512,
  * B >= 256 and the workspace (256-byte aligned, dr_inbatch_softmax_workspace_bytes) is there: it also holds the candidates' two fp16
- * planes and both amax records.  dr_inbatch_softmax_grad_scores has no workspace and stays on the fp32 kernel;
- * dr_inbatch_softmax_grad_scores_ws takes one (the forward's may be reused; its contents are not needed). */
-int dr_inbatch_softmax_grad_scores_ws(const float* q, const float* c, int64_t B, int32_t D,
-                                      const float* cand_prob, const int64_t* cand_ids,
-                                      const float* sample_weight, float inv_temperature, const float* row_lse,
-                                      float d_loss, float* G, int64_t ld_g, float* workspace,
-                                      int64_t workspace_bytes, dr_stream_t stream);
+ * planes and both amax records.  dr_inbatch_softmax_grad_scores with workspace NULL / workspace_bytes 0 (or too small) stays on
+ * the fp32 kernel; the forward's workspace may be reused (its contents are not needed). */
 
 /* ------------------------------------------------------------------------------------------
  * K10  exact top-K maximum-inner-product search (BruteForce.call factorized_top_k.py:316-334,
@@ -620,20 +587,17 @@ int dr_softmax_ce_rows_bwd(const float* logits, const float* labels, int64_t B, 
  * dr_axpy: y += alpha * x, applies an all-reduced dense gradient.
  * ---------------------------------------------------------------------------------------- */
 int64_t dr_shard_bucket_workspace_bytes(int64_t n, int32_t world);
-int dr_shard_bucket_ids(const int64_t* ids, int64_t n, int32_t C, int64_t rows_per_shard, int32_t world,
-                        int64_t* counts, int64_t* send_rows, int64_t* pos, int64_t* workspace,
-                        dr_stream_t stream);
 /* Requester-side de-duplication of the exchange (round 4): what [TF] safe_embedding_lookup_sparse's `unique` does inside the lookup
  * reached from keras/models/ranking/fm.py:57-61 -- a row that several slots of a micro-batch look up travels once each way.
  * dr_shard_dedup_slots: rep[p] = the lowest slot looking up the same row as slot p (p itself for an unshared row or a missing id), from
  *   the slot plan of the micro-batch's ids (dr_emb_sort_slots over the global rows row_base[f] + id, with the same num_rows).
- * dr_shard_bucket_ids_dedup: dr_shard_bucket_ids in which only the representatives get a send slot (counts sum to the number of
- *   distinct rows) and pos[p] = pos[rep[p]] for every other slot.  Integer, bit-exact. */
+ * dr_shard_bucket_ids with rep given (may be NULL: every slot gets a send slot): only the representatives get a send slot (counts
+ *   sum to the number of distinct rows) and pos[p] = pos[rep[p]] for every other slot.  Integer, bit-exact. */
 int dr_shard_dedup_slots(const int64_t* sorted_rows, const int32_t* sorted_slots, const int32_t* dup_count, int64_t n,
                          int64_t num_rows, int64_t* rep, dr_stream_t stream);
-int dr_shard_bucket_ids_dedup(const int64_t* ids, const int64_t* rep, int64_t n, int32_t C, int64_t rows_per_shard,
-                              int32_t world, int64_t* counts, int64_t* send_rows, int64_t* pos, int64_t* workspace,
-                              dr_stream_t stream);
+int dr_shard_bucket_ids(const int64_t* ids, const int64_t* rep, int64_t n, int32_t C, int64_t rows_per_shard,
+                        int32_t world, int64_t* counts, int64_t* send_rows, int64_t* pos, int64_t* workspace,
+                        dr_stream_t stream);
 int dr_rows_gather(const int64_t* rows, int64_t n, const float* table, int32_t D, const float* lin_w,
                    float* out_rows, float* out_lin, dr_stream_t stream);
 int dr_rows_scatter_add(const int64_t* rows, int64_t n, const float* grads, int32_t D,
@@ -644,17 +608,13 @@ int dr_axpy(int64_t n, float alpha, const float* x, float* y, dr_stream_t stream
  * layout (pos is a permutation, every destination is written exactly once):
  *   out_rows[pos[b,f],:] = d_concat[b, f*D:(f+1)*D] + d_fm_logit[b] * (sum_x[b,:] - concat[b, f*D:(f+1)*D]) ;
  *   out_lin[pos[b,f]] = d_fm_logit[b] ;  bias_sum[0] += sum_b d_fm_logit[b].
- *   concat / sum_x / d_fm_logit / out_lin / bias_sum may be NULL. */
-int dr_emb_pack_grads(const int64_t* pos, int64_t B, int32_t F, int32_t D, const float* d_concat,
+ *   concat / sum_x / d_fm_logit / out_lin / bias_sum may be NULL.
+ * unique_flags (may be NULL) selects the form for a de-duplicated exchange: pos maps the slots of a shared row to ONE destination;
+ * unique_flags [B * F] (the slot plan's flags of the micro-batch) says which slots own their row -- those store, the others ADD with
+ * fp32 atomics (their order is not fixed).  out_rows / out_lin must then be zero-filled by the caller. */
+int dr_emb_pack_grads(const int64_t* pos, const uint8_t* unique_flags, int64_t B, int32_t F, int32_t D, const float* d_concat,
                       int64_t ld_dconcat, const float* concat, int64_t ld_concat, const float* sum_x,
-                      const float* d_fm_logit, float* out_rows, float* out_lin, float* bias_sum,
-                      dr_stream_t stream);
-/* the same for a de-duplicated exchange: pos maps the slots of a shared row to ONE destination; unique_flags [B * F] (the slot plan's
- * flags of the micro-batch) says which slots own their row -- those store, the others ADD with fp32 atomics (their order is not
- * fixed).  out_rows / out_lin must be zero-filled by the caller. */
-int dr_emb_pack_grads_dedup(const int64_t* pos, const uint8_t* unique_flags, int64_t B, int32_t F, int32_t D, const float* d_concat,
-                            int64_t ld_dconcat, const float* concat, int64_t ld_concat, const float* sum_x,
-                            const float* d_fm_logit, float* out_rows, float* out_lin, float* bias_sum, dr_stream_t stream);
+                      const float* d_fm_logit, float* out_rows, float* out_lin, float* bias_sum, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * K7p  first (wide) tower layer on PRE-SPLIT operands -- the "planes" form of the bf16x3 product mode.
@@ -730,20 +690,15 @@ int dr_bf3_cross_fwd(const float* x0, const float* x, int64_t ld, const void* wt
  *        K - 64 F dense features of every example, zero-padded to 32 (NULL iff K == 64 F), W^T planes [3][N][ld_planes]
  *        (columns [K, roundup(K, 32)) zero), bias [N]
  *   out: concat[:, 0 : 64 F) (for the backward kernels; the caller places the dense features in concat[:, 64 F : K) itself),
- *        sum_x [M, 64], fm_logit [M] (as dr_emb_pool_fwd), out [M, N] = act(x W + bias), x = [embeddings, dense features]. */
+ *        sum_x [M, 64], fm_logit [M] (as dr_emb_pool_fwd), out [M, N] = act(x W + bias), x = [embeddings, dense features];
+ *        lin_vals_t [F, M] field-major (may be NULL): the first-order weight of every slot as it was read, lin_vals_t[f * M + m] =
+ *        lin_w[row_base[f] + ids[m, f]] (undefined for a missing id; ignored when lin_w == NULL).  Handed to dr_emb_pool_bwd_sorted
+ *        as `lin_old_t`, it turns the first-order update of a row that is unique in the batch into ONE write. */
 int dr_bf3_emb_linear_fwd(const int64_t* ids, int64_t M, int32_t F, const int64_t* row_base, int64_t field_rows_max,
                           const float* table, int32_t D, const float* lin_w, const float* lin_bias, const float* dense_pad, float* concat,
                           int64_t ld_concat, int32_t K, const void* wt_planes, int64_t plane_stride, int64_t ld_planes, int32_t N,
                           const float* bias, int32_t act, float* sum_x, float* fm_logit, float* out, int64_t ld_out,
-                          dr_stream_t stream);
-/* dr_bf3_emb_linear_fwd that also saves the first-order weight of every slot as it was read: lin_vals_t [F, M] field-major,
- * lin_vals_t[f * M + m] = lin_w[row_base[f] + ids[m, f]] (undefined for a missing id; ignored when lin_w == NULL).  Handed to
- * dr_emb_pool_bwd_sorted_ex as `lin_old_t`, it turns the first-order update of a row that is unique in the batch into ONE write. */
-int dr_bf3_emb_linear_fwd_lv(const int64_t* ids, int64_t M, int32_t F, const int64_t* row_base, int64_t field_rows_max,
-                             const float* table, int32_t D, const float* lin_w, const float* lin_bias, const float* dense_pad, float* concat,
-                             int64_t ld_concat, int32_t K, const void* wt_planes, int64_t plane_stride, int64_t ld_planes, int32_t N,
-                             const float* bias, int32_t act, float* sum_x, float* fm_logit, float* out, int64_t ld_out,
-                             float* lin_vals_t, dr_stream_t stream);
+                          float* lin_vals_t, dr_stream_t stream);
 int64_t dr_bf3_wgrad_workspace_bytes(int64_t R, int32_t F, int32_t N);
 int dr_bf3_wgrad(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, int64_t R, int32_t F, int32_t N,
                  float scale, float* dstW, int64_t ld_w, float* dstb, void* workspace, int64_t workspace_bytes,
@@ -752,15 +707,12 @@ int dr_bf3_wgrad(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, i
  * a buffer (D = 64; F = in_dim in [64 nf, 64 nf + 32]): ids_t [nf][R] int32 field-major ids (dr_ids_transpose_i32, -1 = missing),
  * dense_pad [R, 32] zero-padded dense features (NULL iff F == 64 nf).  Same workspace as dr_bf3_wgrad(R, F, N).  Every field
  * must have fewer than 2^24 - 1 rows (ids index a 4 GB raw buffer per field; -1 falls outside it and reads as zero).
- * Autodiff of the first Dense of keras/models/ranking/deepfm.py:30-34 w.r.t. its kernel, with deepfm.py:44-45's concat never built. */
+ * Autodiff of the first Dense of keras/models/ranking/deepfm.py:30-34 w.r.t. its kernel, with deepfm.py:44-45's concat never built.
+ * In two halves like dr_linear_bwd_narrow: parts = 1 the split-K GEMM into the workspace, 2 the fixed-order reduce that applies it to
+ * dstW / dstb, 3 = both; any other value is DR_EINVAL. */
 int dr_bf3_wgrad_emb(const int32_t* ids_t, int64_t R, int32_t nf, const int64_t* row_base, const float* table, int32_t D,
                      const float* dense_pad, const float* dy, int64_t ld_dy, int32_t F, int32_t N, float scale, float* dstW,
-                     int64_t ld_w, float* dstb, void* workspace, int64_t workspace_bytes, dr_stream_t stream);
-/* ... in two halves like dr_linear_bwd_narrow_parts: parts = 1 the split-K GEMM into the workspace, 2 the fixed-order reduce that
- * applies it to dstW / dstb, 3 = both */
-int dr_bf3_wgrad_emb_parts(const int32_t* ids_t, int64_t R, int32_t nf, const int64_t* row_base, const float* table, int32_t D,
-                           const float* dense_pad, const float* dy, int64_t ld_dy, int32_t F, int32_t N, float scale, float* dstW,
-                           int64_t ld_w, float* dstb, void* workspace, int64_t workspace_bytes, int32_t parts, dr_stream_t stream);
+                     int64_t ld_w, float* dstb, void* workspace, int64_t workspace_bytes, int32_t parts, dr_stream_t stream);
 int64_t dr_bf3_gemm_tn_workspace_bytes(int64_t R, int32_t F, int32_t N);
 int dr_bf3_gemm_tn(const void* x_planes, int64_t x_plane_stride, int64_t x_ld, const void* y_planes,
                    int64_t y_plane_stride, int64_t y_ld, int64_t R, int32_t F, int32_t N, float scale, float* dst,
@@ -768,12 +720,12 @@ int dr_bf3_gemm_tn(const void* x_planes, int64_t x_plane_stride, int64_t x_ld, c
                    dr_stream_t stream);
 
 /* ---- "f16x2" operand mode of the first tower layer's three GEMMs (round 4) ---------------------------------------------------------
- * The same products as dr_bf3_emb_linear_fwd_lv / dr_bf3_linear_nt / dr_bf3_wgrad(_emb) (keras/models/ranking/deepfm.py:30-34 of the
+ * The same products as dr_bf3_emb_linear_fwd / dr_bf3_linear_nt / dr_bf3_wgrad(_emb) (keras/models/ranking/deepfm.py:30-34 of the
  * reference and its autodiff; fp32 in, fp32 accumulate, fp32 out) with every operand value carried as TWO fp16 terms of x * s (22
  * significant bits) and a product formed from THREE matrix instructions instead of the bf16x3 mode's six.  s is a power of two per
  * TENSOR, derived inside the kernels from the tensor's `amax record`: one uint32 in device memory holding max |x| as float bits (or an
- * upper bound of it).  Records are written by dr_h2_amax or maintained by the tensor's producer (dr_emb_pool_bwd_sorted_ex and
- * dr_emb_pool_bwd_sorted_adam_ex keep the table's as a running maximum); a record that is too SMALL by a factor of 4 or more
+ * upper bound of it).  Records are written by dr_h2_amax or maintained by the tensor's producer (dr_emb_pool_bwd_sorted and
+ * dr_emb_pool_bwd_sorted_adam keep the table's as a running maximum); a record that is too SMALL by a factor of 4 or more
  * saturates values instead of producing inf (still wrong: keep it an upper bound).  Accuracy: tests/test_gpu_h2_gemm.py.
  * Errors as the bf3 calls, plus DR_EINVAL for a missing record. */
 int dr_h2_amax(const float* src, int64_t ld, int64_t R, int32_t C, uint32_t* amax, int32_t reset, dr_stream_t stream);
@@ -794,9 +746,9 @@ int dr_h2_linear_nt(const float* A, int64_t lda, const uint32_t* a_amax, const v
  * fields, SGD):  dx[m, 64 f + d] = sum_k dy[m][k] W[64 f + d][k] is the gradient row of slot (m, f).  For every slot whose table row no other
  * slot of the batch shares (unique_flags [M, F] of dr_emb_sort_slots; ids_t [F, M] int32 from dr_ids_transpose_i32, -1 = missing) the
  * kernel applies K4's update on the spot --  g = dx + d_fm_logit[m] (sum_x[m] - x), table[row] = x + scale g with x the row as it stands,
- * lin_w[row] = lin_old_t[f, m] + scale d_fm_logit[m]  -- operation for operation what dr_emb_pool_bwd_sorted_ex does with the stored
+ * lin_w[row] = lin_old_t[f, m] + scale d_fm_logit[m]  -- operation for operation what dr_emb_pool_bwd_sorted does with the stored
  * gradient (bit-identical tables); the other slots' dx goes to d_concat [M, ld_dconcat] for the duplicate pass.  Follow with
- * dr_emb_pool_bwd_sorted_ex(parts | 8) on the same stream (grad = d_concat): rows shared by several slots, hot rows, first-order
+ * dr_emb_pool_bwd_sorted(parts | 8) on the same stream (grad = d_concat): rows shared by several slots, hot rows, first-order
  * bias.  The tables must not be read by anything that needs their pre-step value after this call (run the first-layer wgrad that
  * gathers x BEFORE it).  w_planes: two fp16 planes [2][>= 64 F rows][w_ld] of the layer's kernel (dr_h2_split / dr_h2_refresh_weight's
  * `w`), w_ld >= roundup(K, 32); lin_w / lin_old_t both NULL or both given; table_amax (may be NULL): the table's running record, raised
@@ -809,9 +761,6 @@ int dr_h2_dgrad_emb_sgd(const float* dy, int64_t ld_dy, const uint32_t* dy_amax,
 int dr_h2_cross_fwd(const float* x0, const float* x, int64_t ld, const uint32_t* x_amax, const void* wt_planes, int64_t plane_stride,
                     int64_t ld_planes, const uint32_t* w_amax, const float* b, float diag_scale, int64_t M, int32_t Dm, float* out,
                     float* prod_out, uint32_t* out_amax, dr_stream_t stream);
-/* dr_cross_combine_bwd that also leaves the record of d_prod (the operand of the cross layer's dgrad and wgrad) */
-int dr_cross_combine_bwd_amax(const float* x0, const float* prod, const float* d_out, int64_t M, int32_t Dm, int64_t ld, float diag_scale,
-                              float* d_prod, float* d_x0_accum, float* d_x_accum, uint32_t* d_prod_amax, dr_stream_t stream);
 /* dense_amax: the record of dense_pad, required iff K > 64 F; lin_vals_t may be NULL */
 int dr_h2_emb_linear_fwd(const int64_t* ids, int64_t M, int32_t F, const int64_t* row_base, int64_t field_rows_max, const float* table,
                          int32_t D, const uint32_t* table_amax, const float* lin_w, const float* lin_bias, const float* dense_pad,

@@ -1,5 +1,5 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library builds, loads, and exports exactly the
-symbols include/dr_hotpath.h declares; the ctypes binding covers all of them; the product path refuses to
+symbols include/dr_hotpath.h declares; the ctypes binding reads its signatures from that header; the product path refuses to
 run without the library or without a GPU (no silent fallback)."""
 import ctypes
 import os
@@ -27,11 +27,63 @@ def test_library_builds_and_exports_every_declared_symbol():
         assert hasattr(L, n), "libdr_hotpath.so does not export %s" % n
 
 
-def test_ctypes_binding_covers_header():
-    from deep_recommenders_amd import _lib
+def _known_answers():
+    """prototypes copied from the three headers by hand, as literal ctypes types: between them every kind of type the parser maps"""
+    p, cp, i, i32, i64, u32, u64, f32 = (ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
+                                         ctypes.c_uint64, ctypes.c_float)
+    tail = [p] * 55         # dr_h2_emb_linear_tail_fwd: 55 arguments, pointers but for ...
+    for at in (2, 6, 14, 19, 21, 30, 35, 52):        # F, D, K, N, act, H, loss_mode, parts
+        tail[at] = i32
+    for at in (1, 4, 13, 16, 17, 25, 28, 32, 38, 41, 46, 48, 51):     # M, field_rows_max, the leading dimensions / strides, workspace_bytes
+        tail[at] = i64
+    tail[36] = f32          # scale
+    return {
+        "dr_hotpath.h": {
+            "dr_fm2_fwd": (i, [p, i64, i32, i32, p, p]),
+            "dr_version": (cp, []),
+            "dr_dropout_fwd": (i, [p, i64, i64, i32, f32, u64, p, i64, p, p]),
+            "dr_linear_bwd_narrow_workspace_bytes": (i64, [i64, i32, i32]),
+            "dr_set_gemm_mode": (i32, [i32]),
+            "dr_adam_step": (i, [p, p, p, p, i64, f32, f32, f32, f32, f32, p]),
+            # x, ld_x, dy, ld_dy, W, ld_w, M, K, N, relu_mask, scale, dstW, ld_dstw, dstb, dx, ld_dx, workspace, workspace_bytes, parts, dx_amax, stream
+            "dr_linear_bwd_narrow": (i, [p, i64, p, i64, p, i64, i64, i32, i32, i32, f32, p, i64, p, p, i64, p, i64, i32, p, p]),
+            "dr_h2_emb_linear_tail_fwd": (i, tail),
+        },
+        "dr_input.h": {
+            "dri_crc32c": (u32, [p, i64]),
+            "dri_example_bytes": (i, [p, p, i64, cp, i32, p, i64, p, i64, p, p]),
+        },
+        "dr_collectives.h": {
+            "dr_coll_init": (i, [p, i32, i32, p]),
+            "dr_coll_alltoallv": (i, [p, p, p, p, p, i64, p]),
+        },
+    }
+
+
+def test_ctypes_signatures_are_read_from_the_header():
+    """The bindings' argtypes / restype come from include/*.h (_cabi.py).  Two independent readings of dr_hotpath.h find the same names;
+    hand-copied prototypes come out as the ctypes types written here; a type the parser does not know is an error that names the
+    function, not a guess; and the loaded library carries the parsed signatures."""
+    from deep_recommenders_amd import _cabi, _lib
+    inc = os.path.join(ROOT, "include")
+    assert sorted(_cabi.prototypes(os.path.join(inc, "dr_hotpath.h"))) == _declared()
+    for header, known in _known_answers().items():
+        got = _cabi.prototypes(os.path.join(inc, header))
+        for name, (restype, argtypes) in known.items():
+            assert got[name][0] == restype, name
+            assert list(got[name][1]) == argtypes, name
+    assert len(_cabi.prototypes(os.path.join(inc, "dr_hotpath.h"))["dr_h2_emb_linear_tail_fwd"][1]) == 55
+    with pytest.raises(ValueError, match="dr_bad"):
+        _cabi.parse("typedef void* dr_stream_t;\nint dr_good(const float* x, int64_t n, dr_stream_t stream);\n"
+                    "int dr_bad(const float* x, unsigned long n, dr_stream_t stream);\n")
+    with pytest.raises(ValueError, match="dr_bad"):
+        _cabi.parse("struct dr_thing dr_bad(void);\n")
     assert sorted(_lib.SIGNATURES) == _declared()
-    _lib.lib()
-    assert b"gfx950" in _lib.lib().dr_version()
+    L = _lib.lib()
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype == restype and list(fn.argtypes) == list(argtypes), name
+    assert b"gfx950" in L.dr_version()
 
 
 def test_no_cpu_fallback():

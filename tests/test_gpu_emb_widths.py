@@ -864,6 +864,42 @@ def test_emb_bwd_sorted_adam_every_width(D, radix):
                 assert err <= 4 * yard, (name, err, yard)
 
 
+@gpu
+def test_emb_bwd_sorted_adam_lin_old_t_changes_no_bit():
+    """lin_old_t hands the Adam form the first-order weights the forward read, so that a row unique in the batch is not read again:
+    the same values by another route.  One step (FM term, non-zero moments) over a batch with a unique row, a row five slots share
+    and a missing id: table, m, v and the first-order w, m, v equal the call without lin_old_t bit for bit."""
+    ops = _ops()
+    rng = np.random.default_rng(77)
+    B, F, D, V = 64, 3, 8, 50
+    R = F * V
+    ids = rng.integers(0, V - 1, size=(B, F))
+    ids[0, 0] = V - 1                                       # a row no other slot looks up
+    ids[1:6, 1] = 7                                         # a row several slots share
+    ids[2, 2] = -1                                          # a missing id
+    assert (ids[:, 0] == V - 1).sum() == 1 and (ids[:, 1] == 7).sum() >= 5 and (ids < 0).sum() == 1
+    row_base = (np.arange(F) * V).astype(np.int64)
+    rb, ids_d = _dev(row_base), _dev(ids)
+    plan = ops.emb_sort_slots(ids_d, rb, R)
+    flags = plan.flags.cpu().numpy()[:B * F].reshape(B, F)
+    assert flags[0, 0] == 1 and not flags[1:6, 1].any()      # the plan sees them as unique / shared
+    start = [_dev(a.astype(np.float32)) for a in (rng.standard_normal((R, D)), 0.1 * rng.standard_normal((R, D)), rng.random((R, D)),
+                                                  rng.standard_normal(R), 0.1 * rng.standard_normal(R), rng.random(R))]
+    grad = _dev(rng.standard_normal((B, F * D)).astype(np.float32))
+    dl = _dev(rng.standard_normal(B).astype(np.float32))
+    concat, sum_x, _ = ops.emb_pool_fwd(ids_d, F, None, rb, start[0], start[3], torch.zeros(1, device="cuda"))
+    lin_old_t = start[3][_dev(np.maximum(ids + row_base[None, :], 0))].t().contiguous()
+    results = []
+    for lo in (None, lin_old_t):
+        t, m, v, l, ml, vl = (a.clone() for a in start)
+        ops.emb_pool_bwd_sorted_adam(ids_d, rb, plan, D, R, grad, dl, ops.adam_lr_t(ADAM_LR, B1, B2, 3), B1, B2, EPS, t, m, v, l, ml, vl,
+                                     concat=concat, sum_x=sum_x, lin_old_t=lo)
+        results.append((t, m, v, l, ml, vl))
+    for name, a0, plain, saved in zip(("w", "m", "v", "lin w", "lin m", "lin v"), start, *results):
+        assert not torch.equal(plain, a0), name              # the step moved it
+        _same(saved, plain.cpu().numpy(), name)
+
+
 # ----------------------------------------------------------------------------------------------------------------------------------
 # 6. dr_adam_catchup_rows
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-"""GPU parity: the first-layer dgrad with K4's unique-row pass as its epilogue (dr_h2_dgrad_emb_sgd + dr_emb_pool_bwd_sorted_ex parts | 8)
-against the two launches it replaces (dr_h2_linear_nt into d_concat, then dr_emb_pool_bwd_sorted_ex).  The epilogue repeats K4's
+"""GPU parity: the first-layer dgrad with K4's unique-row pass as its epilogue (dr_h2_dgrad_emb_sgd + dr_emb_pool_bwd_sorted parts | 8)
+against the two launches it replaces (dr_h2_linear_nt into d_concat, then dr_emb_pool_bwd_sorted).  The epilogue repeats K4's
 arithmetic operation for operation, so tables, first-order weights and bias must come out BIT-identical -- which carries every
 oracle-backed tolerance of the K4 / engine tests over to the fused step (autodiff of keras/models/ranking/deepfm.py:30-34,44-45 and
 fm.py:23-37 of the reference w.r.t. the embedding tables)."""

@@ -2,7 +2,7 @@
 (every lane chooses the row and the 16-byte chunk it fetches) and read twice, as the MFMA operand and position-wise for the concat
 stores; a swizzle that the three places do not share shows up as permuted columns in `out`, `sum_x` or `concat`.
 
-Entry points: dr_h2_emb_linear_fwd and dr_bf3_emb_linear_fwd_lv.  M = 256 + 19 (a full row tile and a ragged one: rows 16-31 of
+Entry points: dr_h2_emb_linear_fwd and dr_bf3_emb_linear_fwd (with lin_vals_t).  M = 256 + 19 (a full row tile and a ragged one: rows 16-31 of
 a wave are the ones the swizzle's second term moves), F = 3 fields with and without 13 dense features (the k-tile that comes from
 `dense_pad`), N = 256, `concat` stored and NULL, some ids -1.
 

@@ -311,7 +311,7 @@ def test_engine_f16x2_step_tracks_the_bf16x3_step(optimizer, monkeypatch):
 
 
 def test_h2_gemm_epilogues_leave_the_amax_record_of_what_they_store(ops):
-    """out_amax of dr_h2_linear_nt / dr_h2_cross_fwd and d_prod_amax of dr_cross_combine_bwd_amax: exactly max |stored value| as float
+    """out_amax of dr_h2_linear_nt / dr_h2_cross_fwd and d_prod_amax of dr_cross_combine_bwd: exactly max |stored value| as float
     bits (reset by the call) -- a chain of GEMMs hands each output to the next as an operand without a pass over it."""
     g = torch.Generator(device="cuda").manual_seed(21)
     for (M, K, N) in ((1000, 83, 40), (4100, 300, 520)):

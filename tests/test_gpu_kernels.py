@@ -344,6 +344,80 @@ def test_tower_head_fused(ops, M, K, H, mode):
     np.testing.assert_allclose(b2d.cpu().numpy(), b2 + scale * tb2.grad.numpy(), rtol=0, atol=2e-6)
 
 
+def test_linear_bwd_narrow_in_two_halves(ops):
+    """parts = 1 then parts = 2 of dr_linear_bwd_narrow: the same two launches as one call (parts = 3), so the same bits; part 1 alone
+    leaves dx complete and the weights untouched.  M = 32 * 515: 512 blocks, three of them with a second chunk; N = 17: a ragged
+    column tile.  dx and the weight step also against the fp64 definition, tolerances of test_linear_bwd_narrow_fused."""
+    rng = np.random.default_rng(32)
+    M, K, N, scale = 32 * 515, 256, 17, -0.01
+    x = np.maximum(rng.standard_normal((M, K)), 0).astype(np.float32)
+    dy = rng.standard_normal((M, N)).astype(np.float32)
+    W = (rng.standard_normal((K, N)) / np.sqrt(K)).astype(np.float32)
+    b = rng.standard_normal(N).astype(np.float32)
+    xd = _dev(x)
+    dyd = torch.zeros((M, 20), device="cuda")[:, :N]
+    dyd.copy_(_dev(dy))
+
+    def fresh():
+        Wd = torch.zeros((K, 20), device="cuda")[:, :N]
+        Wd.copy_(_dev(W))
+        return Wd, _dev(b).clone(), torch.full((M, K), 7.0, device="cuda")
+    ws = ops.linear_bwd_narrow_workspace(M, K, N, "cuda")
+    W3, b3, dx3 = fresh()
+    ops.linear_bwd_narrow(xd, dyd, W3, scale, W3, b3, dx3, workspace=ws)
+    ws.fill_(float("nan"))
+    W12, b12, dx12 = fresh()
+    ops.linear_bwd_narrow(xd, dyd, W12, scale, W12, b12, dx12, workspace=ws, parts=1)
+    assert torch.equal(dx12, dx3) and torch.equal(W12, _dev(W)) and torch.equal(b12, _dev(b))
+    ops.linear_bwd_narrow(xd, dyd, W12, scale, W12, b12, dx12, workspace=ws, parts=2)
+    assert torch.equal(W12, W3) and torch.equal(b12, b3) and torch.equal(dx12, dx3)
+    want_dx = (dy.astype(np.float64) @ W.T.astype(np.float64)) * (x > 0)
+    np.testing.assert_allclose(dx3.cpu().numpy(), want_dx, rtol=0, atol=2e-6 * np.sqrt(N) * (np.abs(want_dx).max() + 1))
+    gW = x.T.astype(np.float64) @ dy.astype(np.float64)
+    np.testing.assert_allclose(W3.cpu().numpy(), W + scale * gW, rtol=0, atol=abs(scale) * 4e-6 * np.sqrt(M) * (np.abs(gW).max() + 1) + 1e-7)
+    with pytest.raises(RuntimeError, match="DR_EINVAL"):
+        ops.linear_bwd_narrow(xd, dyd, W12, scale, W12, b12, dx12, workspace=ws, parts=4)
+
+
+def test_tower_head_in_two_halves(ops):
+    """parts = 1 then parts = 2 of dr_tower_head_fwd_bwd against one call (parts = 3, checked against torch at this shape by
+    test_tower_head_fused): the same two launches, so the same bits; part 1 alone leaves prob, d_logit and d_h complete and w2, b2 and the
+    loss untouched.  M = 513: full row tiles and a ragged one; H = 17, K = 100: ragged in both."""
+    rng = np.random.default_rng(41)
+    M, K, H, mode, scale = 513, 100, 17, 2, -0.05
+    xd = torch.zeros((M, K), device="cuda")
+    xd.copy_(_dev(np.maximum(rng.standard_normal((M, K)), 0).astype(np.float32)))
+    W1 = _dev((rng.standard_normal((K, H)) / np.sqrt(K)).astype(np.float32))
+    b1 = _dev((rng.standard_normal(H) * 0.1).astype(np.float32))
+    w2 = _dev((rng.standard_normal((H, 1)) / np.sqrt(H)).astype(np.float32))
+    b2 = _dev(np.array([0.05], np.float32))
+    extra, z = _dev(rng.standard_normal(M).astype(np.float32)), _dev((rng.random(M) < 0.3).astype(np.float32))
+
+    def run(parts_seq):
+        w2d = torch.zeros((H, 4), device="cuda")[:, :1]
+        w2d.copy_(w2)
+        o = dict(w2=w2d, b2=b2.clone(), loss=torch.full((1,), 7.0, device="cuda"), prob=torch.full((M,), 7.0, device="cuda"),
+                 d_logit=torch.full((M,), 7.0, device="cuda"), d_h=torch.full((M, 20), 7.0, device="cuda")[:, :H],
+                 ws=ops.tower_head_workspace(M, "cuda"))
+        o["ws"].fill_(float("nan"))
+        snaps = []
+        for parts in parts_seq:
+            ops.tower_head_fwd_bwd(xd, W1, b1, o["w2"], o["b2"], extra, z, mode, scale, prob=o["prob"], d_logit=o["d_logit"], d_h=o["d_h"],
+                                   loss=o["loss"], workspace=o["ws"], parts=parts)
+            snaps.append({k: o[k].clone() for k in ("w2", "b2", "loss", "prob", "d_logit", "d_h")})
+        return snaps
+    whole, = run([3])
+    first, second = run([1, 2])
+    for k in ("prob", "d_logit", "d_h"):
+        assert torch.equal(first[k], whole[k]) and torch.equal(second[k], whole[k]), k
+    assert torch.equal(first["w2"], w2) and torch.equal(first["b2"], b2) and first["loss"].item() == 7.0
+    for k in ("w2", "b2", "loss"):
+        assert torch.equal(second[k], whole[k]), k
+    assert not torch.equal(whole["w2"], w2) and whole["loss"].item() != 7.0
+    with pytest.raises(RuntimeError, match="DR_EINVAL"):
+        run([0])
+
+
 @pytest.mark.parametrize("M,K,H,mode", [(128, 256, 32, 0), (4096, 128, 32, 1), (2048 + 32, 256, 17, 2), (65536, 256, 32, 0)])
 def test_tower_tail_fused_one_pass(ops, M, K, H, mode):
     """dr_tower_tail_fused == dr_tower_head_fwd_bwd (relu) followed by dr_linear_bwd_narrow (relu mask) of the same layer, and both
@@ -517,7 +591,7 @@ def test_shard_bucket_ids_bit_exact(ops, world):
 
 @pytest.mark.parametrize("V,path", [(50_000, "claim"), (300, "radix")])
 def test_shard_dedup_bucketing_and_pack(ops, V, path):
-    """Requester-side de-duplication (dr_shard_dedup_slots / dr_shard_bucket_ids_dedup / dr_emb_pack_grads_dedup): the lowest slot of
+    """Requester-side de-duplication (dr_shard_dedup_slots / dr_shard_bucket_ids with rep / dr_emb_pack_grads with unique_flags): the lowest slot of
     every row is its representative (bit-exact against NumPy), only representatives get a send slot, every slot's position points at
     its row's place, and the pack sums the gradients of the slots that share a row.  V = 300: nearly every slot shares its row (the
     plan's radix path, every slot in the sorted arrays); V = 50 000: mostly unique rows (the claim path: only the shared-row slots)."""

@@ -347,7 +347,7 @@ def test_engine_next_batch_prefetch_is_bit_identical(optimizer, D, V):
 @pytest.mark.parametrize("switch,value", [("DR_REDUCE_SIDE", "1"), ("DR_REDUCE_SIDE", "2"), ("DR_PREFETCH_EARLY", "0"), ("DR_PREFETCH_EARLY", "1")])
 def test_engine_schedule_switches_are_bit_identical(switch, value, monkeypatch):
     """Round 4's measured-and-rejected schedules stay correct: the step's small reduce kernels on the side stream
-    (dr_tower_head_fwd_bwd_parts / dr_linear_bwd_narrow_parts / dr_bf3_wgrad_emb_parts: the two halves of each call on two streams),
+    (parts of dr_tower_head_fwd_bwd / dr_linear_bwd_narrow / dr_bf3_wgrad_emb: the two halves of each call on two streams),
     and the next batch's hash + plan issued at the start of the step (round 5's default) or beside K4 (rounds 2-4) instead of behind the
     fused first layer (round 6).  Same kernels, same arithmetic order: parameters and losses
     must be bit-identical to the default schedule over prefetched steps (D = 64: fused first layer, gathering wgrad, planes)."""

@@ -1,6 +1,6 @@
 """The register-split wgrad (csrc/bf3_wgrad.hip) bit for bit: all four instantiations of bf3_gemm_tn_rs_kernel and the reduce.
 
-Entry points: dr_h2_wgrad_emb and dr_bf3_wgrad_emb(_parts) (x gathered from the tables), dr_h2_wgrad and dr_bf3_wgrad (x read from a
+Entry points: dr_h2_wgrad_emb and dr_bf3_wgrad_emb (x gathered from the tables), dr_h2_wgrad and dr_bf3_wgrad (x read from a
 buffer).  What the shapes reach: R = 32 * 33 + 5 = 1024 + 37 = 1061 rows give split = 3 slices of 384, 384 and 293 rows -- a last
 slice shorter than the others whose last k-tile holds 5 rows; nf = 3 fields + 13 dense features (F = 205) is one f-tile, whose blocks
 store the column sums; nf = 5 + 13 (F = 333) adds a second f-tile that does not, with waves whose columns lie past F (and, in the
@@ -144,7 +144,7 @@ def _check_workspace(c, ws, factor, with_b, what):
 @pytest.mark.parametrize("R", R_CASES)
 @pytest.mark.parametrize("mode", ["h2", "bf3"])
 def test_wgrad_emb_parts_and_whole(mode, R, nf, N, ld, with_b):
-    """dr_h2_wgrad_emb / dr_bf3_wgrad_emb(_parts): part 1 leaves the exact partial sums (and column sums) in a NaN-poisoned
+    """dr_h2_wgrad_emb / dr_bf3_wgrad_emb: part 1 leaves the exact partial sums (and column sums) in a NaN-poisoned
     workspace, part 2 applies them; one call (parts = 3) gives the same bits"""
     from deep_recommenders_amd import ops
     c = case(R, nf, N)
