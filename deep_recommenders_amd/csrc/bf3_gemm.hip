@@ -974,7 +974,7 @@ extern "C" int dr_h2_linear_nt_pack(const float* dy, int64_t ld_dy, const uint32
 
 // internal (C++ linkage, used by retrieval.hip): the top-K scan's scores = a @ B^T on the register-split kernel -- a [M, K] fp32
 // queries, B = a corpus chunk as planes [3][N rows][b_ld] -- filtered against tau into per-row candidate lists (the epilogue of
-// dense.hip's dr_scores_nt_filter on this file's tile: 256 x 256, weights through the LDS ring, activations split in registers)
+// dense_scores.hip's dr_scores_nt_filter on this file's tile: 256 x 256, weights through the LDS ring, activations split in registers)
 int dr_bf3_scores_filter(const float* a, int64_t lda, const void* b_planes, int64_t b_plane_stride, int64_t b_ld, int64_t M, int32_t N,
                          int32_t K, const float* tau, float* cand_s, int32_t* cand_c, int32_t* cand_cnt, int64_t cand_cap,
                          dr_stream_t stream) {
@@ -987,7 +987,7 @@ int dr_bf3_scores_filter(const float* a, int64_t lda, const void* b_planes, int6
     return rs_launch(g, dr_s(stream));
 }
 
-// internal (C++ linkage, used by dense.hip's dr_inbatch_softmax_*): the in-batch softmax's two score passes on the register-split
+// internal (C++ linkage, used by dense_scores.hip's dr_inbatch_softmax_*): the in-batch softmax's two score passes on the register-split
 // f16x2 kernel.  q [B, D] fp32 with its record, c as two fp16 planes [2][B][c_ld] with its record.
 int dr_h2_inbatch_lse(const float* q, int64_t ldq, const uint32_t* q_amax, const void* c_planes, int64_t c_ps, int64_t c_ld,
                       const uint32_t* c_amax, int64_t B, int32_t D, const float* cand_prob, const int64_t* cand_ids, float inv_t,

@@ -1,9 +1,9 @@
 // Shared by the bf3_*.hip translation units (bf3_planes, bf3_gemm, bf3_emb_linear, bf3_wgrad): the operand format, the LDS images and
 // the device code more than one of those kernel families uses, each thing once.
 //
-// The "planes" form of the bf16x3 product mode (dense.hip):
+// The "planes" form of the bf16x3 product mode (gemm_f32_core.h):
 //
-// dense.hip's bf16x3 kernel splits every fp32 operand value into three bf16 terms on its way into LDS: per k-tile 24
+// gemm_f32_core.h's bf16x3 kernel splits every fp32 operand value into three bf16 terms on its way into LDS: per k-tile 24
 // v_cvt_pk + 48 exact subtractions + 24 ds_write_b64 per thread sit between the global loads and the 48 MFMAs, and the
 // kernel reaches 0.33-0.38 of the bf16 pipe's fp32-equivalent ceiling (2.5 PFLOP/s / 6).  Here the PRODUCERS of the
 // operands write the three planes once (K3 writes the pooled embeddings as planes, the tower-tail backward writes its

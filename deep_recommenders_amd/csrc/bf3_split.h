@@ -6,7 +6,7 @@
 // |x2| <= 2^-16 |x|, and x2 is the exact remainder (24 - 16 = 8 significant bits left): (x2 + x1) + x0 == x bit for bit,
 // so the planes REPLACE the fp32 matrix (bf3_join below), they are not an approximation of it.
 // A GEMM forms a * b as a0b2 + a1b1 + a2b0 + a0b1 + a1b0 + a0b0 on the bf16 matrix pipe (fp32 accumulate); the dropped
-// cross terms are below 2^-24 |ab| (dense.hip has the derivation and the accuracy tests).
+// cross terms are below 2^-24 |ab| (gemm_f32_core.h has the derivation, tests/test_bf16x3_model.py the accuracy model).
 // Out of range: +-inf or a value whose bf16 rounding overflows gives inf - inf = NaN in x1.
 #pragma once
 #include <hip/hip_runtime.h>

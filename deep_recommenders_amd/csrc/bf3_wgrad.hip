@@ -11,7 +11,7 @@
 //           its own, tn_img_swizzle: the 8 consecutive rows of a store's lane group must be spread too); the 8 waves' pieces
 //           make the tile that all of them read.  Two LDS stages: step g's MFMAs read stage g while stage g + 1 is
 //           written from registers loaded during step g - 1.
-// The in-kernel-split wgrad of dense.hip re-stages BOTH operands through the LDS per 128 x 128 tile; here x never touches
+// The in-kernel-split wgrad of dense.hip (the kernel template of gemm_f32_core.h) re-stages BOTH operands through the LDS per 128 x 128 tile; here x never touches
 // it and each dy element is split once per 256 rows of x.
 // Partials go to a padded workspace [split][tiles_f * 256][tiles_n * 256] (+ [split][tiles_n * 256] column sums): every store of
 // the epilogue is unconditional; a fixed-order reduce applies them (deterministic).

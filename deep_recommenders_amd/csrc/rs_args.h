@@ -73,7 +73,7 @@ int occ_nt_launch(const RsArgs& g, hipStream_t stream);
 }  // namespace drrs
 
 // ---- internal cross-file entry points ---------------------------------------------------------------------------------------
-// dense.hip: scores = a @ b^T for two reduction-contiguous fp32 operands, filtered against tau into per-row candidate lists
+// dense_scores.hip: scores = a @ b^T for two reduction-contiguous fp32 operands, filtered against tau into per-row candidate lists
 int dr_scores_nt_filter(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t M, int32_t N, int32_t D,
                         const float* tau, float* cand_s, int32_t* cand_c, int32_t* cand_cnt, int64_t cand_cap,
                         dr_stream_t stream);
@@ -84,7 +84,7 @@ int dr_bf3_scores_filter(const float* a, int64_t lda, const void* b_planes, int6
 int dr_h2_scores_filter(const float* a, int64_t lda, const uint32_t* a_amax, const void* b_planes, int64_t b_plane_stride, int64_t b_ld,
                         const uint32_t* b_amax, int64_t M, int32_t N, int32_t K, const float* tau, float* cand_s, int32_t* cand_c,
                         int32_t* cand_cnt, int64_t cand_cap, dr_stream_t stream);
-// bf3_gemm.hip: the in-batch softmax's two score passes on the register-split f16x2 kernel; dense.hip's dr_inbatch_softmax_*
+// bf3_gemm.hip: the in-batch softmax's two score passes on the register-split f16x2 kernel; dense_scores.hip's dr_inbatch_softmax_*
 int dr_h2_inbatch_lse(const float* q, int64_t ldq, const uint32_t* q_amax, const void* c_planes, int64_t c_ps, int64_t c_ld,
                       const uint32_t* c_amax, int64_t B, int32_t D, const float* cand_prob, const int64_t* cand_ids, float inv_t,
                       float* part_m, float* part_l, float* pos, dr_stream_t stream);

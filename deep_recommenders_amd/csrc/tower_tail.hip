@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void linear_bwd_narrow_reduce_kernel(const flo
 //       K / 4 columns: lane (row m, half h) reads 16 KT consecutive floats of row m as the A operand of 16 KT
 //       v_mfma_f32_32x32x2_f32, W1's rows sit in registers as the B operand -- and the four partial [32, 32] tiles are summed
 //       through the LDS by wave 0;
-//   (2) wave 0 runs the head epilogue of dense.hip (bias, ReLU, Dense(1) as a 32-lane butterfly, + extra logit, BCE terms,
+//   (2) wave 0 runs the head epilogue of gemm_f32_core.h (bias, ReLU, Dense(1) as a 32-lane butterfly, + extra logit, BCE terms,
 //       d logit, d h = d logit (x) w2 * ReLU') and leaves d h in the LDS where the narrow backward expects its dy chunk;
 //   (3) all four waves run the narrow backward of the kernel above on the x values they still hold in registers.
 // x is read once, d x written once; prob / d_logit / (optionally) d_h go out as before; the Dense(1) gradient, its bias gradient
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(64 * NWV, (DR_TAIL_DBG & 1) ? 4 : 2) void tower_tai
             for (int reg = 0; reg < 16; ++reg) red[wave][tt_row(reg, h) * TT_P + c] = acc1[reg];
         }
         tail_lds_barrier();
-        // ---- (2) head epilogue (dense.hip EPI_HEAD) of the rows of accumulator registers RPW wave .. + RPW - 1; d h -> dys ------------
+        // ---- (2) head epilogue (gemm_f32_core.h EPI_HEAD) of the rows of accumulator registers RPW wave .. + RPW - 1; d h -> dys ------------
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
             const int reg = wave * RPW + rr;                  // (wave-uniform)
@@ -425,7 +425,7 @@ __global__ __launch_bounds__(64 * NWV, (DR_TAIL_DBG & 1) ? 4 : 2) void tower_tai
 }
 
 // Both fixed-order reduces of the one-pass tail in ONE launch: blocks 0 .. K apply the narrow layer's partials (as
-// linear_bwd_narrow_reduce_kernel), block K + 1 the head's (as head_finish_kernel of dense.hip: dst_w2 / dst_b2 / loss).
+// linear_bwd_narrow_reduce_kernel), block K + 1 the head's (as head_finish_kernel of dense_head.hip: dst_w2 / dst_b2 / loss).
 __global__ __launch_bounds__(256) void tower_tail_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ head_partial,
                                                                 int32_t nparts, int32_t K, int32_t N, float scale, float inv_n,
                                                                 float* __restrict__ dstW, int64_t ldw, float* __restrict__ dstb,

@@ -11,7 +11,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TT_ROWS = 32;     // rows per chunk (one MFMA tile)
 constexpr int TT_P = 33;        // LDS pitch of the dy chunk
-constexpr int TAIL_HEAD_PART = 34;          // == HEAD_PART of dense.hip: dw2[32], db2, loss
+constexpr int TAIL_HEAD_PART = 34;          // == HEAD_PART of gemm_f32_core.h: dw2[32], db2, loss
 
 // s_barrier behind the wave's own LDS traffic only.  __syncthreads() also waits vmcnt(0): with it every barrier of the tail's loop would
 // sit out the NEXT chunk's prefetch (and this chunk's dx stores) -- three times per chunk.  The hazards the barriers order are all
@@ -35,7 +35,7 @@ __device__ __forceinline__ int tt_row(int j, int h) { return (j & 3) + 8 * (j >>
         ACC1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v.w, W1F[4 * q + 3], ACC1, 0, 0, 0);             \
     }
 
-// Head epilogue of ONE row (dense.hip EPI_HEAD), lane c = hidden unit: V comes in as the row's pre-activation sum (the slices' partial
+// Head epilogue of ONE row (gemm_f32_core.h EPI_HEAD), lane c = hidden unit: V comes in as the row's pre-activation sum (the slices' partial
 // products added in slice order) and leaves as the activation; Dense(1) as a 32-lane butterfly, + the extra logit EXT, the BCE terms
 // against the label LAB (BCE = false: a timing experiment of tower_tail.hip), GS = d logit / n, DH = d h1.  A row that is not LIVE
 // contributes no loss and no gradient.  Declares P, L, GS, DH (and dot, lg, gr) in the caller's scope.

@@ -1,4 +1,4 @@
-"""CPU model of the bf16x3 product mode of the GEMMs (deep_recommenders_amd/csrc/dense.hip: put4_bf3 + the six-product MFMA
+"""CPU model of the bf16x3 product mode of the GEMMs (deep_recommenders_amd/csrc/gemm_f32_core.h: put4_bf3 + the six-product MFMA
 sequence), in numpy: the properties DESIGN.md section 6 relies on, checked without a GPU.  The GPU parity test proper is
 tests/test_gpu_kernels.py::test_gemm_bf16x3_matches_fp64_as_well_as_native."""
 import numpy as np

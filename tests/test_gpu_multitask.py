@@ -43,6 +43,7 @@ def _close(got, want, what):
 
 GROUPED_SHAPES = [(G, M, K, N) for G in (1, 2, 3, 8) for M in (1, 1000, 4096) for K in (10, 32, 256) for N in (1, 10, 32, 64)
                   if not (M == 4096 and G == 8 and K == 256)]
+GROUPED_SHAPES.append((2, 130, 3, 1))                   # skinny (K < 4, N < 4) kernels, two row slabs per group
 
 
 @pytest.mark.parametrize("G,M,K,N", GROUPED_SHAPES)
@@ -73,6 +74,10 @@ def test_grouped_linear_matches_float64(gemm_mode, G, M, K, N):
     gW2 = torch.zeros(G, K, N, device="cuda")
     gb2 = torch.zeros(G, N, device="cuda")
     ops.linear_bwd_dw_grouped(xd, ldx, K, dyd, ldy, N, M, K, N, G, 1.0, gW2, N, K * N, gb2, N, workspace=ws)
+    # without a workspace: the atomic form of the weight gradient (any summation order)
+    gW3 = torch.zeros(G, K, N, device="cuda")
+    gb3 = torch.zeros(G, N, device="cuda")
+    ops.linear_bwd_dw_grouped(xd, ldx, K, dyd, ldy, N, M, K, N, G, 1.0, gW3, N, K * N, gb3, N)
     torch.cuda.synchronize()
     assert torch.equal(y, y2) and torch.equal(dx, dx2) and torch.equal(gW, gW2) and torch.equal(gb, gb2)
     assert torch.all(y[:, G * N:] == 7.0), "wrote past the groups"
@@ -84,6 +89,8 @@ def test_grouped_linear_matches_float64(gemm_mode, G, M, K, N):
         _close(dx[:, z * K:(z + 1) * K], (dyz @ Wz.T) * (relu_src[:, z * K:(z + 1) * K] > 0).double(), "dx g%d" % z)
         _close(gW[z], xz.T @ dyz, "dW g%d" % z)
         _close(gb[z], dyz.sum(0), "db g%d" % z)
+        _close(gW3[z], xz.T @ dyz, "dW (no workspace) g%d" % z)
+        _close(gb3[z], dyz.sum(0), "db (no workspace) g%d" % z)
 
 
 @pytest.mark.parametrize("G,M,K,N", [(2, 1000, 32, 64), (3, 4096, 256, 32), (8, 1000, 10, 10), (2, 4096, 64, 128)])
