@@ -6,3 +6,5 @@ from deep_recommenders_amd.keras.models.ranking.xdeepfm import CINNetwork
 from deep_recommenders_amd.keras.models.ranking.xdeepfm import XDeepFM
 from deep_recommenders_amd.keras.models.ranking.dlrm import DotInteraction
 from deep_recommenders_amd.keras.models.ranking.dlrm import DLRM
+from deep_recommenders_amd.keras.models.ranking.afm import AttentionalPooling
+from deep_recommenders_amd.keras.models.ranking.afm import AFM

@@ -927,3 +927,39 @@ def dot_interaction(dense, emb, self_interaction=False):
         raise ValueError("dot_interaction: emb must be [B, F, D], or [B, F * D] next to a dense [B, D]; got emb %s, dense %s"
                          % (tuple(emb.shape), None if dense is None else tuple(dense.shape)))
     return _DotInteractFn.apply(dense, emb, F, D, bool(self_interaction))
+
+
+# ---- AFM: attention pooling over field pairs (csrc/afm_pool.hip) -----------------------------------------------------------------------
+class _AfmPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, emb, W, b, h, F, want_attention):
+        out, lse, attn = ops.afm_pool_fwd(emb, W, b, h, F, want_attention)
+        ctx.F = F
+        ctx.emb_shape = emb.shape
+        ctx.save_for_backward(emb, W, b, h, out, lse)
+        if attn is None:
+            return out, None
+        ctx.mark_non_differentiable(attn)
+        return out, attn
+
+    @staticmethod
+    def backward(ctx, d_out, _d_attn):
+        emb, W, b, h, out, lse = ctx.saved_tensors
+        if d_out.dim() != 2 or (d_out.shape[0] > 1 and (d_out.stride(1) != 1 or d_out.stride(0) % 4 != 0 or d_out.stride(0) < d_out.shape[1])):
+            d_out = d_out.contiguous()                         # layout only: D is a multiple of 4
+        d_emb, dW, db, dh = ops.afm_pool_bwd(emb, W, b, h, ctx.F, out, lse, d_out)
+        return d_emb.reshape(ctx.emb_shape), dW, db, dh, None, None
+
+
+def afm_pooling(emb, W, b, h, want_attention=False, F=None):
+    """(out [B, D], attn [B, P] | None): AFM's attention pooling of the pair products e_i * e_j (j < i, P = F (F - 1) / 2 pairs in
+    DotInteraction's order): z = p W + b, s = relu(z) h, attn = softmax over the pairs, out = sum_q attn_q p_q.  emb: [B, F, D]
+    contiguous, or a [B, F * D] matrix (a column-strided view of the slab's concat is read in place) together with F; W [D, A], b [A],
+    h [A].  One kernel each way, no [B, P, .] tensor; attn carries no gradient."""
+    if emb.dim() == 3:
+        if F is not None and int(F) != emb.shape[1]:
+            raise ValueError("afm_pooling: F = %d does not match emb %s" % (int(F), tuple(emb.shape)))
+        F = int(emb.shape[1])
+    elif emb.dim() != 2 or F is None:
+        raise ValueError("afm_pooling: emb must be [B, F, D], or [B, F * D] together with F; got emb %s, F %s" % (tuple(emb.shape), F))
+    return _AfmPoolFn.apply(emb, W, b, h, int(F), bool(want_attention))

@@ -1606,6 +1606,116 @@ def dot_interact_bwd(dense, emb, F, D, d_out, self_interaction=False, d_dense=No
     return (d_dense if dense is not None else None), d_emb
 
 
+# ---- AFM: attention pooling over field pairs (csrc/afm_pool.hip) -----------------------------------------------------------------------
+def afm_num_pairs(F):
+    """P = F (F - 1) / 2: the pairs (i, j), j < i, numbered q = i (i - 1) / 2 + j"""
+    return int(F) * (int(F) - 1) // 2
+
+
+def _afm_rows(t, cols, what):
+    """row stride of a [B, cols] fp32 matrix with unit column stride; ValueError unless it is a multiple of 4 and >= cols"""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError("afm_pool: %s must be fp32 [B, %d], got %s %s" % (what, cols, t.dtype, tuple(t.shape)))
+    ok = t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= cols
+    if not ok and t.shape[0] <= 1 and t.stride(1) == 1:
+        return _pad4(cols)                                     # a single row has no pitch to speak of
+    if not ok:
+        raise ValueError("afm_pool: %s needs unit column stride and a row stride that is a multiple of 4 and >= %d, got strides %s"
+                         % (what, cols, tuple(t.stride())))
+    return t.stride(0)
+
+
+def _afm_dims(emb, W, b, h, F):
+    """validates the domain of dr_afm_pool_* (include/dr_hotpath.h) without a device; returns (emb as [B, F * D], B, F, D, A, P)"""
+    F = int(F)
+    if W.dim() != 2 or b.dim() != 1 or h.dim() != 1 or b.shape[0] != W.shape[1] or h.shape[0] != W.shape[1]:
+        raise ValueError("afm_pool: W [D, A], b [A], h [A] expected, got %s, %s, %s" % (tuple(W.shape), tuple(b.shape), tuple(h.shape)))
+    if any(t.dtype != torch.float32 for t in (emb, W, b, h)):
+        raise ValueError("afm_pool: fp32 tensors only")
+    D, A = int(W.shape[0]), int(W.shape[1])
+    if D % 4 != 0 or not 4 <= D <= 256:
+        raise ValueError("afm_pool: D must be a multiple of 4 in [4, 256], got %d" % D)
+    if not 1 <= A <= 128:
+        raise ValueError("afm_pool: the attention factor A must be in [1, 128], got %d" % A)
+    if not 2 <= F <= 64:
+        raise ValueError("afm_pool: needs 2 <= F <= 64 fields, got %d" % F)
+    pow2 = lambda n: 1 << (n - 1).bit_length()                                                 # noqa: E731
+    DT, AT, P = pow2((D + 15) // 16), pow2((A + 15) // 16), F * (F - 1) // 2
+    if DT * AT > 32:
+        raise ValueError("afm_pool: D = %d with A = %d is outside the kernels' register budget (ceil(D / 16) * ceil(A / 16), each rounded "
+                         "up to a power of two, must not exceed 32)" % (D, A))
+    PE, PW = 16 * DT + 4, 16 * AT + 4
+    if 16 * DT * PW + 32 * AT + (P + 15) // 16 * 16 + 2 * F * PE + 16 * DT + 16 * PW + 16 * PE > 40000:
+        raise ValueError("afm_pool: F = %d, D = %d, A = %d do not fit the LDS" % (F, D, A))
+    if emb.dim() == 3:
+        if tuple(emb.shape[1:]) != (F, D) or not emb.is_contiguous():
+            raise ValueError("afm_pool: a 3-d emb must be contiguous [B, %d, %d], got %s" % (F, D, tuple(emb.shape)))
+        emb = emb.reshape(emb.shape[0], F * D)
+    elif emb.dim() != 2 or emb.shape[1] != F * D:
+        raise ValueError("afm_pool: emb must be [B, %d, %d] or [B, %d], got %s" % (F, D, F * D, tuple(emb.shape)))
+    return emb, int(emb.shape[0]), F, D, A, P
+
+
+def _afm_status(st, what):
+    if st in (_lib.DR_EINVAL, _lib.DR_ESHAPE):
+        raise ValueError("%s: %s (outside the kernel's domain, or a base address that is not 16-byte aligned)" % (what, _lib._ERR[st]))
+    check(st, what)
+
+
+def afm_pool_fwd(emb, W, b, h, F, want_attention=False, out=None):
+    """(out [B, D], lse [B], attn [B, P] | None) of dr_afm_pool_fwd.  emb: [B, F, D] contiguous, or [B, F * D] with any row stride that
+    is a multiple of 4 (the slab's concat, read in place); W [D, A], b [A], h [A].  out: a [B, D] view to write into."""
+    emb, B, F, D, A, P = _afm_dims(emb, W, b, h, F)
+    ld_emb = _afm_rows(emb, F * D, "emb")
+    if out is None:
+        out = torch.empty((B, D), dtype=torch.float32, device=emb.device)
+    ld_out = _afm_rows(out, D, "out")
+    lse = torch.empty((B,), dtype=torch.float32, device=emb.device)
+    attn = torch.empty((B, P), dtype=torch.float32, device=emb.device) if want_attention else None
+    if B == 0:
+        return out, lse, attn
+    W, b, h = W.contiguous(), b.contiguous(), h.contiguous()
+    st = lib().dr_afm_pool_fwd(ptr(emb), ld_emb, ptr(W), ptr(b), ptr(h), B, F, D, A, ptr(out), ld_out, ptr(lse), ptr(attn), P,
+                               stream_ptr())
+    _afm_status(st, "dr_afm_pool_fwd")
+    return out, lse, attn
+
+
+def afm_pool_bwd(emb, W, b, h, F, out, lse, d_out, d_emb=None, workspace=None):
+    """(d_emb [B, F * D], dW [D, A], db [A], dh [A]) of dr_afm_pool_bwd from d_out [B, D], with out and lse of afm_pool_fwd.  d_emb: a
+    [B, F * D] buffer to overwrite; workspace: fp32, at least dr_afm_pool_bwd_workspace_bytes(B, F, D, A) bytes (allocated when None)."""
+    emb, B, F, D, A, P = _afm_dims(emb, W, b, h, F)
+    ld_emb = _afm_rows(emb, F * D, "emb")
+    ld_out = _afm_rows(out, D, "out")
+    ld_dout = _afm_rows(d_out, D, "d_out")
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (B,) or not lse.is_contiguous():
+        raise ValueError("afm_pool: lse must be contiguous fp32 [%d], got %s %s" % (B, lse.dtype, tuple(lse.shape)))
+    if out.shape[0] != B or d_out.shape[0] != B:
+        raise ValueError("afm_pool: emb, out and d_out disagree on the batch size")
+    if d_emb is None:
+        d_emb = torch.empty((B, F * D), dtype=torch.float32, device=emb.device)
+    ld_demb = _afm_rows(d_emb, F * D, "d_emb")
+    dW = torch.empty((D, A), dtype=torch.float32, device=emb.device)
+    db = torch.empty((A,), dtype=torch.float32, device=emb.device)
+    dh = torch.empty((A,), dtype=torch.float32, device=emb.device)
+    if B == 0:
+        return d_emb, dW.zero_(), db.zero_(), dh.zero_()
+    need = lib().dr_afm_pool_bwd_workspace_bytes(B, F, D, A)
+    if need < 0:
+        _afm_status(int(need), "dr_afm_pool_bwd_workspace_bytes")
+    if workspace is None:
+        workspace = torch.empty((max(need // 4, 4),), dtype=torch.float32, device=emb.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise ValueError("afm_pool: the workspace holds %d bytes, dr_afm_pool_bwd_workspace_bytes asks for %d"
+                         % (workspace.numel() * workspace.element_size(), need))
+    W, b, h = W.contiguous(), b.contiguous(), h.contiguous()
+    st = lib().dr_afm_pool_bwd(ptr(emb), ld_emb, ptr(W), ptr(b), ptr(h), ptr(out), ld_out, ptr(lse), ptr(d_out), ld_dout, B, F, D, A,
+                               ptr(d_emb), ld_demb, ptr(dW), ptr(db), ptr(dh), ptr(workspace),
+                               workspace.numel() * workspace.element_size(), stream_ptr())
+    _afm_status(st, "dr_afm_pool_bwd")
+    return d_emb, dW, db, dh
+
+
 def din_concat_fwd(x, y, mode):
     x, y = _c(x, torch.float32), _c(y, torch.float32)
     B, D = x.shape

@@ -857,6 +857,42 @@ int dr_dot_interact_bwd(const float* dense, int64_t ld_dense, const float* emb, 
                         int64_t ld_demb, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * AFM's attention pooling over field pairs (Xiao et al., IJCAI 2017; the reference's README lists AFM among its ranking models and
+ * ships no code for it), csrc/afm_pool.hip.  All fp32.  emb[b] holds the F rows e_0 .. e_{F-1} of example b ([F * D], field-major: the
+ * slab's concat, read in place at the pitch ld_emb); W [D, A], b [A], h [A] dense.  Pairs are numbered q = i (i - 1) / 2 + j for
+ * 0 <= j < i < F (the order of dr_dot_interact_fwd without the diagonal), P = F (F - 1) / 2.
+ *   dr_afm_pool_fwd   p_q = e_i * e_j [D];  z_q = p_q W + b [A];  s_q = sum_a max(z_qa, 0) h_a;  a = softmax over q of s;
+ *                     out[b, 0:D] = sum_q a_q p_q;  lse[b] = log sum_q exp(s_q);  attn[b, q] = a_q when attn != NULL (ld_attn >= P).
+ *                     One launch; a wave owns an example, the softmax is online over tiles of 16 pairs; p, z and s are never written
+ *                     (s passes through attn when that is given).  Writes D columns of out and P of attn, nothing else.
+ *   dr_afm_pool_bwd   from g = d_out [B, D], with out and lse of the forward (z is recomputed):
+ *                       ds_q = a_q (<g, p_q> - <g, out>);  dz_q = ds_q h * [z_q > 0]  (the derivative of max(z, 0) at 0 is 0)
+ *                       dh = sum_b sum_q ds_q max(z_q, 0);  db = sum_b sum_q dz_q;  dW = sum_b sum_q p_q^T dz_q
+ *                       dp_q = a_q g + dz_q W^T;  d_emb[b, i] = sum_{j != i} dp_(ij) * e_j     (F * D columns of d_emb are overwritten)
+ *                     dW [D, A], db [A], dh [A] are overwritten.  Two launches: the main kernel and the sum of its per-block partials.
+ *                     workspace: 16-byte aligned, at least dr_afm_pool_bwd_workspace_bytes(B, F, D, A) bytes
+ *                       = 4 * blocks * (D * A + 2 * A),  blocks = min(ceil(B / waves), 512)
+ *                     [one partial of dW, db and dh per block, added in block order], with `waves` as below.  It does not grow with
+ *                     B * P.  dr_afm_pool_bwd_workspace_bytes returns DR_EINVAL / DR_ESHAPE (negative) outside the domain.
+ *   The three products (z, dz W^T, p^T dz) run on the fp32-input MFMA; every sum has one owner and a fixed order: no float atomics in
+ *   memory or LDS, results bit-identical from run to run, and out, lse, attn and d_emb of an example do not depend on its batch.
+ *   Domain: D % 4 == 0, 4 <= D <= 256, 1 <= A <= 128, 2 <= F <= 64, ld_emb, ld_demb >= F * D, ld_out, ld_dout >= D, all four multiples of
+ *   4, emb, out, d_out, d_emb and the workspace 16-byte aligned; anything else, a NULL required pointer or a short workspace is DR_EINVAL.
+ *   NARROWER THAN D <= 256 AND A <= 128 TOGETHER: with DT = ceil(D / 16) and AT = ceil(A / 16), each rounded up to a power of two,
+ *     DT * AT <= 32    (a wave keeps dW in 4 DT AT accumulator registers per lane; D 256 goes with A <= 32, D 128 with A <= 64,
+ *                       D <= 64 with A <= 128), and
+ *     16 DT (16 AT + 4) + 32 AT + 16 ceil(P / 16) + waves * (2 F (16 DT + 4) + 16 DT + 16 (16 AT + 4) + 16 (16 DT + 4)) <= 40000
+ *                      floats of LDS for waves = 4, else 2, else 1 (the first that fits is the block's number of waves),
+ *   else DR_ESHAPE, from all three entry points alike.  B == 0 is DR_OK and launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+int dr_afm_pool_fwd(const float* emb, int64_t ld_emb, const float* W, const float* b, const float* h, int64_t B, int32_t F, int32_t D,
+                    int32_t A, float* out, int64_t ld_out, float* lse, float* attn, int64_t ld_attn, dr_stream_t stream);
+int64_t dr_afm_pool_bwd_workspace_bytes(int64_t B, int32_t F, int32_t D, int32_t A);
+int dr_afm_pool_bwd(const float* emb, int64_t ld_emb, const float* W, const float* b, const float* h, const float* out, int64_t ld_out,
+                    const float* lse, const float* d_out, int64_t ld_dout, int64_t B, int32_t F, int32_t D, int32_t A, float* d_emb,
+                    int64_t ld_demb, float* dW, float* db, float* dh, void* ws, int64_t ws_bytes, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * DIN ActivationUnit input (keras/models/ranking/din.py:59-67): out[b, :] = concat(x[b], y[b], interacter(x, y)[b])
  * mode 0: no interacter (2 D columns), 1: x - y (keras Subtract, the reference test's interacter), 2: x * y (Multiply).
  * The two Dense layers that follow (:69-70) are dr_linear_fwd / dr_linear_bwd_*.
