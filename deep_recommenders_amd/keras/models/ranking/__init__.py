@@ -8,3 +8,8 @@ from deep_recommenders_amd.keras.models.ranking.dlrm import DotInteraction
 from deep_recommenders_amd.keras.models.ranking.dlrm import DLRM
 from deep_recommenders_amd.keras.models.ranking.afm import AttentionalPooling
 from deep_recommenders_amd.keras.models.ranking.afm import AFM
+from deep_recommenders_amd.keras.models.ranking.dien import GRU
+from deep_recommenders_amd.keras.models.ranking.dien import AUGRU
+from deep_recommenders_amd.keras.models.ranking.dien import InterestExtractor
+from deep_recommenders_amd.keras.models.ranking.dien import InterestEvolution
+from deep_recommenders_amd.keras.models.ranking.dien import DIEN

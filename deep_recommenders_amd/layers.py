@@ -963,3 +963,49 @@ def afm_pooling(emb, W, b, h, want_attention=False, F=None):
     elif emb.dim() != 2 or F is None:
         raise ValueError("afm_pooling: emb must be [B, F, D], or [B, F * D] together with F; got emb %s, F %s" % (tuple(emb.shape), F))
     return _AfmPoolFn.apply(emb, W, b, h, int(F), bool(want_attention))
+
+
+# ---- DIEN: the GRU / AUGRU recurrence and the evolution layer's attention (csrc/dien.hip) -------------------------------------------------
+class _GruSeqFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xp, U, h0, lengths, att):
+        hs, h_last = ops.gru_seq_fwd(xp, U, h0, lengths, att)
+        ctx.lengths = lengths
+        ctx.save_for_backward(xp, U, h0, att, hs)
+        return hs, h_last
+
+    @staticmethod
+    def backward(ctx, d_hs, d_h_last):
+        xp, U, h0, att, hs = ctx.saved_tensors
+        d_xp, dU, d_h0, d_att = ops.gru_seq_bwd(xp, U, h0, ctx.lengths, att, hs, d_hs, d_h_last)
+        return d_xp, dU, (d_h0 if h0 is not None else None), None, d_att
+
+
+def gru_sequence(xp, U, h0=None, lengths=None, att=None):
+    """(hs [B, T, H], h_last [B, H]): the GRU recurrence over the input-side pre-activations xp [B, T, 3H] = x W + b (gate columns
+    [u | r | c], the paper's form: h_t = (1 - u) h_{t-1} + u c with c = tanh(xp_c + r * (h_{t-1} U_c))), U [H, 3H], h0 [B, H] (None:
+    zeros).  lengths [B]: steps t >= lengths[b] carry the state, give hs[b, t] = 0 and read neither xp nor att there.  att [B, T]
+    turns it into DIEN's AUGRU (the update gate is scaled by att[b, t]) and receives a gradient.  One kernel forward (the time loop
+    runs on chip); the backward recomputes the gates and keeps nothing per step but hs."""
+    return _GruSeqFn.apply(xp, U, h0, lengths, att)
+
+
+class _SeqAttnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hs, q, lengths):
+        a = ops.seq_attn_fwd(hs, q, lengths)
+        ctx.lengths = lengths
+        ctx.save_for_backward(hs, q, a)
+        return a
+
+    @staticmethod
+    def backward(ctx, d_a):
+        hs, q, a = ctx.saved_tensors
+        d_hs, d_q = ops.seq_attn_bwd(hs, q, ctx.lengths, a, d_a)
+        return d_hs, d_q, None
+
+
+def sequence_attention(hs, q, lengths=None):
+    """a [B, T]: the softmax over the valid steps t < lengths[b] of <hs[b, t], q[b]>, 0 at masked steps (a row of zeros when
+    lengths[b] == 0)."""
+    return _SeqAttnFn.apply(hs, q, lengths)

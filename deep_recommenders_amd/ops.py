@@ -1716,6 +1716,179 @@ def afm_pool_bwd(emb, W, b, h, F, out, lse, d_out, d_emb=None, workspace=None):
     return d_emb, dW, db, dh
 
 
+# ---- DIEN: the GRU / AUGRU recurrence and the evolution layer's attention (csrc/dien.hip) -------------------------------------------------
+def _gru_seq3(t, B, T, width, what, may_copy=True):
+    """(tensor, ld) of a [B, T, width] fp32 tensor whose rows (b, t) lie at the uniform pitch ld (a multiple of 4, >= width) from a
+    16-byte aligned base -- what dr_gru_seq_* address.  Any other layout (a [:, :-1] view, a pitch that is no multiple of 4) is copied
+    when may_copy, else a ValueError; a misaligned base is always a ValueError."""
+    if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape) != (B, T, width):
+        raise ValueError("gru_seq: %s must be fp32 [%d, %d, %d], got %s %s" % (what, B, T, width, t.dtype, tuple(t.shape)))
+    if B * T <= 1:
+        ld, ok = _pad4(width), t.stride(2) == 1 or width == 1
+    elif T == 1:
+        ld, ok = t.stride(0), t.stride(2) == 1
+    else:
+        ld, ok = t.stride(1), t.stride(2) == 1 and (B == 1 or t.stride(0) == T * t.stride(1))
+    ok = ok and ld % 4 == 0 and ld >= width
+    if not ok:
+        if not may_copy:
+            raise ValueError("gru_seq: %s needs unit column stride and rows (b, t) at one pitch that is a multiple of 4 and >= %d, got "
+                             "strides %s" % (what, width, tuple(t.stride())))
+        t, ld = t.contiguous(), width
+    if t.numel() and t.data_ptr() % 16 != 0:
+        raise ValueError("gru_seq: %s must start at a 16-byte aligned address" % what)
+    return t, ld
+
+
+def _gru_dense(t, shape, what, dtype=torch.float32, aligned=False):
+    if t is None:
+        return None
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError("gru_seq: %s must be %s %s, got %s %s" % (what, dtype, list(shape), t.dtype, tuple(t.shape)))
+    t = t.contiguous()
+    if aligned and t.numel() and t.data_ptr() % 16 != 0:
+        raise ValueError("gru_seq: %s must start at a 16-byte aligned address" % what)
+    return t
+
+
+def _gru_lengths(lengths, B):
+    """int32 [B]; values outside [0, T] are clamped by the kernels (no host check: it would wait for the device)"""
+    if lengths is None:
+        return None
+    if lengths.dim() != 1 or lengths.shape[0] != B or lengths.dtype not in (torch.int32, torch.int64):
+        raise ValueError("gru_seq: lengths must be int32 or int64 [%d], got %s %s" % (B, lengths.dtype, tuple(lengths.shape)))
+    return lengths.to(torch.int32).contiguous()
+
+
+def _gru_dims(xp, U):
+    """validates the domain of dr_gru_seq_* (include/dr_hotpath.h) without a device; returns (B, T, H)"""
+    if U.dim() != 2 or U.dtype != torch.float32 or U.shape[1] != 3 * U.shape[0]:
+        raise ValueError("gru_seq: U must be fp32 [H, 3H], got %s %s" % (U.dtype, tuple(U.shape)))
+    H = int(U.shape[0])
+    if H % 4 != 0 or not 4 <= H <= 128:
+        raise ValueError("gru_seq: H must be a multiple of 4 in [4, 128], got %d" % H)
+    if xp.dim() != 3 or xp.shape[2] != 3 * H:
+        raise ValueError("gru_seq: xp must be [B, T, %d], got %s" % (3 * H, tuple(xp.shape)))
+    B, T = int(xp.shape[0]), int(xp.shape[1])
+    if T < 1:
+        raise ValueError("gru_seq: needs T >= 1 time steps, got %d" % T)
+    return B, T, H
+
+
+def _gru_status(st, what):
+    if st in (_lib.DR_EINVAL, _lib.DR_ESHAPE):
+        raise ValueError("%s: %s (outside the kernel's domain, or a base address that is not 16-byte aligned)" % (what, _lib._ERR[st]))
+    check(st, what)
+
+
+def gru_seq_fwd(xp, U, h0=None, lengths=None, att=None, hs=None):
+    """(hs [B, T, H], h_last [B, H]) of dr_gru_seq_fwd: the GRU (att None) or AUGRU recurrence over xp [B, T, 3H] = x W + b with gate
+    columns [u | r | c], U [H, 3H], h0 [B, H] (None: zeros), lengths [B] (None: all T; clamped to [0, T]), att [B, T].  hs: a
+    [B, T, H] buffer to write into (rows at one pitch)."""
+    B, T, H = _gru_dims(xp, U)
+    xp, ld_xp = _gru_seq3(xp, B, T, 3 * H, "xp")
+    U = _gru_dense(U, (H, 3 * H), "U")
+    h0 = _gru_dense(h0, (B, H), "h0", aligned=True)
+    att = _gru_dense(att, (B, T), "att")
+    lengths = _gru_lengths(lengths, B)
+    if hs is None:
+        hs = torch.empty((B, T, H), dtype=torch.float32, device=xp.device)
+    hs, ld_hs = _gru_seq3(hs, B, T, H, "hs", may_copy=False)
+    h_last = torch.empty((B, H), dtype=torch.float32, device=xp.device)
+    if B == 0:
+        return hs, h_last
+    st = lib().dr_gru_seq_fwd(ptr(xp), ld_xp, ptr(U), ptr(h0), ptr(lengths), ptr(att), B, T, H, ptr(hs), ld_hs, ptr(h_last), stream_ptr())
+    _gru_status(st, "dr_gru_seq_fwd")
+    return hs, h_last
+
+
+def gru_seq_bwd_workspace(B, T, H, device):
+    need = lib().dr_gru_seq_bwd_workspace_bytes(int(B), int(T), int(H))
+    if need < 0:
+        _gru_status(int(need), "dr_gru_seq_bwd_workspace_bytes")
+    return torch.empty((max(need // 4, 4),), dtype=torch.float32, device=device)
+
+
+def gru_seq_bwd(xp, U, h0, lengths, att, hs, d_hs=None, d_h_last=None, d_xp=None, workspace=None):
+    """(d_xp [B, T, 3H], dU [H, 3H], d_h0 [B, H], d_att [B, T] | None) of dr_gru_seq_bwd from d_hs [B, T, H] and d_h_last [B, H] (None:
+    zeros), with the forward's inputs and its hs.  d_xp: a [B, T, 3H] buffer to overwrite; workspace: fp32, at least
+    dr_gru_seq_bwd_workspace_bytes(B, T, H) bytes (allocated when None)."""
+    B, T, H = _gru_dims(xp, U)
+    xp, ld_xp = _gru_seq3(xp, B, T, 3 * H, "xp")
+    U = _gru_dense(U, (H, 3 * H), "U")
+    h0 = _gru_dense(h0, (B, H), "h0", aligned=True)
+    att = _gru_dense(att, (B, T), "att")
+    lengths = _gru_lengths(lengths, B)
+    hs, ld_hs = _gru_seq3(hs, B, T, H, "hs")
+    ld_dhs = H
+    if d_hs is not None:
+        d_hs, ld_dhs = _gru_seq3(d_hs, B, T, H, "d_hs")
+    d_h_last = _gru_dense(d_h_last, (B, H), "d_h_last")
+    dev = xp.device
+    if d_xp is None:
+        d_xp = torch.empty((B, T, 3 * H), dtype=torch.float32, device=dev)
+    d_xp, ld_dxp = _gru_seq3(d_xp, B, T, 3 * H, "d_xp", may_copy=False)
+    dU = torch.empty((H, 3 * H), dtype=torch.float32, device=dev)
+    d_h0 = torch.empty((B, H), dtype=torch.float32, device=dev)
+    d_att = torch.empty((B, T), dtype=torch.float32, device=dev) if att is not None else None
+    if B == 0:
+        return d_xp, dU.zero_(), d_h0, d_att
+    need = lib().dr_gru_seq_bwd_workspace_bytes(B, T, H)
+    if need < 0:
+        _gru_status(int(need), "dr_gru_seq_bwd_workspace_bytes")
+    if workspace is None:
+        workspace = torch.empty((max(need // 4, 4),), dtype=torch.float32, device=dev)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise ValueError("gru_seq: the workspace holds %d bytes, dr_gru_seq_bwd_workspace_bytes asks for %d"
+                         % (workspace.numel() * workspace.element_size(), need))
+    st = lib().dr_gru_seq_bwd(ptr(xp), ld_xp, ptr(U), ptr(h0), ptr(lengths), ptr(att), ptr(hs), ld_hs, B, T, H, ptr(d_hs), ld_dhs,
+                              ptr(d_h_last), ptr(d_xp), ld_dxp, ptr(dU), ptr(d_h0), ptr(d_att), ptr(workspace),
+                              workspace.numel() * workspace.element_size(), stream_ptr())
+    _gru_status(st, "dr_gru_seq_bwd")
+    return d_xp, dU, d_h0, d_att
+
+
+def _seq_attn_dims(hs, q):
+    if hs.dim() != 3 or q.dim() != 2 or q.dtype != torch.float32 or q.shape[0] != hs.shape[0] or q.shape[1] != hs.shape[2]:
+        raise ValueError("seq_attn: hs [B, T, H] and q [B, H] fp32 expected, got %s and %s" % (tuple(hs.shape), tuple(q.shape)))
+    B, T, H = (int(s) for s in hs.shape)
+    if H % 4 != 0 or not 4 <= H <= 128:
+        raise ValueError("seq_attn: H must be a multiple of 4 in [4, 128], got %d" % H)
+    if T < 1:
+        raise ValueError("seq_attn: needs T >= 1 time steps, got %d" % T)
+    return B, T, H
+
+
+def seq_attn_fwd(hs, q, lengths=None):
+    """a [B, T] of dr_seq_attn_fwd: the softmax over t < lengths[b] of <hs[b, t], q[b]>, 0 at masked steps (hs is not read there)."""
+    B, T, H = _seq_attn_dims(hs, q)
+    hs, ld_hs = _gru_seq3(hs, B, T, H, "hs")
+    q = _gru_dense(q, (B, H), "q", aligned=True)
+    lengths = _gru_lengths(lengths, B)
+    a = torch.empty((B, T), dtype=torch.float32, device=hs.device)
+    if B == 0:
+        return a
+    _gru_status(lib().dr_seq_attn_fwd(ptr(hs), ld_hs, ptr(q), ptr(lengths), B, T, H, ptr(a), stream_ptr()), "dr_seq_attn_fwd")
+    return a
+
+
+def seq_attn_bwd(hs, q, lengths, a, d_a):
+    """(d_hs [B, T, H], d_q [B, H]) of dr_seq_attn_bwd from d_a [B, T], with the forward's a."""
+    B, T, H = _seq_attn_dims(hs, q)
+    hs, ld_hs = _gru_seq3(hs, B, T, H, "hs")
+    q = _gru_dense(q, (B, H), "q", aligned=True)
+    lengths = _gru_lengths(lengths, B)
+    a = _gru_dense(a, (B, T), "a")
+    d_a = _gru_dense(d_a, (B, T), "d_a")
+    d_hs = torch.empty((B, T, H), dtype=torch.float32, device=hs.device)
+    d_q = torch.empty((B, H), dtype=torch.float32, device=hs.device)
+    if B == 0:
+        return d_hs, d_q
+    _gru_status(lib().dr_seq_attn_bwd(ptr(hs), ld_hs, ptr(q), ptr(lengths), ptr(a), ptr(d_a), B, T, H, ptr(d_hs), H, ptr(d_q),
+                                      stream_ptr()), "dr_seq_attn_bwd")
+    return d_hs, d_q
+
+
 def din_concat_fwd(x, y, mode):
     x, y = _c(x, torch.float32), _c(y, torch.float32)
     B, D = x.shape

@@ -893,6 +893,56 @@ int dr_afm_pool_bwd(const float* emb, int64_t ld_emb, const float* W, const floa
                     int64_t ld_demb, float* dW, float* db, float* dh, void* ws, int64_t ws_bytes, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DIEN's recurrences (Zhou et al., AAAI 2019; the reference's README lists DIEN after DIN and ships no code for it), csrc/dien.hip.
+ * All fp32.  xp [B, T, 3H] holds the input-side pre-activations x_t W + b (the dense path's product over all B * T rows), gate columns
+ * [u | r | c]; row (b, t) starts at xp + (b * T + t) * ld_xp, and hs, d_hs, d_xp are addressed the same way with their own ld.
+ * U [H, 3H], h0 / h_last / d_h_last / d_h0 [B, H], att / d_att / a / d_a [B, T] and q / d_q [B, H] are dense.  lengths [B] int32,
+ * 0 <= len <= T (values outside are clamped); NULL = all T.  h0 NULL = zeros.  att NULL = a plain GRU, else AUGRU.
+ *   dr_gru_seq_fwd    for t < len[b]:  g = h_{t-1} U;  u = sigmoid(xp_u + g_u);  r = sigmoid(xp_r + g_r);  c = tanh(xp_c + r * g_c);
+ *                       u' = att[b, t] u  (u' = u without att);  h_t = (1 - u') h_{t-1} + u' c;  hs[b, t] = h_t
+ *                     for t >= len[b]: h_t = h_{t-1}, hs[b, t] = 0, and xp[b, t], att[b, t] are not read (NaN there reaches nothing).
+ *                     h_last[b] = h_{len - 1} (h0, or zeros, when len == 0).  Keras's / PyTorch's update gate is z = 1 - u.
+ *                     One launch: a block owns 16 examples and runs the time loop; its waves hold their column slices of U in
+ *                     registers for all T steps, h crosses between waves through a 16 x H LDS tile with one barrier per step.
+ *   dr_gru_seq_bwd    from d_hs [B, T, H] and d_h_last [B, H] (either may be NULL = zeros; d_hs at masked steps is ignored), with the
+ *                     forward's hs; t runs downward and g, u, r, c are recomputed:
+ *                       dh += d_hs[b, t];  dc = dh u';  du' = dh (c - h_{t-1});  dh_prev = dh (1 - u');  d_att[b, t] = sum_j du'_j u_j
+ *                       du = att du';  dpc = dc (1 - c^2);  dpu = du u (1 - u);  dpr = dpc g_c r (1 - r)
+ *                       d_xp[b, t] = [dpu | dpr | dpc];  dg = [dpu | dpr | dpc r];  dh_prev += dg U^T;  dU += h_{t-1}^T dg
+ *                     d_xp (3H columns per row), dU [H, 3H], d_h0 and d_att are overwritten; d_h0 and d_att may be NULL.  d_xp and
+ *                     d_att are exactly 0 at masked steps; for len == 0, d_h0[b] = d_h_last[b].
+ *                     workspace: 16-byte aligned, at least dr_gru_seq_bwd_workspace_bytes(B, T, H) bytes
+ *                       = 4 * B * (T + 1) * 3H  +  max(dr_linear_bwd_dw_workspace_bytes(B * T, H, 3H),
+ *                                                      dr_linear_bwd_dw_workspace_bytes(B, H, 3H)) rounded up to 16
+ *                     [dg of every step: the rows t = 0 first, then the rows t >= 1 shifted by one with a zero last row, so that row
+ *                     (b, s) pairs with hs[b, s]; dU is then dr_linear_bwd_dw(hs, dg) plus dr_linear_bwd_dw(h0, dg rows 0) with that
+ *                     call's deterministic reduce, in the GEMM mode of dr_set_gemm_mode].  0 for B == 0; DR_EINVAL / DR_ESHAPE
+ *                     (negative) outside the domain.
+ *   dr_seq_attn_fwd   a[b, t] = softmax over t < len[b] of <hs[b, t], q[b]>; 0 for t >= len[b] (a whole row of zeros when len == 0);
+ *                     masked rows of hs are not read.  One wave per example.
+ *   dr_seq_attn_bwd   ds_t = a_t (d_a_t - sum_t' a_t' d_a_t');  d_hs[b, t] = ds_t q[b] (H columns per row, 0 at masked steps);
+ *                     d_q[b] = sum_t ds_t hs[b, t].  Both overwritten.  No workspace.
+ *   The recurrent products run on the fp32-input MFMA (v_mfma_f32_16x16x4_f32); every sum has one owner and a fixed order: no float
+ *   atomics in memory or LDS, results bit-identical from run to run, and hs, h_last, d_xp, d_h0, d_att, a, d_hs, d_q of an example do
+ *   not depend on its batch.  Nothing of size B * T * 3H is written except d_xp and dg.
+ *   Domain (all five alike): H % 4 == 0, 4 <= H <= 128, T >= 1, B >= 0, B * T <= 2^40; every ld a multiple of 4 and at least the width
+ *   it covers (3H for xp and d_xp, H for hs and d_hs); xp, hs, d_hs, d_xp, h0, q and the workspace 16-byte aligned (the other
+ *   arrays need only their 4 bytes).  H > 128 or B * T > 2^40 is DR_ESHAPE; anything else, a NULL required pointer or a short workspace is
+ *   DR_EINVAL.  B == 0 is DR_OK and launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+int dr_gru_seq_fwd(const float* xp, int64_t ld_xp, const float* U, const float* h0, const int32_t* lengths, const float* att, int64_t B,
+                   int32_t T, int32_t H, float* hs, int64_t ld_hs, float* h_last, dr_stream_t stream);
+int64_t dr_gru_seq_bwd_workspace_bytes(int64_t B, int32_t T, int32_t H);
+int dr_gru_seq_bwd(const float* xp, int64_t ld_xp, const float* U, const float* h0, const int32_t* lengths, const float* att,
+                   const float* hs, int64_t ld_hs, int64_t B, int32_t T, int32_t H, const float* d_hs, int64_t ld_dhs,
+                   const float* d_h_last, float* d_xp, int64_t ld_dxp, float* dU, float* d_h0, float* d_att, void* ws, int64_t ws_bytes,
+                   dr_stream_t stream);
+int dr_seq_attn_fwd(const float* hs, int64_t ld_hs, const float* q, const int32_t* lengths, int64_t B, int32_t T, int32_t H, float* a,
+                    dr_stream_t stream);
+int dr_seq_attn_bwd(const float* hs, int64_t ld_hs, const float* q, const int32_t* lengths, const float* a, const float* d_a, int64_t B,
+                    int32_t T, int32_t H, float* d_hs, int64_t ld_dhs, float* d_q, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * DIN ActivationUnit input (keras/models/ranking/din.py:59-67): out[b, :] = concat(x[b], y[b], interacter(x, y)[b])
  * mode 0: no interacter (2 D columns), 1: x - y (keras Subtract, the reference test's interacter), 2: x * y (Multiply).
  * The two Dense layers that follow (:69-70) are dr_linear_fwd / dr_linear_bwd_*.
