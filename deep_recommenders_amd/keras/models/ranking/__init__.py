@@ -8,6 +8,8 @@ from deep_recommenders_amd.keras.models.ranking.dlrm import DotInteraction
 from deep_recommenders_amd.keras.models.ranking.dlrm import DLRM
 from deep_recommenders_amd.keras.models.ranking.afm import AttentionalPooling
 from deep_recommenders_amd.keras.models.ranking.afm import AFM
+from deep_recommenders_amd.keras.models.ranking.ffm import FieldAwareInteraction
+from deep_recommenders_amd.keras.models.ranking.ffm import FFM
 from deep_recommenders_amd.keras.models.ranking.dien import GRU
 from deep_recommenders_amd.keras.models.ranking.dien import AUGRU
 from deep_recommenders_amd.keras.models.ranking.dien import InterestExtractor

@@ -1009,3 +1009,72 @@ def sequence_attention(hs, q, lengths=None):
     """a [B, T]: the softmax over the valid steps t < lengths[b] of <hs[b, t], q[b]>, 0 at masked steps (a row of zeros when
     lengths[b] == 0)."""
     return _SeqAttnFn.apply(hs, q, lengths)
+
+
+# ---- FFM: the field-aware interaction (csrc/ffm.hip) -------------------------------------------------------------------------------------
+class _FfmFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, F, k):
+        ctx.F, ctx.k = F, k
+        ctx.rows_shape = rows.shape
+        ctx.save_for_backward(rows)
+        return ops.ffm_fwd(rows, F, k)
+
+    @staticmethod
+    def backward(ctx, d_inter):
+        rows, = ctx.saved_tensors
+        d_rows = ops.ffm_bwd(rows, ctx.F, ctx.k, d_inter.contiguous())
+        return d_rows.reshape(ctx.rows_shape), None, None
+
+
+def ffm_interaction(rows, F, k):
+    """inter [B]: FFM's sum over the pairs of fields j < i of <A[i, j, :], A[j, i, :]>, A [F, F, k] being the example's F gathered rows of
+    F k-vectors each (block j of row i = field i's factor towards field j).  rows: [B, F, F, k] or [B, F, F * k] contiguous, or a
+    [B, F * F * k] matrix (a column-strided view of the slab's concat is read in place).  One kernel each way; the diagonal blocks are
+    never read and get a gradient of exactly 0."""
+    return _FfmFn.apply(rows, int(F), int(k))
+
+
+class _FfmGatherFn(torch.autograd.Function):
+    """dr_ffm_gather_fwd forward; dr_ffm_gather_bwd then K4 backward.  `sparse_lr` as in _EmbPoolFn: None produces dense gradient
+    buffers, a value applies the fused SGD update in place to the slab."""
+
+    @staticmethod
+    def forward(ctx, table, lin_w, lin_bias, ids, row_base, F, k, sparse_lr):
+        inter, first = ops.ffm_gather_fwd(ids, row_base, table, F, k, lin_w, lin_bias)
+        ctx.F, ctx.k, ctx.sparse_lr = F, k, sparse_lr
+        ctx.has_bias = lin_bias is not None and lin_w is not None
+        ctx.bias_data = lin_bias.data if ctx.has_bias else None
+        ctx.save_for_backward(table, lin_w, ids, row_base)
+        return inter, first
+
+    @staticmethod
+    def backward(ctx, d_inter, d_first):
+        table, lin_w, ids, row_base = ctx.saved_tensors
+        F, k = ctx.F, ctx.k
+        if lin_w is None:
+            d_first = None
+        if d_inter is None and d_first is None:
+            return (None,) * 8
+        d_rows = ops.ffm_gather_bwd(ids, row_base, table, F, k, d_inter.contiguous()) if d_inter is not None else None
+        if d_first is not None:
+            d_first = d_first.contiguous()
+        has_bias = ctx.has_bias and d_first is not None
+        col_start = torch.arange(F + 1, dtype=torch.int32, device=ids.device)
+        if ctx.sparse_lr is None:
+            g_table = torch.zeros_like(table)
+            g_lin = torch.zeros_like(lin_w) if lin_w is not None else None
+            g_bias = torch.zeros(1, dtype=torch.float32, device=table.device) if has_bias else None
+            ops.emb_pool_bwd(ids, F, col_start, row_base, F * k, d_rows, None, None, d_first, 1.0, g_table, g_lin, g_bias)
+            return g_table, g_lin, g_bias, None, None, None, None, None
+        ops.emb_pool_bwd(ids, F, col_start, row_base, F * k, d_rows, None, None, d_first, -float(ctx.sparse_lr), table.data,
+                         lin_w.data if lin_w is not None else None, ctx.bias_data if has_bias else None)
+        return (None,) * 8
+
+
+def ffm_gather(table, lin_w, lin_bias, ids, row_base, F, k, sparse_lr=None):
+    """(inter [B], first_order [B] | None) for single-valued fields, ids [B, F]: FFM's interaction computed straight from the table rows
+    table[row_base[f] + ids[b, f]] ([R, F * k]; an id < 0 is a row of zeros) without writing them, and lin_bias + sum_f lin_w[row] when
+    lin_w is given.  The backward writes d_rows once (dr_ffm_gather_bwd) and hands it to K4, which owns duplicate rows, the first-order
+    gradient and, with `sparse_lr`, the fused SGD step."""
+    return _FfmGatherFn.apply(table, lin_w, lin_bias, ids, row_base, int(F), int(k), sparse_lr)

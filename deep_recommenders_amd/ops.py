@@ -2469,3 +2469,125 @@ def din_pool_bwd(query, keys, mask, W, b, w_out, b_out, mode, act, d_out, d_scor
                                 ptr(d_query), D, ptr(d_keys), D, ptr(dW), ptr(db), ptr(d_w_out), ptr(d_b_out), ptr(dalpha), ptr(ws),
                                 ws.numel() * 4, stream_ptr()), "dr_din_pool_bwd")
     return d_query, d_keys, dW, db, d_w_out, d_b_out, dalpha
+
+
+# ---- FFM: the field-aware interaction (csrc/ffm.hip) -------------------------------------------------------------------------------------
+def _ffm_dims(F, k):
+    """validates the domain of dr_ffm_*; returns (F, k) as ints"""
+    F, k = int(F), int(k)
+    if k % 4 != 0 or not 4 <= k <= 128:
+        raise ValueError("ffm: the latent size k must be a multiple of 4 in [4, 128], got %d" % k)
+    if not 2 <= F <= 64:
+        raise ValueError("ffm: needs 2 <= F <= 64 fields, got F = %d" % F)
+    if F * k > 256:
+        raise ValueError("ffm: a table row holds one k-vector per field and F * k <= 256 is the slab's limit, got F = %d, k = %d, "
+                         "F * k = %d" % (F, k, F * k))
+    return F, k
+
+
+def ffm_row_width(F, k):
+    """F * k: the width of an FFM table row (one k-vector towards every field); an example's gathered rows are F of them"""
+    F, k = _ffm_dims(F, k)
+    return F * k
+
+
+def _ffm_rows(t, F, k, what):
+    """(t as [B, F * F * k], its row stride) of a fp32 matrix of gathered rows with unit column stride; ValueError unless the stride is a
+    multiple of 4 and >= F * F * k.  [B, F, F, k] and [B, F, F * k] contiguous are taken as they are."""
+    cols = F * F * k
+    if t.dtype != torch.float32:
+        raise ValueError("ffm: %s must be fp32, got %s" % (what, t.dtype))
+    if t.dim() in (3, 4):
+        if tuple(t.shape[1:]) not in ((F, F, k), (F, F * k)) or not t.is_contiguous():
+            raise ValueError("ffm: a %d-d %s must be contiguous [B, %d, %d, %d] or [B, %d, %d], got %s"
+                             % (t.dim(), what, F, F, k, F, F * k, tuple(t.shape)))
+        t = t.reshape(t.shape[0], cols)
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError("ffm: %s must be [B, %d] (F * F * k columns), got %s" % (what, cols, tuple(t.shape)))
+    if t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= cols:
+        return t, t.stride(0)
+    if t.shape[0] <= 1 and t.stride(1) == 1:
+        return t, cols                                         # a single row has no pitch to speak of
+    raise ValueError("ffm: %s needs unit column stride and a row stride that is a multiple of 4 and >= %d, got strides %s"
+                     % (what, cols, tuple(t.stride())))
+
+
+def _ffm_vec(t, B, what):
+    if t.dtype != torch.float32 or t.numel() != B:
+        raise ValueError("ffm: %s must be fp32 with one value per example (%d), got %s %s" % (what, B, t.dtype, tuple(t.shape)))
+    return t.reshape(B).contiguous()
+
+
+def _ffm_status(st, what):
+    if st == _lib.DR_EINVAL:
+        raise ValueError("%s: DR_EINVAL (outside the kernel's domain, or a base address that is not 16-byte aligned)" % what)
+    check(st, what)
+
+
+def ffm_fwd(rows, F, k):
+    """inter [B] of dr_ffm_fwd: sum over the pairs j < i of <A[i, j, :], A[j, i, :]> with A [F, F, k] the example's gathered rows.  rows:
+    [B, F, F, k] or [B, F, F * k] contiguous, or [B, F * F * k] with any row stride that is a multiple of 4 (the slab's concat, in place)."""
+    F, k = _ffm_dims(F, k)
+    rows, ld = _ffm_rows(rows, F, k, "rows")
+    B = rows.shape[0]
+    inter = torch.empty((B,), dtype=torch.float32, device=rows.device)
+    if B == 0:
+        return inter
+    _ffm_status(lib().dr_ffm_fwd(ptr(rows), ld, B, F, k, ptr(inter), stream_ptr()), "dr_ffm_fwd")
+    return inter
+
+
+def ffm_bwd(rows, F, k, d_inter, d_rows=None):
+    """d_rows [B, F * F * k] of dr_ffm_bwd: d_rows[b, i, j, :] = d_inter[b] * A[b, j, i, :], the diagonal blocks +0.0.  d_rows: a buffer to
+    overwrite (only its first F * F * k columns are written)."""
+    F, k = _ffm_dims(F, k)
+    rows, ld = _ffm_rows(rows, F, k, "rows")
+    B = rows.shape[0]
+    d_inter = _ffm_vec(d_inter, B, "d_inter")
+    if d_rows is None:
+        d_rows = torch.empty((B, F * F * k), dtype=torch.float32, device=rows.device)
+    d_rows, ld_d = _ffm_rows(d_rows, F, k, "d_rows")
+    if B == 0:
+        return d_rows
+    _ffm_status(lib().dr_ffm_bwd(ptr(rows), ld, ptr(d_inter), B, F, k, ptr(d_rows), ld_d, stream_ptr()), "dr_ffm_bwd")
+    return d_rows
+
+
+def _ffm_gather_args(ids, row_base, table, F, k):
+    F, k = _ffm_dims(F, k)
+    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[1] != F:
+        raise ValueError("ffm: ids must be int64 [B, %d] (one id per field), got %s %s" % (F, ids.dtype, tuple(ids.shape)))
+    if row_base.dtype != torch.int64 or row_base.numel() != F:
+        raise ValueError("ffm: row_base must be int64 [%d], got %s %s" % (F, row_base.dtype, tuple(row_base.shape)))
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != F * k or not table.is_contiguous():
+        raise ValueError("ffm: table must be contiguous fp32 [R, %d] (F * k columns), got %s %s" % (F * k, table.dtype, tuple(table.shape)))
+    return F, k, ids.contiguous(), row_base.contiguous()
+
+
+def ffm_gather_fwd(ids, row_base, table, F, k, lin_w=None, lin_bias=None):
+    """(inter [B], first_order [B] | None) of dr_ffm_gather_fwd for single-valued fields: the rows table[row_base[f] + ids[b, f]] are read
+    from the table and written nowhere; an id < 0 is a row of zeros.  first_order = lin_bias + sum_f lin_w[row] when lin_w is given."""
+    F, k, ids, row_base = _ffm_gather_args(ids, row_base, table, F, k)
+    B = ids.shape[0]
+    inter = torch.empty((B,), dtype=torch.float32, device=ids.device)
+    first = torch.empty((B,), dtype=torch.float32, device=ids.device) if lin_w is not None else None
+    if B == 0:
+        return inter, first
+    _ffm_status(lib().dr_ffm_gather_fwd(ptr(ids), B, F, ptr(row_base), ptr(table), k, ptr(lin_w), ptr(lin_bias), ptr(inter), ptr(first),
+                                        stream_ptr()), "dr_ffm_gather_fwd")
+    return inter, first
+
+
+def ffm_gather_bwd(ids, row_base, table, F, k, d_inter, d_rows=None):
+    """d_rows [B, F * F * k] of dr_ffm_gather_bwd, from the table and d_inter: what emb_pool_bwd takes as d_concat with D = F * k."""
+    F, k, ids, row_base = _ffm_gather_args(ids, row_base, table, F, k)
+    B = ids.shape[0]
+    d_inter = _ffm_vec(d_inter, B, "d_inter")
+    if d_rows is None:
+        d_rows = torch.empty((B, F * F * k), dtype=torch.float32, device=ids.device)
+    d_rows, ld_d = _ffm_rows(d_rows, F, k, "d_rows")
+    if B == 0:
+        return d_rows
+    _ffm_status(lib().dr_ffm_gather_bwd(ptr(ids), B, F, ptr(row_base), ptr(table), k, ptr(d_inter), ptr(d_rows), ld_d, stream_ptr()),
+                "dr_ffm_gather_bwd")
+    return d_rows

@@ -943,6 +943,37 @@ int dr_seq_attn_bwd(const float* hs, int64_t ld_hs, const float* q, const int32_
                     int32_t T, int32_t H, float* d_hs, int64_t ld_dhs, float* d_q, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FFM's field-aware interaction (Juan et al., RecSys 2016; the reference's README lists FFM among its ranking models and ships no code
+ * for it), csrc/ffm.hip.  All fp32.  The table row of a feature of field i is F * k wide: block j of it, row[j * k : (j + 1) * k], is
+ * that feature's factor towards field j.  Example b therefore owns A [F, F, k], A[i, j, :] = block j of field i's row.
+ *   inter[b]            = sum_{i = 1 .. F-1} sum_{j < i} sum_c A[i, j, c] * A[j, i, c]
+ *   d_rows[b, i, j, :]  = d_inter[b] * A[j, i, :] for j != i (one fp32 multiply per element, no sum);  d_rows[b, i, i, :] = +0.0
+ *   The diagonal blocks A[i, i, :] take no part and are never read (NaN there reaches nothing).
+ *   dr_ffm_fwd / dr_ffm_bwd          rows [B, F * F * k] at the pitch ld_rows: the slab's concat over columns of dimension F * k, read
+ *                                    in place (multi-valued fields, or a caller that already holds the rows).  d_rows at the pitch ld_d:
+ *                                    F * F * k columns are overwritten, nothing beyond them.
+ *   dr_ffm_gather_fwd / _gather_bwd  single-valued fields, ids [B, F]: row i of example b is table + (row_base[i] + ids[b, i]) * F * k,
+ *                                    read straight from the table and never written anywhere.  An id < 0 is a row of zeros (as K3).
+ *                                    first_order[b] = lin_bias[0] + sum_f lin_w[row_base[f] + ids[b, f]], added in field order (missing
+ *                                    ids skipped), is written when first_order and lin_w are both given; lin_bias NULL counts as 0.
+ *                                    lin_w, lin_bias and first_order may be NULL.  d_rows [B, F * F * k] is what dr_emb_pool_bwd takes
+ *                                    as d_concat (with D = F * k) to update or differentiate the table.
+ *   A group of lanes (a wave from F = 12 up) owns an example and adds its products in an order that depends on (F, k) alone: no atomics,
+ *   no workspace, no LDS; results are bit-identical from run to run and an example's bits depend neither on its batch nor on its place
+ *   in it.  The gather entry points run the same arithmetic in the same order as the rows entry points: on K3's concat of single-valued
+ *   fields inter and d_rows agree bit for bit.  One launch each.
+ *   Domain: k % 4 == 0, 4 <= k <= 128, 2 <= F <= 64, F * k <= 256, ld_rows and ld_d multiples of 4 and >= F * F * k, rows, d_rows and
+ *   table 16-byte aligned; anything else or a NULL required pointer is DR_EINVAL.  B == 0 is DR_OK and launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+int dr_ffm_fwd(const float* rows, int64_t ld_rows, int64_t B, int32_t F, int32_t k, float* inter, dr_stream_t stream);
+int dr_ffm_bwd(const float* rows, int64_t ld_rows, const float* d_inter, int64_t B, int32_t F, int32_t k, float* d_rows, int64_t ld_d,
+               dr_stream_t stream);
+int dr_ffm_gather_fwd(const int64_t* ids, int64_t B, int32_t F, const int64_t* row_base, const float* table, int32_t k,
+                      const float* lin_w, const float* lin_bias, float* inter, float* first_order, dr_stream_t stream);
+int dr_ffm_gather_bwd(const int64_t* ids, int64_t B, int32_t F, const int64_t* row_base, const float* table, int32_t k,
+                      const float* d_inter, float* d_rows, int64_t ld_d, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * DIN ActivationUnit input (keras/models/ranking/din.py:59-67): out[b, :] = concat(x[b], y[b], interacter(x, y)[b])
  * mode 0: no interacter (2 D columns), 1: x - y (keras Subtract, the reference test's interacter), 2: x * y (Multiply).
  * The two Dense layers that follow (:69-70) are dr_linear_fwd / dr_linear_bwd_*.
