@@ -965,6 +965,57 @@ def afm_pooling(emb, W, b, h, want_attention=False, F=None):
     return _AfmPoolFn.apply(emb, W, b, h, int(F), bool(want_attention))
 
 
+# ---- PNN: the outer-product layer (csrc/pnn_outer.hip) ------------------------------------------------------------------------------------
+class _PnnOuterFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, emb, W, addend, F):
+        out, u = ops.pnn_outer_fwd(emb, W, F, addend)
+        ctx.F = F
+        ctx.emb_shape = emb.shape
+        ctx.has_addend = addend is not None
+        ctx.save_for_backward(u, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        u, W = ctx.saved_tensors
+        d_emb, dW = ops.pnn_outer_bwd(u, W, ctx.F, d_out)
+        return d_emb.reshape(ctx.emb_shape), dW, (d_out if ctx.has_addend else None), None
+
+
+def pnn_outer(emb, W, addend=None, F=None):
+    """[B, N]: PNN's outer-product layer.  With u = the sum of the F field rows of an example, out[n] = sum_{d,e} u_d u_e W[d * D + e, n]
+    (+ addend[n]): (u (x) u) flattened row-major times W [D * D, N], without the [B, D * D] matrix.  emb: [B, F, D] contiguous, or a
+    [B, F * D] matrix (a column-strided view of the slab's concat is read in place) together with F.  The backward keeps u only; the
+    addend's gradient is the output's."""
+    if emb.dim() == 3:
+        if F is not None and int(F) != emb.shape[1]:
+            raise ValueError("pnn_outer: F = %d does not match emb %s" % (int(F), tuple(emb.shape)))
+        F = int(emb.shape[1])
+    elif emb.dim() != 2 or F is None:
+        raise ValueError("pnn_outer: emb must be [B, F, D], or [B, F * D] together with F; got emb %s, F %s" % (tuple(emb.shape), F))
+    return _PnnOuterFn.apply(emb, W, addend, int(F))
+
+
+class _ActFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, act):
+        y = ops.act_fwd_(x.clone(memory_format=torch.contiguous_format), act)
+        ctx.act = act
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        return ops.act_bwd_(y, dy.clone(memory_format=torch.contiguous_format), ctx.act), None
+
+
+def activation(x, act):
+    """act(x) for a [M, N] matrix that is the sum of several layers' outputs; act: 0 linear, 1 relu, 2 sigmoid, 3 tanh (dr_act_fwd)"""
+    return x if int(act) == 0 else _ActFn.apply(x, int(act))
+
+
 # ---- DIEN: the GRU / AUGRU recurrence and the evolution layer's attention (csrc/dien.hip) -------------------------------------------------
 class _GruSeqFn(torch.autograd.Function):
     @staticmethod

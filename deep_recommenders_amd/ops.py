@@ -1716,6 +1716,124 @@ def afm_pool_bwd(emb, W, b, h, F, out, lse, d_out, d_emb=None, workspace=None):
     return d_emb, dW, db, dh
 
 
+# ---- PNN: the outer-product layer (csrc/pnn_outer.hip) ------------------------------------------------------------------------------------
+def _pnn_dims(emb, W, F):
+    """validates the domain of dr_pnn_outer_* (include/dr_hotpath.h) without a device; returns (emb as [B, F * D], B, F, D, N)"""
+    F = int(F)
+    if not 1 <= F <= 64:
+        raise ValueError("pnn_outer: needs 1 <= F <= 64 fields, got %d" % F)
+    if emb.dtype != torch.float32 or W.dtype != torch.float32:
+        raise ValueError("pnn_outer: fp32 tensors only")
+    if emb.dim() == 3:
+        if emb.shape[1] != F or not emb.is_contiguous():
+            raise ValueError("pnn_outer: a 3-d emb must be contiguous [B, %d, D], got %s" % (F, tuple(emb.shape)))
+        emb = emb.reshape(emb.shape[0], F * emb.shape[2])
+    elif emb.dim() != 2 or emb.shape[1] % F != 0:
+        raise ValueError("pnn_outer: emb must be [B, %d, D] or [B, %d * D], got %s" % (F, F, tuple(emb.shape)))
+    D = int(emb.shape[1]) // F
+    if D % 4 != 0 or not 4 <= D <= 128:
+        raise ValueError("pnn_outer: D must be a multiple of 4 in [4, 128], got %d" % D)
+    if W.dim() != 2 or W.shape[0] != D * D:
+        raise ValueError("pnn_outer: W must be [D * D, N] = [%d, N], got %s" % (D * D, tuple(W.shape)))
+    N = int(W.shape[1])
+    if not 1 <= N <= 4096:
+        raise ValueError("pnn_outer: N must be in [1, 4096], got %d" % N)
+    return emb, int(emb.shape[0]), F, D, N
+
+
+def _pnn_rows(t, rows, cols, what, may_copy):
+    """a [rows, cols] fp32 matrix with unit column stride and a row stride that is a multiple of 4 and >= cols, every row readable up
+    to 4 ceil(cols / 4) floats.  An input in another layout is copied into a padded buffer (as _rowmajor_ld4 does); an output is a
+    ValueError."""
+    if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (rows, cols):
+        raise ValueError("pnn_outer: %s must be fp32 [%d, %d], got %s %s" % (what, rows, cols, t.dtype, tuple(t.shape)))
+    if t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= cols:
+        return t
+    if rows <= 1 and t.stride(1) == 1 and (cols % 4 == 0 or not may_copy):
+        return t                                               # a single row has no pitch to speak of (_pnn_ld)
+    if not may_copy:
+        raise ValueError("pnn_outer: %s needs unit column stride and a row stride that is a multiple of 4 and >= %d, got strides %s"
+                         % (what, cols, tuple(t.stride())))
+    buf = torch.zeros((rows, _pad4(cols)), dtype=torch.float32, device=t.device)
+    buf[:, :cols].copy_(t)
+    return buf[:, :cols]
+
+
+def _pnn_ld(t):
+    return t.stride(0) if t.shape[0] > 1 else _pad4(t.shape[1])
+
+
+def _pnn_status(st, what):
+    if st in (_lib.DR_EINVAL, _lib.DR_ESHAPE):
+        raise ValueError("%s: %s (outside the kernel's domain, or a base address that is not 16-byte aligned)" % (what, _lib._ERR[st]))
+    check(st, what)
+
+
+def pnn_outer_fwd(emb, W, F, addend=None, out=None):
+    """(out [B, N], u [B, D]) of dr_pnn_outer_fwd: u = the sum of the F rows of every example, out = (u (x) u) W + addend.  emb: [B, F, D]
+    contiguous, or [B, F * D] with any row stride that is a multiple of 4 (the slab's concat, read in place); W [D * D, N], row d * D + e
+    for u_d u_e; addend [B, N] or None; out: a [B, N] view to write into."""
+    emb, B, F, D, N = _pnn_dims(emb, W, F)
+    emb = _pnn_rows(emb, B, F * D, "emb", False)
+    if addend is not None:
+        addend = _pnn_rows(addend, B, N, "addend", True)
+    if out is None:
+        out = torch.empty((B, _pad4(N)), dtype=torch.float32, device=emb.device)[:, :N]
+    out = _pnn_rows(out, B, N, "out", False)
+    u = torch.empty((B, D), dtype=torch.float32, device=emb.device)
+    if B == 0:
+        return out, u
+    W = _pnn_rows(W, D * D, N, "W", True)
+    st = lib().dr_pnn_outer_fwd(ptr(emb), _pnn_ld(emb), ptr(W), _pnn_ld(W), ptr(addend), _pnn_ld(addend) if addend is not None else 0,
+                                B, F, D, N, ptr(u), D, ptr(out), _pnn_ld(out), stream_ptr())
+    _pnn_status(st, "dr_pnn_outer_fwd")
+    return out, u
+
+
+def pnn_outer_bwd_workspace(B, F, D, N, device):
+    """an fp32 buffer of dr_pnn_outer_bwd_workspace_bytes(B, F, D, N) bytes; ValueError outside the domain"""
+    need = int(lib().dr_pnn_outer_bwd_workspace_bytes(int(B), int(F), int(D), int(N)))
+    if need < 0:
+        _pnn_status(need, "dr_pnn_outer_bwd_workspace_bytes")
+    return torch.empty((max(need // 4, 4),), dtype=torch.float32, device=device)
+
+
+def pnn_outer_bwd(u, W, F, d_out, d_emb=None, accumulate=False, workspace=None):
+    """(d_emb [B, F * D], dW [D * D, N]) of dr_pnn_outer_bwd from d_out [B, N] and the forward's u [B, D].  d_emb: a [B, F * D] buffer
+    to overwrite, or to add to with accumulate=True (then it is required); workspace: fp32, as pnn_outer_bwd_workspace gives it
+    (allocated when None)."""
+    F = int(F)
+    if not 1 <= F <= 64:
+        raise ValueError("pnn_outer: needs 1 <= F <= 64 fields, got %d" % F)
+    if u.dim() != 2 or u.dtype != torch.float32:
+        raise ValueError("pnn_outer: u must be fp32 [B, D], got %s %s" % (u.dtype, tuple(u.shape)))
+    _, B, _, D, N = _pnn_dims(u, W, 1)
+    if accumulate and d_emb is None:
+        raise ValueError("pnn_outer: accumulate=True needs the d_emb to add to")
+    u = _pnn_rows(u, B, D, "u", True)
+    d_out = _pnn_rows(d_out, B, N, "d_out", True)
+    if d_emb is None:
+        d_emb = torch.empty((B, F * D), dtype=torch.float32, device=u.device)
+    d_emb = _pnn_rows(d_emb, B, F * D, "d_emb", False)
+    dW = torch.empty((D * D, _pad4(N)), dtype=torch.float32, device=u.device)[:, :N]
+    if B == 0:
+        return d_emb, dW.zero_()
+    need = int(lib().dr_pnn_outer_bwd_workspace_bytes(B, F, D, N))
+    if need < 0:
+        _pnn_status(need, "dr_pnn_outer_bwd_workspace_bytes")
+    if workspace is None:
+        workspace = torch.empty((max(need // 4, 4),), dtype=torch.float32, device=u.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise ValueError("pnn_outer: the workspace holds %d bytes, dr_pnn_outer_bwd_workspace_bytes asks for %d"
+                         % (workspace.numel() * workspace.element_size(), need))
+    W = _pnn_rows(W, D * D, N, "W", True)
+    st = lib().dr_pnn_outer_bwd(ptr(u), _pnn_ld(u), ptr(W), _pnn_ld(W), ptr(d_out), _pnn_ld(d_out), B, F, D, N, ptr(d_emb),
+                                _pnn_ld(d_emb), 1 if accumulate else 0, ptr(dW), _pnn_ld(dW), ptr(workspace),
+                                workspace.numel() * workspace.element_size(), stream_ptr())
+    _pnn_status(st, "dr_pnn_outer_bwd")
+    return d_emb, dW
+
+
 # ---- DIEN: the GRU / AUGRU recurrence and the evolution layer's attention (csrc/dien.hip) -------------------------------------------------
 def _gru_seq3(t, B, T, width, what, may_copy=True):
     """(tensor, ld) of a [B, T, width] fp32 tensor whose rows (b, t) lie at the uniform pitch ld (a multiple of 4, >= width) from a

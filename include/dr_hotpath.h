@@ -974,6 +974,40 @@ int dr_ffm_gather_bwd(const int64_t* ids, int64_t B, int32_t F, const int64_t* r
                       const float* d_inter, float* d_rows, int64_t ld_d, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PNN's outer-product layer (Qu et al., ICDM 2016; the reference's README lists PNN among its ranking models and ships no code for
+ * it), csrc/pnn_outer.hip.  All fp32.  emb[b] holds the F rows of example b ([F * D], field-major: the slab's concat, read in place at
+ * the pitch ld_emb); W [D * D, N] row-major at the pitch ld_w, row d * D + e multiplies u_d u_e (the full square, not a triangle).
+ *   dr_pnn_outer_fwd   u[b, d] = sum_i emb[b, i * D + d], i ascending ([B, D] at ld_u; the backward reads it instead of emb);
+ *                      out[b, n] = sum_{d,e} u[b,d] u[b,e] W[d * D + e, n], plus addend[b, n] when addend != NULL.
+ *                      Writes D columns of u and N columns of out, nothing else.  F == 1: u = emb.  Two launches (u, then the GEMM
+ *                      M = B, K = D^2 whose left operand is formed in LDS from the row tile's u, one multiply per lane).
+ *   dr_pnn_outer_bwd   from g = d_out [B, N] (the addend's gradient is g itself and needs no kernel):
+ *                        dW[d * D + e, n] = sum_b u[b,d] u[b,e] g[b,n]                      (N columns of every row are overwritten)
+ *                        S[b,d,e] = sum_n g[b,n] W[d * D + e, n];  du[b,d] = sum_e (S[b,d,e] + S[b,e,d]) u[b,e]
+ *                        d_emb[b, i * D + d] = du[b,d] for every field i; accumulate 1: added to what d_emb holds, 0: overwrites
+ *                      (S + S^T is one product with W[(d,e)] + W[(e,d)], added as the tile is staged).  Three launches.
+ *                      workspace: 16-byte aligned, at least dr_pnn_outer_bwd_workspace_bytes(B, F, D, N) bytes
+ *                        = 4 * parts * D * D * 4 ceil(N / 4),  per = 128 * max(1, ceil(B / 8192)),  parts = max(1, ceil(B / per)) <= 64
+ *                      [dW of each run of `per` examples, added in run order].  It does not grow with B beyond 64 copies of dW.
+ *                      dr_pnn_outer_bwd_workspace_bytes returns DR_EINVAL / DR_ESHAPE (negative) outside the domain.
+ *   All products run on the fp32-input MFMA (v_mfma_f32_32x32x2_f32).  No tensor of B * D^2 or B * N * D elements is written in either
+ *   direction.  Every sum has one owner and a fixed order: no float atomics in memory or LDS, results bit-identical from run to run,
+ *   and u, out and d_emb of an example do not depend on its batch.
+ *   Every row of W, addend and d_out, the last one too, must be readable up to 4 ceil(N / 4) floats (the pitch covers that); what the
+ *   padding holds, NaN included, reaches nothing.
+ *   Domain: D % 4 == 0, 4 <= D <= 128, 1 <= N <= 4096, 1 <= F <= 64, accumulate 0 or 1; every ld a multiple of 4 and at least the width
+ *   it covers (ld_emb, ld_demb >= F * D; ld_u >= D; ld_w, ld_add, ld_out, ld_dout, ld_dw >= N); every pointer 16-byte aligned.
+ *   Anything else, a NULL required pointer (addend may be NULL) or a short workspace is DR_EINVAL.  B > 2^31 is DR_ESHAPE from all
+ *   three entry points alike.  B == 0 is DR_OK and launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+int dr_pnn_outer_fwd(const float* emb, int64_t ld_emb, const float* W, int64_t ld_w, const float* addend, int64_t ld_add, int64_t B,
+                     int32_t F, int32_t D, int32_t N, float* u, int64_t ld_u, float* out, int64_t ld_out, dr_stream_t stream);
+int64_t dr_pnn_outer_bwd_workspace_bytes(int64_t B, int32_t F, int32_t D, int32_t N);
+int dr_pnn_outer_bwd(const float* u, int64_t ld_u, const float* W, int64_t ld_w, const float* d_out, int64_t ld_dout, int64_t B,
+                     int32_t F, int32_t D, int32_t N, float* d_emb, int64_t ld_demb, int32_t accumulate, float* dW, int64_t ld_dw,
+                     void* ws, int64_t ws_bytes, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * DIN ActivationUnit input (keras/models/ranking/din.py:59-67): out[b, :] = concat(x[b], y[b], interacter(x, y)[b])
  * mode 0: no interacter (2 D columns), 1: x - y (keras Subtract, the reference test's interacter), 2: x * y (Multiply).
  * The two Dense layers that follow (:69-70) are dr_linear_fwd / dr_linear_bwd_*.
