@@ -22,6 +22,72 @@ def _pad4(n):
 # --------------------------------------------------------------------------------------------------
 # autograd glue
 # --------------------------------------------------------------------------------------------------
+def _rows(t, pitch4=False, aligned=False, dense=False):
+    """The one place where a Function turns a tensor autograd hands it -- an incoming gradient, or an input that may be a view -- into
+    rows a kernel can address: [..., W] with unit column stride whose rows lie at ONE pitch >= W, so that a kernel handed that pitch as
+    its leading dimension reads every row where it is.  pitch4: the pitch is a multiple of 4 floats; aligned: the base is 16-byte
+    aligned; dense: the pitch is W (the kernel takes no leading dimension).  A tensor that already is all of that is returned as it
+    is, same storage, same data_ptr -- the gradient a loss produces is, so the models' path has no copy.  Dimensions of size 1 impose
+    nothing (torch leaves their strides arbitrary, e.g. 0 after an expand): they are restrided in place, without a copy.  Anything
+    else -- a broadcast gradient with a 0 stride, a transposed one, rows at several pitches -- is copied once into a fresh buffer
+    (padded to a multiple of 4 columns with pitch4).  Layout only: no value changes."""
+    if t is None:
+        return None
+    if t.dtype != torch.float32:
+        raise TypeError("expected an fp32 tensor, got %s" % t.dtype)
+    W = t.shape[-1]
+    ok = W <= 1 or t.stride(-1) == 1
+    pitch, span = None, None
+    for d in range(t.dim() - 2, -1, -1):
+        n = t.shape[d]
+        if n == 1 or not ok:
+            continue
+        if pitch is None:
+            pitch = t.stride(d)
+        elif t.stride(d) != span:
+            ok = False
+        span = t.stride(d) * n
+    if pitch is None:                                         # a single row
+        pitch = _pad4(W) if pitch4 and not dense else W
+    ok = ok and pitch >= W and (not dense or pitch == W) and (not pitch4 or dense or pitch % 4 == 0)
+    if ok and aligned and t.numel() and t.data_ptr() % 16 != 0:
+        ok = False
+    if ok and t.numel() == 0:
+        return t
+    if ok:
+        strides = [1] * t.dim()
+        step = pitch
+        for d in range(t.dim() - 2, -1, -1):
+            strides[d] = step
+            step *= t.shape[d]
+        if tuple(strides) == tuple(t.stride()):
+            return t
+        return t.as_strided(t.shape, strides, t.storage_offset())
+    buf = torch.empty(tuple(t.shape[:-1]) + (_pad4(W) if pitch4 and not dense else W,), dtype=torch.float32, device=t.device)
+    buf = buf[..., :W]
+    buf.copy_(t)
+    return buf
+
+
+def _needed_only(backward):
+    """Every backward here returns None in the slot of an input that needs no gradient (a frozen parameter, a non-tensor argument):
+    what a fused kernel computed for it anyway is dropped here, in one place, instead of travelling on as if it had been asked for."""
+    def masked(ctx, *grads):
+        out = backward(ctx, *grads)
+        out = out if isinstance(out, tuple) else (out,)
+        if len(out) != len(ctx.needs_input_grad):
+            return out                                        # autograd names the mismatch
+        return tuple(g if need else None for g, need in zip(out, ctx.needs_input_grad))
+    masked.__name__, masked.__doc__ = backward.__name__, backward.__doc__
+    return masked
+
+
+def _param_grad(p):
+    """a zeroed gradient buffer for the parameter p: its shape, row-major whatever p's own strides are (a transposed or expanded view
+    of a parameter has strides no kernel writes through; autograd takes a gradient in any layout)"""
+    return torch.zeros(p.shape, dtype=torch.float32, device=p.device)
+
+
 class _EmbPoolFn(torch.autograd.Function):
     """K3 forward / K4 backward.  `sparse_lr` None: dense gradient buffers are produced (small tables,
     any torch optimizer).  `sparse_lr` set: the backward applies the fused SGD update in place to the
@@ -39,23 +105,21 @@ class _EmbPoolFn(torch.autograd.Function):
         return concat, fm, sum_x
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_concat, d_fm, _d_sum_x):
         table, lin_w, ids, col_start, row_base, concat, sum_x = ctx.saved_tensors
         F, D = ctx.F, table.shape[1]
         if col_start is None:
             col_start = torch.arange(F + 1, dtype=torch.int32, device=ids.device)
-        if d_concat is not None:
-            d_concat = d_concat if d_concat.stride(1) == 1 else d_concat.contiguous()
-        if d_fm is not None:
-            d_fm = d_fm.contiguous()
+        d_concat, d_fm = _rows(d_concat), _rows(d_fm, dense=True)
         if d_concat is None and d_fm is None:
             return (None,) * 10
         has_bias = ctx.has_bias and d_fm is not None
         if not ctx.second_order:          # first-order-only logit: its gradient reaches lin_w / bias, not the rows
             concat, sum_x = None, None
         if ctx.sparse_lr is None:
-            g_table = torch.zeros_like(table)
-            g_lin = torch.zeros_like(lin_w) if lin_w is not None else None
+            g_table = _param_grad(table)
+            g_lin = _param_grad(lin_w) if lin_w is not None else None
             g_bias = torch.zeros(1, dtype=torch.float32, device=table.device) if has_bias else None
             ops.emb_pool_bwd(ids, F, col_start, row_base, D, d_concat, concat, sum_x, d_fm, 1.0, g_table, g_lin, g_bias)
             return g_table, g_lin, g_bias, None, None, None, None, None, None, None
@@ -74,11 +138,11 @@ class _LinFieldsFn(torch.autograd.Function):
         return ops.lin_fields_fwd(ids, F, col_start, row_base, lin_w)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out):
         lin_w, ids, col_start, row_base = ctx.saved_tensors
-        g = torch.zeros_like(lin_w)
-        d_out = d_out if d_out.stride(1) == 1 else d_out.contiguous()
-        ops.lin_fields_bwd(ids, ctx.F, col_start, row_base, d_out, 1.0, g)
+        g = _param_grad(lin_w)
+        ops.lin_fields_bwd(ids, ctx.F, col_start, row_base, _rows(d_out), 1.0, g)
         return g, None, None, None, None
 
 
@@ -91,9 +155,10 @@ class _Fm2Fn(torch.autograd.Function):
         return ops.fm2_fwd(x)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out):
         (x,) = ctx.saved_tensors
-        return ops.fm2_bwd(x, d_out.reshape(-1).contiguous())
+        return ops.fm2_bwd(x, _rows(d_out, dense=True).reshape(-1))
 
 
 class _MlpFn(torch.autograd.Function):
@@ -116,22 +181,25 @@ class _MlpFn(torch.autograd.Function):
         return h
 
     @staticmethod
+    @_needed_only
     def backward(ctx, dy):
         acts = ctx.acts
         n = len(acts)
         saved = ctx.saved_tensors
         hs, params = saved[:n + 1], saved[n + 1:]
         grads = [None] * (2 * n)
-        dy = dy.contiguous()
+        dy = _rows(dy)
         for i in range(n - 1, -1, -1):
             W, b = params[2 * i], params[2 * i + 1]
             if acts[i] in (2, 3) or (acts[i] == 1 and i == n - 1):
                 # the activation's derivative through the saved output (a relu BELOW the top layer is folded into the dx GEMM)
-                dy = ops.act_bwd_(hs[i + 1], dy.clone() if i == n - 1 else dy, acts[i])
-            gW = torch.zeros_like(W)
-            gb = torch.zeros_like(b) if b is not None else None
-            ops.linear_bwd_dw(hs[i], dy, 1.0, gW, gb)
-            grads[2 * i], grads[2 * i + 1] = gW, gb
+                dy = ops.act_bwd_(hs[i + 1], dy.clone(memory_format=torch.contiguous_format) if i == n - 1 else dy, acts[i])
+            need_b = b is not None and ctx.needs_input_grad[3 + 2 * i]
+            if ctx.needs_input_grad[2 + 2 * i] or need_b:
+                gW = _param_grad(W)
+                gb = _param_grad(b) if need_b else None
+                ops.linear_bwd_dw(hs[i], dy, 1.0, gW, gb)
+                grads[2 * i], grads[2 * i + 1] = gW, gb
             need_dx = i > 0 or ctx.needs_input_grad[0]
             if need_dx:
                 relu_src = hs[i] if (i > 0 and acts[i - 1] == 1) else None
@@ -144,15 +212,16 @@ class _DropoutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, rate, seed):
-        y, mask = ops.dropout_fwd(x if x.stride(1) == 1 else x.contiguous(), rate, seed)
+        y, mask = ops.dropout_fwd(_rows(x), rate, seed)
         ctx.rate = rate
         ctx.save_for_backward(mask)
         return y
 
     @staticmethod
+    @_needed_only
     def backward(ctx, dy):
         mask, = ctx.saved_tensors
-        return ops.dropout_bwd(dy if dy.stride(1) == 1 else dy.contiguous(), mask, ctx.rate), None, None
+        return ops.dropout_bwd(_rows(dy), mask, ctx.rate), None, None
 
 
 class _L2Fn(torch.autograd.Function):
@@ -165,9 +234,10 @@ class _L2Fn(torch.autograd.Function):
         return ops.reduce_sum(w, squared=True, alpha=coeff).reshape(())
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d):
         w, = ctx.saved_tensors
-        g = torch.zeros_like(w, memory_format=torch.contiguous_format)
+        g = _param_grad(w)
         ops.axpy(2.0 * ctx.coeff * float(d), w.contiguous(), g)
         return g, None
 
@@ -188,6 +258,7 @@ class _CrossLowRankFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out):
         x0, x, U, V, u, prod = ctx.saved_tensors
         ld = x.stride(0)
@@ -195,7 +266,7 @@ class _CrossLowRankFn(torch.autograd.Function):
         d_x0 = torch.zeros((x.shape[0], ld), dtype=torch.float32, device=x.device)[:, :x.shape[1]]
         d_x = torch.zeros((x.shape[0], ld), dtype=torch.float32, device=x.device)[:, :x.shape[1]]
         d_prod = ops.cross_combine_bwd(x0, prod, d_out, ctx.diag, d_x0, d_x)
-        gV, gU = torch.zeros_like(V), torch.zeros_like(U)
+        gV, gU = _param_grad(V), _param_grad(U)
         gb = torch.zeros(x.shape[1], dtype=torch.float32, device=x.device) if ctx.has_b else None
         ops.linear_bwd_dw(u, d_prod, 1.0, gV, gb)                           # dV = u^T d_prod ; db = colsum(d_prod)
         d_u = ops.linear_bwd_dx(d_prod, V)
@@ -206,7 +277,10 @@ class _CrossLowRankFn(torch.autograd.Function):
 
 def _ld_like(t, ld):
     """a [M, N] tensor with leading dimension `ld` (the cross kernels want x0 / x / prod / gradients on one pitch)"""
-    if t.stride(1) == 1 and t.stride(0) == ld:
+    t = _rows(t)
+    if t.shape[0] <= 1 and t.shape[1] <= ld:                  # one row has no pitch of its own
+        return t.as_strided(t.shape, (ld, 1), t.storage_offset())
+    if t.stride(0) == ld:
         return t
     buf = torch.zeros((t.shape[0], ld), dtype=torch.float32, device=t.device)
     buf[:, :t.shape[1]].copy_(t)
@@ -225,26 +299,23 @@ class _CrossFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out):
         x0, x, W, b, prod = ctx.saved_tensors
         M, Dm = x.shape
         ld = prod.stride(0)
 
-        def same_ld(t):
-            if t.stride(0) == ld and t.stride(1) == 1:
-                return t
-            buf = torch.zeros((M, ld), dtype=torch.float32, device=t.device)[:, :Dm]
-            buf.copy_(t)
-            return buf
-
-        d_out_, x0_ = same_ld(d_out), same_ld(x0)
+        d_out_, x0_ = _ld_like(d_out, ld), _ld_like(x0, ld)
         d_x0 = torch.zeros((M, ld), dtype=torch.float32, device=x.device)[:, :Dm]
         d_x = torch.zeros((M, ld), dtype=torch.float32, device=x.device)[:, :Dm]
         d_prod = ops.cross_combine_bwd(x0_, prod, d_out_, ctx.diag, d_x0, d_x)
         ops.linear_bwd_dx(d_prod, W, None, accumulate=True, out=d_x)
-        gW = torch.zeros_like(W)
-        gb = torch.zeros_like(b) if b is not None else None
-        ops.linear_bwd_dw(x, d_prod, 1.0, gW, gb)
+        gW, gb = None, None
+        need_b = b is not None and ctx.needs_input_grad[3]
+        if ctx.needs_input_grad[2] or need_b:
+            gW = _param_grad(W)
+            gb = _param_grad(b) if need_b else None
+            ops.linear_bwd_dw(x, d_prod, 1.0, gW, gb)
         return d_x0, d_x, gW, gb, None
 
 
@@ -400,15 +471,16 @@ class _GatherColsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, num, emb, col_map, emb_map, K):
         out = torch.empty((num.shape[0], K), dtype=torch.float32, device=emb.device)
-        ops.gather_cols(num, emb, col_map, out)
+        ops.gather_cols(_rows(num), _rows(emb), col_map, out)
         ctx.save_for_backward(emb_map)
         ctx.emb_shape = emb.shape
         return out
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out):
         emb_map, = ctx.saved_tensors
-        d_out = d_out if d_out.stride(1) == 1 else d_out.contiguous()
+        d_out = _rows(d_out)
         d_emb = torch.empty(ctx.emb_shape, dtype=torch.float32, device=d_out.device)
         ops.gather_cols(d_out, None, emb_map, d_emb)
         return None, d_emb, None, None, None
@@ -582,10 +654,11 @@ class _SpmmFn(torch.autograd.Function):
         return adj.spmm(X)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d):
         if not ctx.needs_input_grad[0]:
             return None, None
-        return ctx.adj.transpose().spmm(d), None
+        return ctx.adj.transpose().spmm(_rows(d, pitch4=True, aligned=True)), None
 
 
 class _DenseAggFn(torch.autograd.Function):
@@ -597,6 +670,7 @@ class _DenseAggFn(torch.autograd.Function):
         return ops.linear_fwd(adj, X)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d):
         if not ctx.needs_input_grad[0]:
             return None, None
@@ -604,7 +678,7 @@ class _DenseAggFn(torch.autograd.Function):
         M, K = adj.shape
         N = d.shape[1]
         dX = torch.zeros((K, N), dtype=torch.float32, device=d.device)
-        ops.linear_bwd_dw(adj, d, 1.0, dX, None, workspace=ops.linear_bwd_dw_workspace(M, K, N, d.device))
+        ops.linear_bwd_dw(adj, _rows(d), 1.0, dX, None, workspace=ops.linear_bwd_dw_workspace(M, K, N, d.device))
         return dX, None
 
 
@@ -618,14 +692,15 @@ def aggregate(adj, X):
 class _SoftmaxRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        y = ops.softmax_rows_fwd(x)
+        y = ops.softmax_rows_fwd(_rows(x))
         ctx.save_for_backward(y)
         return y
 
     @staticmethod
+    @_needed_only
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
-        return ops.softmax_rows_bwd(y, dy if dy.stride(1) == 1 else dy.contiguous())
+        return ops.softmax_rows_bwd(y, _rows(dy))
 
 
 def softmax_rows(logits):
@@ -646,6 +721,7 @@ class _AddFn(torch.autograd.Function):
         return y
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d):
         return d, d
 
@@ -666,10 +742,11 @@ class _AttentionFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out):
         q, k, v, stats = ctx.saved_tensors
         n_heads, future, rate, seed = ctx.cfg
-        dq, dk, dv = ops.attn_bwd(q, k, v, n_heads, d_out, stats, ctx.key_mask, future, rate, seed)
+        dq, dk, dv = ops.attn_bwd(q, k, v, n_heads, _rows(d_out), stats, ctx.key_mask, future, rate, seed)
         return dq, dk, dv, None, None, None, None, None
 
 
@@ -691,9 +768,10 @@ class _AddLayerNormFn(torch.autograd.Function):
         return y.reshape(shape)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, dy):
         a2, b2, gamma, stats = ctx.saved_tensors
-        d_s, d_gamma, d_beta = ops.add_layernorm_bwd(a2, b2, gamma, stats, dy.reshape(a2.shape))
+        d_s, d_gamma, d_beta = ops.add_layernorm_bwd(a2, b2, gamma, stats, _rows(dy).reshape(a2.shape))
         d_s = d_s.reshape(dy.shape)
         return d_s, (d_s if ctx.has_b else None), d_gamma, d_beta, None
 
@@ -712,11 +790,12 @@ class _TokenEmbeddingFn(torch.autograd.Function):
         return ops.token_embedding_fwd(ids, table, pos, rate, seed)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out):
         (ids,) = ctx.saved_tensors
         rate, seed = ctx.cfg
         d_table = torch.zeros(ctx.table_shape, dtype=torch.float32, device=d_out.device)
-        ops.token_embedding_bwd(ids, d_out, d_table, rate, seed)
+        ops.token_embedding_bwd(ids, _rows(d_out, dense=True), d_table, rate, seed)
         return d_table, None, None, None, None
 
 
@@ -736,15 +815,16 @@ class _TiedProjectionFn(torch.autograd.Function):
         return ops.scores_nt(x, table)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d):
         x, table = ctx.saved_tensors
-        d = d if d.stride(1) == 1 else d.contiguous()
+        d = _rows(d)
         M, V = d.shape
         D = table.shape[1]
         dx = ops.linear_fwd(d, table) if ctx.needs_input_grad[0] else None
         d_table = None
         if ctx.needs_input_grad[1]:
-            d_table = torch.zeros_like(table)
+            d_table = _param_grad(table)
             ops.linear_bwd_dw(d, x, 1.0, d_table, None, workspace=ops.linear_bwd_dw_workspace(M, V, D, d.device))
         return dx, d_table
 
@@ -780,9 +860,10 @@ class _DiceFn(torch.autograd.Function):
         return ops.dice_fwd(x, alpha, eps)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, dy):
         x, alpha = ctx.saved_tensors
-        dx, dalpha = ops.dice_bwd(x, alpha, dy, ctx.eps)
+        dx, dalpha = ops.dice_bwd(x, alpha, _rows(dy), ctx.eps)
         return dx, dalpha, None
 
 
@@ -802,10 +883,12 @@ class _DinPoolFn(torch.autograd.Function):
         return out, scores
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out, d_scores):
         query, keys, mask, W, b, w_out, b_out, alpha = ctx.saved_tensors
         mode, act, eps, wo_shape = ctx.cfg
-        d_q, d_k, dW, db, d_wo, d_bo, dalpha = ops.din_pool_bwd(query, keys, mask, W, b, w_out, b_out, mode, act, d_out, d_scores, alpha, eps)
+        d_q, d_k, dW, db, d_wo, d_bo, dalpha = ops.din_pool_bwd(query, keys, mask, W, b, w_out, b_out, mode, act,
+                                                                _rows(d_out, aligned=True, dense=True), _rows(d_scores, dense=True), alpha, eps)
         return d_q, d_k, None, dW, db, d_wo.reshape(wo_shape), d_bo, None, None, (dalpha if alpha is not None else None), None
 
 
@@ -830,12 +913,14 @@ class _CinPoolFn(torch.autograd.Function):
         return out, pooled
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out, d_pooled):
         x0, x, W, out = ctx.saved_tensors
         if d_out is None and d_pooled is None:
             return None, None, None, None, None, None
         # one layer cannot know what else feeds x0: d_x0 is returned and autograd adds (cin_stack below is where accumulate_x0 is used)
-        d_x0, d_x, dW, dbias = ops.cin_pool_bwd(x0, x, W, ctx.act, out, d_out, d_pooled, want_bias=ctx.has_bias)
+        d_x0, d_x, dW, dbias = ops.cin_pool_bwd(x0, x, W, ctx.act, out, _rows(d_out, dense=True), _rows(d_pooled, dense=True),
+                                                want_bias=ctx.has_bias)
         return d_x0, d_x, dW, dbias, None, None
 
 
@@ -865,6 +950,7 @@ class _CinStackFn(torch.autograd.Function):
         return torch.cat(pooled, dim=1) if n > 1 else pooled[0]
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_res):
         n = ctx.n
         saved = ctx.saved_tensors
@@ -875,10 +961,11 @@ class _CinStackFn(torch.autograd.Function):
         # every layer sends a gradient to the same x0: the last layer's call writes d_x0 and the others add to it in the kernel
         # (accumulate_x0); only the first layer's d_x, whose x IS x0, costs an elementwise add
         d_x0, d_next = None, None
+        d_res = _rows(d_res)
         dWs, dbs = [None] * n, [None] * n
         for k in reversed(range(n)):
             xk = x0 if k == 0 else outs[k - 1]
-            d_x0, d_next, dWs[k], dbs[k] = ops.cin_pool_bwd(x0, xk, Ws[k], ctx.act, outs[k], d_next, d_res[:, offs[k]:offs[k] + sizes[k]],
+            d_x0, d_next, dWs[k], dbs[k] = ops.cin_pool_bwd(x0, xk, Ws[k], ctx.act, outs[k], d_next, _rows(d_res[:, offs[k]:offs[k] + sizes[k]], dense=True),
                                                             want_bias=ctx.has_bias[k], d_x0=d_x0)
         d_x0 += d_next
         return (d_x0, None, None) + tuple(dWs) + tuple(dbs)
@@ -903,12 +990,10 @@ class _DotInteractFn(torch.autograd.Function):
         return ops.dot_interact_fwd(dense, emb, F, D, self_interaction)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out):
         dense, emb = ctx.saved_tensors
-        if d_out.dim() != 2 or (d_out.shape[0] > 1 and (d_out.stride(1) != 1 or d_out.stride(0) % 4 != 0 or d_out.stride(0) < d_out.shape[1])):
-            buf = torch.empty((d_out.shape[0], _pad4(d_out.shape[1])), dtype=torch.float32, device=d_out.device)[:, :d_out.shape[1]]
-            buf.copy_(d_out)                                   # layout only: the kernel reads rows at a pitch that is a multiple of 4
-            d_out = buf
+        d_out = _rows(d_out, pitch4=True, aligned=True)       # the kernel reads rows at a pitch that is a multiple of 4
         d_dense, d_emb = ops.dot_interact_bwd(dense, emb, ctx.F, ctx.D, d_out, ctx.self_interaction)
         return d_dense, d_emb.reshape(ctx.emb_shape), None, None, None
 
@@ -943,11 +1028,10 @@ class _AfmPoolFn(torch.autograd.Function):
         return out, attn
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out, _d_attn):
         emb, W, b, h, out, lse = ctx.saved_tensors
-        if d_out.dim() != 2 or (d_out.shape[0] > 1 and (d_out.stride(1) != 1 or d_out.stride(0) % 4 != 0 or d_out.stride(0) < d_out.shape[1])):
-            d_out = d_out.contiguous()                         # layout only: D is a multiple of 4
-        d_emb, dW, db, dh = ops.afm_pool_bwd(emb, W, b, h, ctx.F, out, lse, d_out)
+        d_emb, dW, db, dh = ops.afm_pool_bwd(emb, W, b, h, ctx.F, out, lse, _rows(d_out, pitch4=True, aligned=True))
         return d_emb.reshape(ctx.emb_shape), dW, db, dh, None, None
 
 
@@ -977,9 +1061,10 @@ class _PnnOuterFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_out):
         u, W = ctx.saved_tensors
-        d_emb, dW = ops.pnn_outer_bwd(u, W, ctx.F, d_out)
+        d_emb, dW = ops.pnn_outer_bwd(u, W, ctx.F, _rows(d_out, pitch4=True, aligned=True))
         return d_emb.reshape(ctx.emb_shape), dW, (d_out if ctx.has_addend else None), None
 
 
@@ -1006,6 +1091,7 @@ class _ActFn(torch.autograd.Function):
         return y
 
     @staticmethod
+    @_needed_only
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
         return ops.act_bwd_(y, dy.clone(memory_format=torch.contiguous_format), ctx.act), None
@@ -1026,9 +1112,11 @@ class _GruSeqFn(torch.autograd.Function):
         return hs, h_last
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_hs, d_h_last):
         xp, U, h0, att, hs = ctx.saved_tensors
-        d_xp, dU, d_h0, d_att = ops.gru_seq_bwd(xp, U, h0, ctx.lengths, att, hs, d_hs, d_h_last)
+        d_xp, dU, d_h0, d_att = ops.gru_seq_bwd(xp, U, h0, ctx.lengths, att, hs, _rows(d_hs, pitch4=True, aligned=True),
+                                                _rows(d_h_last, dense=True))
         return d_xp, dU, (d_h0 if h0 is not None else None), None, d_att
 
 
@@ -1050,9 +1138,10 @@ class _SeqAttnFn(torch.autograd.Function):
         return a
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_a):
         hs, q, a = ctx.saved_tensors
-        d_hs, d_q = ops.seq_attn_bwd(hs, q, ctx.lengths, a, d_a)
+        d_hs, d_q = ops.seq_attn_bwd(hs, q, ctx.lengths, a, _rows(d_a, dense=True))
         return d_hs, d_q, None
 
 
@@ -1072,9 +1161,10 @@ class _FfmFn(torch.autograd.Function):
         return ops.ffm_fwd(rows, F, k)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_inter):
         rows, = ctx.saved_tensors
-        d_rows = ops.ffm_bwd(rows, ctx.F, ctx.k, d_inter.contiguous())
+        d_rows = ops.ffm_bwd(rows, ctx.F, ctx.k, _rows(d_inter, dense=True))
         return d_rows.reshape(ctx.rows_shape), None, None
 
 
@@ -1100,6 +1190,7 @@ class _FfmGatherFn(torch.autograd.Function):
         return inter, first
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_inter, d_first):
         table, lin_w, ids, row_base = ctx.saved_tensors
         F, k = ctx.F, ctx.k
@@ -1107,14 +1198,13 @@ class _FfmGatherFn(torch.autograd.Function):
             d_first = None
         if d_inter is None and d_first is None:
             return (None,) * 8
-        d_rows = ops.ffm_gather_bwd(ids, row_base, table, F, k, d_inter.contiguous()) if d_inter is not None else None
-        if d_first is not None:
-            d_first = d_first.contiguous()
+        d_rows = ops.ffm_gather_bwd(ids, row_base, table, F, k, _rows(d_inter, dense=True)) if d_inter is not None else None
+        d_first = _rows(d_first, dense=True)
         has_bias = ctx.has_bias and d_first is not None
         col_start = torch.arange(F + 1, dtype=torch.int32, device=ids.device)
         if ctx.sparse_lr is None:
-            g_table = torch.zeros_like(table)
-            g_lin = torch.zeros_like(lin_w) if lin_w is not None else None
+            g_table = _param_grad(table)
+            g_lin = _param_grad(lin_w) if lin_w is not None else None
             g_bias = torch.zeros(1, dtype=torch.float32, device=table.device) if has_bias else None
             ops.emb_pool_bwd(ids, F, col_start, row_base, F * k, d_rows, None, None, d_first, 1.0, g_table, g_lin, g_bias)
             return g_table, g_lin, g_bias, None, None, None, None, None

@@ -109,7 +109,7 @@ def lin_fields_fwd(ids, F, col_start, row_base, lin_w):
 def lin_fields_bwd(ids, F, col_start, row_base, d_out, scale, dst_lin):
     ids = _c(ids, torch.int64)
     B, C = ids.shape
-    assert d_out.stride(1) == 1
+    _check_ld(d_out, "lin_fields_bwd: d_out")
     check(lib().dr_lin_fields_bwd(ptr(ids), B, F, C, ptr(col_start), ptr(row_base), ptr(d_out), d_out.stride(0), float(scale),
                                   ptr(dst_lin), stream_ptr()), "dr_lin_fields_bwd")
 
@@ -118,6 +118,7 @@ def emb_pool_bwd(ids, F, col_start, row_base, D, d_concat, concat, sum_x, d_fm_l
                  dst_bias=None):
     ids = _c(ids, torch.int64)
     B, C = ids.shape
+    _check_ld(d_concat, "emb_pool_bwd: d_concat")
     check(lib().dr_emb_pool_bwd(ptr(ids), B, F, C, ptr(col_start), ptr(row_base), D,
                                 ptr(d_concat), d_concat.stride(0) if d_concat is not None else 0,
                                 ptr(concat), concat.stride(0) if concat is not None else 0,
@@ -152,6 +153,21 @@ def _pad4(n):
     return (n + 3) // 4 * 4
 
 
+def _check_ld(t, what):
+    """t [M, N] goes to a kernel with t.stride(0) as its leading dimension: unit column stride and, with more than one row, a row
+    stride >= N.  A smaller one (0 for an expanded tensor) is no layout: every example would read the same or overlapping rows."""
+    if t is None:
+        return
+    if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError("%s must be fp32 [M, N] with unit column stride and a row stride >= N, got %s %s with strides %s"
+                         % (what, t.dtype, tuple(t.shape), tuple(t.stride())))
+
+
+def _vec_f32(b):
+    """a bias / per-column vector the kernel reads densely (an expanded one has a 0 stride and a single element behind it)"""
+    return None if b is None else _c(b, torch.float32)
+
+
 def _rowmajor_ld4(t):
     """Returns a [M, K] fp32 view whose row stride is a multiple of 4 floats and base 16-B aligned."""
     assert t.dim() == 2 and t.dtype == torch.float32
@@ -169,6 +185,7 @@ def linear_fwd(x, W, b=None, act=0, out=None):
     """y = act(x @ W + b); x [M,K] (row stride % 4 == 0), W [K,N] row-major."""
     x = _rowmajor_ld4(x)
     W = _rowmajor_ld4(W)
+    b = _vec_f32(b)
     M, K = x.shape
     N = W.shape[1]
     if out is None:
@@ -336,6 +353,7 @@ def cross_fwd(x0, x, W, b, diag_scale=0.0, want_prod=False, prod=None):
         x0 = _rowmajor_ld4(x0.contiguous())
     M, Dm = x.shape
     ld = x.stride(0)
+    b = _vec_f32(b)
     out = torch.empty((M, ld), dtype=torch.float32, device=x.device)[:, :Dm]
     if W is not None:
         W = _rowmajor_ld4(W)
@@ -2019,7 +2037,7 @@ def din_concat_fwd(x, y, mode):
 
 def din_concat_bwd(x, y, mode, d_out):
     B, D = x.shape
-    assert d_out.stride(1) == 1
+    _check_ld(d_out, "din_concat_bwd: d_out")
     d_x, d_y = torch.empty_like(x), torch.empty_like(y)
     check(lib().dr_din_concat_bwd(ptr(x), ptr(y), B, D, int(mode), ptr(d_out), d_out.stride(0), ptr(d_x), ptr(d_y), stream_ptr()),
           "dr_din_concat_bwd")
@@ -2029,20 +2047,22 @@ def din_concat_bwd(x, y, mode, d_out):
 # ---- element-wise pieces around the GEMM path (csrc/elementwise.hip) ------------------------------------------------------------
 def act_fwd_(x, act):
     """in place: x = act(x) for act in {2: sigmoid, 3: tanh} (1 = relu also accepted); x [M, N] with unit column stride"""
-    assert x.dim() == 2 and x.stride(1) == 1
+    _check_ld(x, "act_fwd_: x")
     check(lib().dr_act_fwd(ptr(x), x.shape[0], x.shape[1], x.stride(0), int(act), stream_ptr()), "dr_act_fwd")
     return x
 
 
 def act_bwd_(y, dy, act):
     """in place: dy *= act'(.) expressed through the saved output y"""
-    assert y.shape == dy.shape and y.stride(1) == 1 and dy.stride(1) == 1
+    assert y.shape == dy.shape
+    _check_ld(y, "act_bwd_: y")
+    _check_ld(dy, "act_bwd_: dy")
     check(lib().dr_act_bwd(ptr(y), y.stride(0), ptr(dy), dy.stride(0), y.shape[0], y.shape[1], int(act), stream_ptr()), "dr_act_bwd")
     return dy
 
 
 def dropout_fwd(x, rate, seed):
-    assert x.dim() == 2 and x.stride(1) == 1
+    _check_ld(x, "dropout_fwd: x")
     M, N = x.shape
     y = torch.empty((M, _pad4(N)), dtype=torch.float32, device=x.device)[:, :N]
     mask = torch.empty(M * N, dtype=torch.uint8, device=x.device)
@@ -2052,7 +2072,7 @@ def dropout_fwd(x, rate, seed):
 
 
 def dropout_bwd(dy, mask, rate):
-    assert dy.dim() == 2 and dy.stride(1) == 1
+    _check_ld(dy, "dropout_bwd: dy")
     M, N = dy.shape
     dx = torch.empty((M, _pad4(N)), dtype=torch.float32, device=dy.device)[:, :N]
     check(lib().dr_dropout_bwd(ptr(dy), dy.stride(0), ptr(mask), M, N, float(rate), ptr(dx), dx.stride(0), stream_ptr()),
@@ -2247,6 +2267,9 @@ def gather_cols(a, b, col_map, out):
     M, N = out.shape
     if col_map.dtype != torch.int32 or col_map.numel() != N:
         raise ValueError("gather_cols: col_map must be int32 [%d]" % N)
+    _check_ld(a, "gather_cols: a")            # dr_gather_cols takes lda / ldb as they come
+    _check_ld(b, "gather_cols: b")
+    _check_ld(out, "gather_cols: out")
     check(lib().dr_gather_cols(ptr(a), a.stride(0) if a is not None else 0, ptr(b), b.stride(0) if b is not None else 0, ptr(col_map),
                                M, N, ptr(out), out.stride(0), stream_ptr()), "dr_gather_cols")
     return out
@@ -2318,7 +2341,7 @@ def csr_transpose(row_ptr, col, val, n_rows, n_cols, nnz):
 
 
 def softmax_rows_fwd(x, out=None):
-    assert x.dim() == 2 and x.stride(1) == 1
+    _check_ld(x, "softmax_rows_fwd: x")
     B, C = x.shape
     if out is None:
         out = torch.empty((B, C), dtype=torch.float32, device=x.device)
@@ -2327,7 +2350,9 @@ def softmax_rows_fwd(x, out=None):
 
 
 def softmax_rows_bwd(y, dy, out=None):
-    assert y.shape == dy.shape and y.stride(1) == 1 and dy.stride(1) == 1
+    assert y.shape == dy.shape
+    _check_ld(y, "softmax_rows_bwd: y")
+    _check_ld(dy, "softmax_rows_bwd: dy")
     B, C = y.shape
     if out is None:
         out = torch.empty((B, C), dtype=torch.float32, device=y.device)
@@ -2411,7 +2436,11 @@ def attn_bwd(q, k, v, n_heads, d_out, stats, key_mask=None, future=False, rate=0
 def _rows_f32(t, what):
     if t.dtype != torch.float32 or t.dim() != 2:
         raise TypeError("%s must be a [M, D] fp32 tensor" % what)
-    return t if (t.stride(1) == 1 and t.stride(0) >= t.shape[1]) or t.shape[0] == 0 else t.contiguous()
+    if t.shape[0] == 0 or ((t.stride(1) == 1 or t.shape[1] == 1) and t.stride(0) >= t.shape[1] and t.shape[0] > 1):
+        return t
+    if t.shape[0] == 1 and (t.stride(1) == 1 or t.shape[1] == 1):     # one row has no pitch: name a legal one (no copy)
+        return t.as_strided(t.shape, (t.shape[1], 1), t.storage_offset())
+    return t.contiguous()
 
 
 def add_layernorm_fwd(a, b, gamma, beta, eps=1e-8):

@@ -51,8 +51,7 @@ def _mask(B, Lk):
     return m
 
 
-def _dhp(dh):
-    return 16 if dh <= 16 else 32 if dh <= 32 else 64 if dh <= 64 else 128
+_dhp = R.dhp
 
 
 def _oracle(q, k, v, d_out, H, mask, future, keep, rate, dtype):
@@ -62,30 +61,7 @@ def _oracle(q, k, v, d_out, H, mask, future, keep, rate, dtype):
     return [t.detach().to(torch.float64).numpy() for t in (out, tq.grad, tk.grad, tv.grad)]
 
 
-def _magnitudes(q, k, v, d_out, H, mask, future, keep, rate):
-    """the formulas of out, dq, dk, dv evaluated on absolute values (float64), [B, L, W] each"""
-    B, Lq, W = q.shape
-    Lk = k.shape[1]
-    dh = W // H
-    t64 = lambda a: torch.from_numpy(a).to(torch.float64)                                  # noqa: E731
-    heads = lambda a: t64(a).reshape(a.shape[0], a.shape[1], H, dh).permute(0, 2, 1, 3)    # noqa: E731
-    merge = lambda a: a.permute(0, 2, 1, 3).reshape(a.shape[0], a.shape[2], W).numpy()     # noqa: E731
-    P = R.attention_probabilities(t64(q), t64(k), H, mask, future)
-    D = torch.from_numpy(np.asarray(keep)).to(torch.float64) / (1.0 - float(np.float32(rate))) if rate > 0 else torch.ones_like(P)
-    qa, ka, va, ga = heads(np.abs(q)), heads(np.abs(k)), heads(np.abs(v)), heads(np.abs(d_out))
-    Pd = P * D
-    mag_out = Pd @ va
-    mag_dv = Pd.transpose(2, 3) @ ga
-    mag_dp = D * (ga @ va.transpose(2, 3))
-    mag_delta = (P * mag_dp).sum(-1, keepdim=True)
-    mag_ds = P * (mag_dp + mag_delta)
-    if future:
-        mag_ds = torch.where(torch.triu(torch.ones(Lq, Lk, dtype=torch.bool), 1), torch.zeros((), dtype=torch.float64), mag_ds)
-    mag_dq = mag_ds @ ka / math.sqrt(dh)
-    mag_dk = mag_ds.transpose(2, 3) @ qa / math.sqrt(dh)
-    # the score error: gamma(padded dh) max_ij |q_i| . |k_j| / sqrt(dh)
-    es = gamma(_dhp(dh) + 2) * float((qa @ ka.transpose(2, 3)).max()) / math.sqrt(dh)
-    return [merge(m) for m in (mag_out, mag_dq, mag_dk, mag_dv)], es
+_magnitudes = R.attention_magnitudes
 
 
 def _run(q, k, v, d_out, H, mask, future, rate, seed, extra):
