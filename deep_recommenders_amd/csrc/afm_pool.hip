@@ -23,10 +23,9 @@
 //           their registers in wave order into LDS, the block writes one partial to the workspace, and a second launch adds the partials
 //           in block order.  The number of blocks depends on (B, F, D, A) only.
 #include "dr_common.h"
+#include "dr_sum_partials.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int AFM_MAX_F = 64;
 constexpr int AFM_MAX_D = 256;
@@ -48,8 +47,6 @@ struct AfmP {
 };
 
 struct AfmGeo { int DT, AT, nw, D16, A16, P, P16; size_t lds_fwd, lds_bwd; };
-
-__device__ __forceinline__ float afm_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
 // W [D16][PW] (zero beyond D and A), b [A16], h [A16], the pair table [P16] ((i << 8) | j; the pad entries name pair (1, 0))
 template <int AT>
@@ -87,10 +84,10 @@ __device__ __forceinline__ void afm_stage_rows(const AfmP& p, float* el, int64_t
 // this lane's part of <g, p> (chunks s, elements e in order; summed over q4 by the caller).
 template <int AT>
 __device__ __forceinline__ float afm_z_tile(const float* Wl, const float* ei, const float* ej, const float* gl, int KC, int c, int q4,
-                                            f32x4* acc) {
+                                            dr_f32x4* acc) {
     constexpr int PW = 16 * AT + 4;
 #pragma unroll
-    for (int at = 0; at < AT; ++at) acc[at] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int at = 0; at < AT; ++at) acc[at] = (dr_f32x4){0.f, 0.f, 0.f, 0.f};
     float gp = 0.f;
     for (int s = 0; s < KC; ++s) {
         const float4 x = *reinterpret_cast<const float4*>(ei + 16 * s + 4 * q4);
@@ -137,7 +134,7 @@ __global__ __launch_bounds__(256) void afm_fwd_kernel(const AfmP p) {
         float* attn = (p.attn != nullptr && valid) ? p.attn + b * p.ld_attn : nullptr;
         for (int t = 0; t < ntiles; ++t) {
             const int ij = tab[16 * t + c];
-            f32x4 acc[AT];
+            dr_f32x4 acc[AT];
             afm_z_tile<AT>(Wl, el + (ij >> 8) * PE, el + (ij & 255) * PE, nullptr, p.KC, c, q4, acc);
             float sp = 0.f;
 #pragma unroll
@@ -169,7 +166,7 @@ __global__ __launch_bounds__(256) void afm_fwd_kernel(const AfmP p) {
             for (int n = 0; n < 4; ++n) oacc[n] *= scale;
 #pragma unroll
             for (int kk = 0; kk < 16; ++kk) {
-                const float wk = afm_lane(w, kk);
+                const float wk = dr_readlane(w, kk);
                 const int ijk = __builtin_amdgcn_readlane(ij, kk);
                 const float* ri = el + (ijk >> 8) * PE;
                 const float* rj = el + (ijk & 255) * PE;
@@ -212,14 +209,14 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmP p) {
     float* dzl = gl + D16;
     float* dpl = dzl + 16 * PW;
     afm_stage_shared<AT>(p, Wl, bl, hl, tab);
-    f32x4 dWacc[DT][AT];
-    f32x4 dbacc[AT], dhacc[AT];
+    dr_f32x4 dWacc[DT][AT];
+    dr_f32x4 dbacc[AT], dhacc[AT];
 #pragma unroll
     for (int at = 0; at < AT; ++at) {
-        dbacc[at] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        dhacc[at] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        dbacc[at] = (dr_f32x4){0.f, 0.f, 0.f, 0.f};
+        dhacc[at] = (dr_f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) dWacc[dt][at] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int dt = 0; dt < DT; ++dt) dWacc[dt][at] = (dr_f32x4){0.f, 0.f, 0.f, 0.f};
     }
     const int64_t stride = (int64_t)gridDim.x * nw;
     const int64_t iters = (p.B + stride - 1) / stride;
@@ -248,7 +245,7 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmP p) {
         }
         for (int t = 0; t < ntiles; ++t) {
             const int ij = tab[16 * t + c];
-            f32x4 acc[AT];
+            dr_f32x4 acc[AT];
             float gp = afm_z_tile<AT>(Wl, el + (ij >> 8) * PE, el + (ij & 255) * PE, gl, p.KC, c, q4, acc);
             gp += __shfl_xor(gp, 16, 64);
             gp += __shfl_xor(gp, 32, 64);
@@ -269,7 +266,7 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmP p) {
             const bool qv = valid && 16 * t + c < p.P;
             const float aq = qv ? expf(sp - lse) : 0.f;
             const float ds = qv ? aq * (gp - go) : 0.f;
-            f32x4 dz[AT];
+            dr_f32x4 dz[AT];
 #pragma unroll
             for (int at = 0; at < AT; ++at) {
                 const float hv[4] = {hreg[at].x, hreg[at].y, hreg[at].z, hreg[at].w};
@@ -285,7 +282,7 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmP p) {
             // dp^T = W dz^T, then + a_q g; to dpl[pair][d]
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
-                f32x4 dp = (f32x4){0.f, 0.f, 0.f, 0.f};
+                dr_f32x4 dp = (dr_f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int at = 0; at < AT; ++at) {
                     const float4 wv = *reinterpret_cast<const float4*>(Wl + (16 * dt + c) * PW + 16 * at + 4 * q4);
@@ -387,28 +384,11 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const AfmP p) {
     }
 }
 
-// dW | db | dh = the blocks' partials added in block order
-__global__ __launch_bounds__(256) void afm_bwd_reduce_kernel(const float* __restrict__ ws, int nblk, int DA, int A, float* __restrict__ dW,
-                                                             float* __restrict__ db, float* __restrict__ dh) {
-    const int n = DA + 2 * A;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n) return;
-    float acc = 0.f;
-    for (int k = 0; k < nblk; ++k) acc += ws[(size_t)k * n + idx];
-    if (idx < DA) dW[idx] = acc;
-    else if (idx < DA + A) db[idx - DA] = acc;
-    else dh[idx - DA - A] = acc;
-}
-
-bool afm_aligned(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-
-int afm_pow2(int n) { int v = 1; while (v < n) v <<= 1; return v; }
-
 // DR_OK and the launch geometry, DR_EINVAL outside the domain, DR_ESHAPE where the registers or the LDS do not hold the problem
 int afm_geometry(AfmGeo& g, int64_t B, int32_t F, int32_t D, int32_t A) {
     if (B < 0 || F < 2 || F > AFM_MAX_F || D < 4 || D > AFM_MAX_D || (D & 3) || A < 1 || A > AFM_MAX_A) return DR_EINVAL;
-    g.DT = afm_pow2((D + 15) / 16);
-    g.AT = afm_pow2((A + 15) / 16);
+    g.DT = dr_pow2_ceil((D + 15) / 16);
+    g.AT = dr_pow2_ceil((A + 15) / 16);
     if (g.DT * g.AT > AFM_MAX_TILES) return DR_ESHAPE;
     g.D16 = 16 * g.DT;
     g.A16 = 16 * g.AT;
@@ -437,20 +417,10 @@ void afm_fill(AfmP& p, const AfmGeo& g, const float* emb, int64_t ld_emb, const 
     p.B = B; p.F = F; p.D = D; p.A = A; p.P = g.P; p.P16 = g.P16; p.D16 = g.D16; p.KC = (D + 15) / 16;
 }
 
-template <typename K>
-int afm_launch(K kernel, int64_t grid, int nw, size_t lds, const AfmP& p, dr_stream_t stream) {
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DR_ELAUNCH;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64 * nw), lds, dr_s(stream), p);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
-}
-
 }  // namespace
 
 #define AFM_BWD_CASE(dt, at) \
-    case (dt) * 16 + (at): return afm_launch(afm_bwd_kernel<dt, at>, grid, g.nw, g.lds_bwd, p, stream)
+    case (dt) * 16 + (at): return dr_launch(afm_bwd_kernel<dt, at>, dim3((unsigned)grid), dim3(64 * g.nw), g.lds_bwd, dr_s(stream), p)
 
 static int afm_bwd_dispatch(const AfmGeo& g, int64_t grid, const AfmP& p, dr_stream_t stream) {
     switch (g.DT * 16 + g.AT) {
@@ -469,21 +439,22 @@ extern "C" int dr_afm_pool_fwd(const float* emb, int64_t ld_emb, const float* W,
     AfmGeo g = {};
     const int st = afm_geometry(g, B, F, D, A);
     if (st != DR_OK) return st;
-    if ((ld_emb & 3) || ld_emb < (int64_t)F * D || (ld_out & 3) || ld_out < D) return DR_EINVAL;
+    if (dr_bad_ld(ld_emb, (int64_t)F * D) || dr_bad_ld(ld_out, D)) return DR_EINVAL;
     if (attn != nullptr && ld_attn < g.P) return DR_EINVAL;
     if (B == 0) return DR_OK;                                  // nothing to read or write: empty tensors have no address
-    if (!emb || !W || !b || !h || !out || !lse || !afm_aligned(emb) || !afm_aligned(out)) return DR_EINVAL;
+    if (!emb || !W || !b || !h || !out || !lse || !dr_aligned16(emb) || !dr_aligned16(out)) return DR_EINVAL;
     AfmP p = {};
     afm_fill(p, g, emb, ld_emb, W, b, h, B, F, D, A);
     p.D16 = 16 * p.KC;                                         // the forward has no D tiles: rows as wide as the k chunks
     p.out = out; p.ld_out = ld_out; p.lse = lse; p.attn = attn; p.ld_attn = ld_attn;
     int64_t grid = (B + g.nw - 1) / g.nw;
     if (grid > AFM_FWD_BLOCKS) grid = AFM_FWD_BLOCKS;
+    const dim3 blocks((unsigned)grid), threads(64 * g.nw);
     switch (g.AT) {
-        case 1: return afm_launch(afm_fwd_kernel<1>, grid, g.nw, g.lds_fwd, p, stream);
-        case 2: return afm_launch(afm_fwd_kernel<2>, grid, g.nw, g.lds_fwd, p, stream);
-        case 4: return afm_launch(afm_fwd_kernel<4>, grid, g.nw, g.lds_fwd, p, stream);
-        default: return afm_launch(afm_fwd_kernel<8>, grid, g.nw, g.lds_fwd, p, stream);
+        case 1: return dr_launch(afm_fwd_kernel<1>, blocks, threads, g.lds_fwd, dr_s(stream), p);
+        case 2: return dr_launch(afm_fwd_kernel<2>, blocks, threads, g.lds_fwd, dr_s(stream), p);
+        case 4: return dr_launch(afm_fwd_kernel<4>, blocks, threads, g.lds_fwd, dr_s(stream), p);
+        default: return dr_launch(afm_fwd_kernel<8>, blocks, threads, g.lds_fwd, dr_s(stream), p);
     }
 }
 
@@ -501,11 +472,11 @@ extern "C" int dr_afm_pool_bwd(const float* emb, int64_t ld_emb, const float* W,
     AfmGeo g = {};
     const int st = afm_geometry(g, B, F, D, A);
     if (st != DR_OK) return st;
-    if ((ld_emb & 3) || ld_emb < (int64_t)F * D || (ld_demb & 3) || ld_demb < (int64_t)F * D) return DR_EINVAL;
-    if ((ld_out & 3) || ld_out < D || (ld_dout & 3) || ld_dout < D) return DR_EINVAL;
+    if (dr_bad_ld(ld_emb, (int64_t)F * D) || dr_bad_ld(ld_demb, (int64_t)F * D)) return DR_EINVAL;
+    if (dr_bad_ld(ld_out, D) || dr_bad_ld(ld_dout, D)) return DR_EINVAL;
     if (B == 0) return DR_OK;
     if (!emb || !W || !b || !h || !out || !lse || !d_out || !d_emb || !dW || !db || !dh || !ws) return DR_EINVAL;
-    if (!afm_aligned(emb) || !afm_aligned(out) || !afm_aligned(d_out) || !afm_aligned(d_emb) || !afm_aligned(ws)) return DR_EINVAL;
+    if (!dr_aligned16(emb) || !dr_aligned16(out) || !dr_aligned16(d_out) || !dr_aligned16(d_emb) || !dr_aligned16(ws)) return DR_EINVAL;
     const int64_t grid = afm_bwd_blocks(g, B);
     if (ws_bytes < grid * ((int64_t)D * A + 2 * A) * (int64_t)sizeof(float)) return DR_EINVAL;
     AfmP p = {};
@@ -514,9 +485,6 @@ extern "C" int dr_afm_pool_bwd(const float* emb, int64_t ld_emb, const float* W,
     p.d_emb = d_emb; p.ld_demb = ld_demb; p.ws = static_cast<float*>(ws);
     const int st2 = afm_bwd_dispatch(g, grid, p, stream);
     if (st2 != DR_OK) return st2;
-    const int n = D * A + 2 * A;
-    hipLaunchKernelGGL(afm_bwd_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, dr_s(stream), p.ws, (int)grid, D * A, A, dW,
-                       db, dh);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
+    // dW | db | dh = the blocks' partials added in block order
+    return dr_sum_partials(p.ws, grid, dW, D * A, db, A, dh, A, (unsigned)((D * A + 2 * A + 255) / 256), dr_s(stream));
 }

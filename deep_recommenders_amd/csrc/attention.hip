@@ -19,12 +19,11 @@
 // Determinism: the dK/dV sweep owns a key block and runs over all queries, the dQ sweep owns a query block and runs over all keys
 // (with the delta pass nine products instead of five); no float atomics, no waiting between workgroups; the dropout mask is regenerated from the hash.
 #include "dr_common.h"
+#include "dr_sum_partials.h"
 #include <math.h>
 #include <algorithm>
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr float ATTN_MASK = -4294967296.f;      // float32(-2^32 + 1)
 constexpr int ATTN_TILE = 64;                   // rows of a tile in LDS; 4 waves x 16 owned rows per block
@@ -50,9 +49,9 @@ __device__ __forceinline__ void attn_load_tile(float* lds, const float* base, in
         constexpr int C4 = DHP / 4;
         for (int i = threadIdx.x; i < ATTN_TILE * C4; i += 256) {
             const int r = i / C4, c = (i - r * C4) * 4;
-            f4 val = {0.f, 0.f, 0.f, 0.f};
-            if (r0 + r < L && c < dh) val = *reinterpret_cast<const f4*>(base + (int64_t)(r0 + r) * ld + c);
-            *reinterpret_cast<f4*>(lds + r * LS + c) = val;
+            dr_f32x4 val = {0.f, 0.f, 0.f, 0.f};
+            if (r0 + r < L && c < dh) val = *reinterpret_cast<const dr_f32x4*>(base + (int64_t)(r0 + r) * ld + c);
+            *reinterpret_cast<dr_f32x4*>(lds + r * LS + c) = val;
         }
     } else {
         for (int i = threadIdx.x; i < ATTN_TILE * DHP; i += 256) {
@@ -76,16 +75,16 @@ __device__ __forceinline__ void attn_load_frag(float (&reg)[DHP / 4], const floa
 
 // transposed accumulators (acc[dt][r] = column 16dt + 4g + r of the lane's row) -> row[d] = acc * mul / div
 template <int DHP>
-__device__ __forceinline__ void attn_store_frag(float* row, const f4 (&acc)[DHP / 16], float mul, float div, int dh, int g, bool vec) {
+__device__ __forceinline__ void attn_store_frag(float* row, const dr_f32x4 (&acc)[DHP / 16], float mul, float div, int dh, int g, bool vec) {
     if (!row) return;
 #pragma unroll
     for (int dt = 0; dt < DHP / 16; ++dt) {
         const int d0 = 16 * dt + 4 * g;
-        f4 val;
+        dr_f32x4 val;
 #pragma unroll
         for (int r = 0; r < 4; ++r) val[r] = acc[dt][r] * mul / div;
         if (vec) {
-            if (d0 < dh) *reinterpret_cast<f4*>(row + d0) = val;
+            if (d0 < dh) *reinterpret_cast<dr_f32x4*>(row + d0) = val;
         } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -109,14 +108,14 @@ __device__ __forceinline__ bool attn_keep(const AttnP& p, uint64_t row_base, int
 
 // S^T tile: acc[t][r] = sum_d tile[16t + 4g + r][d] * own[i16][d]
 template <int DHP>
-__device__ __forceinline__ void attn_tile_dot(const float* tile, const float (&own)[DHP / 4], int i16, int g, f4 (&acc)[4]) {
+__device__ __forceinline__ void attn_tile_dot(const float* tile, const float (&own)[DHP / 4], int i16, int g, dr_f32x4 (&acc)[4]) {
     constexpr int LS = DHP + 4;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        f4 a4 = {0.f, 0.f, 0.f, 0.f};
+        dr_f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < DHP / 16; ++c) {
-            const f4 a = *reinterpret_cast<const f4*>(tile + (16 * t + i16) * LS + 16 * c + 4 * g);
+            const dr_f32x4 a = *reinterpret_cast<const dr_f32x4*>(tile + (16 * t + i16) * LS + 16 * c + 4 * g);
 #pragma unroll
             for (int e = 0; e < 4; ++e) a4 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], own[4 * c + e], a4, 0, 0, 0);
         }
@@ -126,7 +125,7 @@ __device__ __forceinline__ void attn_tile_dot(const float* tile, const float (&o
 
 // out^T += tile^T w: out[dt][r'] (column 16dt + 4g + r' of row i16) += sum_{t, r} tile[16t + 4g + r][.] * w[t][r]
 template <int DHP>
-__device__ __forceinline__ void attn_tile_acc(const float* tile, const f4 (&w)[4], int i16, int g, f4 (&out)[DHP / 16]) {
+__device__ __forceinline__ void attn_tile_acc(const float* tile, const dr_f32x4 (&w)[4], int i16, int g, dr_f32x4 (&out)[DHP / 16]) {
     constexpr int LS = DHP + 4;
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -153,9 +152,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnP p) {
     const float* Vb = p.v + (int64_t)b * p.Lk * p.ld_v + h * p.dh;
     float qreg[DHP / 4];
     attn_load_frag<DHP>(qreg, qok ? p.q + ((int64_t)b * p.Lq + qi) * p.ld_q + h * p.dh : nullptr, p.dh, g);
-    f4 oacc[NC];
+    dr_f32x4 oacc[NC];
 #pragma unroll
-    for (int dt = 0; dt < NC; ++dt) oacc[dt] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < NC; ++dt) oacc[dt] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, l = 0.f;
     const uint64_t row_base = ((uint64_t)bh * p.Lq + (uint64_t)qi) * (uint64_t)p.Lk;
     for (int kt = 0; kt < p.Lk; kt += ATTN_TILE) {
@@ -167,7 +166,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnP p) {
             mvs[threadIdx.x] = (p.mask && j < p.Lk && p.mask[(int64_t)b * p.Lk + j]) ? ATTN_MASK : 0.f;
         }
         __syncthreads();
-        f4 s[4];
+        dr_f32x4 s[4];
         attn_tile_dot<DHP>(Ks, qreg, i16, g, s);
         float mx = -INFINITY;
 #pragma unroll
@@ -237,9 +236,9 @@ __device__ __forceinline__ void attn_bwd_q_sweep(const AttnP& p) {
         linv = 1.f / st[1];
         if (!DELTA_ONLY) delta = p.delta[(int64_t)bh * p.Lq + qi];
     }
-    f4 acc[NC];
+    dr_f32x4 acc[NC];
 #pragma unroll
-    for (int dt = 0; dt < NC; ++dt) acc[dt] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < NC; ++dt) acc[dt] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
     const uint64_t row_base = ((uint64_t)bh * p.Lq + (uint64_t)qi) * (uint64_t)p.Lk;
     for (int kt = 0; kt < p.Lk; kt += ATTN_TILE) {
         __syncthreads();
@@ -250,7 +249,7 @@ __device__ __forceinline__ void attn_bwd_q_sweep(const AttnP& p) {
             mvs[threadIdx.x] = (p.mask && j < p.Lk && p.mask[(int64_t)b * p.Lk + j]) ? ATTN_MASK : 0.f;
         }
         __syncthreads();
-        f4 s[4], dp[4];
+        dr_f32x4 s[4], dp[4];
         attn_tile_dot<DHP>(Ks, qreg, i16, g, s);
         attn_tile_dot<DHP>(Vs, doreg, i16, g, dp);
 #pragma unroll
@@ -298,9 +297,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnP p) {
     attn_load_frag<DHP>(kreg, kok ? p.k + ((int64_t)b * p.Lk + kj) * p.ld_k + h * p.dh : nullptr, p.dh, g);
     attn_load_frag<DHP>(vreg, kok ? p.v + ((int64_t)b * p.Lk + kj) * p.ld_v + h * p.dh : nullptr, p.dh, g);
     const float mask_add = (p.mask && kok && p.mask[(int64_t)b * p.Lk + kj]) ? ATTN_MASK : 0.f;
-    f4 dkacc[NC], dvacc[NC];
+    dr_f32x4 dkacc[NC], dvacc[NC];
 #pragma unroll
-    for (int dt = 0; dt < NC; ++dt) dkacc[dt] = dvacc[dt] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < NC; ++dt) dkacc[dt] = dvacc[dt] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
     for (int qt = 0; qt < p.Lq; qt += ATTN_TILE) {
         __syncthreads();
         attn_load_tile<DHP>(Qs, Qb, p.ld_q, qt, p.Lq, p.dh, p.vec_q);
@@ -319,7 +318,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnP p) {
             des[threadIdx.x] = de;
         }
         __syncthreads();
-        f4 s[4], dp[4];
+        dr_f32x4 s[4], dp[4];
         attn_tile_dot<DHP>(Qs, kreg, i16, g, s);
         attn_tile_dot<DHP>(Gs, vreg, i16, g, dp);
 #pragma unroll
@@ -460,19 +459,6 @@ __global__ __launch_bounds__(256) void add_ln_bwd_partial_kernel(const float* __
         partial[((int64_t)blockIdx.x * 2) * D + c] = dg;
         partial[((int64_t)blockIdx.x * 2 + 1) * D + c] = db;
     }
-}
-// stage 2: the partials summed in chunk order
-__global__ __launch_bounds__(256) void add_ln_bwd_final_kernel(const float* __restrict__ partial, int64_t chunks, int32_t D,
-                                                               float* __restrict__ d_gamma, float* __restrict__ d_beta) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= D) return;
-    float dg = 0.f, db = 0.f;
-    for (int64_t k = 0; k < chunks; ++k) {
-        dg += partial[(k * 2) * D + c];
-        db += partial[(k * 2 + 1) * D + c];
-    }
-    d_gamma[c] = dg;
-    d_beta[c] = db;
 }
 
 inline int ln_group(int32_t D) {
@@ -624,10 +610,8 @@ extern "C" int dr_add_layernorm_bwd(const float* a, int64_t ld_a, const float* b
     const unsigned cy = (unsigned)std::min<int64_t>((D + 255) / 256, 64);
     hipLaunchKernelGGL(add_ln_bwd_partial_kernel, dim3((unsigned)chunks, cy), dim3(256), 0, dr_s(stream), a, ld_a, b, ld_b, stats, dy, ld_dy,
                        M, D, workspace);
-    hipLaunchKernelGGL(add_ln_bwd_final_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, dr_s(stream), workspace, chunks, D, d_gamma,
-                       d_beta);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
+    // stage 2: d_gamma | d_beta = the partials summed in chunk order
+    return dr_sum_partials(workspace, chunks, d_gamma, D, d_beta, D, nullptr, 0, (unsigned)((D + 255) / 256), dr_s(stream));
 }
 
 extern "C" int dr_token_embedding_fwd(const int64_t* ids, int64_t N, int32_t L, const float* table, int64_t V, int32_t D, const float* pos,

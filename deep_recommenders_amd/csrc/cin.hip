@@ -19,8 +19,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int CIN_ROWS = 64;        // (b, d) rows per block
 constexpr int CIN_PITCH = 65;       // LDS pitch of a field's row values (bank-conflict-free for the per-field reads)
 
@@ -52,7 +50,7 @@ __global__ __launch_bounds__(256) void cin_fwd_kernel(const float* __restrict__ 
     const int f = blockIdx.y * 64 + (wave >> 1) * 32 + l31;   // this lane's feature map (operand A row)
     const bool fv = f < Fm;
     const int fc = fv ? f : Fm - 1;
-    f32x16 acc;
+    dr_f32x16 acc;
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = 0.f;
     for (int i = 0; i < H0; ++i) {
@@ -157,16 +155,11 @@ extern "C" int dr_cin_fwd(const float* x0, const float* x, int64_t B, int32_t H0
     if (!x0 || !x || !W || !out) return DR_EINVAL;
     const size_t lds = (size_t)(H0 + Hk) * CIN_PITCH * sizeof(float);
     if (lds > 160 * 1024) return DR_ESHAPE;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(cin_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DR_ELAUNCH;
     const int64_t rows = B * D;
     const int64_t gx = (rows + CIN_ROWS - 1) / CIN_ROWS;
     if (gx > 0x7fffffff) return DR_EINVAL;
-    hipLaunchKernelGGL(cin_fwd_kernel, dim3((unsigned)gx, (unsigned)((Fm + 63) / 64)), dim3(256), lds, dr_s(stream), x0, x, B, H0, Hk,
-                       D, W, Fm, bias, act, out);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
+    return dr_launch(cin_fwd_kernel, dim3((unsigned)gx, (unsigned)((Fm + 63) / 64)), dim3(256), lds, dr_s(stream), x0, x, B, H0, Hk, D, W,
+                     Fm, bias, act, out);
 }
 
 extern "C" int dr_cin_bwd(const float* x0, const float* x, int64_t B, int32_t H0, int32_t Hk, int32_t D, const float* W,

@@ -23,10 +23,9 @@
 //           adds the partials in chunk order.
 #include "dr_common.h"
 #include "dr_cin_act.h"
+#include "dr_sum_partials.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CP_COLS = 64;          // (b, d) rows per block tile
 constexpr int CP_PITCH = 65;         // LDS pitch of one field's / feature map's row values (conflict-free per 32-lane half)
@@ -70,7 +69,7 @@ __global__ __launch_bounds__(256) void cin_pool_fwd_kernel(const float* __restri
             cp_lds[(size_t)fld * CP_PITCH + cc] = v;
         }
         __syncthreads();
-        f32x16 acc;
+        dr_f32x16 acc;
 #pragma unroll
         for (int k = 0; k < 16; ++k) acc[k] = 0.f;
         for (int i = 0; i < H0; ++i) {
@@ -191,11 +190,11 @@ __global__ __launch_bounds__(256) void cin_pool_bwd_dx_kernel(const float* __res
     const int dm = (int)(m - bm * D);
     float* mypx0 = px0 + (size_t)jh * H0 * CP_PITCH;
     for (int jt = jh; jt < njt; jt += 2) {
-        f32x16 ax;
+        dr_f32x16 ax;
 #pragma unroll
         for (int k = 0; k < 16; ++k) ax[k] = 0.f;
         for (int i = 0; i < H0; ++i) {
-            f32x16 T;
+            dr_f32x16 T;
 #pragma unroll
             for (int k = 0; k < 16; ++k) T[k] = 0.f;
             const float4* wp = Wp + ((int64_t)i * njt + jt) * fq * 64 + lane;
@@ -258,7 +257,7 @@ __global__ __launch_bounds__(256) void cin_pool_bwd_dw_kernel(const float* __res
     const int njt = min(4, cp_ceil(Hk - j0, 32));        // j-tiles of this super-tile (uniform)
     const bool wact = wave * 32 < nf && fb0 + wave * 32 < Fm;   // this wave's f-tile exists (uniform per wave)
     const bool do_bias = i == 0 && js == 0;
-    f32x16 acc[4];
+    dr_f32x16 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -315,18 +314,6 @@ __global__ __launch_bounds__(256) void cin_pool_bwd_dw_kernel(const float* __res
     }
 }
 
-// dW / dbias = the chunks' partials added in chunk order
-__global__ __launch_bounds__(256) void cin_pool_bwd_reduce_kernel(const float* __restrict__ part, int32_t chunks, int64_t nw, int32_t Fm,
-                                                                  float* __restrict__ dW, float* __restrict__ dbias) {
-    const int64_t total = nw + Fm, stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-        float s = 0.f;
-        for (int c = 0; c < chunks; ++c) s += part[(int64_t)c * total + t];
-        if (t < nw) dW[t] = s;
-        else if (dbias != nullptr) dbias[t - nw] = s;
-    }
-}
-
 struct CpPlan {
     int32_t njt, fq;          // dx: j-tiles of 32, f groups of 8
     int32_t nsj, nsf, nj, nf; // dw: super-tiles along j / f and a block's staged j / f rows
@@ -374,16 +361,11 @@ extern "C" int dr_cin_pool_fwd(const float* x0, const float* x, int64_t B, int32
     if (!x0 || !x || !W || (!out && !pooled)) return DR_EINVAL;
     const int64_t lds = ((int64_t)H0 + Hk + 64) * CP_PITCH * (int64_t)sizeof(float);
     if (lds > CP_LDS_MAX) return DR_ESHAPE;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(cin_pool_fwd_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DR_ELAUNCH;
     const int32_t E = D <= CP_COLS ? CP_COLS / D : 1;
     const int64_t gx = (B + E - 1) / E;
     if (gx > 0x7fffffff) return DR_EINVAL;
-    hipLaunchKernelGGL(cin_pool_fwd_kernel, dim3((unsigned)gx, (unsigned)((Fm + 63) / 64)), dim3(256), (size_t)lds, dr_s(stream), x0, x, B,
-                       H0, Hk, D, W, Fm, bias, act, out, pooled, E);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
+    return dr_launch(cin_pool_fwd_kernel, dim3((unsigned)gx, (unsigned)((Fm + 63) / 64)), dim3(256), (size_t)lds, dr_s(stream), x0, x, B, H0,
+                     Hk, D, W, Fm, bias, act, out, pooled, E);
 }
 
 extern "C" int64_t dr_cin_pool_bwd_workspace_bytes(int64_t B, int32_t H0, int32_t Hk, int32_t D, int32_t Fm) {
@@ -401,27 +383,21 @@ extern "C" int dr_cin_pool_bwd(const float* x0, const float* x, int64_t B, int32
     if (!x0 || !x || !W || !d_x0 || !d_x || !dW || (!d_out && !d_pooled) || (act != 0 && !out)) return DR_EINVAL;
     const CpPlan p = cp_plan(B, H0, Hk, D, Fm);
     if (p.lds_dx > CP_LDS_MAX || p.lds_dw > CP_LDS_MAX) return DR_ESHAPE;
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15) || ws_bytes < (p.wp_floats + p.part_floats) * (int64_t)sizeof(float)) return DR_EINVAL;
+    if (!ws || !dr_aligned16(ws) || ws_bytes < (p.wp_floats + p.part_floats) * (int64_t)sizeof(float)) return DR_EINVAL;
     const int64_t rows = B * D;
     const int64_t gx = (rows + CP_COLS - 1) / CP_COLS;
     if (gx > 0x7fffffff || H0 > 65535 || (int64_t)p.nsj * p.nsf > 65535) return DR_EINVAL;
-    if (p.lds_dx > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(cin_pool_bwd_dx_kernel),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_dx) != hipSuccess)
-        return DR_ELAUNCH;
-    if (p.lds_dw > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(cin_pool_bwd_dw_kernel),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_dw) != hipSuccess)
-        return DR_ELAUNCH;
     float4* Wp = static_cast<float4*>(ws);
     float* part = static_cast<float*>(ws) + p.wp_floats;
     hipLaunchKernelGGL(cin_pool_pack_w_kernel, dim3(dr_grid_for(p.wp_floats / 4, 256)), dim3(256), 0, dr_s(stream), W, H0, Hk, Fm, p.njt,
                        p.fq, Wp);
-    hipLaunchKernelGGL(cin_pool_bwd_dx_kernel, dim3((unsigned)gx), dim3(256), (size_t)p.lds_dx, dr_s(stream), x0, x, rows, H0, Hk, D, Wp, Fm,
+    int st = dr_launch(cin_pool_bwd_dx_kernel, dim3((unsigned)gx), dim3(256), (size_t)p.lds_dx, dr_s(stream), x0, x, rows, H0, Hk, D, Wp, Fm,
                        p.njt, p.fq, act, out, d_out, d_pooled, d_x0, accumulate_x0, d_x);
-    hipLaunchKernelGGL(cin_pool_bwd_dw_kernel, dim3((unsigned)p.chunks, (unsigned)H0, (unsigned)(p.nsj * p.nsf)), dim3(256), (size_t)p.lds_dw,
-                       dr_s(stream), x0, x, rows, p.chunk_rows, H0, Hk, D, Fm, p.nsj, p.nf, p.nj, act, out, d_out, d_pooled, part);
+    if (st != DR_OK) return st;
+    st = dr_launch(cin_pool_bwd_dw_kernel, dim3((unsigned)p.chunks, (unsigned)H0, (unsigned)(p.nsj * p.nsf)), dim3(256), (size_t)p.lds_dw,
+                   dr_s(stream), x0, x, rows, p.chunk_rows, H0, Hk, D, Fm, p.nsj, p.nf, p.nj, act, out, d_out, d_pooled, part);
+    if (st != DR_OK) return st;
+    // dW / dbias = the chunks' partials added in chunk order
     const int64_t nw = (int64_t)H0 * Hk * Fm;
-    hipLaunchKernelGGL(cin_pool_bwd_reduce_kernel, dim3(dr_grid_for(nw + Fm, 256)), dim3(256), 0, dr_s(stream), part, p.chunks, nw, Fm, dW,
-                       dbias);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
+    return dr_sum_partials(part, p.chunks, dW, nw, dbias, Fm, nullptr, 0, dr_grid_for(nw + Fm, 256), dr_s(stream));
 }

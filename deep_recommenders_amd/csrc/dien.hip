@@ -20,7 +20,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int GRU_MAX_H = 128;
 constexpr int GRU_MAX_BLOCKS = 512;
@@ -35,7 +34,6 @@ struct GruP {
     int32_t T, H;
 };
 
-__device__ __forceinline__ float gru_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ureg[tp][g][s][e] = U[k = 16 s + 4 q4 + e][g H + 16 jt + c] (zero beyond H), jt = wave + NW tp
 template <int JT, int NW, int TPW>
@@ -59,11 +57,11 @@ __device__ __forceinline__ void gru_load_u(const GruP& p, int wave, int c, int q
 // acc[tp][g] = rows of hl times the wave's columns of U
 template <int JT, int TPW>
 __device__ __forceinline__ void gru_h_times_u(const float* hl, int PH, int c, int q4, const float (&ureg)[TPW][3][JT][4],
-                                              f32x4 (&acc)[TPW][3]) {
+                                              dr_f32x4 (&acc)[TPW][3]) {
 #pragma unroll
     for (int tp = 0; tp < TPW; ++tp)
 #pragma unroll
-        for (int g = 0; g < 3; ++g) acc[tp][g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < 3; ++g) acc[tp][g] = (dr_f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < JT; ++s) {
         const float4 a4 = *reinterpret_cast<const float4*>(hl + c * PH + 16 * s + 4 * q4);
@@ -142,7 +140,7 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const GruP p) {
                     for (int g = 0; g < 3; ++g) x[tp][g][r] = xn[tp][g][r];
             }
             if (t + 1 < lmax) prefetch(t + 1);
-            f32x4 acc[TPW][3];
+            dr_f32x4 acc[TPW][3];
             gru_h_times_u<JT, TPW>(hl[cur], PH, c, q4, ureg, acc);
 #pragma unroll
             for (int tp = 0; tp < TPW; ++tp) {
@@ -154,8 +152,8 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const GruP p) {
                     if (j < H && b < p.B) {
                         float out = 0.f;
                         if (t < len[r]) {
-                            const float u = gru_sigmoid(x[tp][0][r] + acc[tp][0][r]);
-                            const float rg = gru_sigmoid(x[tp][1][r] + acc[tp][1][r]);
+                            const float u = dr_sigmoidf(x[tp][0][r] + acc[tp][0][r]);
+                            const float rg = dr_sigmoidf(x[tp][1][r] + acc[tp][1][r]);
                             const float cc = tanhf(fmaf(rg, acc[tp][2][r], x[tp][2][r]));
                             const float up = p.att != nullptr ? a[r] * u : u;
                             h[tp][r] = fmaf(up, cc - h[tp][r], h[tp][r]);
@@ -297,7 +295,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const GruP p) {
                 prefetch(t - 1);
                 load_hprev(t - 1);
             }
-            f32x4 acc[TPW][3];
+            dr_f32x4 acc[TPW][3];
             gru_h_times_u<JT, TPW>(hl[cur], PH, c, q4, ureg, acc);
             float part[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -314,8 +312,8 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const GruP p) {
                         if (t < len[r]) {
                             const float hp = hl[cur][ex * PH + j];
                             const float gc = acc[tp][2][r];
-                            const float u = gru_sigmoid(x[tp][0][r] + acc[tp][0][r]);
-                            const float rg = gru_sigmoid(x[tp][1][r] + acc[tp][1][r]);
+                            const float u = dr_sigmoidf(x[tp][0][r] + acc[tp][0][r]);
+                            const float rg = dr_sigmoidf(x[tp][1][r] + acc[tp][1][r]);
                             const float cc = tanhf(fmaf(rg, gc, x[tp][2][r]));
                             const float up = p.att != nullptr ? a[r] * u : u;
                             const float d = dh[tp][r] + dv[tp][r];
@@ -358,9 +356,9 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const GruP p) {
                 p.d_att[(b0 + threadIdx.x) * T + t] = s;
             }
             // dh_prev += dg U^T
-            f32x4 acc2[TPW];
+            dr_f32x4 acc2[TPW];
 #pragma unroll
-            for (int tp = 0; tp < TPW; ++tp) acc2[tp] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int tp = 0; tp < TPW; ++tp) acc2[tp] = (dr_f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int g = 0; g < 3; ++g)
 #pragma unroll
@@ -475,16 +473,12 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(const float* __restri
     }
 }
 
-bool gru_aligned(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-
 // DR_OK inside the domain of all five entry points
 int gru_domain(int64_t B, int32_t T, int32_t H) {
     if (B < 0 || T < 1 || H < 4 || (H & 3)) return DR_EINVAL;
     if (H > GRU_MAX_H || B * (int64_t)T > (int64_t)1 << 40) return DR_ESHAPE;
     return DR_OK;
 }
-
-bool gru_ld_ok(int64_t ld, int width) { return (ld & 3) == 0 && ld >= width; }
 
 int64_t gru_dw_ws_bytes(int64_t B, int32_t T, int32_t H) {
     const int64_t a = dr_linear_bwd_dw_workspace_bytes(B * T, H, 3 * H), b = dr_linear_bwd_dw_workspace_bytes(B, H, 3 * H);
@@ -495,9 +489,7 @@ template <typename K>
 int gru_launch(K kernel, int JT, const GruP& p, dr_stream_t stream) {
     const int nw = JT < 4 ? JT : 4;
     const int64_t grid = p.ntiles < GRU_MAX_BLOCKS ? p.ntiles : GRU_MAX_BLOCKS;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64 * nw), 0, dr_s(stream), p);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
+    return dr_launch(kernel, dim3((unsigned)grid), dim3(64 * nw), 0, dr_s(stream), p);
 }
 
 }  // namespace
@@ -518,10 +510,10 @@ extern "C" int dr_gru_seq_fwd(const float* xp, int64_t ld_xp, const float* U, co
                               int64_t B, int32_t T, int32_t H, float* hs, int64_t ld_hs, float* h_last, dr_stream_t stream) {
     const int st = gru_domain(B, T, H);
     if (st != DR_OK) return st;
-    if (!gru_ld_ok(ld_xp, 3 * H) || !gru_ld_ok(ld_hs, H)) return DR_EINVAL;
+    if (dr_bad_ld(ld_xp, 3 * H) || dr_bad_ld(ld_hs, H)) return DR_EINVAL;
     if (B == 0) return DR_OK;
     if (!xp || !U || !hs || !h_last) return DR_EINVAL;
-    if (!gru_aligned(xp) || !gru_aligned(hs) || !gru_aligned(h0)) return DR_EINVAL;
+    if (!dr_aligned16(xp) || !dr_aligned16(hs) || !dr_aligned16(h0)) return DR_EINVAL;
     GruP p = {};
     p.xp = xp; p.ld_xp = ld_xp; p.U = U; p.h0 = h0; p.lengths = lengths; p.att = att;
     p.hs = hs; p.ld_hs = ld_hs; p.h_last = h_last;
@@ -542,11 +534,11 @@ extern "C" int dr_gru_seq_bwd(const float* xp, int64_t ld_xp, const float* U, co
                               int64_t ws_bytes, dr_stream_t stream) {
     const int st = gru_domain(B, T, H);
     if (st != DR_OK) return st;
-    if (!gru_ld_ok(ld_xp, 3 * H) || !gru_ld_ok(ld_hs, H) || !gru_ld_ok(ld_dxp, 3 * H)) return DR_EINVAL;
-    if (d_hs != nullptr && !gru_ld_ok(ld_dhs, H)) return DR_EINVAL;
+    if (dr_bad_ld(ld_xp, 3 * H) || dr_bad_ld(ld_hs, H) || dr_bad_ld(ld_dxp, 3 * H)) return DR_EINVAL;
+    if (d_hs != nullptr && dr_bad_ld(ld_dhs, H)) return DR_EINVAL;
     if (B == 0) return DR_OK;
     if (!xp || !U || !hs || !d_xp || !dU || !ws) return DR_EINVAL;
-    if (!gru_aligned(xp) || !gru_aligned(hs) || !gru_aligned(d_xp) || !gru_aligned(ws) || !gru_aligned(h0) || !gru_aligned(d_hs))
+    if (!dr_aligned16(xp) || !dr_aligned16(hs) || !dr_aligned16(d_xp) || !dr_aligned16(ws) || !dr_aligned16(h0) || !dr_aligned16(d_hs))
         return DR_EINVAL;
     if (ws_bytes < dr_gru_seq_bwd_workspace_bytes(B, T, H)) return DR_EINVAL;
     GruP p = {};
@@ -572,9 +564,9 @@ extern "C" int dr_seq_attn_fwd(const float* hs, int64_t ld_hs, const float* q, c
                                float* a, dr_stream_t stream) {
     const int st = gru_domain(B, T, H);
     if (st != DR_OK) return st;
-    if (!gru_ld_ok(ld_hs, H)) return DR_EINVAL;
+    if (dr_bad_ld(ld_hs, H)) return DR_EINVAL;
     if (B == 0) return DR_OK;
-    if (!hs || !q || !a || !gru_aligned(hs) || !gru_aligned(q)) return DR_EINVAL;
+    if (!hs || !q || !a || !dr_aligned16(hs) || !dr_aligned16(q)) return DR_EINVAL;
     hipLaunchKernelGGL(seq_attn_fwd_kernel, dim3(dr_grid_for(B, 4)), dim3(256), 0, dr_s(stream), hs, ld_hs, q, lengths, B, T, H, a);
     DR_CHECK_LAUNCH();
     return DR_OK;
@@ -584,9 +576,9 @@ extern "C" int dr_seq_attn_bwd(const float* hs, int64_t ld_hs, const float* q, c
                                int64_t B, int32_t T, int32_t H, float* d_hs, int64_t ld_dhs, float* d_q, dr_stream_t stream) {
     const int st = gru_domain(B, T, H);
     if (st != DR_OK) return st;
-    if (!gru_ld_ok(ld_hs, H) || !gru_ld_ok(ld_dhs, H)) return DR_EINVAL;
+    if (dr_bad_ld(ld_hs, H) || dr_bad_ld(ld_dhs, H)) return DR_EINVAL;
     if (B == 0) return DR_OK;
-    if (!hs || !q || !a || !d_a || !d_hs || !d_q || !gru_aligned(hs) || !gru_aligned(q) || !gru_aligned(d_hs)) return DR_EINVAL;
+    if (!hs || !q || !a || !d_a || !d_hs || !d_q || !dr_aligned16(hs) || !dr_aligned16(q) || !dr_aligned16(d_hs)) return DR_EINVAL;
     hipLaunchKernelGGL(seq_attn_bwd_kernel, dim3(dr_grid_for(B, 4)), dim3(256), 0, dr_s(stream), hs, ld_hs, q, lengths, a, d_a, B, T, H,
                        d_hs, ld_dhs, d_q);
     DR_CHECK_LAUNCH();

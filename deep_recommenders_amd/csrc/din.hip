@@ -30,13 +30,9 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float din_sigmoid(float z) { return 1.f / (1.f + expf(-z)); }
-
 // Dice of one element given its row's mean m and r = 1 / sqrt(s + eps): p, the PReLU output and y
 __device__ __forceinline__ float dice_elem(float x, float al, float m, float r, float& p, float& pre) {
-    p = din_sigmoid((x - m) * r);
+    p = dr_sigmoidf((x - m) * r);
     pre = fmaxf(x, 0.f) - al * fmaxf(-x, 0.f);
     return pre > 0.f ? p * pre : (1.f - p) * pre;
 }
@@ -290,23 +286,23 @@ __device__ __forceinline__ void pool_setup(const PoolP& p, int64_t b, float* Ws,
 
 // the wave's 16 keys as the MFMA operand: kreg[c][e] = key[16c + 4g + e]; zeros for a key that is masked or outside T
 template <int NC>
-__device__ __forceinline__ void pool_load_keys(f4 (&kreg)[NC], const float* kp, bool valid, int D, int g) {
+__device__ __forceinline__ void pool_load_keys(dr_f32x4 (&kreg)[NC], const float* kp, bool valid, int D, int g) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const int d0 = 16 * c + 4 * g;
-        kreg[c] = f4{0.f, 0.f, 0.f, 0.f};
-        if (valid && d0 < D) kreg[c] = *reinterpret_cast<const f4*>(kp + d0);
+        kreg[c] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
+        if (valid && d0 < D) kreg[c] = *reinterpret_cast<const dr_f32x4*>(kp + d0);
     }
 }
 
 // h[ut][r] = hq[u] + sum_d key[d] Weff[d][u] for the lane's key, u = 16 ut + 4 g + r
 template <int NC, int NU>
-__device__ __forceinline__ void pool_hidden(const float* Ws, const float* hq, const f4 (&kreg)[NC], f4 (&h)[NU], int D16, int U16, int i16,
+__device__ __forceinline__ void pool_hidden(const float* Ws, const float* hq, const dr_f32x4 (&kreg)[NC], dr_f32x4 (&h)[NU], int D16, int U16, int i16,
                                             int g) {
     const int LS = U16 + 4;
 #pragma unroll
     for (int ut = 0; ut < NU; ++ut) {
-        f4 acc = {0.f, 0.f, 0.f, 0.f};
+        dr_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         if (16 * ut < U16) {
 #pragma unroll
             for (int c = 0; c < NC; ++c)
@@ -324,7 +320,7 @@ __device__ __forceinline__ void pool_hidden(const float* Ws, const float* hq, co
 
 // a = act(h) over the lane's hidden units (0 beyond U); for Dice also the row's (m, s, r).  Returns the key's score without b_out.
 template <int NU>
-__device__ __forceinline__ float pool_act(const PoolP& p, const f4 (&h)[NU], f4 (&a)[NU], const float* wo, const float* al, int g, float& m,
+__device__ __forceinline__ float pool_act(const PoolP& p, const dr_f32x4 (&h)[NU], dr_f32x4 (&a)[NU], const float* wo, const float* al, int g, float& m,
                                           float& s, float& r) {
     const int U = p.U;
     m = s = r = 0.f;
@@ -355,7 +351,7 @@ __device__ __forceinline__ float pool_act(const PoolP& p, const f4 (&h)[NU], f4 
             if (u < U) {
                 const float x = h[ut][q];
                 float pp, pre;
-                v = p.act == 1 ? fmaxf(x, 0.f) : p.act == 2 ? din_sigmoid(x) : p.act == 3 ? tanhf(x) : p.act == 4 ? dice_elem(x, al[u], m, r, pp, pre) : x;
+                v = p.act == 1 ? fmaxf(x, 0.f) : p.act == 2 ? dr_sigmoidf(x) : p.act == 3 ? tanhf(x) : p.act == 4 ? dice_elem(x, al[u], m, r, pp, pre) : x;
                 sc = fmaf(v, wo[u], sc);
             }
             a[ut][q] = v;
@@ -378,16 +374,16 @@ __global__ __launch_bounds__(256) void din_pool_fwd_kernel(const PoolP p) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i16 = lane & 15, g = lane >> 4;
     pool_setup(p, b, Ws, nullptr, qs, hq, hqp, wo, al);
     const float b_out = p.b_out ? p.b_out[0] : 0.f;
-    f4 oacc[NC];
+    dr_f32x4 oacc[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) oacc[c] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < NC; ++c) oacc[c] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
     for (int t0 = wave * 16; t0 < T; t0 += 64) {
         const int t = t0 + i16;
         const bool inr = t < T;
         const bool valid = inr && (!p.mask || p.mask[b * T + t] != 0);
         float score = 0.f;
         if (__ballot(valid) != 0ull) {
-            f4 kreg[NC], h[NU], a[NU];
+            dr_f32x4 kreg[NC], h[NU], a[NU];
             pool_load_keys<NC>(kreg, p.keys + (b * T + t) * p.ld_k, valid, D, g);
             pool_hidden<NC, NU>(Ws, hq, kreg, h, D16, U16, i16, g);
             float m, s, r;
@@ -432,34 +428,34 @@ __global__ __launch_bounds__(256) void din_pool_bwd_kernel(const PoolP p) {
     const float b_out = p.b_out ? p.b_out[0] : 0.f;
     const int64_t per = (p.B + p.nblk - 1) / p.nblk;
     const int64_t b_begin = blockIdx.x * per, b_end = b_begin + per < p.B ? b_begin + per : p.B;
-    f4 wacc[NU], aacc[NU];                                     // d_w_out and dalpha of this block's examples
+    dr_f32x4 wacc[NU], aacc[NU];                                     // d_w_out and dalpha of this block's examples
 #pragma unroll
-    for (int ut = 0; ut < NU; ++ut) wacc[ut] = aacc[ut] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int ut = 0; ut < NU; ++ut) wacc[ut] = aacc[ut] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
     float boacc = 0.f;
     for (int64_t b = b_begin; b < b_end; ++b) {
         __syncthreads();                                       // the previous example's readers of the LDS image
         pool_setup(p, b, Ws, W2s, qs, hq, redu, wo, al);       // redu doubles as the setup's scratch
-        f4 doreg[NC], dqacc[NC], dhq[NU];
+        dr_f32x4 doreg[NC], dqacc[NC], dhq[NU];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int d0 = 16 * c + 4 * g;
-            doreg[c] = dqacc[c] = f4{0.f, 0.f, 0.f, 0.f};
-            if (d0 < D) doreg[c] = *reinterpret_cast<const f4*>(p.d_out + b * p.ld_do + d0);
+            doreg[c] = dqacc[c] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
+            if (d0 < D) doreg[c] = *reinterpret_cast<const dr_f32x4*>(p.d_out + b * p.ld_do + d0);
         }
 #pragma unroll
-        for (int ut = 0; ut < NU; ++ut) dhq[ut] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int ut = 0; ut < NU; ++ut) dhq[ut] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
         for (int t0 = wave * 16; t0 < T; t0 += 64) {
             const int t = t0 + i16;
             const bool inr = t < T;
             const bool valid = inr && (!p.mask || p.mask[b * T + t] != 0);
             const int64_t n = b * T + t;
-            f4 dh[NU], dk[NC];
+            dr_f32x4 dh[NU], dk[NC];
 #pragma unroll
-            for (int ut = 0; ut < NU; ++ut) dh[ut] = f4{0.f, 0.f, 0.f, 0.f};
+            for (int ut = 0; ut < NU; ++ut) dh[ut] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int c = 0; c < NC; ++c) dk[c] = f4{0.f, 0.f, 0.f, 0.f};
+            for (int c = 0; c < NC; ++c) dk[c] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
             if (__ballot(valid) != 0ull) {
-                f4 kreg[NC], h[NU], a[NU];
+                dr_f32x4 kreg[NC], h[NU], a[NU];
                 pool_load_keys<NC>(kreg, p.keys + n * p.ld_k, valid, D, g);
                 pool_hidden<NC, NU>(Ws, hq, kreg, h, D16, U16, i16, g);
                 float m, s, r;
@@ -475,7 +471,7 @@ __global__ __launch_bounds__(256) void din_pool_bwd_kernel(const PoolP p) {
                 if (g == 0) boacc += ds;
                 // dH of the lane's key
                 float csum = 0.f, cxsum = 0.f;
-                f4 dpre[NU];
+                dr_f32x4 dpre[NU];
 #pragma unroll
                 for (int ut = 0; ut < NU; ++ut)
 #pragma unroll
@@ -513,19 +509,19 @@ __global__ __launch_bounds__(256) void din_pool_bwd_kernel(const PoolP p) {
 #pragma unroll
                 for (int ut = 0; ut < NU; ++ut) dhq[ut] += dh[ut];
                 // d_keys^T = Weff dH^T (and E^T = W[2D:3D] dH^T for the query's share in mode 2): dk[c][r'] = column 16c + 4g + r'
-                f4 ek[NC];
+                dr_f32x4 ek[NC];
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    ek[c] = f4{0.f, 0.f, 0.f, 0.f};
+                    ek[c] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
                     if (16 * c < D16) {
 #pragma unroll
                         for (int ut = 0; ut < NU; ++ut)
                             if (16 * ut < U16) {
-                                const f4 w = *reinterpret_cast<const f4*>(Ws + (16 * c + i16) * LS + 16 * ut + 4 * g);
+                                const dr_f32x4 w = *reinterpret_cast<const dr_f32x4*>(Ws + (16 * c + i16) * LS + 16 * ut + 4 * g);
 #pragma unroll
                                 for (int q = 0; q < 4; ++q) dk[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[q], dh[ut][q], dk[c], 0, 0, 0);
                                 if (W2s) {
-                                    const f4 w2 = *reinterpret_cast<const f4*>(W2s + (16 * c + i16) * LS + 16 * ut + 4 * g);
+                                    const dr_f32x4 w2 = *reinterpret_cast<const dr_f32x4*>(W2s + (16 * c + i16) * LS + 16 * ut + 4 * g);
 #pragma unroll
                                     for (int q = 0; q < 4; ++q) ek[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2[q], dh[ut][q], ek[c], 0, 0, 0);
                                 }
@@ -535,7 +531,7 @@ __global__ __launch_bounds__(256) void din_pool_bwd_kernel(const PoolP p) {
                         dk[c] += sc * doreg[c];
                         dqacc[c] += kreg[c] * ek[c];
                     } else {
-                        dk[c] = f4{0.f, 0.f, 0.f, 0.f};
+                        dk[c] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
                     }
                 }
             }
@@ -550,7 +546,7 @@ __global__ __launch_bounds__(256) void din_pool_bwd_kernel(const PoolP p) {
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
                     const int d0 = 16 * c + 4 * g;
-                    if (d0 < D) *reinterpret_cast<f4*>(p.d_keys + n * p.ld_dk + d0) = dk[c];
+                    if (d0 < D) *reinterpret_cast<dr_f32x4*>(p.d_keys + n * p.ld_dk + d0) = dk[c];
                 }
             }
         }
@@ -635,13 +631,13 @@ __global__ __launch_bounds__(256) void din_pool_wgrad_kernel(const PoolP p) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i16 = lane & 15, g = lane >> 4;
     const int64_t rows = p.B * T;
     const int64_t n_begin = blockIdx.x * p.rows_per_chunk, n_end = n_begin + p.rows_per_chunk < rows ? n_begin + p.rows_per_chunk : rows;
-    f4 acc0[NDW][NU], acc1[NDW][NU], acc2[NDW][NU];
+    dr_f32x4 acc0[NDW][NU], acc1[NDW][NU], acc2[NDW][NU];
     float dbacc[NU];
 #pragma unroll
     for (int ut = 0; ut < NU; ++ut) {
         dbacc[ut] = 0.f;
 #pragma unroll
-        for (int i = 0; i < NDW; ++i) acc0[i][ut] = acc1[i][ut] = acc2[i][ut] = f4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < NDW; ++i) acc0[i][ut] = acc1[i][ut] = acc2[i][ut] = dr_f32x4{0.f, 0.f, 0.f, 0.f};
     }
     for (int64_t n0 = n_begin; n0 < n_end; n0 += 4) {
         const int64_t n = n0 + g;
@@ -764,33 +760,24 @@ inline int64_t pool_rows_per_chunk(int64_t rows) {
 inline int64_t pool_chunks(int64_t rows) { return std::max<int64_t>(1, (rows + pool_rows_per_chunk(rows) - 1) / pool_rows_per_chunk(rows)); }
 
 inline bool pool_domain(int32_t T, int32_t D, int32_t U) { return D % 4 == 0 && D >= 4 && D <= 128 && U >= 1 && U <= 128 && T >= 1; }
-inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
 
-template <typename K>
-int pool_launch(K kernel, int64_t grid, size_t lds_bytes, const PoolP& p, hipStream_t s) {
-    if (lds_bytes > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-        return DR_ELAUNCH;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds_bytes, s, p);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
-}
-
-// instantiations: D <= 32 / 64 / 128 and U <= 32 / 64 / 128 (the loops skip the 16-blocks beyond round16(D), round16(U))
-#define DIN_DISPATCH(KERNEL, grid, lds_bytes)                                                              \
-    do {                                                                                                   \
+// instantiations: D <= 32 / 64 / 128 and U <= 32 / 64 / 128 (the loops skip the 16-blocks beyond round16(D), round16(U)); these kernels
+// opt in to large dynamic LDS from 48 KiB
+#define DIN_DISPATCH(KERNEL, grid, lds_bytes)                                                               \
+    do {                                                                                                    \
         const int nc_ = p.D16 <= 32 ? 2 : p.D16 <= 64 ? 4 : 8, nu_ = p.U16 <= 32 ? 2 : p.U16 <= 64 ? 4 : 8; \
-        int st_;                                                                                           \
-        if (nc_ == 2 && nu_ == 2) st_ = pool_launch(KERNEL<2, 2>, grid, lds_bytes, p, s);                  \
-        else if (nc_ == 2 && nu_ == 4) st_ = pool_launch(KERNEL<2, 4>, grid, lds_bytes, p, s);             \
-        else if (nc_ == 2) st_ = pool_launch(KERNEL<2, 8>, grid, lds_bytes, p, s);                         \
-        else if (nc_ == 4 && nu_ == 2) st_ = pool_launch(KERNEL<4, 2>, grid, lds_bytes, p, s);             \
-        else if (nc_ == 4 && nu_ == 4) st_ = pool_launch(KERNEL<4, 4>, grid, lds_bytes, p, s);             \
-        else if (nc_ == 4) st_ = pool_launch(KERNEL<4, 8>, grid, lds_bytes, p, s);                         \
-        else if (nu_ == 2) st_ = pool_launch(KERNEL<8, 2>, grid, lds_bytes, p, s);                         \
-        else if (nu_ == 4) st_ = pool_launch(KERNEL<8, 4>, grid, lds_bytes, p, s);                         \
-        else st_ = pool_launch(KERNEL<8, 8>, grid, lds_bytes, p, s);                                       \
-        if (st_ != DR_OK) return st_;                                                                      \
+        const dim3 g_((unsigned)(grid));                                                                    \
+        int st_;                                                                                            \
+        if (nc_ == 2 && nu_ == 2) st_ = dr_launch<48>(KERNEL<2, 2>, g_, dim3(256), lds_bytes, s, p);        \
+        else if (nc_ == 2 && nu_ == 4) st_ = dr_launch<48>(KERNEL<2, 4>, g_, dim3(256), lds_bytes, s, p);   \
+        else if (nc_ == 2) st_ = dr_launch<48>(KERNEL<2, 8>, g_, dim3(256), lds_bytes, s, p);               \
+        else if (nc_ == 4 && nu_ == 2) st_ = dr_launch<48>(KERNEL<4, 2>, g_, dim3(256), lds_bytes, s, p);   \
+        else if (nc_ == 4 && nu_ == 4) st_ = dr_launch<48>(KERNEL<4, 4>, g_, dim3(256), lds_bytes, s, p);   \
+        else if (nc_ == 4) st_ = dr_launch<48>(KERNEL<4, 8>, g_, dim3(256), lds_bytes, s, p);               \
+        else if (nu_ == 2) st_ = dr_launch<48>(KERNEL<8, 2>, g_, dim3(256), lds_bytes, s, p);               \
+        else if (nu_ == 4) st_ = dr_launch<48>(KERNEL<8, 4>, g_, dim3(256), lds_bytes, s, p);               \
+        else st_ = dr_launch<48>(KERNEL<8, 8>, g_, dim3(256), lds_bytes, s, p);                             \
+        if (st_ != DR_OK) return st_;                                                                       \
     } while (0)
 
 }  // namespace
@@ -846,7 +833,7 @@ static int din_pool_params(PoolP& p, const float* query, int64_t ld_q, const flo
                            int32_t U, int32_t mode, int32_t act, float eps) {
     if (B < 0 || !pool_domain(T, D, U)) return DR_ESHAPE;
     if (mode < 0 || mode > 2 || act < 0 || act > 4 || (act == 4 && !alpha)) return DR_EINVAL;
-    if (B > 0 && (!query || !keys || !W || !w_out || ld_q < D || ld_k < D || (ld_k & 3) || !aligned16(keys))) return DR_EINVAL;
+    if (B > 0 && (!query || !keys || !W || !w_out || ld_q < D || dr_bad_ld(ld_k, D) || !dr_aligned16(keys))) return DR_EINVAL;
     p = PoolP{};
     p.q = query; p.keys = keys; p.mask = mask; p.W = W; p.b = b; p.w_out = w_out; p.b_out = b_out; p.alpha = act == 4 ? alpha : nullptr;
     p.ld_q = ld_q; p.ld_k = ld_k; p.B = B; p.T = T; p.D = D; p.U = U; p.D16 = pool_round16(D); p.U16 = pool_round16(U);
@@ -895,8 +882,8 @@ extern "C" int dr_din_pool_bwd(const float* query, int64_t ld_q, const float* ke
         if (dalpha && hipMemsetAsync(dalpha, 0, (size_t)U * sizeof(float), s) != hipSuccess) return DR_ELAUNCH;
         return DR_OK;
     }
-    if (!d_out || !d_query || !d_keys || !workspace || ld_do < D || ld_dq < D || ld_dk < D || (ld_do & 3) || (ld_dk & 3) || !aligned16(d_out) ||
-        !aligned16(d_keys) || !aligned16(workspace))
+    if (!d_out || !d_query || !d_keys || !workspace || dr_bad_ld(ld_do, D) || ld_dq < D || dr_bad_ld(ld_dk, D) || !dr_aligned16(d_out) ||
+        !dr_aligned16(d_keys) || !dr_aligned16(workspace))
         return DR_EINVAL;
     if (workspace_bytes < dr_din_pool_bwd_workspace_bytes(B, T, D, U)) return DR_EINVAL;
     const int64_t rows = B * T, chunks = pool_chunks(rows);

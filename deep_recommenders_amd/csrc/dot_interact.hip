@@ -23,8 +23,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int DI_WAVES = 4;          // examples per block
 constexpr int DI_MAX_N = 64;
 constexpr int DI_MAX_D = 256;
@@ -56,9 +54,9 @@ __global__ __launch_bounds__(256) void dot_interact_fwd_kernel(const DiP p) {
     const int64_t b = (int64_t)blockIdx.x * DI_WAVES + wave;
     if (b >= p.B) return;                                      // wave-uniform; the kernel has no barrier
     constexpr int NACC = NT * (NT + 1) / 2;
-    f32x4 acc[NACC];
+    dr_f32x4 acc[NACC];
 #pragma unroll
-    for (int t = 0; t < NACC; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < NACC; ++t) acc[t] = (dr_f32x4){0.f, 0.f, 0.f, 0.f};
     const float* row[NT];
     bool rv[NT];
 #pragma unroll
@@ -149,11 +147,11 @@ __global__ __launch_bounds__(256) void dot_interact_bwd_kernel(const DiP p) {
     for (int blk = 0; blk < nblk; ++blk) {
         const int d = 64 * blk + 4 * c;
         const bool dv = d < p.D;                               // D % 4 == 0: a float4 of columns is whole or absent
-        f32x4 acc[NT][4];
+        dr_f32x4 acc[NT][4];
 #pragma unroll
         for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[ti][e] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int e = 0; e < 4; ++e) acc[ti][e] = (dr_f32x4){0.f, 0.f, 0.f, 0.f};
         auto load = [&](int ks) {                                // row 4 ks + q of T, columns d .. d + 3; zero beyond N and D
             const int k = 4 * ks + q;
             return (dv && k < p.N) ? *reinterpret_cast<const float4*>(di_row(p, b, k) + d) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -192,16 +190,14 @@ __global__ __launch_bounds__(256) void dot_interact_bwd_kernel(const DiP p) {
     }
 }
 
-bool di_aligned(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-
 // fills the sizes; DR_OK, or DR_EINVAL outside the domain
 int di_sizes(DiP& p, const float* dense, int64_t ld_dense, const float* emb, int64_t ld_emb, int64_t B, int32_t F, int32_t D,
              int32_t self) {
     if (B < 0 || F < 1 || D < 4 || D > DI_MAX_D || (D & 3) || (self != 0 && self != 1)) return DR_EINVAL;
     const int32_t N = F + (dense != nullptr ? 1 : 0);
     if (N < 2 || N > DI_MAX_N) return DR_EINVAL;
-    if ((ld_emb & 3) || ld_emb < (int64_t)F * D) return DR_EINVAL;
-    if (dense != nullptr && ((ld_dense & 3) || ld_dense < D)) return DR_EINVAL;
+    if (dr_bad_ld(ld_emb, (int64_t)F * D)) return DR_EINVAL;
+    if (dense != nullptr && dr_bad_ld(ld_dense, D)) return DR_EINVAL;
     p.dense = dense; p.ld_dense = ld_dense; p.emb = emb; p.ld_emb = ld_emb;
     p.B = B; p.F = F; p.D = D; p.N = N; p.self = self;
     p.c0 = dense != nullptr ? D : 0;
@@ -211,12 +207,12 @@ int di_sizes(DiP& p, const float* dense, int64_t ld_dense, const float* emb, int
 
 }  // namespace
 
-#define DI_DISPATCH(kernel, nt, grid, lds)                                                                        \
-    switch (nt) {                                                                                                  \
-        case 1: hipLaunchKernelGGL(kernel<1>, dim3((unsigned)(grid)), dim3(256), (lds), dr_s(stream), p); break;   \
-        case 2: hipLaunchKernelGGL(kernel<2>, dim3((unsigned)(grid)), dim3(256), (lds), dr_s(stream), p); break;   \
-        case 3: hipLaunchKernelGGL(kernel<3>, dim3((unsigned)(grid)), dim3(256), (lds), dr_s(stream), p); break;   \
-        default: hipLaunchKernelGGL(kernel<4>, dim3((unsigned)(grid)), dim3(256), (lds), dr_s(stream), p); break;  \
+#define DI_DISPATCH(kernel, nt, grid, lds)                                                               \
+    switch (nt) {                                                                                         \
+        case 1: return dr_launch(kernel<1>, dim3((unsigned)(grid)), dim3(256), (lds), dr_s(stream), p);   \
+        case 2: return dr_launch(kernel<2>, dim3((unsigned)(grid)), dim3(256), (lds), dr_s(stream), p);   \
+        case 3: return dr_launch(kernel<3>, dim3((unsigned)(grid)), dim3(256), (lds), dr_s(stream), p);   \
+        default: return dr_launch(kernel<4>, dim3((unsigned)(grid)), dim3(256), (lds), dr_s(stream), p);  \
     }
 
 extern "C" int dr_dot_interact_fwd(const float* dense, int64_t ld_dense, const float* emb, int64_t ld_emb, int64_t B, int32_t F, int32_t D,
@@ -224,16 +220,14 @@ extern "C" int dr_dot_interact_fwd(const float* dense, int64_t ld_dense, const f
     DiP p = {};
     const int st = di_sizes(p, dense, ld_dense, emb, ld_emb, B, F, D, self_interaction);
     if (st != DR_OK) return st;
-    if ((ld_out & 3) || ld_out < (int64_t)p.c0 + p.P) return DR_EINVAL;
+    if (dr_bad_ld(ld_out, (int64_t)p.c0 + p.P)) return DR_EINVAL;
     if (B == 0) return DR_OK;                                  // nothing to read or write: empty tensors have no address
-    if (!emb || !out || !di_aligned(emb) || !di_aligned(dense)) return DR_EINVAL;
+    if (!emb || !out || !dr_aligned16(emb) || !dr_aligned16(dense)) return DR_EINVAL;
     const int64_t grid = (B + DI_WAVES - 1) / DI_WAVES;
     if (grid > 0x7fffffff) return DR_EINVAL;
     p.out = out; p.ld_out = ld_out;
     const int nt = (p.N + 15) / 16;
     DI_DISPATCH(dot_interact_fwd_kernel, nt, grid, 0);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
 }
 
 extern "C" int dr_dot_interact_bwd(const float* dense, int64_t ld_dense, const float* emb, int64_t ld_emb, const float* d_out,
@@ -242,21 +236,16 @@ extern "C" int dr_dot_interact_bwd(const float* dense, int64_t ld_dense, const f
     DiP p = {};
     const int st = di_sizes(p, dense, ld_dense, emb, ld_emb, B, F, D, self_interaction);
     if (st != DR_OK) return st;
-    if ((ld_dout & 3) || ld_dout < (int64_t)p.c0 + p.P || (ld_demb & 3) || ld_demb < (int64_t)F * D) return DR_EINVAL;
-    if (dense != nullptr && ((ld_ddense & 3) || ld_ddense < D)) return DR_EINVAL;
+    if (dr_bad_ld(ld_dout, (int64_t)p.c0 + p.P) || dr_bad_ld(ld_demb, (int64_t)F * D)) return DR_EINVAL;
+    if (dense != nullptr && dr_bad_ld(ld_ddense, D)) return DR_EINVAL;
     if (B == 0) return DR_OK;
     if (!emb || !d_out || !d_emb || (dense != nullptr && !d_dense)) return DR_EINVAL;
-    if (!di_aligned(emb) || !di_aligned(dense) || !di_aligned(d_emb) || (dense != nullptr && !di_aligned(d_dense))) return DR_EINVAL;
+    if (!dr_aligned16(emb) || !dr_aligned16(dense) || !dr_aligned16(d_emb) || (dense != nullptr && !dr_aligned16(d_dense))) return DR_EINVAL;
     const int64_t grid = (B + DI_WAVES - 1) / DI_WAVES;
     if (grid > 0x7fffffff) return DR_EINVAL;
     p.d_out = d_out; p.ld_dout = ld_dout; p.d_dense = d_dense; p.ld_ddense = ld_ddense; p.d_emb = d_emb; p.ld_demb = ld_demb;
     const int nt = (p.N + 15) / 16;
-    const size_t lds = (size_t)DI_WAVES * 16 * nt * (4 * ((p.N + 3) / 4) + 1) * sizeof(float);   // at most 4 x 64 x 65 floats = 65 KB
-    if (lds > 64 * 1024 &&                                     // N >= 61 only, so NT = 4
-        hipFuncSetAttribute(reinterpret_cast<const void*>(dot_interact_bwd_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return DR_ELAUNCH;
+    // at most 4 x 64 x 65 floats = 65 KB: above the 64 KiB that need the opt-in for N >= 61 only, so NT = 4
+    const size_t lds = (size_t)DI_WAVES * 16 * nt * (4 * ((p.N + 3) / 4) + 1) * sizeof(float);
     DI_DISPATCH(dot_interact_bwd_kernel, nt, grid, lds);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
 }

@@ -22,10 +22,51 @@ static inline int dr_grid_for(int64_t work_items, int items_per_block, int max_b
     return (int)g;
 }
 
+// ---- argument checks shared by the entry points ----
+// float4 access needs a 16-byte address; a null pointer is aligned (whether it may be null is the caller's test)
+static inline bool dr_aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
+// a row pitch in floats that float4 rows of `width` floats cannot use
+static inline bool dr_bad_ld(int64_t ld, int64_t width) { return (ld & 3) != 0 || ld < width; }
+// the smallest power of two >= n (1 for n <= 1)
+static inline int dr_pow2_ceil(int n) { int v = 1; while (v < n) v <<= 1; return v; }
+
+// Launches `kernel` with `lds` bytes of dynamic LDS and returns DR_OK or DR_ELAUNCH.  A request above OPTIN_KB KiB first raises the
+// kernel's hipFuncAttributeMaxDynamicSharedMemorySize to it (64 KiB is the runtime's limit without it; din.hip and metrics.hip
+// opt in from 48 KiB).
+template <int OPTIN_KB = 64, typename K, typename... Args>
+static inline int dr_launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args) {
+    if (lds > (size_t)OPTIN_KB * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return DR_ELAUNCH;
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    DR_CHECK_LAUNCH();
+    return DR_OK;
+}
+
+// ---- device vocabulary ----
+typedef float dr_f32x4 __attribute__((ext_vector_type(4)));
+typedef float dr_f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ float4 dr_zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+
 __device__ __forceinline__ float dr_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+__device__ __forceinline__ float dr_wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int dr_wave_max(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// lane `src`'s value on every lane; src is wave-uniform (a scalar read)
+__device__ __forceinline__ float dr_readlane(float v, int src) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
 }
 
 // lowbias32-style integer hash of (seed, index): well mixed, one multiply chain per element.  The dropout kernels (dr_dropout_fwd,

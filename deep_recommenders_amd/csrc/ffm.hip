@@ -45,8 +45,6 @@ struct FfmP {
     int32_t F, k, k4, D;                         // k4 = k / 4, D = F k
 };
 
-__device__ __forceinline__ float4 ffm_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
 // the example's rows as the items address them: load(i, j * k + 4 c) is the float4 A[i, j, 4 c ..]
 template <int G, bool GATHER>
 struct FfmRows {
@@ -58,7 +56,7 @@ struct FfmRows {
         if constexpr (GATHER) {
             const int64_t r = __shfl(my_row, i, G);
             const float4 v = *reinterpret_cast<const float4*>(table + (r >= 0 ? r : 0) * D + off_in_row);   // row 0 stands in, unused
-            return r >= 0 ? v : ffm_zero();
+            return r >= 0 ? v : dr_zero4();
         } else {
             return *reinterpret_cast<const float4*>(base + (int64_t)i * D + off_in_row);
         }
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(256) void ffm_fwd_kernel(const FfmP p) {
             ffm_pair(pr, i, j);
             x[u] = A.load(i, j * p.k + 4 * c);
             y[u] = A.load(j, i * p.k + 4 * c);
-            if (!tv) { x[u] = ffm_zero(); y[u] = ffm_zero(); }
+            if (!tv) { x[u] = dr_zero4(); y[u] = dr_zero4(); }
         }
 #pragma unroll
         for (int u = 0; u < FFM_U; ++u) {
@@ -170,13 +168,11 @@ __global__ __launch_bounds__(256) void ffm_bwd_kernel(const FfmP p) {
 #pragma unroll
         for (int u = 0; u < FFM_U; ++u) {
             const int t = t0 + u * G + gl;
-            const float4 g = diag[u] ? ffm_zero() : make_float4(d * y[u].x, d * y[u].y, d * y[u].z, d * y[u].w);
+            const float4 g = diag[u] ? dr_zero4() : make_float4(d * y[u].x, d * y[u].y, d * y[u].z, d * y[u].w);
             if (bv && t < T) *reinterpret_cast<float4*>(out + 4 * t) = g;
         }
     }
 }
-
-bool ffm_aligned(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
 
 // fills the sizes; DR_OK, or DR_EINVAL outside the domain
 int ffm_sizes(FfmP& p, int64_t B, int32_t F, int32_t k) {
@@ -185,14 +181,10 @@ int ffm_sizes(FfmP& p, int64_t B, int32_t F, int32_t k) {
     return DR_OK;
 }
 
-bool ffm_ld_ok(int64_t ld, int32_t F, int32_t k) { return (ld & 3) == 0 && ld >= (int64_t)F * F * k; }
-
 // lanes per example: a power of two that covers the fields (the gather keeps one row index per lane) and, up to a wave, the forward's items
 int ffm_group(int32_t F, int32_t k) {
     const int need = std::max(F, F * (F - 1) / 2 * (k >> 2));
-    int g = 8;
-    while (g < 64 && g < need) g <<= 1;
-    return g;
+    return std::min(64, std::max(8, dr_pow2_ceil(need)));
 }
 
 }  // namespace
@@ -203,22 +195,20 @@ int ffm_group(int32_t F, int32_t k) {
         const int64_t grid = (p.B + 256 / g - 1) / (256 / g);                                                          \
         if (grid > 0x7fffffff) return DR_EINVAL;                                                                       \
         switch (g) {                                                                                                   \
-            case 8: hipLaunchKernelGGL((kernel<8, gather>), dim3((unsigned)grid), dim3(256), 0, dr_s(stream), p); break;   \
-            case 16: hipLaunchKernelGGL((kernel<16, gather>), dim3((unsigned)grid), dim3(256), 0, dr_s(stream), p); break; \
-            case 32: hipLaunchKernelGGL((kernel<32, gather>), dim3((unsigned)grid), dim3(256), 0, dr_s(stream), p); break; \
-            default: hipLaunchKernelGGL((kernel<64, gather>), dim3((unsigned)grid), dim3(256), 0, dr_s(stream), p); break; \
+            case 8: return dr_launch(kernel<8, gather>, dim3((unsigned)grid), dim3(256), 0, dr_s(stream), p);          \
+            case 16: return dr_launch(kernel<16, gather>, dim3((unsigned)grid), dim3(256), 0, dr_s(stream), p);        \
+            case 32: return dr_launch(kernel<32, gather>, dim3((unsigned)grid), dim3(256), 0, dr_s(stream), p);        \
+            default: return dr_launch(kernel<64, gather>, dim3((unsigned)grid), dim3(256), 0, dr_s(stream), p);        \
         }                                                                                                              \
-        DR_CHECK_LAUNCH();                                                                                             \
-        return DR_OK;                                                                                                  \
     }
 
 extern "C" int dr_ffm_fwd(const float* rows, int64_t ld_rows, int64_t B, int32_t F, int32_t k, float* inter, dr_stream_t stream) {
     FfmP p = {};
     const int st = ffm_sizes(p, B, F, k);
     if (st != DR_OK) return st;
-    if (!ffm_ld_ok(ld_rows, F, k)) return DR_EINVAL;
+    if (dr_bad_ld(ld_rows, (int64_t)F * F * k)) return DR_EINVAL;
     if (B == 0) return DR_OK;                                  // nothing to read or write: empty tensors have no address
-    if (!rows || !inter || !ffm_aligned(rows)) return DR_EINVAL;
+    if (!rows || !inter || !dr_aligned16(rows)) return DR_EINVAL;
     p.rows = rows; p.ld_rows = ld_rows; p.inter = inter;
     FFM_LAUNCH(ffm_fwd_kernel, false)
 }
@@ -228,9 +218,9 @@ extern "C" int dr_ffm_bwd(const float* rows, int64_t ld_rows, const float* d_int
     FfmP p = {};
     const int st = ffm_sizes(p, B, F, k);
     if (st != DR_OK) return st;
-    if (!ffm_ld_ok(ld_rows, F, k) || !ffm_ld_ok(ld_d, F, k)) return DR_EINVAL;
+    if (dr_bad_ld(ld_rows, (int64_t)F * F * k) || dr_bad_ld(ld_d, (int64_t)F * F * k)) return DR_EINVAL;
     if (B == 0) return DR_OK;
-    if (!rows || !d_inter || !d_rows || !ffm_aligned(rows) || !ffm_aligned(d_rows)) return DR_EINVAL;
+    if (!rows || !d_inter || !d_rows || !dr_aligned16(rows) || !dr_aligned16(d_rows)) return DR_EINVAL;
     p.rows = rows; p.ld_rows = ld_rows; p.d_inter = d_inter; p.d_rows = d_rows; p.ld_d = ld_d;
     FFM_LAUNCH(ffm_bwd_kernel, false)
 }
@@ -241,7 +231,7 @@ extern "C" int dr_ffm_gather_fwd(const int64_t* ids, int64_t B, int32_t F, const
     const int st = ffm_sizes(p, B, F, k);
     if (st != DR_OK) return st;
     if (B == 0) return DR_OK;
-    if (!ids || !row_base || !table || !inter || !ffm_aligned(table)) return DR_EINVAL;
+    if (!ids || !row_base || !table || !inter || !dr_aligned16(table)) return DR_EINVAL;
     p.ids = ids; p.row_base = row_base; p.table = table; p.lin_w = lin_w; p.lin_bias = lin_bias; p.inter = inter;
     p.first_order = first_order;
     FFM_LAUNCH(ffm_fwd_kernel, true)
@@ -252,9 +242,9 @@ extern "C" int dr_ffm_gather_bwd(const int64_t* ids, int64_t B, int32_t F, const
     FfmP p = {};
     const int st = ffm_sizes(p, B, F, k);
     if (st != DR_OK) return st;
-    if (!ffm_ld_ok(ld_d, F, k)) return DR_EINVAL;
+    if (dr_bad_ld(ld_d, (int64_t)F * F * k)) return DR_EINVAL;
     if (B == 0) return DR_OK;
-    if (!ids || !row_base || !table || !d_inter || !d_rows || !ffm_aligned(table) || !ffm_aligned(d_rows)) return DR_EINVAL;
+    if (!ids || !row_base || !table || !d_inter || !d_rows || !dr_aligned16(table) || !dr_aligned16(d_rows)) return DR_EINVAL;
     p.ids = ids; p.row_base = row_base; p.table = table; p.d_inter = d_inter; p.d_rows = d_rows; p.ld_d = ld_d;
     FFM_LAUNCH(ffm_bwd_kernel, true)
 }

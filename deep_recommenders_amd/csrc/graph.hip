@@ -19,17 +19,6 @@ constexpr int64_t LONG_ROW = DR_CSR_LONG_ROW;
 constexpr int64_t CHUNK = 512;     // entries per chunk of a long row
 constexpr int BATCH = 8;           // row gathers in flight per lane
 
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // columns 4s .. 4s+3 of a row (fewer at the tail: scalar loads, never past column D)
 __device__ __forceinline__ float4 load_cols(const float* __restrict__ row, int s, int D) {
     const int c = 4 * s;
@@ -78,7 +67,7 @@ __device__ __forceinline__ float4 gather_seg(const int32_t* __restrict__ col, co
     const int gl = lane & (G - 1);
     const int gbase = lane - gl;
     const int64_t len = ke > kb ? ke - kb : 0;
-    const int n_it = wave_max_i((int)((len + PAIRS - 1) / PAIRS));
+    const int n_it = dr_wave_max((int)((len + PAIRS - 1) / PAIRS));
     const bool col_ok = 4 * s < D;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int it = 0; it < n_it; ++it) {
@@ -445,7 +434,7 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* __restric
         const float* xr = x + r * ld_x;
         float m = -INFINITY;
         for (int c = lane; c < C; c += 64) m = fmaxf(m, xr[c]);
-        m = wave_max_f(m);
+        m = dr_wave_max(m);
         float s = 0.f;
         for (int c = lane; c < C; c += 64) s += expf(xr[c] - m);
         s = dr_wave_sum(s);
@@ -499,7 +488,6 @@ __global__ __launch_bounds__(256) void cce_prob_kernel(const float* __restrict__
 }
 
 inline int rows_grid(int64_t B) { return dr_grid_for(B, 4, 65535); }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int G>
 void launch_spmm(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n_rows, int64_t nnz, const float* X,
@@ -564,10 +552,10 @@ extern "C" int dr_csr_spmm(const int64_t* row_ptr, const int32_t* col, const flo
                            int64_t ld_out, const int64_t* plan, float* workspace, int64_t workspace_bytes, dr_stream_t stream) {
     if (n_rows < 0 || nnz < 0 || D < 1) return DR_EINVAL;
     if (n_rows == 0) return DR_OK;
-    if (!row_ptr || !out || ld_out < D || (ld_out & 3) || !al16(out)) return DR_EINVAL;
-    if (nnz > 0 && (!col || !val || !X || ld_x < D || (ld_x & 3) || !al16(X))) return DR_EINVAL;
-    if (relu_src != nullptr && (ld_relu_src < D || (ld_relu_src & 3) || !al16(relu_src))) return DR_EINVAL;
-    if (plan_max_long(nnz) > 0 && (!plan || !workspace || !al16(workspace) || workspace_bytes < dr_csr_spmm_workspace_bytes(nnz, D)))
+    if (!row_ptr || !out || dr_bad_ld(ld_out, D) || !dr_aligned16(out)) return DR_EINVAL;
+    if (nnz > 0 && (!col || !val || !X || dr_bad_ld(ld_x, D) || !dr_aligned16(X))) return DR_EINVAL;
+    if (relu_src != nullptr && (dr_bad_ld(ld_relu_src, D) || !dr_aligned16(relu_src))) return DR_EINVAL;
+    if (plan_max_long(nnz) > 0 && (!plan || !workspace || !dr_aligned16(workspace) || workspace_bytes < dr_csr_spmm_workspace_bytes(nnz, D)))
         return DR_EINVAL;
     const int D4 = (D + 3) / 4;
     hipStream_t st = dr_s(stream);

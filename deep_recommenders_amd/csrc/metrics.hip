@@ -187,14 +187,11 @@ int hist_launch(const float* pred, const float* labels, const float* weights, in
                 double* hist, void* workspace, hipStream_t s) {
     const int nbins = 2 * (T + 1);
     const size_t lds = (size_t)nbins * (WEIGHTED ? 8 : 4) + (size_t)T * 4;
-    auto k1 = confusion_hist_stage1<WEIGHTED, LOGITS>;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DR_ELAUNCH;
     const int grid = hist_grid(n, T);
     const uintptr_t a = reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(weights);
-    hipLaunchKernelGGL(k1, dim3(grid), dim3(HIST_BLOCK), lds, s, pred, labels, weights, n, thresholds, (int)T, (int)((a & 15) == 0),
-                       workspace);
+    const int st = dr_launch<48>(confusion_hist_stage1<WEIGHTED, LOGITS>, dim3(grid), dim3(HIST_BLOCK), lds, s, pred, labels, weights, n,
+                                 thresholds, (int)T, (int)((a & 15) == 0), workspace);
+    if (st != DR_OK) return st;
     hipLaunchKernelGGL(confusion_hist_stage2<WEIGHTED>, dim3((nbins + 63) / 64), dim3(256), 0, s, workspace, grid, nbins, hist);
     DR_CHECK_LAUNCH();
     return DR_OK;

@@ -13,16 +13,6 @@ namespace {
 constexpr int MT_MAX_T = 16;   // tasks per gate-mix row (registers per lane)
 constexpr int MT_MAX_E = 64;   // experts: one lane each
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-// lane `src`'s value (src wave-uniform) on every lane
-__device__ __forceinline__ float bcast(float v, int src) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
-
 // One 64-lane wave per batch row, 4 rows per block, rows grid-strided.  Lane e < E holds p[t][e] for every task; the mixture is
 // computed 64 columns u at a time (lane = u), summing over e in ascending order.
 __global__ __launch_bounds__(256) void gate_mix_fwd_kernel(const float* __restrict__ h, int64_t ld_h, const float* __restrict__ l,
@@ -37,7 +27,7 @@ __global__ __launch_bounds__(256) void gate_mix_fwd_kernel(const float* __restri
             pr[t] = 0.f;
             if (t < T) {
                 const float v = lane < E ? l[row * ld_l + t * E + lane] : -INFINITY;
-                const float mx = wave_max(v);
+                const float mx = dr_wave_max(v);
                 const float ex = lane < E ? expf(v - mx) : 0.f;
                 const float s = dr_wave_sum(ex);
                 pr[t] = ex / s;
@@ -55,7 +45,7 @@ __global__ __launch_bounds__(256) void gate_mix_fwd_kernel(const float* __restri
                 const float hv = u < U ? hr[(int64_t)e * U + u] : 0.f;
 #pragma unroll
                 for (int t = 0; t < MT_MAX_T; ++t)
-                    if (t < T) acc[t] = fmaf(bcast(pr[t], e), hv, acc[t]);
+                    if (t < T) acc[t] = fmaf(dr_readlane(pr[t], e), hv, acc[t]);
             }
             if (u < U) {
 #pragma unroll
@@ -94,7 +84,7 @@ __global__ __launch_bounds__(256) void gate_mix_bwd_kernel(const float* __restri
                 float dh = 0.f;
 #pragma unroll
                 for (int t = 0; t < MT_MAX_T; ++t)
-                    if (t < T) dh = fmaf(bcast(pr[t], e), dv[t], dh);
+                    if (t < T) dh = fmaf(dr_readlane(pr[t], e), dv[t], dh);
                 if (u < U) dhr[(int64_t)e * U + u] = dh;
 #pragma unroll
                 for (int t = 0; t < MT_MAX_T; ++t)

@@ -22,8 +22,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int PNN_MAX_F = 64;
 constexpr int PNN_MAX_D = 128;
 constexpr int PNN_MAX_N = 4096;
@@ -44,8 +42,6 @@ struct PnnP {
     int64_t ld_u, B, per;
     int32_t F, D, N, Npad, accumulate;
 };
-
-__device__ __forceinline__ float4 pnn_zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
 __global__ __launch_bounds__(256) void pnn_usum_kernel(const float* __restrict__ emb, int64_t ld_emb, int64_t B, int F, int D,
                                                        float* __restrict__ u, int64_t ld_u) {
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(256, 2) void pnn_fwd_kernel(const PnnP p) {
     const float* wp = p.W + (int64_t)wr * p.ld_w + wcol;
     const int64_t w_q = WROWS * p.ld_w, w_it = (int64_t)PNN_BK * p.ld_w;
 
-    f32x16 acc[T][T];
+    dr_f32x16 acc[T][T];
 #pragma unroll
     for (int a = 0; a < T; ++a)
 #pragma unroll
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void pnn_fwd_kernel(const PnnP p) {
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
     const int nk = D * D / PNN_BK;
-    float4 vb0, vb1 = pnn_zero4();
+    float4 vb0, vb1 = dr_zero4();
     vb0 = *reinterpret_cast<const float4*>(wp);
     if (T == 2) vb1 = *reinterpret_cast<const float4*>(wp + w_q);
     wp += w_it;
@@ -201,14 +197,14 @@ __global__ __launch_bounds__(256, 2) void pnn_dw_kernel(const PnnP p) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int64_t bu = bb + ur[q], bg = bb + gr + 8 * q;
-            vu[q] = pnn_zero4();
-            vg[q] = pnn_zero4();
+            vu[q] = dr_zero4();
+            vg[q] = dr_zero4();
             if (uv[q] && bu < b_end) vu[q] = *reinterpret_cast<const float4*>(p.u_in + bu * p.ld_u + uk[q]);
             if (bg < b_end) vg[q] = *reinterpret_cast<const float4*>(p.g + bg * p.ld_g + gcol);
         }
     };
 
-    f32x16 acc[2][2];
+    dr_f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -326,7 +322,7 @@ __global__ __launch_bounds__(256, 2) void pnn_du_kernel(const PnnP p) {
         // an element at or past N is zero in BOTH operands: the padding of d_out and W may hold anything
         auto load = [&](int nn) {
             const int n = nn + or4;
-            vg = pnn_zero4(); vw[0] = pnn_zero4(); vw[1] = pnn_zero4();
+            vg = dr_zero4(); vw[0] = dr_zero4(); vw[1] = dr_zero4();
             if (n < N) {
                 vg = *reinterpret_cast<const float4*>(gp + n);
 #pragma unroll
@@ -341,7 +337,7 @@ __global__ __launch_bounds__(256, 2) void pnn_du_kernel(const PnnP p) {
             }
         };
 
-        f32x16 acc[2];
+        dr_f32x16 acc[2];
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -409,9 +405,6 @@ __global__ __launch_bounds__(256, 2) void pnn_du_kernel(const PnnP p) {
     }
 }
 
-bool pnn_aligned(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-bool pnn_bad_ld(int64_t ld, int64_t width) { return (ld & 3) != 0 || ld < width; }
-
 int pnn_domain(int64_t B, int32_t F, int32_t D, int32_t N) {
     if (B < 0 || F < 1 || F > PNN_MAX_F || D < 4 || D > PNN_MAX_D || (D & 3) || N < 1 || N > PNN_MAX_N) return DR_EINVAL;
     if (B > ((int64_t)1 << 31)) return DR_ESHAPE;              // keeps every grid below 2^31 blocks
@@ -426,16 +419,6 @@ void pnn_parts(int64_t B, int64_t& per, int& parts) {
     if (parts < 1) parts = 1;
 }
 
-template <typename K>
-int pnn_launch(K kernel, dim3 grid, size_t lds, const PnnP& p, dr_stream_t stream) {
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DR_ELAUNCH;
-    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, dr_s(stream), p);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
-}
-
 }  // namespace
 
 extern "C" int dr_pnn_outer_fwd(const float* emb, int64_t ld_emb, const float* W, int64_t ld_w, const float* addend, int64_t ld_add,
@@ -443,11 +426,11 @@ extern "C" int dr_pnn_outer_fwd(const float* emb, int64_t ld_emb, const float* W
                                 dr_stream_t stream) {
     const int st = pnn_domain(B, F, D, N);
     if (st != DR_OK) return st;
-    if (pnn_bad_ld(ld_emb, (int64_t)F * D) || pnn_bad_ld(ld_w, N) || pnn_bad_ld(ld_u, D) || pnn_bad_ld(ld_out, N)) return DR_EINVAL;
-    if (addend != nullptr && pnn_bad_ld(ld_add, N)) return DR_EINVAL;
+    if (dr_bad_ld(ld_emb, (int64_t)F * D) || dr_bad_ld(ld_w, N) || dr_bad_ld(ld_u, D) || dr_bad_ld(ld_out, N)) return DR_EINVAL;
+    if (addend != nullptr && dr_bad_ld(ld_add, N)) return DR_EINVAL;
     if (B == 0) return DR_OK;                                  // nothing to read or write: empty tensors have no address
     if (!emb || !W || !u || !out) return DR_EINVAL;
-    if (!pnn_aligned(emb) || !pnn_aligned(W) || !pnn_aligned(addend) || !pnn_aligned(u) || !pnn_aligned(out)) return DR_EINVAL;
+    if (!dr_aligned16(emb) || !dr_aligned16(W) || !dr_aligned16(addend) || !dr_aligned16(u) || !dr_aligned16(out)) return DR_EINVAL;
     hipLaunchKernelGGL(pnn_usum_kernel, dim3(dr_grid_for(B * (D >> 2), 256)), dim3(256), 0, dr_s(stream), emb, ld_emb, B, F, D, u, ld_u);
     DR_CHECK_LAUNCH();
     PnnP p = {};
@@ -455,9 +438,9 @@ extern "C" int dr_pnn_outer_fwd(const float* emb, int64_t ld_emb, const float* W
     p.B = B; p.F = F; p.D = D; p.N = N; p.Npad = (N + 3) & ~3;
     const int64_t grid = ((B + 127) / 128) * ((N + 127) / 128);
     if (grid >= PNN_FWD_MIN_BLOCKS)
-        return pnn_launch(pnn_fwd_kernel<2>, dim3((unsigned)grid), (size_t)(D + PNN_BK) * 132 * sizeof(float), p, stream);
+        return dr_launch(pnn_fwd_kernel<2>, dim3((unsigned)grid), dim3(256), (size_t)(D + PNN_BK) * 132 * sizeof(float), dr_s(stream), p);
     const int64_t small = ((B + 63) / 64) * ((N + 63) / 64);
-    return pnn_launch(pnn_fwd_kernel<1>, dim3((unsigned)small), (size_t)(D + PNN_BK) * 68 * sizeof(float), p, stream);
+    return dr_launch(pnn_fwd_kernel<1>, dim3((unsigned)small), dim3(256), (size_t)(D + PNN_BK) * 68 * sizeof(float), dr_s(stream), p);
 }
 
 extern "C" int64_t dr_pnn_outer_bwd_workspace_bytes(int64_t B, int32_t F, int32_t D, int32_t N) {
@@ -473,12 +456,12 @@ extern "C" int dr_pnn_outer_bwd(const float* u, int64_t ld_u, const float* W, in
                                 float* dW, int64_t ld_dw, void* ws, int64_t ws_bytes, dr_stream_t stream) {
     const int st = pnn_domain(B, F, D, N);
     if (st != DR_OK) return st;
-    if (pnn_bad_ld(ld_u, D) || pnn_bad_ld(ld_w, N) || pnn_bad_ld(ld_dout, N) || pnn_bad_ld(ld_demb, (int64_t)F * D) || pnn_bad_ld(ld_dw, N))
+    if (dr_bad_ld(ld_u, D) || dr_bad_ld(ld_w, N) || dr_bad_ld(ld_dout, N) || dr_bad_ld(ld_demb, (int64_t)F * D) || dr_bad_ld(ld_dw, N))
         return DR_EINVAL;
     if (accumulate != 0 && accumulate != 1) return DR_EINVAL;
     if (B == 0) return DR_OK;
     if (!u || !W || !d_out || !d_emb || !dW || !ws) return DR_EINVAL;
-    if (!pnn_aligned(u) || !pnn_aligned(W) || !pnn_aligned(d_out) || !pnn_aligned(d_emb) || !pnn_aligned(dW) || !pnn_aligned(ws))
+    if (!dr_aligned16(u) || !dr_aligned16(W) || !dr_aligned16(d_out) || !dr_aligned16(d_emb) || !dr_aligned16(dW) || !dr_aligned16(ws))
         return DR_EINVAL;
     int64_t per; int parts;
     pnn_parts(B, per, parts);
@@ -489,11 +472,11 @@ extern "C" int dr_pnn_outer_bwd(const float* u, int64_t ld_u, const float* W, in
     p.part = static_cast<float*>(ws); p.per = per; p.accumulate = accumulate;
     p.B = B; p.F = F; p.D = D; p.N = N; p.Npad = Npad;
     const int tiles = ((DD + 127) / 128) * ((N + 127) / 128);
-    int rc = pnn_launch(pnn_dw_kernel, dim3((unsigned)tiles, (unsigned)parts), 0, p, stream);
+    int rc = dr_launch(pnn_dw_kernel, dim3((unsigned)tiles, (unsigned)parts), dim3(256), 0, dr_s(stream), p);
     if (rc != DR_OK) return rc;
     hipLaunchKernelGGL(pnn_dw_reduce_kernel, dim3(dr_grid_for((int64_t)DD * (Npad >> 2), 256)), dim3(256), 0, dr_s(stream), p.part, parts,
                        DD, N, Npad, dW, ld_dw);
     DR_CHECK_LAUNCH();
     const size_t lds = (size_t)(PNN_DU_BM * PNN_LDT + 2 * PNN_DU_BM * (D + 1) + PNN_BK * (PNN_DU_BM + 1) + PNN_BK * PNN_LDT) * sizeof(float);
-    return pnn_launch(pnn_du_kernel, dim3((unsigned)((B + PNN_DU_BM - 1) / PNN_DU_BM)), lds, p, stream);
+    return dr_launch(pnn_du_kernel, dim3((unsigned)((B + PNN_DU_BM - 1) / PNN_DU_BM)), dim3(256), lds, dr_s(stream), p);
 }

@@ -15,6 +15,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import ops
+from .ops import _pad4
 
 
 _SIDE_STREAMS = {}
@@ -28,10 +29,6 @@ def _side_streams(device):
     if key not in _SIDE_STREAMS:
         _SIDE_STREAMS[key] = (torch.cuda.Stream(device=device), torch.cuda.Stream(device=device))
     return _SIDE_STREAMS[key]
-
-
-def _pad4(n):
-    return (n + 3) // 4 * 4
 
 
 class DeepFMEngine:

@@ -12,11 +12,8 @@ import torch
 from torch import nn
 
 from . import ops
+from .ops import _pad4
 from . import feature_column as fc
-
-
-def _pad4(n):
-    return (n + 3) // 4 * 4
 
 
 # --------------------------------------------------------------------------------------------------

@@ -153,6 +153,29 @@ def _pad4(n):
     return (n + 3) // 4 * 4
 
 
+def _status(st, what):
+    """check() for the entry points that validate their whole domain in C: an argument they refuse is a ValueError, as it is where
+    the Python side sees it first"""
+    if st in (_lib.DR_EINVAL, _lib.DR_ESHAPE):
+        raise ValueError("%s: %s (outside the kernel's domain, or a base address that is not 16-byte aligned)" % (what, _lib._ERR[st]))
+    check(st, what)
+
+
+def _row_pitch(family, t, cols, what, written_to_pitch=False):
+    """row stride of a [B, cols] fp32 matrix with unit column stride; ValueError (in `family`'s name) unless it is a multiple of 4 and
+    >= cols.  A single row has no pitch to speak of, except where the kernel writes up to it (written_to_pitch: dot_interact's zero
+    padding)."""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError("%s: %s must be fp32 [B, %d], got %s %s" % (family, what, cols, t.dtype, tuple(t.shape)))
+    ok = t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= cols
+    if not ok and t.shape[0] <= 1 and t.stride(1) == 1 and (cols % 4 == 0 or not written_to_pitch):
+        return _pad4(cols)
+    if not ok:
+        raise ValueError("%s: %s needs unit column stride and a row stride that is a multiple of 4 and >= %d, got strides %s"
+                         % (family, what, cols, tuple(t.stride())))
+    return t.stride(0)
+
+
 def _check_ld(t, what):
     """t [M, N] goes to a kernel with t.stride(0) as its leading dimension: unit column stride and, with more than one row, a row
     stride >= N.  A smaller one (0 for an expanded tensor) is no layout: every example would read the same or overlapping rows."""
@@ -1536,20 +1559,6 @@ def cin_pool_bwd(x0, x, W, act, out, d_out, d_pooled, want_bias=False, d_x0=None
 
 
 # ---- DLRM: the pairwise dot interaction (csrc/dot_interact.hip) ------------------------------------------------------------------------
-def _di_rows(t, cols, what, written_to_pitch=False):
-    """row stride of a [B, cols] fp32 device matrix with unit column stride; ValueError unless it is a multiple of 4 and >= cols.
-    A single row has no pitch to speak of, except where the kernel writes up to it (written_to_pitch: the forward's zero padding)."""
-    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols:
-        raise ValueError("dot_interact: %s must be fp32 [B, %d], got %s %s" % (what, cols, t.dtype, tuple(t.shape)))
-    ok = t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= cols
-    if not ok and t.shape[0] <= 1 and t.stride(1) == 1 and (cols % 4 == 0 or not written_to_pitch):
-        return _pad4(cols)
-    if not ok:
-        raise ValueError("dot_interact: %s needs unit column stride and a row stride that is a multiple of 4 and >= %d, got strides %s"
-                         % (what, cols, tuple(t.stride())))
-    return t.stride(0)
-
-
 def _di_dims(dense, emb, F, D, self_interaction):
     """validates the domain of dr_dot_interact_*; returns (emb as [B, F * D], B, N, c0, P)"""
     F, D = int(F), int(D)
@@ -1581,22 +1590,20 @@ def dot_interact_fwd(dense, emb, F, D, self_interaction=False, out=None, ld_out=
     first D columns, then the row-major lower triangle of T T^T for T = [dense; emb's F rows].  emb: [B, F, D] contiguous, or
     [B, F * D] with any row stride that is a multiple of 4.  out: a [B, c0 + P] view to write into (its row stride is ld_out)."""
     emb, B, N, c0, P = _di_dims(dense, emb, F, D, self_interaction)
-    ld_emb = _di_rows(emb, F * D, "emb")
-    ld_dense = 0 if dense is None else _di_rows(dense, D, "dense")
+    ld_emb = _row_pitch("dot_interact", emb, F * D, "emb")
+    ld_dense = 0 if dense is None else _row_pitch("dot_interact", dense, D, "dense")
     if out is None:
         ld_out = _pad4(c0 + P) if ld_out is None else int(ld_out)
         if ld_out % 4 != 0 or ld_out < c0 + P:
             raise ValueError("dot_interact: ld_out must be a multiple of 4 and >= %d, got %d" % (c0 + P, ld_out))
         out = torch.empty((B, ld_out), dtype=torch.float32, device=emb.device)[:, :c0 + P]
     else:
-        ld_out = _di_rows(out, c0 + P, "out", written_to_pitch=True)
+        ld_out = _row_pitch("dot_interact", out, c0 + P, "out", written_to_pitch=True)
     if B == 0:
         return out
     st = lib().dr_dot_interact_fwd(ptr(dense), ld_dense, ptr(emb), ld_emb, B, int(F), int(D), int(bool(self_interaction)), ptr(out),
                                    ld_out, stream_ptr())
-    if st == _lib.DR_EINVAL:
-        raise ValueError("dr_dot_interact_fwd: DR_EINVAL (outside the kernel's domain, or a base address that is not 16-byte aligned)")
-    check(st, "dr_dot_interact_fwd")
+    _status(st, "dr_dot_interact_fwd")
     return out
 
 
@@ -1604,23 +1611,21 @@ def dot_interact_bwd(dense, emb, F, D, d_out, self_interaction=False, d_dense=No
     """(d_dense [B, D] | None, d_emb [B, F * D]) of dr_dot_interact_bwd from d_out [B, c0 + P] (row stride a multiple of 4; columns
     beyond c0 + P are not read).  d_dense / d_emb: buffers to overwrite (only their first D / F * D columns are written)."""
     emb, B, N, c0, P = _di_dims(dense, emb, F, D, self_interaction)
-    ld_emb = _di_rows(emb, F * D, "emb")
-    ld_dense = 0 if dense is None else _di_rows(dense, D, "dense")
-    ld_dout = _di_rows(d_out, c0 + P, "d_out")
+    ld_emb = _row_pitch("dot_interact", emb, F * D, "emb")
+    ld_dense = 0 if dense is None else _row_pitch("dot_interact", dense, D, "dense")
+    ld_dout = _row_pitch("dot_interact", d_out, c0 + P, "d_out")
     if d_emb is None:
         d_emb = torch.empty((B, F * D), dtype=torch.float32, device=emb.device)
     if dense is not None and d_dense is None:
         d_dense = torch.empty((B, D), dtype=torch.float32, device=emb.device)
-    ld_demb = _di_rows(d_emb, F * D, "d_emb")
-    ld_ddense = 0 if dense is None else _di_rows(d_dense, D, "d_dense")
+    ld_demb = _row_pitch("dot_interact", d_emb, F * D, "d_emb")
+    ld_ddense = 0 if dense is None else _row_pitch("dot_interact", d_dense, D, "d_dense")
     if B == 0:
         return (d_dense if dense is not None else None), d_emb
     st = lib().dr_dot_interact_bwd(ptr(dense), ld_dense, ptr(emb), ld_emb, ptr(d_out), ld_dout, B, int(F), int(D),
                                    int(bool(self_interaction)), ptr(d_dense) if dense is not None else None, ld_ddense, ptr(d_emb), ld_demb,
                                    stream_ptr())
-    if st == _lib.DR_EINVAL:
-        raise ValueError("dr_dot_interact_bwd: DR_EINVAL (outside the kernel's domain, or a base address that is not 16-byte aligned)")
-    check(st, "dr_dot_interact_bwd")
+    _status(st, "dr_dot_interact_bwd")
     return (d_dense if dense is not None else None), d_emb
 
 
@@ -1628,19 +1633,6 @@ def dot_interact_bwd(dense, emb, F, D, d_out, self_interaction=False, d_dense=No
 def afm_num_pairs(F):
     """P = F (F - 1) / 2: the pairs (i, j), j < i, numbered q = i (i - 1) / 2 + j"""
     return int(F) * (int(F) - 1) // 2
-
-
-def _afm_rows(t, cols, what):
-    """row stride of a [B, cols] fp32 matrix with unit column stride; ValueError unless it is a multiple of 4 and >= cols"""
-    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols:
-        raise ValueError("afm_pool: %s must be fp32 [B, %d], got %s %s" % (what, cols, t.dtype, tuple(t.shape)))
-    ok = t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= cols
-    if not ok and t.shape[0] <= 1 and t.stride(1) == 1:
-        return _pad4(cols)                                     # a single row has no pitch to speak of
-    if not ok:
-        raise ValueError("afm_pool: %s needs unit column stride and a row stride that is a multiple of 4 and >= %d, got strides %s"
-                         % (what, cols, tuple(t.stride())))
-    return t.stride(0)
 
 
 def _afm_dims(emb, W, b, h, F):
@@ -1674,20 +1666,14 @@ def _afm_dims(emb, W, b, h, F):
     return emb, int(emb.shape[0]), F, D, A, P
 
 
-def _afm_status(st, what):
-    if st in (_lib.DR_EINVAL, _lib.DR_ESHAPE):
-        raise ValueError("%s: %s (outside the kernel's domain, or a base address that is not 16-byte aligned)" % (what, _lib._ERR[st]))
-    check(st, what)
-
-
 def afm_pool_fwd(emb, W, b, h, F, want_attention=False, out=None):
     """(out [B, D], lse [B], attn [B, P] | None) of dr_afm_pool_fwd.  emb: [B, F, D] contiguous, or [B, F * D] with any row stride that
     is a multiple of 4 (the slab's concat, read in place); W [D, A], b [A], h [A].  out: a [B, D] view to write into."""
     emb, B, F, D, A, P = _afm_dims(emb, W, b, h, F)
-    ld_emb = _afm_rows(emb, F * D, "emb")
+    ld_emb = _row_pitch("afm_pool", emb, F * D, "emb")
     if out is None:
         out = torch.empty((B, D), dtype=torch.float32, device=emb.device)
-    ld_out = _afm_rows(out, D, "out")
+    ld_out = _row_pitch("afm_pool", out, D, "out")
     lse = torch.empty((B,), dtype=torch.float32, device=emb.device)
     attn = torch.empty((B, P), dtype=torch.float32, device=emb.device) if want_attention else None
     if B == 0:
@@ -1695,7 +1681,7 @@ def afm_pool_fwd(emb, W, b, h, F, want_attention=False, out=None):
     W, b, h = W.contiguous(), b.contiguous(), h.contiguous()
     st = lib().dr_afm_pool_fwd(ptr(emb), ld_emb, ptr(W), ptr(b), ptr(h), B, F, D, A, ptr(out), ld_out, ptr(lse), ptr(attn), P,
                                stream_ptr())
-    _afm_status(st, "dr_afm_pool_fwd")
+    _status(st, "dr_afm_pool_fwd")
     return out, lse, attn
 
 
@@ -1703,16 +1689,16 @@ def afm_pool_bwd(emb, W, b, h, F, out, lse, d_out, d_emb=None, workspace=None):
     """(d_emb [B, F * D], dW [D, A], db [A], dh [A]) of dr_afm_pool_bwd from d_out [B, D], with out and lse of afm_pool_fwd.  d_emb: a
     [B, F * D] buffer to overwrite; workspace: fp32, at least dr_afm_pool_bwd_workspace_bytes(B, F, D, A) bytes (allocated when None)."""
     emb, B, F, D, A, P = _afm_dims(emb, W, b, h, F)
-    ld_emb = _afm_rows(emb, F * D, "emb")
-    ld_out = _afm_rows(out, D, "out")
-    ld_dout = _afm_rows(d_out, D, "d_out")
+    ld_emb = _row_pitch("afm_pool", emb, F * D, "emb")
+    ld_out = _row_pitch("afm_pool", out, D, "out")
+    ld_dout = _row_pitch("afm_pool", d_out, D, "d_out")
     if lse.dtype != torch.float32 or tuple(lse.shape) != (B,) or not lse.is_contiguous():
         raise ValueError("afm_pool: lse must be contiguous fp32 [%d], got %s %s" % (B, lse.dtype, tuple(lse.shape)))
     if out.shape[0] != B or d_out.shape[0] != B:
         raise ValueError("afm_pool: emb, out and d_out disagree on the batch size")
     if d_emb is None:
         d_emb = torch.empty((B, F * D), dtype=torch.float32, device=emb.device)
-    ld_demb = _afm_rows(d_emb, F * D, "d_emb")
+    ld_demb = _row_pitch("afm_pool", d_emb, F * D, "d_emb")
     dW = torch.empty((D, A), dtype=torch.float32, device=emb.device)
     db = torch.empty((A,), dtype=torch.float32, device=emb.device)
     dh = torch.empty((A,), dtype=torch.float32, device=emb.device)
@@ -1720,7 +1706,7 @@ def afm_pool_bwd(emb, W, b, h, F, out, lse, d_out, d_emb=None, workspace=None):
         return d_emb, dW.zero_(), db.zero_(), dh.zero_()
     need = lib().dr_afm_pool_bwd_workspace_bytes(B, F, D, A)
     if need < 0:
-        _afm_status(int(need), "dr_afm_pool_bwd_workspace_bytes")
+        _status(int(need), "dr_afm_pool_bwd_workspace_bytes")
     if workspace is None:
         workspace = torch.empty((max(need // 4, 4),), dtype=torch.float32, device=emb.device)
     elif workspace.numel() * workspace.element_size() < need:
@@ -1730,7 +1716,7 @@ def afm_pool_bwd(emb, W, b, h, F, out, lse, d_out, d_emb=None, workspace=None):
     st = lib().dr_afm_pool_bwd(ptr(emb), ld_emb, ptr(W), ptr(b), ptr(h), ptr(out), ld_out, ptr(lse), ptr(d_out), ld_dout, B, F, D, A,
                                ptr(d_emb), ld_demb, ptr(dW), ptr(db), ptr(dh), ptr(workspace),
                                workspace.numel() * workspace.element_size(), stream_ptr())
-    _afm_status(st, "dr_afm_pool_bwd")
+    _status(st, "dr_afm_pool_bwd")
     return d_emb, dW, db, dh
 
 
@@ -1765,13 +1751,11 @@ def _pnn_rows(t, rows, cols, what, may_copy):
     ValueError."""
     if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (rows, cols):
         raise ValueError("pnn_outer: %s must be fp32 [%d, %d], got %s %s" % (what, rows, cols, t.dtype, tuple(t.shape)))
-    if t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= cols:
-        return t
-    if rows <= 1 and t.stride(1) == 1 and (cols % 4 == 0 or not may_copy):
-        return t                                               # a single row has no pitch to speak of (_pnn_ld)
     if not may_copy:
-        raise ValueError("pnn_outer: %s needs unit column stride and a row stride that is a multiple of 4 and >= %d, got strides %s"
-                         % (what, cols, tuple(t.stride())))
+        _row_pitch("pnn_outer", t, cols, what)                 # used in place or refused; the pitch handed to C is _pnn_ld's
+        return t
+    if t.stride(1) == 1 and (t.stride(0) % 4 == 0 and t.stride(0) >= cols or rows <= 1 and cols % 4 == 0):
+        return t                                               # a single row has no pitch to speak of (_pnn_ld)
     buf = torch.zeros((rows, _pad4(cols)), dtype=torch.float32, device=t.device)
     buf[:, :cols].copy_(t)
     return buf[:, :cols]
@@ -1779,12 +1763,6 @@ def _pnn_rows(t, rows, cols, what, may_copy):
 
 def _pnn_ld(t):
     return t.stride(0) if t.shape[0] > 1 else _pad4(t.shape[1])
-
-
-def _pnn_status(st, what):
-    if st in (_lib.DR_EINVAL, _lib.DR_ESHAPE):
-        raise ValueError("%s: %s (outside the kernel's domain, or a base address that is not 16-byte aligned)" % (what, _lib._ERR[st]))
-    check(st, what)
 
 
 def pnn_outer_fwd(emb, W, F, addend=None, out=None):
@@ -1804,7 +1782,7 @@ def pnn_outer_fwd(emb, W, F, addend=None, out=None):
     W = _pnn_rows(W, D * D, N, "W", True)
     st = lib().dr_pnn_outer_fwd(ptr(emb), _pnn_ld(emb), ptr(W), _pnn_ld(W), ptr(addend), _pnn_ld(addend) if addend is not None else 0,
                                 B, F, D, N, ptr(u), D, ptr(out), _pnn_ld(out), stream_ptr())
-    _pnn_status(st, "dr_pnn_outer_fwd")
+    _status(st, "dr_pnn_outer_fwd")
     return out, u
 
 
@@ -1812,7 +1790,7 @@ def pnn_outer_bwd_workspace(B, F, D, N, device):
     """an fp32 buffer of dr_pnn_outer_bwd_workspace_bytes(B, F, D, N) bytes; ValueError outside the domain"""
     need = int(lib().dr_pnn_outer_bwd_workspace_bytes(int(B), int(F), int(D), int(N)))
     if need < 0:
-        _pnn_status(need, "dr_pnn_outer_bwd_workspace_bytes")
+        _status(need, "dr_pnn_outer_bwd_workspace_bytes")
     return torch.empty((max(need // 4, 4),), dtype=torch.float32, device=device)
 
 
@@ -1838,7 +1816,7 @@ def pnn_outer_bwd(u, W, F, d_out, d_emb=None, accumulate=False, workspace=None):
         return d_emb, dW.zero_()
     need = int(lib().dr_pnn_outer_bwd_workspace_bytes(B, F, D, N))
     if need < 0:
-        _pnn_status(need, "dr_pnn_outer_bwd_workspace_bytes")
+        _status(need, "dr_pnn_outer_bwd_workspace_bytes")
     if workspace is None:
         workspace = torch.empty((max(need // 4, 4),), dtype=torch.float32, device=u.device)
     elif workspace.numel() * workspace.element_size() < need:
@@ -1848,7 +1826,7 @@ def pnn_outer_bwd(u, W, F, d_out, d_emb=None, accumulate=False, workspace=None):
     st = lib().dr_pnn_outer_bwd(ptr(u), _pnn_ld(u), ptr(W), _pnn_ld(W), ptr(d_out), _pnn_ld(d_out), B, F, D, N, ptr(d_emb),
                                 _pnn_ld(d_emb), 1 if accumulate else 0, ptr(dW), _pnn_ld(dW), ptr(workspace),
                                 workspace.numel() * workspace.element_size(), stream_ptr())
-    _pnn_status(st, "dr_pnn_outer_bwd")
+    _status(st, "dr_pnn_outer_bwd")
     return d_emb, dW
 
 
@@ -1911,12 +1889,6 @@ def _gru_dims(xp, U):
     return B, T, H
 
 
-def _gru_status(st, what):
-    if st in (_lib.DR_EINVAL, _lib.DR_ESHAPE):
-        raise ValueError("%s: %s (outside the kernel's domain, or a base address that is not 16-byte aligned)" % (what, _lib._ERR[st]))
-    check(st, what)
-
-
 def gru_seq_fwd(xp, U, h0=None, lengths=None, att=None, hs=None):
     """(hs [B, T, H], h_last [B, H]) of dr_gru_seq_fwd: the GRU (att None) or AUGRU recurrence over xp [B, T, 3H] = x W + b with gate
     columns [u | r | c], U [H, 3H], h0 [B, H] (None: zeros), lengths [B] (None: all T; clamped to [0, T]), att [B, T].  hs: a
@@ -1934,14 +1906,14 @@ def gru_seq_fwd(xp, U, h0=None, lengths=None, att=None, hs=None):
     if B == 0:
         return hs, h_last
     st = lib().dr_gru_seq_fwd(ptr(xp), ld_xp, ptr(U), ptr(h0), ptr(lengths), ptr(att), B, T, H, ptr(hs), ld_hs, ptr(h_last), stream_ptr())
-    _gru_status(st, "dr_gru_seq_fwd")
+    _status(st, "dr_gru_seq_fwd")
     return hs, h_last
 
 
 def gru_seq_bwd_workspace(B, T, H, device):
     need = lib().dr_gru_seq_bwd_workspace_bytes(int(B), int(T), int(H))
     if need < 0:
-        _gru_status(int(need), "dr_gru_seq_bwd_workspace_bytes")
+        _status(int(need), "dr_gru_seq_bwd_workspace_bytes")
     return torch.empty((max(need // 4, 4),), dtype=torch.float32, device=device)
 
 
@@ -1971,7 +1943,7 @@ def gru_seq_bwd(xp, U, h0, lengths, att, hs, d_hs=None, d_h_last=None, d_xp=None
         return d_xp, dU.zero_(), d_h0, d_att
     need = lib().dr_gru_seq_bwd_workspace_bytes(B, T, H)
     if need < 0:
-        _gru_status(int(need), "dr_gru_seq_bwd_workspace_bytes")
+        _status(int(need), "dr_gru_seq_bwd_workspace_bytes")
     if workspace is None:
         workspace = torch.empty((max(need // 4, 4),), dtype=torch.float32, device=dev)
     elif workspace.numel() * workspace.element_size() < need:
@@ -1980,7 +1952,7 @@ def gru_seq_bwd(xp, U, h0, lengths, att, hs, d_hs=None, d_h_last=None, d_xp=None
     st = lib().dr_gru_seq_bwd(ptr(xp), ld_xp, ptr(U), ptr(h0), ptr(lengths), ptr(att), ptr(hs), ld_hs, B, T, H, ptr(d_hs), ld_dhs,
                               ptr(d_h_last), ptr(d_xp), ld_dxp, ptr(dU), ptr(d_h0), ptr(d_att), ptr(workspace),
                               workspace.numel() * workspace.element_size(), stream_ptr())
-    _gru_status(st, "dr_gru_seq_bwd")
+    _status(st, "dr_gru_seq_bwd")
     return d_xp, dU, d_h0, d_att
 
 
@@ -2004,7 +1976,7 @@ def seq_attn_fwd(hs, q, lengths=None):
     a = torch.empty((B, T), dtype=torch.float32, device=hs.device)
     if B == 0:
         return a
-    _gru_status(lib().dr_seq_attn_fwd(ptr(hs), ld_hs, ptr(q), ptr(lengths), B, T, H, ptr(a), stream_ptr()), "dr_seq_attn_fwd")
+    _status(lib().dr_seq_attn_fwd(ptr(hs), ld_hs, ptr(q), ptr(lengths), B, T, H, ptr(a), stream_ptr()), "dr_seq_attn_fwd")
     return a
 
 
@@ -2020,7 +1992,7 @@ def seq_attn_bwd(hs, q, lengths, a, d_a):
     d_q = torch.empty((B, H), dtype=torch.float32, device=hs.device)
     if B == 0:
         return d_hs, d_q
-    _gru_status(lib().dr_seq_attn_bwd(ptr(hs), ld_hs, ptr(q), ptr(lengths), ptr(a), ptr(d_a), B, T, H, ptr(d_hs), H, ptr(d_q),
+    _status(lib().dr_seq_attn_bwd(ptr(hs), ld_hs, ptr(q), ptr(lengths), ptr(a), ptr(d_a), B, T, H, ptr(d_hs), H, ptr(d_q),
                                       stream_ptr()), "dr_seq_attn_bwd")
     return d_hs, d_q
 
@@ -2651,24 +2623,13 @@ def _ffm_rows(t, F, k, what):
         t = t.reshape(t.shape[0], cols)
     if t.dim() != 2 or t.shape[1] != cols:
         raise ValueError("ffm: %s must be [B, %d] (F * F * k columns), got %s" % (what, cols, tuple(t.shape)))
-    if t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= cols:
-        return t, t.stride(0)
-    if t.shape[0] <= 1 and t.stride(1) == 1:
-        return t, cols                                         # a single row has no pitch to speak of
-    raise ValueError("ffm: %s needs unit column stride and a row stride that is a multiple of 4 and >= %d, got strides %s"
-                     % (what, cols, tuple(t.stride())))
+    return t, _row_pitch("ffm", t, cols, what)                 # a single row's pitch is _pad4(cols) = cols: k is a multiple of 4
 
 
 def _ffm_vec(t, B, what):
     if t.dtype != torch.float32 or t.numel() != B:
         raise ValueError("ffm: %s must be fp32 with one value per example (%d), got %s %s" % (what, B, t.dtype, tuple(t.shape)))
     return t.reshape(B).contiguous()
-
-
-def _ffm_status(st, what):
-    if st == _lib.DR_EINVAL:
-        raise ValueError("%s: DR_EINVAL (outside the kernel's domain, or a base address that is not 16-byte aligned)" % what)
-    check(st, what)
 
 
 def ffm_fwd(rows, F, k):
@@ -2680,7 +2641,7 @@ def ffm_fwd(rows, F, k):
     inter = torch.empty((B,), dtype=torch.float32, device=rows.device)
     if B == 0:
         return inter
-    _ffm_status(lib().dr_ffm_fwd(ptr(rows), ld, B, F, k, ptr(inter), stream_ptr()), "dr_ffm_fwd")
+    _status(lib().dr_ffm_fwd(ptr(rows), ld, B, F, k, ptr(inter), stream_ptr()), "dr_ffm_fwd")
     return inter
 
 
@@ -2696,7 +2657,7 @@ def ffm_bwd(rows, F, k, d_inter, d_rows=None):
     d_rows, ld_d = _ffm_rows(d_rows, F, k, "d_rows")
     if B == 0:
         return d_rows
-    _ffm_status(lib().dr_ffm_bwd(ptr(rows), ld, ptr(d_inter), B, F, k, ptr(d_rows), ld_d, stream_ptr()), "dr_ffm_bwd")
+    _status(lib().dr_ffm_bwd(ptr(rows), ld, ptr(d_inter), B, F, k, ptr(d_rows), ld_d, stream_ptr()), "dr_ffm_bwd")
     return d_rows
 
 
@@ -2720,7 +2681,7 @@ def ffm_gather_fwd(ids, row_base, table, F, k, lin_w=None, lin_bias=None):
     first = torch.empty((B,), dtype=torch.float32, device=ids.device) if lin_w is not None else None
     if B == 0:
         return inter, first
-    _ffm_status(lib().dr_ffm_gather_fwd(ptr(ids), B, F, ptr(row_base), ptr(table), k, ptr(lin_w), ptr(lin_bias), ptr(inter), ptr(first),
+    _status(lib().dr_ffm_gather_fwd(ptr(ids), B, F, ptr(row_base), ptr(table), k, ptr(lin_w), ptr(lin_bias), ptr(inter), ptr(first),
                                         stream_ptr()), "dr_ffm_gather_fwd")
     return inter, first
 
@@ -2735,6 +2696,6 @@ def ffm_gather_bwd(ids, row_base, table, F, k, d_inter, d_rows=None):
     d_rows, ld_d = _ffm_rows(d_rows, F, k, "d_rows")
     if B == 0:
         return d_rows
-    _ffm_status(lib().dr_ffm_gather_bwd(ptr(ids), B, F, ptr(row_base), ptr(table), k, ptr(d_inter), ptr(d_rows), ld_d, stream_ptr()),
+    _status(lib().dr_ffm_gather_bwd(ptr(ids), B, F, ptr(row_base), ptr(table), k, ptr(d_inter), ptr(d_rows), ld_d, stream_ptr()),
                 "dr_ffm_gather_bwd")
     return d_rows

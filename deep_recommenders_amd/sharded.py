@@ -28,10 +28,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-
-
-def _pad4(n):
-    return (n + 3) // 4 * 4
+from .ops import _pad4
 
 
 class HipPrims:

@@ -21,10 +21,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import ops
-
-
-def _pad4(n):
-    return (n + 3) // 4 * 4
+from .ops import _pad4
 
 
 class _Tower:
