@@ -1,2 +1,3 @@
 from deep_recommenders_amd.keras.models.nlp.multi_head_attention import MultiHeadAttention
 from deep_recommenders_amd.keras.models.nlp.transformer import Transformer
+from deep_recommenders_amd.keras.models.nlp.word2vec import Word2Vec

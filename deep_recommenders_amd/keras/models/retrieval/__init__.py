@@ -1,3 +1,7 @@
 # same exports as the reference's keras/models/retrieval/__init__.py
 from deep_recommenders_amd.keras.models.retrieval.factorized_top_k import FactorizedTopK
 from deep_recommenders_amd.keras.models.retrieval.gcn import GCN
+# listed in the reference's README, no code there
+from deep_recommenders_amd.keras.models.retrieval.skipgram import SkipGram
+from deep_recommenders_amd.keras.models.retrieval.skipgram import Item2Vec
+from deep_recommenders_amd.keras.models.retrieval.skipgram import DeepWalk

@@ -1216,3 +1216,90 @@ def ffm_gather(table, lin_w, lin_bias, ids, row_base, F, k, sparse_lr=None):
     lin_w is given.  The backward writes d_rows once (dr_ffm_gather_bwd) and hands it to K4, which owns duplicate rows, the first-order
     gradient and, with `sparse_lr`, the fused SGD step."""
     return _FfmGatherFn.apply(table, lin_w, lin_bias, ids, row_base, int(F), int(k), sparse_lr)
+
+
+# ---- skip-gram with negative sampling (csrc/sgns.hip) -------------------------------------------------------------------------------------
+def sgns_apply_rows(table, ids, d_rows, scale, plan=None, scratch=None):
+    """table[ids[b, f], :] += scale * d_rows[b, f * D : (f + 1) * D] for every id >= 0 of ids [B, F] through K4: dr_emb_pool_bwd (fp32
+    atomics) without a plan; with an ops.SortPlan the plan is rebuilt for these ids and dr_emb_pool_bwd_sorted sums the slots of a
+    shared row in a fixed order, hot rows through `scratch` ([B * F, D], clobbered; allocated when None).  Returns the plan used."""
+    B, F = ids.shape
+    D = table.shape[1]
+    row_base = torch.zeros(F, dtype=torch.int64, device=ids.device)
+    if plan is None:
+        col_start = torch.arange(F + 1, dtype=torch.int32, device=ids.device)
+        ops.emb_pool_bwd(ids, F, col_start, row_base, D, d_rows, None, None, None, scale, table, None, None)
+        return None
+    plan = ops.emb_sort_slots(ids, row_base, table.shape[0], plan)
+    if scratch is None or scratch.shape[0] < B * F:
+        scratch = torch.empty((B * F, D), dtype=torch.float32, device=ids.device)
+    ops.emb_pool_bwd_sorted(ids, row_base, plan, D, table.shape[0], d_rows, None, scale, table, x_sorted=scratch)
+    return plan
+
+
+class _SgnsFn(torch.autograd.Function):
+    """dr_sgns_fwd forward; dr_sgns_bwd then K4 on each table backward.  `sparse_lr` as in _EmbPoolFn.  `plans`: None, or a pair of
+    ops.SortPlan (for ids [B, 1] and [B, 1 + K]): the sorted K4, bit-reproducible on hot rows."""
+
+    @staticmethod
+    def forward(ctx, in_table, out_table, centers, contexts, negatives, sample_weight, skip_equal, sparse_lr, plans):
+        loss, coeff, _, _, _ = ops.sgns_fwd(in_table, out_table, centers, contexts, negatives, sample_weight, skip_equal)
+        ctx.skip_equal, ctx.sparse_lr, ctx.plans = skip_equal, sparse_lr, plans
+        ctx.save_for_backward(in_table, out_table, centers, contexts, negatives, coeff)
+        return loss
+
+    @staticmethod
+    @_needed_only
+    def backward(ctx, d_loss):
+        in_table, out_table, centers, contexts, negatives, coeff = ctx.saved_tensors
+        if d_loss is None:
+            return (None,) * 9
+        B = centers.shape[0]
+        d_center, d_ctx = ops.sgns_bwd(in_table, out_table, centers, contexts, negatives, coeff, _rows(d_loss, dense=True), ctx.skip_equal)
+        ids_in = centers.reshape(B, 1)
+        ids_out = contexts.reshape(B, 1) if negatives is None else torch.cat([contexts.reshape(B, 1), negatives], dim=1)
+        plan_in, plan_out = ctx.plans if ctx.plans is not None else (None, None)
+        want_in, want_out = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if ctx.sparse_lr is None:                 # both gradients come from the rows as the forward read them
+            g_in = _param_grad(in_table) if want_in else None
+            g_out = _param_grad(out_table) if want_out else None
+            if want_in:
+                sgns_apply_rows(g_in, ids_in, d_center, 1.0, plan_in)
+            if want_out:
+                sgns_apply_rows(g_out, ids_out, d_ctx, 1.0, plan_out)
+            return g_in, g_out, None, None, None, None, None, None, None
+        if want_in:                               # d_center and d_ctx are complete before either table is touched
+            sgns_apply_rows(in_table.data, ids_in, d_center, -float(ctx.sparse_lr), plan_in)
+        if want_out:
+            sgns_apply_rows(out_table.data, ids_out, d_ctx, -float(ctx.sparse_lr), plan_out)
+        return (None,) * 9
+
+
+def sgns_loss(in_table, out_table, centers, contexts, negatives, sample_weight=None, skip_equal=True, sparse_lr=None, plans=None):
+    """loss_rows [B] of skip-gram with negative sampling: w_b (softplus(-<u, v_0>) + sum_{j >= 1} softplus(<u, v_j>)) with u =
+    in_table[centers[b]], v_0 = out_table[contexts[b]], v_j = out_table[negatives[b, j - 1]].  An example whose center or context is < 0
+    is skipped (loss 0), so is a negative < 0 and, with skip_equal, a negative equal to the context.  One gather kernel each way; the
+    table gradients go through K4 (`sparse_lr` None: dense .grad buffers; a value: the fused SGD step in place; `plans`: a pair of
+    ops.SortPlan for the deterministic K4)."""
+    return _SgnsFn.apply(in_table, out_table, centers, contexts, negatives, sample_weight, bool(skip_equal), sparse_lr, plans)
+
+
+def skipgram_pairs(seqs, window):
+    """(centers, contexts), both int64 [N * L * 2 * window]: for every position (n, t) of seqs [N, L] (padded with -1) and every offset
+    o in (-window .. -1, 1 .. window), the pair (seqs[n, t], seqs[n, t + o]).  An entry is -1 where the partner lies outside the
+    sequence or either side is padding; nothing is compacted, the SGNS kernel skips those pairs.  Integer indexing in torch on seqs'
+    device."""
+    if seqs.dtype != torch.int64 or seqs.dim() != 2:
+        raise ValueError("skipgram_pairs: seqs must be int64 [N, L], got %s %s" % (seqs.dtype, tuple(seqs.shape)))
+    window = int(window)
+    if window < 1:
+        raise ValueError("skipgram_pairs: window must be >= 1, got %d" % window)
+    N, L = seqs.shape
+    offs = torch.tensor([o for o in range(-window, window + 1) if o != 0], dtype=torch.int64, device=seqs.device)
+    pos = torch.arange(L, dtype=torch.int64, device=seqs.device)[:, None] + offs[None, :]            # [L, 2 window]
+    inside = (pos >= 0) & (pos < L)
+    partner = seqs[:, pos.clamp(0, max(L - 1, 0)).reshape(-1)].reshape(N, L, 2 * window)
+    center = seqs[:, :, None].expand(N, L, 2 * window)
+    ok = inside[None, :, :] & (partner >= 0) & (center >= 0)
+    minus = torch.full_like(partner, -1)
+    return torch.where(ok, center, minus).reshape(-1), torch.where(ok, partner, minus).reshape(-1)

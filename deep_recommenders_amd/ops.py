@@ -2699,3 +2699,160 @@ def ffm_gather_bwd(ids, row_base, table, F, k, d_inter, d_rows=None):
     _status(lib().dr_ffm_gather_bwd(ptr(ids), B, F, ptr(row_base), ptr(table), k, ptr(d_inter), ptr(d_rows), ld_d, stream_ptr()),
                 "dr_ffm_gather_bwd")
     return d_rows
+
+
+# ---- skip-gram with negative sampling (csrc/sgns.hip) and the samplers around it (csrc/sampling.hip) -----------------------------------
+SGNS_SKIP_EQUAL = 1     # DR_SGNS_SKIP_EQUAL
+
+
+def _sgns_args(in_table, out_table, centers, contexts, negatives):
+    """validates the domain of dr_sgns_*; returns (B, K, D, centers, contexts, negatives) with the ids contiguous"""
+    for t, what in ((in_table, "in_table"), (out_table, "out_table")):
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError("sgns: %s must be contiguous fp32 [R, D], got %s %s" % (what, t.dtype, tuple(t.shape)))
+    D = in_table.shape[1]
+    if out_table.shape[1] != D:
+        raise ValueError("sgns: in_table and out_table must share D, got %d and %d" % (D, out_table.shape[1]))
+    if D % 4 != 0 or not 4 <= D <= 256:
+        raise ValueError("sgns: D must be a multiple of 4 in [4, 256] (the slab's domain), got %d" % D)
+    if centers.dtype != torch.int64 or centers.dim() != 1:
+        raise ValueError("sgns: centers must be int64 [B], got %s %s" % (centers.dtype, tuple(centers.shape)))
+    B = centers.shape[0]
+    if contexts.dtype != torch.int64 or tuple(contexts.shape) != (B,):
+        raise ValueError("sgns: contexts must be int64 [%d], got %s %s" % (B, contexts.dtype, tuple(contexts.shape)))
+    if negatives is None:
+        negatives = torch.empty((B, 0), dtype=torch.int64, device=centers.device)
+    if negatives.dtype != torch.int64 or negatives.dim() != 2 or negatives.shape[0] != B:
+        raise ValueError("sgns: negatives must be int64 [%d, K], got %s %s" % (B, negatives.dtype, tuple(negatives.shape)))
+    K = negatives.shape[1]
+    if K > 63:
+        raise ValueError("sgns: at most 63 negatives per example (ids [B, 1 + K] go through K4, F <= 64), got K = %d" % K)
+    return B, K, D, centers.contiguous(), contexts.contiguous(), negatives.contiguous()
+
+
+def _sgns_vec(t, B, what):
+    if t.dtype != torch.float32 or t.numel() != B:
+        raise ValueError("sgns: %s must be fp32 with one value per example (%d), got %s %s" % (what, B, t.dtype, tuple(t.shape)))
+    return t.reshape(B).contiguous()
+
+
+def _sgns_grad_buffers(B, K, D, d_center, d_ctx, device):
+    """(d_center [B, D], its pitch, d_ctx [B, (1 + K) D], its pitch): the caller's buffers, checked, or fresh ones"""
+    W = (1 + K) * D
+    if d_center is None:
+        d_center = torch.empty((B, D), dtype=torch.float32, device=device)
+    if d_ctx is None:
+        d_ctx = torch.empty((B, W), dtype=torch.float32, device=device)
+    if d_ctx.dim() == 3 and tuple(d_ctx.shape) == (B, 1 + K, D) and d_ctx.is_contiguous():
+        d_ctx = d_ctx.reshape(B, W)
+    return d_center, _row_pitch("sgns", d_center, D, "d_center"), d_ctx, _row_pitch("sgns", d_ctx, W, "d_ctx")
+
+
+def sgns_fwd(in_table, out_table, centers, contexts, negatives=None, sample_weight=None, skip_equal=True, want_scores=False,
+             row_scale=None, d_center=None, d_ctx=None):
+    """(loss_rows [B], coeff [B, 1 + K], scores [B, 1 + K] | None, d_center | None, d_ctx | None) of dr_sgns_fwd.  centers, contexts
+    int64 [B], negatives int64 [B, K] (None: K = 0); an id < 0 skips its slot (centers / contexts: the example), and with skip_equal a
+    negative equal to the example's context is skipped too.  row_scale (a number) asks for the one-pass training form: d_center [B, D]
+    and d_ctx [B, (1 + K) D], the gradient rows of row_scale * loss_rows, are written in the same pass (into the buffers given, else
+    fresh ones) -- what K4 takes as d_concat for ids [B, 1] and [B, 1 + K]."""
+    B, K, D, centers, contexts, negatives = _sgns_args(in_table, out_table, centers, contexts, negatives)
+    dev = centers.device
+    if sample_weight is not None:
+        sample_weight = _sgns_vec(sample_weight, B, "sample_weight")
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    coeff = torch.empty((B, 1 + K), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, 1 + K), dtype=torch.float32, device=dev) if want_scores else None
+    ld_dc = ld_dx = 0
+    if row_scale is not None:
+        d_center, ld_dc, d_ctx, ld_dx = _sgns_grad_buffers(B, K, D, d_center, d_ctx, dev)
+    elif d_center is not None or d_ctx is not None:
+        raise ValueError("sgns: gradient buffers are written only with a row_scale")
+    if B == 0:
+        return loss, coeff, scores, d_center, d_ctx
+    _status(lib().dr_sgns_fwd(ptr(in_table), ptr(out_table), D, ptr(centers), ptr(contexts), ptr(negatives) if K else None, B, K,
+                              ptr(sample_weight), SGNS_SKIP_EQUAL if skip_equal else 0, float(row_scale or 0.0), ptr(loss), ptr(coeff),
+                              ptr(scores), ptr(d_center), ld_dc, ptr(d_ctx), ld_dx, stream_ptr()), "dr_sgns_fwd")
+    return loss, coeff, scores, d_center, d_ctx
+
+
+def sgns_bwd(in_table, out_table, centers, contexts, negatives, coeff, d_loss, skip_equal=True, d_center=None, d_ctx=None):
+    """(d_center [B, D], d_ctx [B, (1 + K) D]) of dr_sgns_bwd: the gradient rows of sum_b d_loss[b] * loss_rows[b] from the forward's
+    coeff, the rows gathered again.  Same ids and skip_equal as the forward."""
+    B, K, D, centers, contexts, negatives = _sgns_args(in_table, out_table, centers, contexts, negatives)
+    if coeff.dtype != torch.float32 or tuple(coeff.shape) != (B, 1 + K):
+        raise ValueError("sgns: coeff must be fp32 [%d, %d], got %s %s" % (B, 1 + K, coeff.dtype, tuple(coeff.shape)))
+    coeff = coeff.contiguous()
+    d_loss = _sgns_vec(d_loss, B, "d_loss")
+    d_center, ld_dc, d_ctx, ld_dx = _sgns_grad_buffers(B, K, D, d_center, d_ctx, centers.device)
+    if B == 0:
+        return d_center, d_ctx
+    _status(lib().dr_sgns_bwd(ptr(in_table), ptr(out_table), D, ptr(centers), ptr(contexts), ptr(negatives) if K else None, B, K,
+                              SGNS_SKIP_EQUAL if skip_equal else 0, ptr(coeff), ptr(d_loss), ptr(d_center), ld_dc, ptr(d_ctx), ld_dx,
+                              stream_ptr()), "dr_sgns_bwd")
+    return d_center, d_ctx
+
+
+def alias_table(weights):
+    """(prob float32 [V], alias int32 [V]) of Vose's alias method for the distribution weights / sum(weights), NumPy on the host, built
+    once: a draw picks a slot uniformly and returns it with probability prob[slot], else alias[slot].  word2vec's negative distribution
+    is alias_table(counts ** 0.75).  An entry of weight 0 has prob 0 and is nobody's alias: it is never drawn."""
+    import numpy as np
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    V = w.size
+    if V < 1 or V >= 2 ** 31:
+        raise ValueError("alias_table: needs 1 <= V < 2^31 weights, got %d" % V)
+    if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+        raise ValueError("alias_table: weights must be finite, >= 0 and not all zero")
+    p = w * (V / w.sum())
+    prob = np.ones(V, dtype=np.float64)
+    alias = np.arange(V, dtype=np.int32)
+    small = np.flatnonzero(p < 1.0).tolist()
+    large = np.flatnonzero(p >= 1.0).tolist()
+    while small and large:
+        s, l = small.pop(), large.pop()
+        prob[s], alias[s] = p[s], l
+        p[l] = (p[l] + p[s]) - 1.0
+        (small if p[l] < 1.0 else large).append(l)
+    return prob.astype(np.float32), alias            # what is left on either list has p = 1 up to rounding: prob 1, its own alias
+
+
+def alias_sample(prob, alias, n, seed, offset=0, out=None):
+    """n int64 draws of dr_alias_sample from the table (prob fp32 [V], alias int32 [V], on the device): element i depends on
+    (seed, offset + i) alone, so consecutive calls with a running offset continue one stream."""
+    if prob.dtype != torch.float32 or alias.dtype != torch.int32 or prob.dim() != 1 or prob.shape != alias.shape or prob.numel() < 1:
+        raise ValueError("alias_sample: prob fp32 [V] and alias int32 [V], V >= 1, got %s %s and %s %s"
+                         % (prob.dtype, tuple(prob.shape), alias.dtype, tuple(alias.shape)))
+    n = int(n)
+    if n < 0 or int(offset) < 0:
+        raise ValueError("alias_sample: n and offset must be >= 0")
+    prob, alias = prob.contiguous(), alias.contiguous()
+    if out is None:
+        out = torch.empty((n,), dtype=torch.int64, device=prob.device)
+    elif out.dtype != torch.int64 or out.numel() != n or not out.is_contiguous():
+        raise ValueError("alias_sample: out must be contiguous int64 with %d elements" % n)
+    if n == 0:
+        return out
+    _status(lib().dr_alias_sample(ptr(prob), ptr(alias), prob.numel(), n, int(seed) & (2 ** 64 - 1), int(offset), ptr(out), stream_ptr()),
+            "dr_alias_sample")
+    return out
+
+
+def random_walk(row_ptr, col, n_rows, starts, length, seed):
+    """walks int64 [W, length] of dr_random_walk over the CSR graph (row_ptr int64 [n_rows + 1], col int32): uniform next neighbours from
+    starts [W]; a walk that reaches a node without neighbours, or starts outside [0, n_rows), continues as -1."""
+    n_rows, L = int(n_rows), int(length)
+    if row_ptr.dtype != torch.int64 or row_ptr.dim() != 1 or row_ptr.numel() != n_rows + 1 or col.dtype != torch.int32 or col.dim() != 1:
+        raise ValueError("random_walk: row_ptr int64 [n_rows + 1] and col int32 [nnz], got %s %s and %s %s"
+                         % (row_ptr.dtype, tuple(row_ptr.shape), col.dtype, tuple(col.shape)))
+    if starts.dtype != torch.int64 or starts.dim() != 1:
+        raise ValueError("random_walk: starts must be int64 [W], got %s %s" % (starts.dtype, tuple(starts.shape)))
+    if L < 1:
+        raise ValueError("random_walk: a walk has at least its start, got length %d" % L)
+    row_ptr, col, starts = row_ptr.contiguous(), col.contiguous(), starts.contiguous()
+    W = starts.numel()
+    walks = torch.empty((W, L), dtype=torch.int64, device=starts.device)
+    if W == 0:
+        return walks
+    _status(lib().dr_random_walk(ptr(row_ptr), ptr(col) if col.numel() else None, n_rows, ptr(starts), W, L, int(seed) & (2 ** 64 - 1),
+                                 ptr(walks), stream_ptr()), "dr_random_walk")
+    return walks

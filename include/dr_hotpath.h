@@ -974,6 +974,62 @@ int dr_ffm_gather_bwd(const int64_t* ids, int64_t B, int32_t F, const int64_t* r
                       const float* d_inter, float* d_rows, int64_t ld_d, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Skip-gram with negative sampling (Mikolov et al., NIPS 2013): the training step of Word2Vec, Item2Vec and DeepWalk, which the
+ * reference's README lists and ships no code for; csrc/sgns.hip.  All fp32.  in_table [R_in, D] and out_table [R_out, D] dense.
+ * Example b: c = centers[b], o_0 = contexts[b], o_1 .. o_K = negatives[b, :] ([B, K] dense int64), u = in_table[c], v_j = out_table[o_j],
+ * z_j = 1 for j = 0 and 0 otherwise, w_b = sample_weight[b] (1 when sample_weight is NULL).
+ *   s_j    = <u, v_j>
+ *   loss_b = w_b * sum_j softplus((1 - 2 z_j) s_j),   softplus(x) = max(x, 0) + log1p(exp(-|x|))
+ *   g_j    = w_b * (sigmoid(s_j) - z_j)
+ *   Skipped: the whole example when c < 0 or o_0 < 0; a negative with o_j < 0; with flags & DR_SGNS_SKIP_EQUAL a negative with
+ *   o_j == o_0 (the rule of word2vec.c).  A skipped slot has s_j = g_j = 0, adds nothing to loss_b (a skipped example's is 0) and its id
+ *   is never turned into an address that is read: any int64 may stand there.
+ *   dr_sgns_fwd   writes loss_rows [B], coeff [B, 1 + K] (the g_j) and, unless NULL, scores [B, 1 + K] (the s_j), all dense.  With
+ *                 d_center and d_ctx given (both or neither) the same pass also writes the gradient rows of row_scale * loss_b:
+ *                   c_j = row_scale * g_j;  d_ctx[b, j, :] = c_j * u  (+0.0 for a skipped slot);  d_center[b, :] = sum_j c_j * v_j,
+ *                 j ascending, one fused multiply-add per term.  d_center [B, D] at the pitch ld_dc, d_ctx [B, (1 + K) * D] at the
+ *                 pitch ld_dx (D resp. (1 + K) * D columns are overwritten, nothing beyond them; both pitches are ignored without
+ *                 the buffers).  This is the training path: every row is read once.
+ *   dr_sgns_bwd   the same two buffers from coeff and a per-example d_loss [B]: c_j = d_loss[b] * g_j, the rows re-gathered, the same
+ *                 operations in the same order -- with d_loss[b] == row_scale both entry points write the same bits.
+ *   d_center with ids [B, 1] and d_ctx with ids [B, 1 + K] are what the K4 entry points (atomic or sorted form) take as d_concat to
+ *   update or differentiate in_table and out_table; a skipped slot with an id >= 0 adds its row of zeros.
+ *   A group of D / 4 lanes, rounded up to a power of two, owns an example; u stays in registers, four rows v_j are in flight per
+ *   lane.  No atomics, no LDS, no workspace, one launch: results are bit-identical from run to run and an example's bits depend
+ *   neither on its batch nor on its place in it.
+ *   Domain: D % 4 == 0, 4 <= D <= 256, 0 <= K <= 63 (negatives may be NULL when K == 0), flags 0 or DR_SGNS_SKIP_EQUAL, both tables and
+ *   both gradient buffers 16-byte aligned, ld_dc and ld_dx multiples of 4 and >= the width they cover; anything else or a NULL
+ *   required pointer is DR_EINVAL.  B == 0 is DR_OK and launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+#define DR_SGNS_SKIP_EQUAL 1
+int dr_sgns_fwd(const float* in_table, const float* out_table, int32_t D, const int64_t* centers, const int64_t* contexts,
+                const int64_t* negatives, int64_t B, int32_t K, const float* sample_weight, int32_t flags, float row_scale,
+                float* loss_rows, float* coeff, float* scores, float* d_center, int64_t ld_dc, float* d_ctx, int64_t ld_dx,
+                dr_stream_t stream);
+int dr_sgns_bwd(const float* in_table, const float* out_table, int32_t D, const int64_t* centers, const int64_t* contexts,
+                const int64_t* negatives, int64_t B, int32_t K, int32_t flags, const float* coeff, const float* d_loss, float* d_center,
+                int64_t ld_dc, float* d_ctx, int64_t ld_dx, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The integer kernels around the skip-gram step, csrc/sampling.hip.  Both are counter-based on the hash of dr_attn_fwd's dropout
+ * (dr_mix32, spelled out there): an element is a function of (seed, position) alone, never of the launch.
+ *   dr_alias_sample   n draws from a Vose alias table (prob [V] fp32, alias [V] int32 with entries in [0, V), 1 <= V < 2^31), the
+ *                     negative sampler of word2vec over counts^0.75.  Element i, with e = offset + i:
+ *                       h1 = dr_mix32(seed, 2 e);  h2 = dr_mix32(seed, 2 e + 1);  slot = (uint64(h1) * V) >> 32;
+ *                       r = (h2 >> 8) * 2^-24  (exact in fp32);   out[i] = r < prob[slot] ? slot : alias[slot]
+ *                     so that draws [0, n) and then [n, 2 n) with offset = n equal one call of 2 n.
+ *   dr_random_walk    W uniform random walks of L nodes over a CSR graph (row_ptr int64 [n_rows + 1], col int32, as dr_csr_spmm takes
+ *                     them): walks [W, L] dense, walks[w, 0] = starts[w]; at step t >= 1 from v = walks[w, t - 1], with
+ *                     deg = row_ptr[v + 1] - row_ptr[v]:  walks[w, t] = col[row_ptr[v] + ((uint64(dr_mix32(seed, w * L + t)) * deg) >> 32)].
+ *                     v < 0, v >= n_rows or deg == 0 ends the walk: that step and every later one is -1.  One lane per walk.
+ *   n == 0 / W == 0 is DR_OK and launches nothing; V outside its range, L < 1, a negative size or a NULL required pointer is DR_EINVAL.
+ * ---------------------------------------------------------------------------------------- */
+int dr_alias_sample(const float* prob, const int32_t* alias, int64_t V, int64_t n, uint64_t seed, uint64_t offset, int64_t* out,
+                    dr_stream_t stream);
+int dr_random_walk(const int64_t* row_ptr, const int32_t* col, int64_t n_rows, const int64_t* starts, int64_t W, int32_t L,
+                   uint64_t seed, int64_t* walks, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * PNN's outer-product layer (Qu et al., ICDM 2016; the reference's README lists PNN among its ranking models and ships no code for
  * it), csrc/pnn_outer.hip.  All fp32.  emb[b] holds the F rows of example b ([F * D], field-major: the slab's concat, read in place at
  * the pitch ld_emb); W [D * D, N] row-major at the pitch ld_w, row d * D + e multiplies u_d u_e (the full square, not a triangle).
