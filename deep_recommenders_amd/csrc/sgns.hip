@@ -14,13 +14,11 @@
 // A SKIPPED SLOT (the example's c or o_0 < 0; o_j < 0; o_j == o_0 under DR_SGNS_SKIP_EQUAL) loads nothing -- whatever its id would address
 // is never formed into a pointer that is dereferenced -- and has s_j = g_j = 0, a d_ctx row of +0.0 and no term in loss_b or d_center.
 // The one-pass forward and the backward share sgns_grad_slot(): given d_loss[b] == row_scale they write the same bits.
-#include "dr_common.h"
+#include "sgns_common.h"
 
 namespace {
 
-constexpr int SGNS_MAX_D = 256;       // the slab's row width
 constexpr int SGNS_MAX_K = 63;        // ids [B, 1 + K] go through the sorted K4, which takes F <= 64
-constexpr int SGNS_U = 4;             // rows v_j a lane keeps in flight (8 measured no faster: DESIGN.md section 20)
 
 struct SgnsP {
     const float* in_table; const float* out_table;
@@ -34,25 +32,6 @@ struct SgnsP {
     int64_t B;
     int32_t D, K, skip_equal;
 };
-
-__device__ __forceinline__ float sgns_dot4(const float4& a, const float4& b) {
-    float acc = a.x * b.x;
-    acc = fmaf(a.y, b.y, acc);
-    acc = fmaf(a.z, b.z, acc);
-    return fmaf(a.w, b.w, acc);
-}
-
-// slot j's share of the gradient rows, the same instructions in both kernels: one rounded multiply per d_ctx element, one fmaf per
-// d_center element
-__device__ __forceinline__ void sgns_grad_slot(float cj, bool skip, const float4& u, const float4& v, float4& acc, float4& dx) {
-    dx = skip ? dr_zero4() : make_float4(cj * u.x, cj * u.y, cj * u.z, cj * u.w);
-    if (!skip) {
-        acc.x = fmaf(cj, v.x, acc.x);
-        acc.y = fmaf(cj, v.y, acc.y);
-        acc.z = fmaf(cj, v.z, acc.z);
-        acc.w = fmaf(cj, v.w, acc.w);
-    }
-}
 
 // BWD false: scores, loss, coeff and (d_center != NULL) the gradient rows of row_scale * loss_b.  BWD true: the gradient rows from coeff
 // and d_loss.
@@ -103,14 +82,8 @@ __global__ __launch_bounds__(256) void sgns_kernel(const SgnsP p) {
             if constexpr (BWD) {
                 g = gin[t];
             } else {
-                float s = sgns_dot4(u, v[t]);
-#pragma unroll
-                for (int m = G / 2; m > 0; m >>= 1) s += __shfl_xor(s, m, G);
-                const float z = j == 0 ? 1.f : 0.f;
-                const float x = j == 0 ? -s : s;
-                const float l = fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));
-                g = skip[t] ? 0.f : w * (dr_sigmoidf(s) - z);
-                if (!skip[t]) loss += l;
+                const float s = sgns_group_sum<G>(sgns_dot4(u, v[t]));
+                g = sgns_loss_term(s, j == 0, skip[t], w, loss);
                 if (bv && jv && gl == 0) {
                     p.coeff[b * S + j] = g;
                     if (p.scores != nullptr) p.scores[b * S + j] = skip[t] ? 0.f : s;

@@ -1219,13 +1219,16 @@ def ffm_gather(table, lin_w, lin_bias, ids, row_base, F, k, sparse_lr=None):
 
 
 # ---- skip-gram with negative sampling (csrc/sgns.hip) -------------------------------------------------------------------------------------
-def sgns_apply_rows(table, ids, d_rows, scale, plan=None, scratch=None):
+def sgns_apply_rows(table, ids, d_rows, scale, plan=None, scratch=None, row_base=None):
     """table[ids[b, f], :] += scale * d_rows[b, f * D : (f + 1) * D] for every id >= 0 of ids [B, F] through K4: dr_emb_pool_bwd (fp32
     atomics) without a plan; with an ops.SortPlan the plan is rebuilt for these ids and dr_emb_pool_bwd_sorted sums the slots of a
-    shared row in a fixed order, hot rows through `scratch` ([B * F, D], clobbered; allocated when None).  Returns the plan used."""
+    shared row in a fixed order, hot rows through `scratch` ([B * F, D], clobbered; allocated when None).  `row_base` (int64 [F] on
+    the device) makes field f's row row_base[f] + ids[b, f], as the slab's fields share one table; None: every field starts at row 0.
+    Returns the plan used."""
     B, F = ids.shape
     D = table.shape[1]
-    row_base = torch.zeros(F, dtype=torch.int64, device=ids.device)
+    if row_base is None:
+        row_base = torch.zeros(F, dtype=torch.int64, device=ids.device)
     if plan is None:
         col_start = torch.arange(F + 1, dtype=torch.int32, device=ids.device)
         ops.emb_pool_bwd(ids, F, col_start, row_base, D, d_rows, None, None, None, scale, table, None, None)
@@ -1282,6 +1285,68 @@ def sgns_loss(in_table, out_table, centers, contexts, negatives, sample_weight=N
     table gradients go through K4 (`sparse_lr` None: dense .grad buffers; a value: the fused SGD step in place; `plans`: a pair of
     ops.SortPlan for the deterministic K4)."""
     return _SgnsFn.apply(in_table, out_table, centers, contexts, negatives, sample_weight, bool(skip_equal), sparse_lr, plans)
+
+
+# ---- skip-gram with side information (csrc/eges.hip) ---------------------------------------------------------------------------------------
+class _EgesFn(torch.autograd.Function):
+    """dr_eges_fwd forward; dr_eges_bwd then K4 on each of the three tables backward (side_table: ids side_ids with row_base; att: ids
+    att_ids as [B, 1], its rows d_att [B, pad4(S)]; out_table: ids [contexts | negatives]).  `sparse_lr` as in _SgnsFn.  `plans`:
+    None, or three ops.SortPlan in that order: the sorted K4, bit-reproducible on shared rows."""
+
+    @staticmethod
+    def forward(ctx, side_table, att, out_table, row_base, side_ids, att_ids, contexts, negatives, sample_weight, skip_equal, sparse_lr,
+                plans):
+        loss, coeff, alpha, _, _, _, _ = ops.eges_fwd(side_table, row_base, side_ids, att, att_ids, out_table, contexts, negatives,
+                                                      sample_weight, skip_equal)
+        ctx.skip_equal, ctx.sparse_lr, ctx.plans, ctx.has_att = skip_equal, sparse_lr, plans, att is not None
+        ctx.save_for_backward(side_table, att, out_table, row_base, side_ids, att_ids, contexts, negatives, coeff, alpha)
+        return loss
+
+    @staticmethod
+    @_needed_only
+    def backward(ctx, d_loss):
+        side_table, att, out_table, row_base, side_ids, att_ids, contexts, negatives, coeff, alpha = ctx.saved_tensors
+        if d_loss is None:
+            return (None,) * 12
+        B = side_ids.shape[0]
+        d_side, d_att, d_ctx = ops.eges_bwd(side_table, row_base, side_ids, att, att_ids, out_table, contexts, negatives, coeff, alpha,
+                                            _rows(d_loss, dense=True), ctx.skip_equal)
+        ids_out = contexts.reshape(B, -1) if negatives is None else torch.cat([contexts.reshape(B, -1), negatives], dim=1)
+        plan_side, plan_att, plan_out = ctx.plans if ctx.plans is not None else (None, None, None)
+        want_side, want_att, want_out = ctx.needs_input_grad[0], ctx.has_att and ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if want_att and att.shape[1] != d_att.shape[1]:
+            raise ValueError("eges_loss: a trainable att must be [R, %d] (S rounded up to a multiple of 4: K4's row), got %s"
+                             % (d_att.shape[1], tuple(att.shape)))
+        if ctx.sparse_lr is None:                 # all three gradients come from the rows as the forward read them
+            g_side = _param_grad(side_table) if want_side else None
+            g_att = _param_grad(att) if want_att else None
+            g_out = _param_grad(out_table) if want_out else None
+            scale = 1.0
+        else:                                     # the three buffers are complete before any table is touched
+            g_side, g_att, g_out = side_table.data, att.data if want_att else None, out_table.data
+            scale = -float(ctx.sparse_lr)
+        if want_side:
+            sgns_apply_rows(g_side, side_ids, d_side, scale, plan_side, row_base=row_base)
+        if want_att:
+            sgns_apply_rows(g_att, att_ids.reshape(B, 1), d_att, scale, plan_att)
+        if want_out:
+            sgns_apply_rows(g_out, ids_out, d_ctx, scale, plan_out)
+        if ctx.sparse_lr is not None:
+            return (None,) * 12
+        return (g_side, g_att, g_out) + (None,) * 9
+
+
+def eges_loss(side_table, row_base, side_ids, att, att_ids, out_table, contexts, negatives, sample_weight=None, skip_equal=True,
+              sparse_lr=None, plans=None):
+    """loss_rows [B] of skip-gram with side information (EGES): sgns_loss whose centre vector is sum_s alpha_s w_s over the fields of
+    the example that are present (side_ids[b, s] >= 0), w_s = side_table[row_base[s] + side_ids[b, s]], alpha = softmax of
+    att[att_ids[b], :S] over those fields (att None or att_ids[b] < 0: their average, the cold-start rule).  contexts int64 [B, P]
+    (or [B]) are positives, negatives int64 [B, K]; an example with no field or contexts[b, 0] < 0 is skipped (loss 0), so is a slot
+    with an id < 0 and, with skip_equal, a negative equal to one of the example's positives.  One gather kernel each way; the
+    gradients of side_table, att ([R, S rounded up to a multiple of 4]) and out_table go through K4 (`sparse_lr` None: dense .grad
+    buffers; a value: the fused SGD step in place; `plans`: three ops.SortPlan for the deterministic K4)."""
+    return _EgesFn.apply(side_table, att, out_table, row_base, side_ids, att_ids, contexts, negatives, sample_weight, bool(skip_equal),
+                         sparse_lr, plans)
 
 
 def skipgram_pairs(seqs, window):

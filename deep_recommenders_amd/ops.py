@@ -2856,3 +2856,177 @@ def random_walk(row_ptr, col, n_rows, starts, length, seed):
     _status(lib().dr_random_walk(ptr(row_ptr), ptr(col) if col.numel() else None, n_rows, ptr(starts), W, L, int(seed) & (2 ** 64 - 1),
                                  ptr(walks), stream_ptr()), "dr_random_walk")
     return walks
+
+
+def random_walk_weighted(row_ptr, col, cum, n_rows, starts, length, seed):
+    """walks int64 [W, length] of dr_random_walk_weighted: random_walk with the next neighbour drawn in proportion to integer edge
+    weights, given as cum int64 [nnz], their inclusive prefix sums over the whole col array.  Every row's total must stay below 2^32:
+    the caller checks that once per graph (the kernel cannot)."""
+    n_rows, L = int(n_rows), int(length)
+    if row_ptr.dtype != torch.int64 or row_ptr.dim() != 1 or row_ptr.numel() != n_rows + 1 or col.dtype != torch.int32 or col.dim() != 1:
+        raise ValueError("random_walk_weighted: row_ptr int64 [n_rows + 1] and col int32 [nnz], got %s %s and %s %s"
+                         % (row_ptr.dtype, tuple(row_ptr.shape), col.dtype, tuple(col.shape)))
+    if cum.dtype != torch.int64 or cum.shape != col.shape:
+        raise ValueError("random_walk_weighted: cum must be int64 [nnz = %d], got %s %s" % (col.numel(), cum.dtype, tuple(cum.shape)))
+    if starts.dtype != torch.int64 or starts.dim() != 1:
+        raise ValueError("random_walk_weighted: starts must be int64 [W], got %s %s" % (starts.dtype, tuple(starts.shape)))
+    if L < 1:
+        raise ValueError("random_walk_weighted: a walk has at least its start, got length %d" % L)
+    row_ptr, col, cum, starts = row_ptr.contiguous(), col.contiguous(), cum.contiguous(), starts.contiguous()
+    W = starts.numel()
+    walks = torch.empty((W, L), dtype=torch.int64, device=starts.device)
+    if W == 0:
+        return walks
+    some = col.numel() > 0
+    _status(lib().dr_random_walk_weighted(ptr(row_ptr), ptr(col) if some else None, ptr(cum) if some else None, n_rows, ptr(starts), W, L,
+                                          int(seed) & (2 ** 64 - 1), ptr(walks), stream_ptr()), "dr_random_walk_weighted")
+    return walks
+
+
+# ---- skip-gram with side information (csrc/eges.hip) ----------------------------------------------------------------------------------------
+def _eges_one_device(dev, **tensors):
+    """every tensor a dr_eges_* call is handed lives where side_ids does"""
+    for what, t in tensors.items():
+        if t is not None and t.device != dev:
+            raise ValueError("eges: %s is on %s, side_ids on %s; one call takes tensors of one device" % (what, t.device, dev))
+
+
+def _eges_side_args(side_table, row_base, side_ids, att, att_ids):
+    """validates the gather side of dr_eges_*; returns (B, S, D, row_base, side_ids, att, ld_att, att_ids), ids contiguous"""
+    if side_table.dtype != torch.float32 or side_table.dim() != 2 or not side_table.is_contiguous():
+        raise ValueError("eges: side_table must be contiguous fp32 [R, D], got %s %s" % (side_table.dtype, tuple(side_table.shape)))
+    D = side_table.shape[1]
+    if D % 4 != 0 or not 4 <= D <= 256:
+        raise ValueError("eges: D must be a multiple of 4 in [4, 256] (the slab's domain), got %d" % D)
+    if side_ids.dtype != torch.int64 or side_ids.dim() != 2:
+        raise ValueError("eges: side_ids must be int64 [B, S], got %s %s" % (side_ids.dtype, tuple(side_ids.shape)))
+    B, S = side_ids.shape
+    if not 1 <= S <= 16:
+        raise ValueError("eges: 1 <= S <= 16 fields, got %d" % S)
+    _eges_one_device(side_ids.device, side_table=side_table, att=att, att_ids=att_ids if att is not None else None)
+    if row_base.dtype != torch.int64 or tuple(row_base.shape) != (S,) or row_base.device != side_ids.device:
+        raise ValueError("eges: row_base must be int64 [%d] on the ids' device, got %s %s" % (S, row_base.dtype, tuple(row_base.shape)))
+    ld_att = 0
+    if att is not None:
+        if att.dtype != torch.float32 or att.dim() != 2 or att.shape[1] < S or att.stride(1) != 1 or (att.shape[0] > 1 and att.stride(0) < S):
+            raise ValueError("eges: att must be fp32 [R_att, >= %d] with unit column stride, got %s %s" % (S, att.dtype, tuple(att.shape)))
+        if att_ids is None or att_ids.dtype != torch.int64 or tuple(att_ids.shape) != (B,):
+            raise ValueError("eges: att needs att_ids int64 [%d]" % B)
+        ld_att = att.stride(0) if att.shape[0] > 1 else att.shape[1]
+        att_ids = att_ids.contiguous()
+    else:
+        att_ids = None
+    return B, S, D, row_base.contiguous(), side_ids.contiguous(), att, ld_att, att_ids
+
+
+def _eges_slot_args(out_table, contexts, negatives, B, D):
+    """validates the slot side of dr_eges_fwd / _bwd; returns (P, K, contexts [B, P], negatives [B, K]) contiguous"""
+    if out_table.dtype != torch.float32 or out_table.dim() != 2 or not out_table.is_contiguous() or out_table.shape[1] != D:
+        raise ValueError("eges: out_table must be contiguous fp32 [R, %d], got %s %s" % (D, out_table.dtype, tuple(out_table.shape)))
+    if contexts.dtype == torch.int64 and contexts.dim() == 1:
+        contexts = contexts.reshape(-1, 1)
+    if contexts.dtype != torch.int64 or contexts.dim() != 2 or contexts.shape[0] != B:
+        raise ValueError("eges: contexts must be int64 [%d, P], got %s %s" % (B, contexts.dtype, tuple(contexts.shape)))
+    P = contexts.shape[1]
+    if not 1 <= P <= 4:
+        raise ValueError("eges: 1 <= P <= 4 positives per example, got %d" % P)
+    if negatives is None:
+        negatives = torch.empty((B, 0), dtype=torch.int64, device=contexts.device)
+    if negatives.dtype != torch.int64 or negatives.dim() != 2 or negatives.shape[0] != B:
+        raise ValueError("eges: negatives must be int64 [%d, K], got %s %s" % (B, negatives.dtype, tuple(negatives.shape)))
+    K = negatives.shape[1]
+    if P + K > 64:
+        raise ValueError("eges: at most 64 slots per example (ids [B, P + K] go through K4, F <= 64), got P + K = %d" % (P + K))
+    return P, K, contexts.contiguous(), negatives.contiguous()
+
+
+def _eges_slot_devices(dev, out_table, contexts, negatives, **more):
+    _eges_one_device(dev, out_table=out_table, contexts=contexts, negatives=negatives, **more)
+
+
+def _eges_grad_buffers(B, S, J, D, d_side, d_att, d_ctx, device):
+    """(d_side [B, S D], its pitch, d_att [B, pad4(S)], its width, d_ctx [B, J D], its pitch): the caller's buffers, checked, or fresh"""
+    ld_da = _pad4(S)
+    if d_side is None:
+        d_side = torch.empty((B, S * D), dtype=torch.float32, device=device)
+    if d_att is None:
+        d_att = torch.empty((B, ld_da), dtype=torch.float32, device=device)
+    if d_ctx is None:
+        d_ctx = torch.empty((B, J * D), dtype=torch.float32, device=device)
+    if d_att.dtype != torch.float32 or tuple(d_att.shape) != (B, ld_da) or not d_att.is_contiguous():
+        raise ValueError("eges: d_att must be contiguous fp32 [%d, %d] (S rounded up to a multiple of 4), got %s %s"
+                         % (B, ld_da, d_att.dtype, tuple(d_att.shape)))
+    return d_side, _row_pitch("eges", d_side, S * D, "d_side"), d_att, ld_da, d_ctx, _row_pitch("eges", d_ctx, J * D, "d_ctx")
+
+
+def eges_fwd(side_table, row_base, side_ids, att, att_ids, out_table, contexts, negatives=None, sample_weight=None, skip_equal=True,
+             want_scores=False, row_scale=None, d_side=None, d_att=None, d_ctx=None):
+    """(loss_rows [B], coeff [B, P + K], alpha [B, S], scores | None, d_side | None, d_att | None, d_ctx | None) of dr_eges_fwd: SGNS
+    whose centre is the softmax(att[att_ids[b], :S])-weighted sum of the rows side_table[row_base[s] + side_ids[b, s]] of the fields
+    that are present (side_ids >= 0); att None or att_ids[b] < 0: their plain average.  contexts int64 [B, P] (or [B]) are the
+    positives, negatives int64 [B, K].  row_scale (a number) asks for the one-pass training form: d_side [B, S D], d_att [B, pad4(S)]
+    and d_ctx [B, (P + K) D], the gradient rows of row_scale * loss_rows, written in the same pass -- what K4 takes as d_concat for
+    the ids (side_ids with row_base), att_ids [B, 1] and [contexts | negatives]."""
+    B, S, D, row_base, side_ids, att, ld_att, att_ids = _eges_side_args(side_table, row_base, side_ids, att, att_ids)
+    P, K, contexts, negatives = _eges_slot_args(out_table, contexts, negatives, B, D)
+    dev = side_ids.device
+    _eges_slot_devices(dev, out_table, contexts, negatives, sample_weight=sample_weight, d_side=d_side, d_att=d_att, d_ctx=d_ctx)
+    if sample_weight is not None:
+        sample_weight = _sgns_vec(sample_weight, B, "sample_weight")
+    J = P + K
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    coeff = torch.empty((B, J), dtype=torch.float32, device=dev)
+    alpha = torch.empty((B, S), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, J), dtype=torch.float32, device=dev) if want_scores else None
+    ld_ds = ld_da = ld_dx = 0
+    if row_scale is not None:
+        d_side, ld_ds, d_att, ld_da, d_ctx, ld_dx = _eges_grad_buffers(B, S, J, D, d_side, d_att, d_ctx, dev)
+    elif d_side is not None or d_att is not None or d_ctx is not None:
+        raise ValueError("eges: gradient buffers are written only with a row_scale")
+    if B == 0:
+        return loss, coeff, alpha, scores, d_side, d_att, d_ctx
+    _status(lib().dr_eges_fwd(ptr(side_table), D, ptr(row_base), ptr(side_ids), S, ptr(att), ld_att, ptr(att_ids), ptr(out_table),
+                              ptr(contexts), P, ptr(negatives) if K else None, K, B, ptr(sample_weight),
+                              SGNS_SKIP_EQUAL if skip_equal else 0, float(row_scale or 0.0), ptr(loss), ptr(coeff), ptr(alpha),
+                              ptr(scores), ptr(d_side), ld_ds, ptr(d_att), ld_da, ptr(d_ctx), ld_dx, stream_ptr()), "dr_eges_fwd")
+    return loss, coeff, alpha, scores, d_side, d_att, d_ctx
+
+
+def eges_bwd(side_table, row_base, side_ids, att, att_ids, out_table, contexts, negatives, coeff, alpha, d_loss, skip_equal=True,
+             d_side=None, d_att=None, d_ctx=None):
+    """(d_side [B, S D], d_att [B, pad4(S)], d_ctx [B, (P + K) D]) of dr_eges_bwd: the gradient rows of sum_b d_loss[b] * loss_rows[b]
+    from the forward's coeff and alpha, the rows gathered again.  Same ids, att / att_ids and skip_equal as the forward."""
+    B, S, D, row_base, side_ids, att, _, att_ids = _eges_side_args(side_table, row_base, side_ids, att, att_ids)
+    P, K, contexts, negatives = _eges_slot_args(out_table, contexts, negatives, B, D)
+    _eges_slot_devices(side_ids.device, out_table, contexts, negatives, coeff=coeff, alpha=alpha, d_loss=d_loss, d_side=d_side, d_att=d_att,
+                       d_ctx=d_ctx)
+    J = P + K
+    if coeff.dtype != torch.float32 or tuple(coeff.shape) != (B, J):
+        raise ValueError("eges: coeff must be fp32 [%d, %d], got %s %s" % (B, J, coeff.dtype, tuple(coeff.shape)))
+    if alpha.dtype != torch.float32 or tuple(alpha.shape) != (B, S):
+        raise ValueError("eges: alpha must be fp32 [%d, %d], got %s %s" % (B, S, alpha.dtype, tuple(alpha.shape)))
+    coeff, alpha = coeff.contiguous(), alpha.contiguous()
+    d_loss = _sgns_vec(d_loss, B, "d_loss")
+    d_side, ld_ds, d_att, ld_da, d_ctx, ld_dx = _eges_grad_buffers(B, S, J, D, d_side, d_att, d_ctx, side_ids.device)
+    if B == 0:
+        return d_side, d_att, d_ctx
+    _status(lib().dr_eges_bwd(ptr(side_table), D, ptr(row_base), ptr(side_ids), S, ptr(att), ptr(att_ids), ptr(out_table), ptr(contexts),
+                              P, ptr(negatives) if K else None, K, B, SGNS_SKIP_EQUAL if skip_equal else 0, ptr(coeff), ptr(alpha),
+                              ptr(d_loss), ptr(d_side), ld_ds, ptr(d_att), ld_da, ptr(d_ctx), ld_dx, stream_ptr()), "dr_eges_bwd")
+    return d_side, d_att, d_ctx
+
+
+def eges_embed(side_table, row_base, side_ids, att=None, att_ids=None, out=None):
+    """out [n, D] of dr_eges_embed: the aggregated vector of every row of side_ids [n, S] alone; a row with no field present is +0.0"""
+    n, S, D, row_base, side_ids, att, ld_att, att_ids = _eges_side_args(side_table, row_base, side_ids, att, att_ids)
+    if out is None:
+        out = torch.empty((n, D), dtype=torch.float32, device=side_ids.device)
+    _eges_one_device(side_ids.device, out=out)
+    ld_out = _row_pitch("eges", out, D, "out")
+    if out.shape[0] != n:
+        raise ValueError("eges: out must have %d rows, got %d" % (n, out.shape[0]))
+    if n == 0:
+        return out
+    _status(lib().dr_eges_embed(ptr(side_table), D, ptr(row_base), ptr(side_ids), S, ptr(att), ld_att, ptr(att_ids), n, ptr(out), ld_out,
+                                stream_ptr()), "dr_eges_embed")
+    return out

@@ -1011,7 +1011,7 @@ int dr_sgns_bwd(const float* in_table, const float* out_table, int32_t D, const 
                 int64_t ld_dc, float* d_ctx, int64_t ld_dx, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * The integer kernels around the skip-gram step, csrc/sampling.hip.  Both are counter-based on the hash of dr_attn_fwd's dropout
+ * The integer kernels around the skip-gram step, csrc/sampling.hip.  All are counter-based on the hash of dr_attn_fwd's dropout
  * (dr_mix32, spelled out there): an element is a function of (seed, position) alone, never of the launch.
  *   dr_alias_sample   n draws from a Vose alias table (prob [V] fp32, alias [V] int32 with entries in [0, V), 1 <= V < 2^31), the
  *                     negative sampler of word2vec over counts^0.75.  Element i, with e = offset + i:
@@ -1022,12 +1022,75 @@ int dr_sgns_bwd(const float* in_table, const float* out_table, int32_t D, const 
  *                     them): walks [W, L] dense, walks[w, 0] = starts[w]; at step t >= 1 from v = walks[w, t - 1], with
  *                     deg = row_ptr[v + 1] - row_ptr[v]:  walks[w, t] = col[row_ptr[v] + ((uint64(dr_mix32(seed, w * L + t)) * deg) >> 32)].
  *                     v < 0, v >= n_rows or deg == 0 ends the walk: that step and every later one is -1.  One lane per walk.
+ *   dr_random_walk_weighted   the same walk over integer edge weights: cum [nnz] int64 holds the inclusive prefix sums of the weights
+ *                     (>= 0) over the whole col array.  From v, with lo = row_ptr[v], hi = row_ptr[v + 1]:
+ *                       base = lo > 0 ? cum[lo - 1] : 0;  total = cum[hi - 1] - base;
+ *                       t = (uint64(dr_mix32(seed, w * L + t_step)) * uint64(total)) >> 32;
+ *                       walks[w, t_step] = col[e], e the smallest index in [lo, hi) with cum[e] - base > t  (binary search)
+ *                     so an edge is taken for exactly weight(e) of the total values of t and a zero-weight edge never.  hi == lo or
+ *                     total == 0 ends the walk as deg == 0 does.  The caller guarantees total < 2^32 for every row.  With all
+ *                     weights 1 the walks are dr_random_walk's bit for bit.  col and cum may both be NULL for a graph without edges.
  *   n == 0 / W == 0 is DR_OK and launches nothing; V outside its range, L < 1, a negative size or a NULL required pointer is DR_EINVAL.
  * ---------------------------------------------------------------------------------------- */
 int dr_alias_sample(const float* prob, const int32_t* alias, int64_t V, int64_t n, uint64_t seed, uint64_t offset, int64_t* out,
                     dr_stream_t stream);
 int dr_random_walk(const int64_t* row_ptr, const int32_t* col, int64_t n_rows, const int64_t* starts, int64_t W, int32_t L,
                    uint64_t seed, int64_t* walks, dr_stream_t stream);
+int dr_random_walk_weighted(const int64_t* row_ptr, const int32_t* col, const int64_t* cum, int64_t n_rows, const int64_t* starts,
+                            int64_t W, int32_t L, uint64_t seed, int64_t* walks, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Skip-gram with side information: EGES (Wang et al., KDD 2018) and, with one field and two positives, Airbnb's listing embeddings
+ * (Grbovic & Cheng, KDD 2018), which the reference's README lists and ships no code for; csrc/eges.hip.  All fp32.
+ * side_table [R, D] dense; row_base [S] int64 on the device, the first row of field s (as the slab's); side_ids [B, S] int64: field s of
+ * example b is the row row_base[s] + side_ids[b, s], an id < 0 means the field is missing ("present" otherwise).  att [R_att, ld_att]
+ * (ld_att >= S) with att_ids [B] holds the example's attention logits; att == NULL or att_ids[b] < 0: all logits are 0, which with
+ * missing fields is the paper's cold-start rule, the average of the side embeddings that are there.  out_table [R_out, D] dense;
+ * contexts [B, P] (positives) and negatives [B, K] dense int64; w_b = sample_weight[b] (1 when NULL).
+ *   a_s = att[att_ids[b], s] (or 0);  m = max over present s of a_s;  e_s = expf(a_s - m);  Z = sum_present e_s
+ *   alpha_s = e_s / Z (0 for a missing field);   u = sum_present alpha_s w_s,  w_s the field's table row
+ *   slots j = 0 .. P + K - 1: o_j from contexts then negatives, v_j = out_table[o_j], z_j = 1 for j < P
+ *   s_j, loss_b, g_j exactly as documented for dr_sgns_fwd;   c_j = row_scale g_j  (d_loss[b] g_j in dr_eges_bwd)
+ *   d_u = sum_j c_j v_j;   d_ctx[b, j, :] = c_j u;   d_side[b, s, :] = alpha_s d_u   (+0.0 for a missing field)
+ *   q_s = <d_u, w_s>;  r = sum_present alpha_s q_s;  d_att[b, s] = alpha_s (q_s - r)
+ *                      (+0.0 for a missing field, for the columns S .. ld_da - 1, and when the logits were taken as 0)
+ *   Sums run in ascending index order, one fused multiply-add per term added (the first term of u is the rounded product).
+ *   Skipped: the whole example when no field is present or contexts[b, 0] < 0; a slot whose id is < 0; with flags & DR_SGNS_SKIP_EQUAL
+ *   a negative slot whose id equals any non-negative positive of the example.  A skipped slot or example has s = g = 0, rows of +0.0
+ *   (a skipped example's alpha row too) and no term anywhere; the id of a skipped slot or a missing field, and every id of a skipped
+ *   example, is never turned into an address that is read.
+ *   dr_eges_fwd    writes loss_rows [B], coeff [B, P + K], alpha [B, S] and, unless NULL, scores [B, P + K], all dense.  With the three
+ *                  gradient buffers given (all or none) the same pass writes d_side [B, S * D] at the pitch ld_ds, d_att [B, ld_da]
+ *                  (dense; ld_da a multiple of 4 with S <= ld_da <= 16, S rounded up, so that K4 takes it as a D = ld_da row with ids
+ *                  [B, 1]) and d_ctx [B, (P + K) * D] at the pitch ld_dx, for c_j = row_scale g_j.  Nothing beyond the widths named is
+ *                  written; the pitches are ignored without the buffers.
+ *   dr_eges_bwd    the same three buffers from coeff, alpha and a per-example d_loss [B], the rows gathered again, the same operations
+ *                  in the same order: with d_loss[b] == row_scale both entry points write the same bits.  att is only tested against
+ *                  NULL here (with att_ids it says whether the logits were taken as 0).
+ *   dr_eges_embed  the aggregation alone: out [n, D] = u at the pitch ld_out; an example with no present field gets a row of +0.0.
+ *                  What an index over all items, cold ones (no id row) included, is built from.
+ *   d_side with ids side_ids and row_base, d_att with ids att_ids as [B, 1], d_ctx with ids [contexts | negatives] are what the K4
+ *   entry points take as d_concat.  With S = 1, P = 1 and att == NULL, loss_rows, coeff, scores, d_side and d_ctx are dr_sgns_fwd's
+ *   loss_rows, coeff, scores, d_center and d_ctx bit for bit (the slot arithmetic is one set of device functions, csrc/sgns_common.h).
+ *   A group of D / 4 lanes, rounded up to a power of two, owns an example; u and d_u stay in registers, four rows are in flight per
+ *   lane, the S rows w_s are read a second time once d_u is complete.  No atomics, no LDS, no workspace, one launch: results are
+ *   bit-identical from run to run and an example's bits depend neither on its batch nor on its place in it.
+ *   Domain: D % 4 == 0, 4 <= D <= 256, 1 <= S <= 16, 1 <= P <= 4, K >= 0, P + K <= 64 (negatives may be NULL when K == 0), flags 0 or
+ *   DR_SGNS_SKIP_EQUAL, att_ids given whenever att is, both tables, the gradient buffers and out 16-byte aligned, ld_ds, ld_dx and
+ *   ld_out multiples of 4 and >= the width they cover; anything else or a NULL required pointer is DR_EINVAL.  B == 0 / n == 0 is DR_OK
+ *   and launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+int dr_eges_fwd(const float* side_table, int32_t D, const int64_t* row_base, const int64_t* side_ids, int32_t S, const float* att,
+                int64_t ld_att, const int64_t* att_ids, const float* out_table, const int64_t* contexts, int32_t P,
+                const int64_t* negatives, int32_t K, int64_t B, const float* sample_weight, int32_t flags, float row_scale,
+                float* loss_rows, float* coeff, float* alpha, float* scores, float* d_side, int64_t ld_ds, float* d_att, int64_t ld_da,
+                float* d_ctx, int64_t ld_dx, dr_stream_t stream);
+int dr_eges_bwd(const float* side_table, int32_t D, const int64_t* row_base, const int64_t* side_ids, int32_t S, const float* att,
+                const int64_t* att_ids, const float* out_table, const int64_t* contexts, int32_t P, const int64_t* negatives, int32_t K,
+                int64_t B, int32_t flags, const float* coeff, const float* alpha, const float* d_loss, float* d_side, int64_t ld_ds,
+                float* d_att, int64_t ld_da, float* d_ctx, int64_t ld_dx, dr_stream_t stream);
+int dr_eges_embed(const float* side_table, int32_t D, const int64_t* row_base, const int64_t* side_ids, int32_t S, const float* att,
+                  int64_t ld_att, const int64_t* att_ids, int64_t n, float* out, int64_t ld_out, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * PNN's outer-product layer (Qu et al., ICDM 2016; the reference's README lists PNN among its ranking models and ships no code for
