@@ -23,6 +23,7 @@ class _ESMMFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, *params):
         ctx.set_materialize_grads(False)
+        x = L._rows(x)
         seed = lambda: next(_seed_counter) * 1000003 + model.seed       # noqa: E731
         logits, saved = model.towers.forward(x, seed)                    # [B, 2] = (cvr, ctr)
         p_cvr, p_ctr, p_ctcvr = ops.esmm_head_fwd(logits)
@@ -31,6 +32,7 @@ class _ESMMFn(torch.autograd.Function):
         return p_cvr.reshape(-1, 1), p_ctr.reshape(-1, 1), p_ctcvr.reshape(-1, 1)
 
     @staticmethod
+    @L._needed_only
     def backward(ctx, d_cvr, d_ctr, d_ctcvr):
         model = ctx.model
         x, p_cvr, p_ctr = ctx.saved_tensors

@@ -43,6 +43,7 @@ class _MMoEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, *params):
         ctx.set_materialize_grads(False)
+        x = L._rows(x)
         E, T, ne = model.num_experts, model.num_tasks, model.num_experts
         B = x.shape[0]
         seed = lambda: next(_seed_counter) * 1000003 + model.seed       # noqa: E731
@@ -58,6 +59,7 @@ class _MMoEFn(torch.autograd.Function):
         return tuple(y[:, t:t + 1] for t in range(T))
 
     @staticmethod
+    @L._needed_only
     def backward(ctx, *d_outs):
         model = ctx.model
         x, h, p = ctx.saved_tensors

@@ -51,14 +51,16 @@ class _RowDotFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b):
+        a, b = L._rows(a, dense=True), L._rows(b, dense=True)
         ctx.save_for_backward(a, b)
         return ops.rowdot(a, b)
 
     @staticmethod
+    @L._needed_only
     def backward(ctx, g):
         a, b = ctx.saved_tensors
-        g = g.contiguous()
-        return ops.rows_scale(b, g), ops.rows_scale(a, g)
+        g = L._rows(g, dense=True)
+        return (ops.rows_scale(b, g) if ctx.needs_input_grad[0] else None, ops.rows_scale(a, g) if ctx.needs_input_grad[1] else None)
 
 
 class _ItemRowsFn(torch.autograd.Function):
@@ -66,15 +68,17 @@ class _ItemRowsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, ids):
-        ctx.save_for_backward(ids)
-        ctx.shape = table.shape
-        return ops.rows_gather(ids, table)[0]
+        ctx.save_for_backward(ids, table)
+        return ops.rows_gather(ids, L._rows(table, dense=True))[0]
 
     @staticmethod
+    @L._needed_only
     def backward(ctx, g):
-        (ids,) = ctx.saved_tensors
-        d_table = torch.zeros(ctx.shape, dtype=torch.float32, device=g.device)
-        ops.rows_scatter_add(ids, g.contiguous(), None, 1.0, d_table, None)
+        ids, table = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        d_table = L._param_grad(table)
+        ops.rows_scatter_add(ids, L._rows(g, dense=True), None, 1.0, d_table, None)
         return d_table, None
 
 

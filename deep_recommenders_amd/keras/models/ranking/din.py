@@ -38,16 +38,16 @@ class Multiply:
 class _DinConcatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, mode):
+        x, y = L._rows(x, dense=True), L._rows(y, dense=True)
         ctx.mode = mode
         ctx.save_for_backward(x, y)
         return ops.din_concat_fwd(x, y, mode)
 
     @staticmethod
+    @L._needed_only
     def backward(ctx, d_out):
         x, y = ctx.saved_tensors
-        if d_out.stride(1) != 1:
-            d_out = d_out.contiguous()
-        d_x, d_y = ops.din_concat_bwd(x, y, ctx.mode, d_out)
+        d_x, d_y = ops.din_concat_bwd(x, y, ctx.mode, L._rows(d_out))
         return d_x, d_y, None
 
 

@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from deep_recommenders_amd import ops
+from deep_recommenders_amd.layers import _needed_only, _param_grad, _rows
 from deep_recommenders_amd.keras.models.retrieval import FactorizedTopK
 from deep_recommenders_amd.keras.models.retrieval.factorized_top_k import _dev
 
@@ -69,19 +70,21 @@ class _InBatchSoftmaxFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, c, sample_weight, cand_prob, cand_ids, inv_t):
+        q, c = _rows(q, dense=True), _rows(c, dense=True)
         loss, row_lse, _ = ops.inbatch_softmax_fwd(q, c, cand_prob, cand_ids, sample_weight, inv_t)
         ctx.inv_t = inv_t
         ctx.save_for_backward(q, c, row_lse, sample_weight, cand_prob, cand_ids)
         return loss.reshape(())
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_loss):
         q, c, row_lse, w, cp, ci = ctx.saved_tensors
         G = ops.inbatch_softmax_grad_scores(q, c, row_lse, float(d_loss), cp, ci, w, ctx.inv_t)
         dq = ops.linear_fwd(G, c) if ctx.needs_input_grad[0] else None                  # dq = G @ c
         dc = None
         if ctx.needs_input_grad[1]:
-            dc = torch.zeros_like(c)
+            dc = _param_grad(c)
             ops.linear_bwd_dw(G, q, 1.0, dc)                                            # dc = G^T @ q
         return dq, dc, None, None, None, None
 
@@ -92,9 +95,10 @@ class _AdjustFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, scores, labels, cand_prob, cand_ids):
-        return ops.logits_adjust(scores.contiguous(), labels, cand_prob=cand_prob, cand_ids=cand_ids)
+        return ops.logits_adjust(_rows(scores, dense=True), labels, cand_prob=cand_prob, cand_ids=cand_ids)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, g):
         return g, None, None, None
 
@@ -104,17 +108,19 @@ class _ScoresFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, c):
+        q, c = _rows(q), _rows(c)
         ctx.save_for_backward(q, c)
         return ops.scores_nt(q, c).contiguous()
 
     @staticmethod
+    @_needed_only
     def backward(ctx, G):
         q, c = ctx.saved_tensors
-        G = G.contiguous()
+        G = _rows(G)
         dq = ops.linear_fwd(G, c) if ctx.needs_input_grad[0] else None
         dc = None
         if ctx.needs_input_grad[1]:
-            dc = torch.zeros_like(c)
+            dc = _param_grad(c)
             ops.linear_bwd_dw(G, q, 1.0, dc)
         return dq, dc
 
@@ -126,6 +132,7 @@ class _ExplicitSoftmaxFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, c, sample_weight, cand_prob, cand_ids, inv_t):
+        q, c = _rows(q), _rows(c)
         scores = ops.scores_nt(q, c).contiguous()
         labels = torch.eye(scores.shape[0], scores.shape[1], device=scores.device)
         if cand_prob is not None or cand_ids is not None:
@@ -135,13 +142,14 @@ class _ExplicitSoftmaxFn(torch.autograd.Function):
         return ops.softmax_ce_rows(scores, labels, inv_t, sample_weight)
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_loss):
         q, c, scores, labels, w = ctx.saved_tensors
         G = ops.softmax_ce_rows_bwd(scores, labels, ctx.inv_t, w, float(d_loss))
         dq = ops.linear_fwd(G, c) if ctx.needs_input_grad[0] else None              # dq = G @ c
         dc = None
         if ctx.needs_input_grad[1]:
-            dc = torch.zeros_like(c)
+            dc = _param_grad(c)
             ops.linear_bwd_dw(G, q, 1.0, dc)                                          # dc = G^T @ q
         return dq, dc, None, None, None, None
 
@@ -153,6 +161,7 @@ class _HardNegativeSoftmaxFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, c, sample_weight, cand_prob, cand_ids, inv_t, num_hard_negatives):
+        q, c = _rows(q), _rows(c)
         scores = ops.scores_nt(q, c).contiguous()
         B = scores.shape[0]
         labels = torch.eye(B, scores.shape[1], device=scores.device)
@@ -168,6 +177,7 @@ class _HardNegativeSoftmaxFn(torch.autograd.Function):
         return ops.softmax_ce_rows(s_sel, l_sel, inv_t, sample_weight)              # :148-151
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_loss):
         q, c, s_sel, l_sel, indices, w = ctx.saved_tensors
         B = q.shape[0]
@@ -176,7 +186,7 @@ class _HardNegativeSoftmaxFn(torch.autograd.Function):
         dq = ops.linear_fwd(G, c) if ctx.needs_input_grad[0] else None              # dq = G @ c
         dc = None
         if ctx.needs_input_grad[1]:
-            dc = torch.zeros_like(c)
+            dc = _param_grad(c)
             ops.linear_bwd_dw(G, q, 1.0, dc)                                          # dc = G^T @ q
         return dq, dc, None, None, None, None, None
 

@@ -6,19 +6,21 @@ import numpy as np
 import torch
 
 from . import ops
+from .layers import _needed_only, _rows
 
 
 class _SigmoidFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        y = ops.sigmoid_fwd(x)
+        y = ops.sigmoid_fwd(_rows(x, dense=True))
         ctx.save_for_backward(y)
         return y
 
     @staticmethod
+    @_needed_only
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
-        return ops.sigmoid_bwd(y, dy.contiguous())
+        return ops.sigmoid_bwd(y, _rows(dy, dense=True))
 
 
 class _LogitLossFn(torch.autograd.Function):
@@ -30,9 +32,10 @@ class _LogitLossFn(torch.autograd.Function):
         return loss.reshape(())
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_loss):
         (g,) = ctx.saved_tensors
-        return (g * d_loss).reshape(ctx.shape), None, None
+        return (g * d_loss).reshape(ctx.shape) if ctx.needs_input_grad[0] else None, None, None
 
 
 class _ProbLossFn(torch.autograd.Function):
@@ -44,13 +47,14 @@ class _ProbLossFn(torch.autograd.Function):
         return loss.reshape(())
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_loss):
         (g,) = ctx.saved_tensors
-        return (g * d_loss).reshape(ctx.shape), None, None
+        return (g * d_loss).reshape(ctx.shape) if ctx.needs_input_grad[0] else None, None, None
 
 
 def sigmoid(x: torch.Tensor) -> torch.Tensor:
-    return _SigmoidFn.apply(x.contiguous())
+    return _SigmoidFn.apply(x)
 
 
 def sigmoid_cross_entropy(labels, logits):
@@ -77,9 +81,10 @@ class _MseFn(torch.autograd.Function):
         return loss
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_loss):
         (d,) = ctx.saved_tensors
-        return (d * d_loss.reshape(1, -1)).reshape(ctx.shape), None
+        return (d * d_loss.reshape(1, -1)).reshape(ctx.shape) if ctx.needs_input_grad[0] else None, None
 
 
 def mean_squared_error(labels, predictions):
@@ -87,9 +92,7 @@ def mean_squared_error(labels, predictions):
     examples/train_mmoe_on_synthetic_estimator.py:39-40.  predictions [B, 1] (or [B, T]: T losses in one launch, returned [T])."""
     p = predictions if predictions.dim() == 2 else predictions.reshape(-1, 1)
     y = torch.as_tensor(labels, dtype=torch.float32, device=p.device).reshape(p.shape)
-    if p.shape[1] > 1 and p.stride(1) != 1:
-        p = p.contiguous()
-    loss = _MseFn.apply(p, y if y.stride(1) == 1 or y.shape[1] == 1 else y.contiguous())
+    loss = _MseFn.apply(_rows(p), _rows(y))
     return loss.reshape(()) if p.shape[1] == 1 else loss
 
 
@@ -103,9 +106,10 @@ class _SoftmaxCEFn(torch.autograd.Function):
         return loss
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_loss):
         (g,) = ctx.saved_tensors
-        return g * d_loss, None, None
+        return g * d_loss if ctx.needs_input_grad[0] else None, None, None
 
 
 class _CceProbFn(torch.autograd.Function):
@@ -116,9 +120,10 @@ class _CceProbFn(torch.autograd.Function):
         return ops.reduce_sum(row).reshape(())
 
     @staticmethod
+    @_needed_only
     def backward(ctx, d_loss):
         (g,) = ctx.saved_tensors
-        return g * d_loss, None, None
+        return g * d_loss if ctx.needs_input_grad[0] else None, None, None
 
 
 def categorical_crossentropy(y_true, y_pred, sample_weight=None):
@@ -140,4 +145,4 @@ def categorical_crossentropy(y_true, y_pred, sample_weight=None):
         w = w.to(torch.float32).to(y.device)
     if logits is not None:
         return _SoftmaxCEFn.apply(logits.contiguous(), y, w)
-    return _CceProbFn.apply(y_pred if y_pred.stride(1) == 1 else y_pred.contiguous(), y, w)
+    return _CceProbFn.apply(_rows(y_pred), y, w)

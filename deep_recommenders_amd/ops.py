@@ -186,6 +186,24 @@ def _check_ld(t, what):
                          % (what, t.dtype, tuple(t.shape), tuple(t.stride())))
 
 
+def _dense_arg(t, what, dtype=torch.float32, shape=None, numel=None, copy=True):
+    """An argument a kernel addresses densely (row-major, no leading dimension): None passes; another dtype, shape or element count
+    is a ValueError naming the argument; a view (transposed, pitched, expanded) is copied once when the kernel only reads it, and
+    refused (copy=False) when the kernel writes to it -- a copy would swallow the result."""
+    if t is None:
+        return None
+    if t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)) or (numel is not None and t.numel() != numel):
+        raise ValueError("%s must be %s%s, got %s %s" % (what, dtype, " %s" % (tuple(shape),) if shape is not None else
+                                                          " with %d elements" % numel if numel is not None else "", t.dtype,
+                                                          tuple(t.shape)))
+    if t.is_contiguous():
+        return t
+    if not copy:
+        raise ValueError("%s must be contiguous (the kernel writes to it), got strides %s for shape %s"
+                         % (what, tuple(t.stride()), tuple(t.shape)))
+    return t.contiguous()
+
+
 def _vec_f32(b):
     """a bias / per-column vector the kernel reads densely (an expanded one has a 0 stride and a single element behind it)"""
     return None if b is None else _c(b, torch.float32)
@@ -414,6 +432,8 @@ def bce_fwd_bwd(logits, labels, mode=LOSS_SIGMOID_CE, want_prob=True, want_grad=
     logits = _c(logits.reshape(-1), torch.float32)
     labels = _c(labels.reshape(-1), torch.float32)
     n = logits.numel()
+    if labels.numel() != n:
+        raise ValueError("bce_fwd_bwd: labels must have one value per logit (%d), got %d" % (n, labels.numel()))
     dev = logits.device
     if out is not None:
         prob, d_logit, loss = out
@@ -442,6 +462,8 @@ def sigmoid_fwd(x):
 def sigmoid_bwd(y, dy):
     y = _c(y, torch.float32)
     dy = _c(dy, torch.float32)
+    if dy.numel() != y.numel():
+        raise ValueError("sigmoid_bwd: dy must have y's %d elements, got %d" % (y.numel(), dy.numel()))
     dx = torch.empty_like(y)
     check(lib().dr_sigmoid_bwd(ptr(y), ptr(dy), y.numel(), ptr(dx), stream_ptr()), "dr_sigmoid_bwd")
     return dx
@@ -451,6 +473,8 @@ def bce_prob_fwd_bwd(prob, labels, mode, want_grad=True, workspace=None):
     prob = _c(prob.reshape(-1), torch.float32)
     labels = _c(labels.reshape(-1), torch.float32)
     n = prob.numel()
+    if labels.numel() != n:
+        raise ValueError("bce_prob_fwd_bwd: labels must have one value per probability (%d), got %d" % (n, labels.numel()))
     d_prob = torch.empty_like(prob) if want_grad else None
     loss = torch.empty(1, dtype=torch.float32, device=prob.device)
     if workspace is None:
@@ -495,22 +519,40 @@ def shard_bucket_ids(ids, rows_per_shard, world, counts=None, send_rows=None, po
 
 
 def rows_gather(rows, table, lin_w=None, out_rows=None, out_lin=None):
+    """(out_rows [n, D], out_lin [n] | None): table[rows] and lin_w[rows].  The kernel addresses table as row-major [R, D] and lin_w as
+    [R]: a view of either is refused by name (a table is a parameter, and a silent copy of one per call is no layout fix)."""
     rows = _c(rows, torch.int64)
     n = rows.numel()
-    D = table.shape[1]
+    if table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
+        raise ValueError("rows_gather: table must be contiguous fp32 [R, D], got %s %s with strides %s"
+                         % (table.dtype, tuple(table.shape), tuple(table.stride())))
+    R, D = table.shape
+    lin_w = _dense_arg(lin_w, "rows_gather: lin_w", numel=R, copy=False)
     if out_rows is None:
         out_rows = torch.empty((n, D), dtype=torch.float32, device=rows.device)
+    elif out_rows.dtype != torch.float32 or not out_rows.is_contiguous() or out_rows.numel() < n * D:
+        raise ValueError("rows_gather: out_rows must be contiguous fp32 with room for %s, got %s %s" % ((n, D), out_rows.dtype, tuple(out_rows.shape)))
     if out_lin is None and lin_w is not None:
         out_lin = torch.empty(n, dtype=torch.float32, device=rows.device)
+    elif out_lin is not None and (out_lin.dtype != torch.float32 or not out_lin.is_contiguous() or out_lin.numel() < n):
+        raise ValueError("rows_gather: out_lin must be contiguous fp32 with room for %d, got %s %s" % (n, out_lin.dtype, tuple(out_lin.shape)))
     check(lib().dr_rows_gather(ptr(rows), n, ptr(table), D, ptr(lin_w), ptr(out_rows), ptr(out_lin), stream_ptr()),
           "dr_rows_gather")
     return out_rows, out_lin
 
 
 def rows_scatter_add(rows, grads, lin_grads, scale, table, lin_w):
+    """table[rows] += scale * grads, lin_w[rows] += scale * lin_grads (fp32 atomics).  grads [n, D] and lin_grads [n] are read
+    densely: a view is copied once; table and lin_w are written to and must be contiguous."""
     rows = _c(rows, torch.int64)
     n = rows.numel()
-    D = table.shape[1]
+    if table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
+        raise ValueError("rows_scatter_add: table must be contiguous fp32 [R, D], got %s %s with strides %s"
+                         % (table.dtype, tuple(table.shape), tuple(table.stride())))
+    R, D = table.shape
+    grads = _dense_arg(grads, "rows_scatter_add: grads", shape=(n, D))
+    lin_grads = _dense_arg(lin_grads, "rows_scatter_add: lin_grads", numel=n)
+    lin_w = _dense_arg(lin_w, "rows_scatter_add: lin_w", numel=R, copy=False)
     check(lib().dr_rows_scatter_add(ptr(rows), n, ptr(grads), D, ptr(lin_grads), float(scale), ptr(table), ptr(lin_w),
                                     stream_ptr()), "dr_rows_scatter_add")
 
@@ -717,12 +759,14 @@ def _check_inbatch_shapes(q, c, cand_prob, cand_ids, sample_weight):
     for name, t in (("candidate_sampling_probability", cand_prob), ("candidate_ids", cand_ids), ("sample_weight", sample_weight)):
         if t is not None and t.numel() != B:
             raise ValueError("%s must have %d elements, got %d" % (name, B, t.numel()))
+    return (_dense_arg(cand_prob, "candidate_sampling_probability", numel=B), _dense_arg(cand_ids, "candidate_ids", torch.int64, numel=B),
+            _dense_arg(sample_weight, "sample_weight", numel=B))
 
 
 def inbatch_softmax_fwd(q, c, cand_prob=None, cand_ids=None, sample_weight=None, inv_temperature=1.0):
     q = _c(q, torch.float32)
     c = _c(c, torch.float32)
-    _check_inbatch_shapes(q, c, cand_prob, cand_ids, sample_weight)
+    cand_prob, cand_ids, sample_weight = _check_inbatch_shapes(q, c, cand_prob, cand_ids, sample_weight)
     B, D = q.shape
     dev = q.device
     row_lse = torch.empty(B, dtype=torch.float32, device=dev)
@@ -738,10 +782,11 @@ def inbatch_softmax_fwd(q, c, cand_prob=None, cand_ids=None, sample_weight=None,
 
 def inbatch_softmax_grad_scores(q, c, row_lse, d_loss, cand_prob=None, cand_ids=None, sample_weight=None,
                                 inv_temperature=1.0):
-    _check_inbatch_shapes(q, c, cand_prob, cand_ids, sample_weight)
+    cand_prob, cand_ids, sample_weight = _check_inbatch_shapes(q, c, cand_prob, cand_ids, sample_weight)
     B, D = q.shape
     q = _c(q, torch.float32)
     c = _c(c, torch.float32)
+    row_lse = _dense_arg(row_lse, "inbatch_softmax_grad_scores: row_lse", numel=B)
     G = torch.empty((B, _pad4(B)), dtype=torch.float32, device=q.device)[:, :B]
     # with a workspace the pass may run on the f16x2 register-split kernel (it needs the candidates as fp16 planes)
     nbytes = lib().dr_inbatch_softmax_workspace_bytes(B)
@@ -757,6 +802,8 @@ def scores_nt(a, b, out=None):
     b = _rowmajor_ld4(b)
     M, D = a.shape
     N = b.shape[0]
+    if b.shape[1] != D:
+        raise ValueError("scores_nt: a %s and b %s differ in width" % (tuple(a.shape), tuple(b.shape)))
     if out is None:
         out = torch.empty((M, _pad4(N)), dtype=torch.float32, device=a.device)[:, :N]
     check(lib().dr_scores_nt(ptr(a), a.stride(0), ptr(b), b.stride(0), M, N, D, ptr(out), out.stride(0), stream_ptr()),
@@ -770,7 +817,10 @@ def topk_state(Bq, k, device):
 
 def topk_select(scores, k, index_base=0, init=True, state=None):
     """row-wise top-k of an explicit [Bq, n] score matrix, folded into `state` (scores, index)."""
-    assert scores.stride(1) == 1
+    if scores.dtype != torch.float32 or scores.dim() != 2 or (scores.shape[1] > 1 and scores.stride(1) != 1) or \
+            (scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]):
+        raise ValueError("topk_select: scores must be fp32 [Bq, n] with unit column stride and a row stride >= n, got %s %s with strides %s"
+                         % (scores.dtype, tuple(scores.shape), tuple(scores.stride())))
     Bq, n = scores.shape
     if state is None:
         state = topk_state(Bq, k, scores.device)
@@ -922,6 +972,8 @@ def rows_scale(x, s, mode=0, fallback=None, out=None):
     assert s.numel() == M and (fallback is None or (fallback.shape == x.shape and fallback.is_contiguous()))
     if out is None:
         out = torch.empty_like(x)
+    else:
+        _dense_arg(out, "rows_scale: out", shape=(M, D), copy=False)
     check(lib().dr_rows_scale(ptr(x), ptr(s), int(mode), ptr(fallback), M, D, ptr(out), stream_ptr()), "dr_rows_scale")
     return out
 
@@ -929,6 +981,8 @@ def rows_scale(x, s, mode=0, fallback=None, out=None):
 def rowdot(a, b):
     a = _c(a, torch.float32)
     b = _c(b, torch.float32)
+    if a.dim() != 2 or b.shape != a.shape:
+        raise ValueError("rowdot: a and b must be [M, D] alike, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
     out = torch.empty((a.shape[0], 1), dtype=torch.float32, device=a.device)
     check(lib().dr_rowdot(ptr(a), ptr(b), a.shape[0], a.shape[1], ptr(out), stream_ptr()), "dr_rowdot")
     return out
@@ -946,6 +1000,9 @@ def take_along_rows(arr, idx):
     idx = _c(idx, torch.int64)
     arr = arr if arr.stride(1) == 1 else arr.contiguous()
     B, C = arr.shape
+    if idx.dim() != 2 or idx.shape[0] != B or (B > 1 and arr.stride(0) < C):
+        raise ValueError("take_along_rows: arr [B, C] with a row stride >= C and idx [B, K], got %s with strides %s and %s"
+                         % (tuple(arr.shape), tuple(arr.stride()), tuple(idx.shape)))
     K = idx.shape[1]
     out = torch.empty((B, K), dtype=arr.dtype, device=arr.device)
     if arr.dtype == torch.float32:
@@ -978,7 +1035,13 @@ def exclude_adjust(scores, ids, exclude):
 
 def logits_adjust(logits, labels=None, cand_prob=None, cand_ids=None, add_label_scale=0.0):
     logits = _c(logits, torch.float32)
-    labels = _c(labels, torch.float32) if labels is not None else None
+    if logits.dim() != 2:
+        raise ValueError("logits_adjust: logits must be [B, C], got %s" % (tuple(logits.shape),))
+    labels = _dense_arg(labels, "logits_adjust: labels", shape=logits.shape)
+    cand_prob = _dense_arg(cand_prob, "logits_adjust: cand_prob", numel=logits.shape[1])
+    cand_ids = _dense_arg(cand_ids, "logits_adjust: cand_ids", torch.int64, numel=logits.shape[1])
+    if (cand_ids is not None or add_label_scale) and labels is None:
+        raise ValueError("logits_adjust: cand_ids and add_label_scale need labels")
     out = torch.empty_like(logits)
     check(lib().dr_logits_adjust(ptr(logits), ptr(labels), logits.shape[0], logits.shape[1], ptr(cand_prob), ptr(cand_ids),
                                  float(add_label_scale), ptr(out), stream_ptr()), "dr_logits_adjust")
@@ -994,8 +1057,9 @@ def topk_init(Bq, k, device):
 
 def softmax_ce_rows(logits, labels, inv_temperature=1.0, sample_weight=None):
     logits = _c(logits, torch.float32)
-    labels = _c(labels, torch.float32)
+    labels = _dense_arg(labels, "softmax_ce_rows: labels", shape=logits.shape)
     B, C = logits.shape
+    sample_weight = _dense_arg(sample_weight, "softmax_ce_rows: sample_weight", numel=B)
     row = torch.empty(B, dtype=torch.float32, device=logits.device)
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     check(lib().dr_softmax_ce_rows(ptr(logits), ptr(labels), B, C, float(inv_temperature), ptr(sample_weight), ptr(row),
@@ -1006,10 +1070,19 @@ def softmax_ce_rows(logits, labels, inv_temperature=1.0, sample_weight=None):
 def softmax_ce_rows_bwd(logits, labels, inv_temperature, sample_weight, d_loss, cols=None, out=None):
     """gradient of softmax_ce_rows w.r.t. logits; with `cols` scattered into the pre-zeroed matrix `out`."""
     logits = _c(logits, torch.float32)
-    labels = _c(labels, torch.float32)
+    labels = _dense_arg(labels, "softmax_ce_rows_bwd: labels", shape=logits.shape)
     B, C = logits.shape
+    sample_weight = _dense_arg(sample_weight, "softmax_ce_rows_bwd: sample_weight", numel=B)
+    if cols is not None and (cols.dtype != torch.int64 or tuple(cols.shape) != (B, C)):
+        raise ValueError("softmax_ce_rows_bwd: cols must be int64 %s, got %s %s" % ((B, C), cols.dtype, tuple(cols.shape)))
     if out is None:
+        if cols is not None:
+            raise ValueError("softmax_ce_rows_bwd: cols scatter into a pre-zeroed `out`")
         out = torch.empty((B, C), dtype=torch.float32, device=logits.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or (cols is None and out.shape[1] != C) or \
+            (out.shape[1] > 1 and out.stride(1) != 1) or (B > 1 and out.stride(0) < out.shape[1]):
+        raise ValueError("softmax_ce_rows_bwd: out must be fp32 [%d, N] with unit column stride and a row stride >= N, got %s %s with strides %s"
+                         % (B, out.dtype, tuple(out.shape), tuple(out.stride())))
     check(lib().dr_softmax_ce_rows_bwd(ptr(logits), ptr(labels), B, C, float(inv_temperature), ptr(sample_weight), float(d_loss),
                                        ptr(_c(cols, torch.int64)) if cols is not None else None, ptr(out), out.stride(0),
                                        stream_ptr()), "dr_softmax_ce_rows_bwd")
@@ -1486,7 +1559,9 @@ def cin_fwd(x0, x, W, bias=None, act=2):
     B, H0, D = x0.shape
     Hk = x.shape[1]
     Fm = W.shape[1]
-    assert x.shape == (B, Hk, D) and W.shape[0] == H0 * Hk
+    if x.shape != (B, Hk, D) or W.shape[0] != H0 * Hk:
+        raise ValueError("cin_fwd: shapes do not agree (x0 %s, x %s, W %s)" % (tuple(x0.shape), tuple(x.shape), tuple(W.shape)))
+    bias = _dense_arg(bias, "cin_fwd: bias", numel=Fm)
     out = torch.empty((B, Fm, D), dtype=torch.float32, device=x0.device)
     check(lib().dr_cin_fwd(ptr(x0), ptr(x), B, H0, Hk, D, ptr(W), Fm, ptr(bias), int(act), ptr(out), stream_ptr()), "dr_cin_fwd")
     return out
@@ -1496,6 +1571,10 @@ def cin_bwd(x0, x, W, act, out, d_out, want_bias=False):
     x0, x, W, d_out = _c(x0, torch.float32), _c(x, torch.float32), _c(W, torch.float32), _c(d_out, torch.float32)
     B, H0, D = x0.shape
     Hk, Fm = x.shape[1], W.shape[1]
+    if x.shape != (B, Hk, D) or W.shape[0] != H0 * Hk:
+        raise ValueError("cin_bwd: shapes do not agree (x0 %s, x %s, W %s)" % (tuple(x0.shape), tuple(x.shape), tuple(W.shape)))
+    out = _dense_arg(out, "cin_bwd: out", shape=(B, Fm, D))
+    d_out = _dense_arg(d_out, "cin_bwd: d_out", shape=(B, Fm, D))
     d_x0, d_x, dW = torch.empty_like(x0), torch.empty_like(x), torch.empty_like(W)
     dbias = torch.empty(Fm, dtype=torch.float32, device=x0.device) if want_bias else None
     check(lib().dr_cin_bwd(ptr(x0), ptr(x), B, H0, Hk, D, ptr(W), Fm, int(act), ptr(out), ptr(d_out), ptr(d_x0), ptr(d_x), ptr(dW),
@@ -2000,7 +2079,8 @@ def seq_attn_bwd(hs, q, lengths, a, d_a):
 def din_concat_fwd(x, y, mode):
     x, y = _c(x, torch.float32), _c(y, torch.float32)
     B, D = x.shape
-    assert y.shape == (B, D)
+    if y.shape != (B, D) or int(mode) not in (0, 1, 2):
+        raise ValueError("din_concat_fwd: x %s and y %s must be [B, D] alike, mode 0, 1 or 2 (got %r)" % (tuple(x.shape), tuple(y.shape), mode))
     n = (3 if mode else 2) * D
     out = torch.zeros((B, _pad4(n)), dtype=torch.float32, device=x.device)[:, :n]
     check(lib().dr_din_concat_fwd(ptr(x), ptr(y), B, D, int(mode), ptr(out), out.stride(0), stream_ptr()), "dr_din_concat_fwd")
@@ -2008,8 +2088,11 @@ def din_concat_fwd(x, y, mode):
 
 
 def din_concat_bwd(x, y, mode, d_out):
+    x, y = _c(x, torch.float32), _c(y, torch.float32)
     B, D = x.shape
     _check_ld(d_out, "din_concat_bwd: d_out")
+    if y.shape != (B, D) or int(mode) not in (0, 1, 2) or tuple(d_out.shape) != (B, (3 if mode else 2) * D):
+        raise ValueError("din_concat_bwd: x %s, y %s and d_out %s do not agree for mode %r" % (tuple(x.shape), tuple(y.shape), tuple(d_out.shape), mode))
     d_x, d_y = torch.empty_like(x), torch.empty_like(y)
     check(lib().dr_din_concat_bwd(ptr(x), ptr(y), B, D, int(mode), ptr(d_out), d_out.stride(0), ptr(d_x), ptr(d_y), stream_ptr()),
           "dr_din_concat_bwd")
@@ -2054,9 +2137,11 @@ def dropout_bwd(dy, mask, rate):
 
 def reduce_sum(x, squared=False, alpha=1.0, out=None, accumulate=False):
     """out[0] (+)= alpha * sum(x) or alpha * sum(x^2) over a contiguous fp32 tensor (deterministic)."""
-    x = x if x.is_contiguous() else x.contiguous()
+    x = _dense_arg(x, "reduce_sum: x")
     if out is None:
         out = torch.zeros(1, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.numel() < 1:
+        raise ValueError("reduce_sum: out must be an fp32 tensor of at least one element, got %s %s" % (out.dtype, tuple(out.shape)))
     ws = torch.empty(1024, dtype=torch.float32, device=x.device)
     check(lib().dr_reduce_sum(ptr(x), x.numel(), int(bool(squared)), float(alpha), int(bool(accumulate)), ptr(out), ptr(ws),
                               stream_ptr()), "dr_reduce_sum")
@@ -2335,8 +2420,12 @@ def softmax_rows_bwd(y, dy, out=None):
 
 def cce_prob_rows(p, labels, sample_weight=None, want_grad=True):
     """(row_loss [B], grad [B, C] or None) of Keras' categorical_crossentropy on probabilities, rows weighted by sample_weight"""
-    assert p.dim() == 2 and p.stride(1) == 1 and labels.shape == p.shape and labels.stride(1) == 1
+    _check_ld(p, "cce_prob_rows: p")
+    _check_ld(labels, "cce_prob_rows: labels")
+    if labels.shape != p.shape:
+        raise ValueError("cce_prob_rows: p %s and labels %s differ in shape" % (tuple(p.shape), tuple(labels.shape)))
     B, C = p.shape
+    sample_weight = _dense_arg(sample_weight, "cce_prob_rows: sample_weight", numel=B)
     row = torch.empty(B, dtype=torch.float32, device=p.device)
     grad = torch.empty((B, C), dtype=torch.float32, device=p.device) if want_grad else None
     check(lib().dr_cce_prob_rows(ptr(p), p.stride(0), ptr(labels), labels.stride(0), B, C, ptr(sample_weight), ptr(row), ptr(grad),

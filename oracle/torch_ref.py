@@ -133,12 +133,12 @@ def inbatch_softmax_loss(q, c, sample_weight=None, cand_prob=None, cand_ids=None
     import numpy as np
     scores = q @ c.t()
     B = q.shape[0]
-    labels = torch.eye(B, dtype=q.dtype)
+    labels = torch.eye(B, c.shape[0], dtype=q.dtype)             # tf.eye(num_queries, num_candidates), sbcnm.py:131-134
     if cand_prob is not None:
         scores = scores - torch.log(cand_prob)
     if cand_ids is not None:
         ident = cand_ids.reshape(-1, 1)
-        dup = (ident == ident.t()).to(q.dtype) - labels
+        dup = (ident[:B] == ident.t()).to(q.dtype) - labels       # query i's positive is candidate i
         scores = scores + dup * float(np.finfo(np.float32).min / 100.0)
     if temperature is not None:
         scores = scores / temperature

@@ -1,5 +1,5 @@
-"""Every autograd Function of deep_recommenders_amd/layers.py, called directly, with the incoming gradient in every layout torch
-produces.  The table, the recipes, the probe and the references are in tests/layer_autograd_cases.py (checked on the CPU by
+"""Every autograd Function of the package (deep_recommenders_amd/layers.py, losses.py and the model files that define their own),
+called directly, with the incoming gradient in every layout torch produces.  The table, the recipes, the probe and the references are in tests/layer_autograd_cases.py (checked on the CPU by
 tests/test_layer_autograd_cpu.py); this file drives them on the device.
 
 Each case compares the forward value and every gradient with a float64 reference differentiated by torch's autograd, under the
@@ -10,14 +10,21 @@ Held to bit-equality across layouts (the same gradient values, materialised cont
 backward runs in a fixed order -- the CSR and the dense aggregate, softmax, attention, add-layer-norm, token embedding, tied
 projection, Dice, DIN pooling, CIN, dot interaction, AFM, PNN, GRU, sequence attention, FFM interaction, and the element-wise ones.
 Held to the float64 bound only, because partial sums meet in fp32 atomics whose order changes from run to run: mlp, cross and
-cross_low_rank (linear_bwd_dw without a workspace) and the embedding backward without a plan (EmbeddingSlab, _LinFieldsFn,
-ffm_gather through K4).
+cross_low_rank and the retrieval Functions (linear_bwd_dw without a workspace), the embedding backward without a plan (EmbeddingSlab,
+_LinFieldsFn, ffm_gather, sgns_loss and eges_loss through K4) and DIEN's item rows (dr_rows_scatter_add).  sgns_loss and eges_loss
+with plans, the losses, the CIN layer, the row dot product, DIN's concat and the two multi-task Functions (every dW of theirs takes
+a workspace) run in a fixed order and are held to bit-equality.
 
 Not in the table: `activation` with act 0 (it returns its input; there is no Function), `afm_pooling`'s attention output and
-EmbeddingSlab's sum_x (marked non-differentiable: no gradient can be sent into them), `aggregate`'s adjacency (a graph input).
+EmbeddingSlab's sum_x (marked non-differentiable: no gradient can be sent into them), `aggregate`'s adjacency (a graph input), and the
+in-place SGD mode (`sparse_lr`) of sgns_loss and eges_loss, which returns no gradient (tests/test_gpu_sgns.py and test_gpu_eges.py
+check the tables it leaves).  tests/test_layer_autograd_cpu.py reads the package with `ast` and fails when a Function has no entry.
 
 A float64 or float16 gradient handed to torch.autograd.backward does not raise in this torch: the engine casts it to the output's
 dtype before the first backward runs.  test_foreign_dtype_gradient_is_cast_before_the_layer pins that no kernel sees another dtype."""
+import importlib
+import itertools
+
 import pytest
 import torch
 
@@ -31,8 +38,8 @@ REPORT = {}
 
 
 def _usages(n_out):
-    """which outputs are used: all of them, and for two outputs each one alone"""
-    return [(True,) * n_out] if n_out == 1 else [(True, True), (True, False), (False, True)]
+    """which outputs are used: all of them first, then every other non-empty subset (each output alone, every pair, ...)"""
+    return [u for u in itertools.product((True, False), repeat=n_out) if any(u)]
 
 
 def _recipes(res_dims, name, used):
@@ -102,24 +109,25 @@ def test_output_consumed_twice_and_backward_twice(name, B):
 
 
 def _watch_backwards(monkeypatch, returned):
-    """Wraps the backward of every Function of layers.py: what a backward RETURNS is what is checked (autograd drops, without a
-    word, a tensor returned for an input that needs none, so a leaf's .grad cannot show it).  Slot i must be None when
-    needs_input_grad[i] is False -- a frozen input, or an argument that is no tensor.  The Functions whose gradients all come out
-    of one fused kernel (DIN pooling, CIN, AFM, PNN, GRU, attention, add-layer-norm, Dice, the cross combine) still compute an
-    unneeded gradient inside that launch; layers._needed_only drops it before it is returned.  The GEMM-built ones (mlp, cross,
-    tied projection, the aggregates) do not launch the GEMM of a gradient nobody needs."""
-    from deep_recommenders_amd import layers
-    for cls in vars(layers).values():
-        if isinstance(cls, type) and issubclass(cls, torch.autograd.Function) and cls is not torch.autograd.Function:
-            def watched(ctx, *grads, _real=cls.backward, _name=cls.__name__):
-                out = _real(ctx, *grads)
-                out = out if isinstance(out, tuple) else (out,)
-                assert len(out) == len(ctx.needs_input_grad), _name
-                for i, (g, need) in enumerate(zip(out, ctx.needs_input_grad)):
-                    assert need or g is None, "%s.backward returned a gradient in slot %d, which needs none" % (_name, i)
-                returned.append((_name, tuple(g is not None for g in out), tuple(ctx.needs_input_grad)))
-                return out
-            monkeypatch.setattr(cls, "backward", staticmethod(watched))
+    """Wraps the backward of every Function of the package (every class the inventory of tests/layer_autograd_cases.py finds): what a
+    backward RETURNS is what is checked (autograd drops, without a word, a tensor returned for an input that needs none, so a leaf's
+    .grad cannot show it).  Slot i must be None when needs_input_grad[i] is False -- a frozen input, or an argument that is no
+    tensor.  The Functions whose gradients all come out of one fused kernel (DIN pooling, CIN, AFM, PNN, GRU, attention,
+    add-layer-norm, Dice, the cross combine, DIN's concat, the losses) still compute an unneeded gradient inside that launch;
+    layers._needed_only drops it before it is returned.  The GEMM-built ones (mlp, cross, tied projection, the aggregates, the
+    retrieval Functions) and DIEN's row dot product do not launch the kernel of a gradient nobody needs."""
+    for module, cls_name in C.package_functions():
+        cls = getattr(importlib.import_module(module), cls_name)
+
+        def watched(ctx, *grads, _real=cls.backward, _name=cls.__name__):
+            out = _real(ctx, *grads)
+            out = out if isinstance(out, tuple) else (out,)
+            assert len(out) == len(ctx.needs_input_grad), _name
+            for i, (g, need) in enumerate(zip(out, ctx.needs_input_grad)):
+                assert need or g is None, "%s.backward returned a gradient in slot %d, which needs none" % (_name, i)
+            returned.append((_name, tuple(g is not None for g in out), tuple(ctx.needs_input_grad)))
+            return out
+        monkeypatch.setattr(cls, "backward", staticmethod(watched))
 
 
 @pytest.mark.parametrize("name,B", CASES, ids=IDS)
@@ -131,7 +139,7 @@ def test_each_input_frozen_in_turn(name, B, monkeypatch):
     returned = []
     _watch_backwards(monkeypatch, returned)
     full = C.run_layer(entry, case, DEV, recipes, seed=B)
-    assert returned, "no backward of layers.py ran under the watch"
+    assert returned, "no backward of the package ran under the watch"
     for frozen in [k for k in entry.diff if case.get(k) is not None]:
         del returned[:]
         res = C.run_layer(entry, case, DEV, recipes, frozen=(frozen,), seed=B)
@@ -275,3 +283,58 @@ def test_zz_report():
 #   tied_projection_transposed   d_table 0.007  d_x 0.014  out0 0.008
 #   token_embedding              d_table 0.119  out0 0.126
 #   token_embedding_dropout      d_table 0.134  out0 0.146
+#
+# The entries of the rest of the package (losses.py, sbcnm.py, xdeepfm.py, dien.py, din.py, the two multi-task Functions) and of
+# sgns_loss / eges_loss, read on an MI355X when they were added.  row_dot's gradients are one correctly rounded multiply (dr_rows_scale)
+# against a bound of one rounding, and so are the third block of din_concat_mode1 / mode2 and din_subtract / din_multiply forward (one
+# subtraction or product, u |ref|); din_concat_mode0 and mean_squared_error's d_p at 0.000 are copies resp. far inside a 1e-4 bound.
+#   binary_crossentropy         d_x 0.174  out0 0.013
+#   categorical_crossentropy_logits  d_x 0.044  out0 0.002
+#   categorical_crossentropy_logits_weighted  d_x 0.044  out0 0.001
+#   categorical_crossentropy_prob  d_x 0.001  out0 0.006
+#   categorical_crossentropy_prob_weighted  d_x 0.001  out0 0.007
+#   cin_act0                    d_W 0.004  d_x 0.002  d_x0 0.001  out0 0.004
+#   cin_act0_bias               d_W 0.004  d_bias 0.002  d_x 0.002  d_x0 0.001  out0 0.005
+#   cin_act2                    d_W 0.004  d_x 0.003  d_x0 0.004  out0 0.002
+#   cin_act2_bias               d_W 0.005  d_bias 0.034  d_x 0.005  d_x0 0.004  out0 0.002
+#   din_concat_mode0            d_x 0.000  d_y 0.000  out0 0.000
+#   din_concat_mode1            d_x 0.186  d_y 0.153  out0 0.971
+#   din_concat_mode2            d_x 0.120  d_y 0.138  out0 0.962
+#   din_multiply                d_x 0.174  d_y 0.192  out0 0.986
+#   din_subtract                d_x 0.000  d_y 0.000  out0 0.971
+#   eges_loss_att_P1_atomics    d_att 0.003  d_out_table 0.003  d_side_table 0.004  out0 0.010
+#   eges_loss_att_P2_plans      d_att 0.003  d_out_table 0.004  d_side_table 0.003  out0 0.014
+#   eges_loss_noatt_P1_plans    d_out_table 0.002  d_side_table 0.003  out0 0.010
+#   eges_loss_noatt_P2_atomics  d_out_table 0.003  d_side_table 0.003  out0 0.011
+#   esmm                        d_pCTR/dense/bias 0.001  d_pCTR/dense/kernel 0.001  d_pCTR/dense_1/bias 0.002  d_pCTR/dense_1/kernel 0.002
+#                               d_pCVR/dense/bias 0.001  d_pCVR/dense/kernel 0.001  d_pCVR/dense_1/bias 0.001  d_pCVR/dense_1/kernel 0.001
+#                               d_x 0.001  out0 0.001  out1 0.001  out2 0.001
+#   explicit_softmax            d_c 0.002  d_q 0.004  out0 0.003
+#   explicit_softmax_all        d_c 0.004  d_q 0.024  out0 0.001
+#   hard_negative_softmax       d_c 0.002  d_q 0.003  out0 0.000
+#   hard_negative_softmax_all   d_c 0.008  d_q 0.004  out0 0.000
+#   inbatch_softmax             d_c 0.005  d_q 0.009  out0 0.000
+#   inbatch_softmax_all         d_c 0.015  d_q 0.022  out0 0.002
+#   item_rows_pitched           d_table 0.211  out0 0.000
+#   item_rows_transposed        d_table 0.211  out0 0.000
+#   log_loss                    d_x 0.208  out0 0.002
+#   losses_sigmoid              d_x 0.029  out0 0.004
+#   mean_squared_error_T1       d_p 0.000  out0 0.001
+#   mean_squared_error_T3       d_p 0.000  out0 0.000
+#   mmoe                        d_mixture_of_experts/dense/bias 0.001  d_mixture_of_experts/dense/kernel 0.001
+#                               d_mixture_of_experts/dense_1/bias 0.001  d_mixture_of_experts/dense_1/kernel 0.001
+#                               d_mixture_of_experts/dense_2/bias 0.001  d_mixture_of_experts/dense_2/kernel 0.001
+#                               d_multi_gate/dense/kernel 0.001  d_multi_gate/dense_1/kernel 0.003  d_task0/dense/bias 0.003
+#                               d_task0/dense/kernel 0.002  d_task0/dense_1/bias 0.004  d_task0/dense_1/kernel 0.002
+#                               d_task1/dense/bias 0.001  d_task1/dense/kernel 0.001  d_task1/dense_1/bias 0.004
+#                               d_task1/dense_1/kernel 0.001  d_x 0.001  out0 0.001  out1 0.002
+#   retrieval_adjust            d_scores 0.000  out0 0.314
+#   retrieval_adjust_ids        d_scores 0.000  out0 0.314
+#   retrieval_scores            d_c 0.008  d_q 0.034  out0 0.127
+#   retrieval_scores_transposed  d_c 0.008  d_q 0.034  out0 0.127
+#   row_dot                     d_a 0.977  d_b 0.978  out0 0.277
+#   sgns_loss_K0_keep_atomics   d_in_table 0.003  d_out_table 0.002  out0 0.008
+#   sgns_loss_K0_skip_plans     d_in_table 0.003  d_out_table 0.002  out0 0.008
+#   sgns_loss_K5_keep_plans     d_in_table 0.003  d_out_table 0.003  out0 0.009
+#   sgns_loss_K5_skip_atomics   d_in_table 0.002  d_out_table 0.003  out0 0.009
+#   sigmoid_cross_entropy       d_x 0.008  out0 0.003

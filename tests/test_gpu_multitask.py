@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from multitask_ref import _gate_mix_ref, _ref_esmm_x, _ref_input, _ref_mmoe      # the float64 restatements
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -140,13 +142,6 @@ def test_grouped_dw_fused_sgd_form(gemm_mode):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # gate softmax + mixture
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _gate_mix_ref(h, l, E, T, U):
-    B = h.shape[0]
-    p = torch.softmax(l.reshape(B, T, E), dim=2)
-    out = torch.einsum("bte,beu->btu", p, h.reshape(B, E, U)).reshape(B, T * U)
-    return p.reshape(B, T * E), out
-
-
 @pytest.mark.parametrize("E,T,U,B", [(E, T, U, B) for E in (1, 2, 3, 8, 64) for T in (1, 2, 3) for U in (1, 7, 64, 130)
                                      for B in (1, 33, 4096) if not (E == 64 and B == 4096 and U == 130)])
 def test_gate_mix_matches_float64(E, T, U, B):
@@ -231,47 +226,6 @@ def test_esmm_head_matches_float64_and_saturates():
 # ---------------------------------------------------------------------------------------------------------------------------------
 # models against a float64 restatement
 # ---------------------------------------------------------------------------------------------------------------------------------
-_ACT = {"relu": torch.relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
-
-
-def _ref_dnn(x, V, scope, names, act):
-    n = len(names)
-    for i, nm in enumerate(names):
-        x = x @ V[scope + "/" + nm + "/kernel"] + V[scope + "/" + nm + "/bias"]
-        if i < n - 1:
-            x = _ACT[act](x)
-    return x
-
-
-def _dense_names(start, count):
-    return ["dense" if j == 0 else "dense_%d" % j for j in range(start, start + count)]
-
-
-def _ref_input(features, columns, V):
-    from deep_recommenders_amd import feature_column as fc
-    layout, _ = fc.input_layer_layout(columns)
-    blocks = []
-    for name, c, off, w in layout:
-        if isinstance(c, fc.NumericColumn):
-            blocks.append(torch.as_tensor(np.asarray(features[c.key], np.float32)).double().reshape(-1, w))
-        else:
-            ids = torch.as_tensor(np.asarray(features[c.categorical_column.key])).reshape(-1)
-            blocks.append(V["input_layer/%s_embedding/embedding_weights" % c.categorical_column.key][ids])
-    return torch.cat(blocks, 1)
-
-
-def _ref_mmoe(features, columns, V, E, T, eu, tu, act_e="relu", act_t="relu"):
-    x = _ref_input(features, columns, V)
-    experts = [_ref_dnn(x, V, "mixture_of_experts", _dense_names(e * len(eu), len(eu)), act_e) for e in range(E)]
-    moe = torch.stack(experts, 1)
-    outs = []
-    for t in range(T):
-        gate = torch.softmax(x @ V["multi_gate/" + _dense_names(t, 1)[0] + "/kernel"], 1)
-        mix = (gate.unsqueeze(1) @ moe).squeeze(1)
-        outs.append(_ref_dnn(mix, V, "task%d" % t, _dense_names(0, len(tu) + 1), act_t))
-    return outs
-
-
 def _numeric_features(n, B, seed):
     r = np.random.RandomState(seed)
     return {"C%d" % i: r.normal(size=(B, 1)).astype(np.float32) for i in range(n)}
@@ -349,10 +303,7 @@ def test_esmm_parity(gemm_mode):
     feats = _numeric_features(12, B, 3)
 
     def ref(V):
-        x = _ref_input(feats, cols, V)
-        cvr = torch.sigmoid(_ref_dnn(x, V, "pCVR", _dense_names(0, 3), "relu"))
-        ctr = torch.sigmoid(_ref_dnn(x, V, "pCTR", _dense_names(0, 3), "relu"))
-        return cvr, ctr, ctr * cvr
+        return _ref_esmm_x(_ref_input(feats, cols, V), V, 3)
     _check_model_parity(m, ref, feats, [torch.randn(B, 1) for _ in range(3)])
 
 
