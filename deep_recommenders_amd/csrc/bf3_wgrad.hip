@@ -22,6 +22,7 @@
 #define DR_NT_WGRAD_GATHER 0
 #endif
 #include "bf3_rs_core.h"
+#include "tn_rs_reduce.h"
 
 namespace {
 
@@ -39,6 +40,7 @@ struct TnRsArgs {
     const int32_t* ids_t; const int64_t* row_base; const float* table; int32_t nf; const float* dense_pad;
     // f16x2 mode: amax records of x (GATHER: the table's; x2 = the dense features', may be null) and of dy
     const uint32_t* x_amax; const uint32_t* x2_amax; const uint32_t* y_amax;
+    uint32_t* hdr;                               // f16x2 mode: the workspace's header, where the amax words this launch used are saved
 };
 
 // H2: the f16x2 operand mode (h2_split8): both operands split into two fp16 terms with their tensors' scales; the partials carry
@@ -67,6 +69,10 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
     if constexpr (H2) {
         float inv;
         h2_prologue(g.x_amax, g.x2_amax, g.y_amax, h2_sx, h2_sy, inv);
+        if (lid == 0 && tid == 0) {                                     // the words these scales came from, for the reduce
+            g.hdr[0] = max(g.x_amax[0], g.x2_amax != nullptr ? g.x2_amax[0] : 0u);
+            g.hdr[1] = g.y_amax[0];
+        }
     }
 
     // this lane's columns (clamped: columns past the edge only feed outputs nobody reads)
@@ -282,75 +288,20 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
 }
 
 // dst[f][n] += scale * sum_s partial[s][f][n]  (fixed order);  dstb[n] += scale * sum_s colsum[s][n]
-// A streaming kernel: 2-D index (blockIdx.x = row f, a thread = V consecutive columns: no division), V = 4 (16-byte loads and stores)
-// where the pointers and `ld` allow it, eight slices' loads in flight per thread.  The additions of an element run in slice order,
-// one after the other from 0.f, and fmaf(wscale, sum, dst) comes last: any unrolling gives the same bits.  The blocks of row 0 also
-// apply the column sums, each column in slice order.
+// A streaming kernel over tn_rs_reduce_block (tn_rs_reduce.h), one logical block per block.
 template <int V>
-__global__ __launch_bounds__(64) void bf3_tn_rs_reduce_kernel(const float* __restrict__ partial, const float* __restrict__ colsum,
-                                                              int32_t split, int32_t F, int32_t N, int32_t Fp, int32_t Np,
-                                                              float scale, float* __restrict__ dst, int64_t ld,
-                                                              float* __restrict__ dstb, const uint32_t* __restrict__ x_amax = nullptr,
-                                                              const uint32_t* __restrict__ x2_amax = nullptr,
-                                                              const uint32_t* __restrict__ y_amax = nullptr) {
-    typedef float vec_t __attribute__((ext_vector_type(V)));
-    const int f = blockIdx.x;
-    const int n = ((int)blockIdx.y * 64 + (int)threadIdx.x) * V;        // < Np: the padded workspace holds all V columns
-    if (n >= N) return;
-    const int64_t ps = (int64_t)Fp * Np;
-    float wscale = scale;                                               // f16x2 partials carry s_x s_y (powers of two: exact)
-    if (x_amax != nullptr) {
-        float sx, ix, sy, iy;
-        h2_scale_of(max(x_amax[0], x2_amax != nullptr ? x2_amax[0] : 0u), sx, ix);
-        h2_scale_of(y_amax[0], sy, iy);
-        wscale = scale * (ix * iy);
-    }
-    auto sum_slices = [&](const float* p, int64_t stride) -> vec_t {   // sum_s p[s * stride], V columns each, in slice order
-        vec_t acc = 0.f;
-        int s = 0;
-        for (; s + 8 <= split; s += 8) {
-            vec_t v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const vec_t*>(p + (s + u) * stride);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc += v[u];
-        }
-        for (; s < split; ++s) acc += *reinterpret_cast<const vec_t*>(p + s * stride);
-        return acc;
-    };
-    const vec_t acc = sum_slices(partial + (int64_t)f * Np + n, ps);
-    float* d = dst + (int64_t)f * ld + n;
-    if (V == 1 || n + V <= N) {
-        vec_t o = *reinterpret_cast<vec_t*>(d);
-#pragma unroll
-        for (int c = 0; c < V; ++c) o[c] = fmaf(wscale, acc[c], o[c]);
-        *reinterpret_cast<vec_t*>(d) = o;
-    } else {                                                            // the row's last, partial group of columns
-#pragma unroll
-        for (int c = 0; c < V; ++c)
-            if (n + c < N) d[c] = fmaf(wscale, acc[c], d[c]);
-    }
-    if (f == 0 && colsum != nullptr && dstb != nullptr) {
-        const vec_t cacc = sum_slices(colsum + n, Np);
-#pragma unroll
-        for (int c = 0; c < V; ++c)
-            if (n + c < N) dstb[n + c] = fmaf(scale, cacc[c], dstb[n + c]);
-    }
+__global__ __launch_bounds__(TN_RS_RED_THREADS) void bf3_tn_rs_reduce_kernel(TnRsApply a) {
+    tn_rs_reduce_block<V>(a, blockIdx.x, threadIdx.x);
 }
 
-void launch_tn_rs_reduce(const float* partial, const float* colsum, int split, int32_t F, int32_t N, int Fp, int Np, float scale,
-                         float* dst, int64_t ld, float* dstb, const uint32_t* x_amax, const uint32_t* x2_amax, const uint32_t* y_amax,
-                         dr_stream_t stream) {
-    const bool vec = ((reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 && (ld & 3) == 0;
-    if (vec)
-        hipLaunchKernelGGL(bf3_tn_rs_reduce_kernel<4>, dim3(F, (N + 255) / 256), dim3(64), 0, dr_s(stream), partial, colsum, split, F, N,
-                           Fp, Np, scale, dst, ld, dstb, x_amax, x2_amax, y_amax);
-    else
-        hipLaunchKernelGGL(bf3_tn_rs_reduce_kernel<1>, dim3(F, (N + 63) / 64), dim3(64), 0, dr_s(stream), partial, colsum, split, F, N,
-                           Fp, Np, scale, dst, ld, dstb, x_amax, x2_amax, y_amax);
+void launch_tn_rs_reduce(const TnRsApply& a, dr_stream_t stream) {
+    const int nlb = tn_rs_reduce_blocks(a.F, a.N, a.vec);
+    if (a.vec) hipLaunchKernelGGL(bf3_tn_rs_reduce_kernel<4>, dim3(nlb), dim3(TN_RS_RED_THREADS), 0, dr_s(stream), a);
+    else hipLaunchKernelGGL(bf3_tn_rs_reduce_kernel<1>, dim3(nlb), dim3(TN_RS_RED_THREADS), 0, dr_s(stream), a);
 }
+}  // namespace
 
-void tn_rs_plan(int64_t R, int32_t F, int32_t N, int& split, int64_t& per, int& Fp, int& Np) {
+void drrs::tn_rs_plan(int64_t R, int32_t F, int32_t N, int& split, int64_t& per, int& Fp, int& Np) {
     const int tf = (F + 255) / 256, tn = (N + 255) / 256;
     Fp = tf * 256;
     Np = tn * 256;
@@ -361,14 +312,13 @@ void tn_rs_plan(int64_t R, int32_t F, int32_t N, int& split, int64_t& per, int& 
     per = ((R + sp - 1) / sp + BK - 1) / BK * BK;
     split = (int)((R + per - 1) / per);                                 // every slice non-empty
 }
-}  // namespace
 
 extern "C" int64_t dr_bf3_wgrad_workspace_bytes(int64_t R, int32_t F, int32_t N) {
     if (R <= 0 || F <= 0 || N <= 0) return 0;
     int split, Fp, Np;
     int64_t per;
     tn_rs_plan(R, F, N, split, per, Fp, Np);
-    return ((int64_t)split * Fp * Np + (int64_t)split * Np) * (int64_t)sizeof(float);
+    return ((int64_t)split * Fp * Np + (int64_t)split * Np + TN_RS_HDR_WORDS) * (int64_t)sizeof(float);
 }
 
 // dstW[f][n] += scale * sum_r x[r][f] dy[r][n];  dstb[n] += scale * sum_r dy[r][n] (dstb may be NULL).  x [R, F], dy [R, N] fp32
@@ -382,15 +332,14 @@ static int wgrad_impl(const float* x, int64_t ld_x, const float* dy, int64_t ld_
     int split, Fp, Np;
     int64_t per;
     tn_rs_plan(R, F, N, split, per, Fp, Np);
-    float* partial = static_cast<float*>(workspace);
-    float* colsum = partial + (int64_t)split * Fp * Np;
-    TnRsArgs g{x, ld_x, dy, ld_dy, R, F, N, per, split, partial, dstb != nullptr ? colsum : nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-               x_amax, nullptr, dy_amax};
+    const bool h2 = x_amax != nullptr;
+    const TnRsApply ap = tn_rs_apply_of(workspace, split, F, N, Fp, Np, h2, scale, dstW, ld_w, dstb);
+    TnRsArgs g{x, ld_x, dy, ld_dy, R, F, N, per, split, const_cast<float*>(ap.partial), const_cast<float*>(ap.colsum), nullptr, nullptr, nullptr, 0,
+               nullptr, x_amax, nullptr, dy_amax, const_cast<uint32_t*>(ap.hdr)};
     const int grid = (Fp / 256) * (Np / 256) * split;
-    if (x_amax != nullptr) hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<0, 1>), dim3(grid), dim3(512), 0, dr_s(stream), g);
+    if (h2) hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<0, 1>), dim3(grid), dim3(512), 0, dr_s(stream), g);
     else hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<0, 0>), dim3(grid), dim3(512), 0, dr_s(stream), g);
-    launch_tn_rs_reduce(partial, dstb != nullptr ? colsum : nullptr, split, F, N, Fp, Np, scale, dstW, ld_w, dstb, x_amax, nullptr, dy_amax,
-                        stream);
+    launch_tn_rs_reduce(ap, stream);
     DR_CHECK_LAUNCH();
     return DR_OK;
 }
@@ -427,18 +376,16 @@ static int wgrad_emb_impl(const int32_t* ids_t, int64_t R, int32_t nf, const int
     int split, Fp, Np;
     int64_t per;
     tn_rs_plan(R, F, N, split, per, Fp, Np);
-    float* partial = static_cast<float*>(workspace);
-    float* colsum = partial + (int64_t)split * Fp * Np;
-    TnRsArgs g{nullptr, 0, dy, ld_dy, R, F, N, per, split, partial, dstb != nullptr ? colsum : nullptr, ids_t, row_base, table, nf,
-               F > 64 * nf ? dense_pad : nullptr, table_amax, F > 64 * nf ? dense_amax : nullptr, dy_amax};
+    const bool h2 = table_amax != nullptr;
+    const TnRsApply ap = tn_rs_apply_of(workspace, split, F, N, Fp, Np, h2, scale, dstW, ld_w, dstb);
+    TnRsArgs g{nullptr, 0, dy, ld_dy, R, F, N, per, split, const_cast<float*>(ap.partial), const_cast<float*>(ap.colsum), ids_t, row_base, table,
+               nf, F > 64 * nf ? dense_pad : nullptr, table_amax, F > 64 * nf ? dense_amax : nullptr, dy_amax, const_cast<uint32_t*>(ap.hdr)};
     const int grid = (Fp / 256) * (Np / 256) * split;
     if (parts & 1) {
-        if (table_amax != nullptr) hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<1, 1>), dim3(grid), dim3(512), 0, dr_s(stream), g);
+        if (h2) hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<1, 1>), dim3(grid), dim3(512), 0, dr_s(stream), g);
         else hipLaunchKernelGGL((bf3_gemm_tn_rs_kernel<1, 0>), dim3(grid), dim3(512), 0, dr_s(stream), g);
     }
-    if (parts & 2)
-        launch_tn_rs_reduce(partial, dstb != nullptr ? colsum : nullptr, split, F, N, Fp, Np, scale, dstW, ld_w, dstb, table_amax,
-                            F > 64 * nf ? dense_amax : nullptr, dy_amax, stream);
+    if (parts & 2) launch_tn_rs_reduce(ap, stream);
     DR_CHECK_LAUNCH();
     return DR_OK;
 }

@@ -12,6 +12,7 @@
 // variable) reached from optimizer.minimize (examples/train_fm_on_movielens_estimator.py:51-52, reference root).
 #include <cstdlib>
 #include "dr_common.h"
+#include "tn_rs_reduce.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 #include <cstring>
 
@@ -417,6 +418,25 @@ __global__ DR_K4_LB void emb_bwd_sorted_kernel(BwdSortedArgs a, AdamArgs ad, int
                                           a.skip_unique_lin ? nullptr : a.lin_w, a.lin_bias, ad, a.lin_old_t, a.amax);
 }
 
+// The duplicate pass of the fused dgrad + K4 (parts | 8) with a DEFERRED DENSE APPLY riding behind it: blocks [0, grid_d) walk the
+// duplicate segments, block grid_d sums the first-order bias, and the blocks behind it ("riders") run the fixed-order reduce of the
+// first layer's wgrad (tn_rs_reduce.h) -- dstW += scale * sum of the split-K partials that the wgrad's main launch left in its
+// workspace earlier on this stream.  The riders share nothing with the other blocks (the dense weight, not the tables), so nothing
+// orders them inside the launch; the duplicate blocks stay first in the grid so that hot rows start early.  The duplicate pass is a
+// chain of dependent round trips in 2049 nearly empty blocks, the riders stream: together they take the longer of the two.
+template <int LPR>
+__global__ __launch_bounds__(256) void emb_bwd_dups_apply_kernel(BwdSortedArgs a, drrs::TnRsApply ap, int grid_d) {
+    const int bid = blockIdx.x;
+    if (bid < grid_d)
+        emb_bwd_dups_body<LPR, false>(bid, grid_d, a.rows, a.slots, a.n, a.dup_heads, a.dup_count, a.F, a.D, a.num_rows, a.grad, a.ld,
+                                      a.concat, a.ldc, a.sum_x, a.d_fm_logit, a.slot_lin, a.scale, a.table, a.lin_w, AdamArgs{}, a.x_sorted,
+                                      a.det != 0, a.amax);
+    else if (bid == grid_d) {
+        if (a.lin_bias != nullptr && a.d_fm_logit != nullptr) dr_block_sum_axpy(a.d_fm_logit, a.B, a.scale, a.lin_bias);
+    } else
+        drrs::tn_rs_reduce_ride(ap, bid - grid_d - 1, (int)gridDim.x - grid_d - 1, threadIdx.x);
+}
+
 // Second half of the deterministic hot-row update (SGD with x_sorted given): for every row whose slots span more than one piece,
 // the pieces' parked sums -- x_sorted[i] of the segment start, then the CH-aligned positions behind it -- are added in a fixed
 // order, the row's first-order gradient is re-summed over its slots in a fixed order, and the row and its first-order weight
@@ -538,7 +558,7 @@ static int bwd_sorted_impl(const int64_t* ids, const int64_t* row_base, const in
                            int64_t ld_grad, const float* concat, int64_t ld_concat, const float* sum_x,
                            const float* d_fm_logit, const float* slot_lin_grad, float scale, float* dst_table,
                            float* dst_lin, float* dst_bias, const AdamArgs* adam, float* x_sorted, dr_stream_t stream,
-                           int parts, const float* lin_old_t, uint32_t* table_amax) {
+                           int parts, const float* lin_old_t, uint32_t* table_amax, const drrs::TnRsApply* apply = nullptr) {
     if (B < 0 || F <= 0 || F > 64 || D < 4 || D > 256 || (D & 3) || num_rows <= 0) return DR_EINVAL;
     const int64_t n = B * F;
     if (n == 0) return DR_OK;
@@ -569,13 +589,18 @@ static int bwd_sorted_impl(const int64_t* ids, const int64_t* row_base, const in
 #else
     constexpr int K4_U_OVERRIDE = 0;
 #endif
+    // riders of a deferred dense apply: one per logical reduce block, at most 1024 (a rider loops over what is left)
+    const int nlb = apply != nullptr ? drrs::tn_rs_reduce_blocks(apply->F, apply->N, apply->vec) : 0;
+    const int riders = nlb < 1024 ? nlb : 1024;
 #define LAUNCH(L, ADAM_)                                                                                              \
-    {                                                                                                                 \
+    { if (apply != nullptr) {                                                                                         \
+        hipLaunchKernelGGL((emb_bwd_dups_apply_kernel<L>), dim3(grid_d + 1 + riders), dim3(256), 0, dr_s(stream), ba, *apply, grid_d);     \
+    } else {                                                                                                          \
         constexpr int NS_ = 64 / L;                                                                                   \
         constexpr int U_ = K4_U_OVERRIDE > 0 ? K4_U_OVERRIDE : (NS_ >= 16 ? 2 : 4);                                   \
         hipLaunchKernelGGL((emb_bwd_sorted_kernel<L, U_, ADAM_>), dim3(grid_d + ((parts & 8) ? 1 : grid_u)), dim3(256), 0, dr_s(stream), ba, ad,    \
                            grid_d);                                                                                   \
-    }
+    } }
 #define CALL(L)                                                                                                       \
     if (adam != nullptr) LAUNCH(L, true) else LAUNCH(L, false)
     if (parts & 1)
@@ -636,6 +661,33 @@ extern "C" int dr_emb_pool_bwd_sorted(const int64_t* ids, const int64_t* row_bas
     return bwd_sorted_impl(ids, row_base, sorted_rows, sorted_slots, unique_flags, dup_heads, dup_count, B, F, D, num_rows,
                            grad, ld_grad, concat, ld_concat, sum_x, d_fm_logit, slot_lin_grad, scale, dst_table, dst_lin,
                            dst_bias, nullptr, x_sorted, stream, parts, lin_old_t, table_amax);
+}
+
+// dr_emb_pool_bwd_sorted(parts | 8) with a deferred dense apply in its first launch: the duplicate pass's launch gets extra blocks
+// that apply the first layer's wgrad -- the product that part 1 of dr_h2_wgrad_emb (or of dr_bf3_wgrad_emb: wg_h2 = 0) of the SAME
+// (wg_R, wg_F, wg_N) left in wg_workspace earlier on this stream:  dstW[f][n] += wg_scale * sum_s partial[s][f][n], dstb likewise
+// (may be NULL), the bits of that call's part 2 without its launch.  wg_h2 != 0: the partials carry the f16x2 scales of the amax words
+// saved in the workspace (the live records are not read: the dgrad + K4 in front of this call has raised the table's).  parts: 1 | 8 or
+// 3 | 8 (part 1 carries the riders).  DR_EINVAL for a null or short wg_workspace, before anything is launched.
+extern "C" int dr_emb_pool_bwd_dups_apply(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
+                                          const int32_t* sorted_slots, const uint8_t* unique_flags, const int32_t* dup_heads,
+                                          const int32_t* dup_count, int64_t B, int32_t F, int32_t D, int64_t num_rows, const float* grad,
+                                          int64_t ld_grad, const float* sum_x, const float* d_fm_logit, float scale, float* dst_table,
+                                          float* dst_lin, float* dst_bias, float* x_sorted, const float* lin_old_t, int32_t parts,
+                                          uint32_t* table_amax, void* wg_workspace, int64_t wg_workspace_bytes, int64_t wg_R, int32_t wg_F,
+                                          int32_t wg_N, int32_t wg_h2, float wg_scale, float* dstW, int64_t ld_w, float* dstb,
+                                          dr_stream_t stream) {
+    if (parts != 9 && parts != 11) return DR_EINVAL;
+    if (wg_R <= 0 || wg_F <= 0 || wg_N <= 0 || !wg_workspace || !dstW || ld_w < wg_N) return DR_EINVAL;
+    if (wg_workspace_bytes < dr_bf3_wgrad_workspace_bytes(wg_R, wg_F, wg_N)) return DR_EINVAL;
+    if (B <= 0) return DR_EINVAL;                              // (an empty batch launches nothing: the apply would be lost)
+    int split, Fp, Np;
+    int64_t per;
+    drrs::tn_rs_plan(wg_R, wg_F, wg_N, split, per, Fp, Np);
+    const drrs::TnRsApply ap = drrs::tn_rs_apply_of(wg_workspace, split, wg_F, wg_N, Fp, Np, wg_h2 != 0, wg_scale, dstW, ld_w, dstb);
+    return bwd_sorted_impl(ids, row_base, sorted_rows, sorted_slots, unique_flags, dup_heads, dup_count, B, F, D, num_rows, grad, ld_grad,
+                           nullptr, 0, sum_x, d_fm_logit, nullptr, scale, dst_table, dst_lin, dst_bias, nullptr, x_sorted, stream, parts,
+                           lin_old_t, table_amax, &ap);
 }
 
 // dst_lin[row_base[f] + ids[b, f]] += scale * (slot_lin_grad ? slot_lin_grad[b, f] : d_fm_logit[b])  for every slot whose row no other

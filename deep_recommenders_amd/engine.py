@@ -315,6 +315,15 @@ class DeepFMEngine:
         self.overlap_dw = _ov == "1"
         if self.overlap_dw:
             self.no_concat = False       # the gathering wgrad would read the tables while K4 updates them on the other stream
+        # The first-layer wgrad's split-K reduce + SGD step of W0 / b0 (20 - 23 us behind a dependent-launch boundary) as RIDER blocks of
+        # K4's duplicate-pass launch, which is on the training stream anyway (2049 nearly empty blocks: a chain of dependent round trips;
+        # the riders stream 66 MB beside it).  Nothing in between reads W0 -- the fused dgrad reads the previous plane image -- so the
+        # wgrad runs its main launch only and the plane refresh moves behind the duplicate pass.  The reduce takes its f16x2 scales from
+        # the words the main kernel saved in the workspace, not from the table's record, which K4 has raised by then.  Same partials,
+        # same summation order: bit-identical steps (tests/test_gpu_folded_reduces.py).  DR_FOLD_REDUCES=0: the reduce as a launch of
+        # its own behind the wgrad.  (The tower tail's reduce riding in the wgrad's main launch was measured too: DESIGN.md 3.5.)
+        self.fold_reduces = (os.environ.get("DR_FOLD_REDUCES", "1") != "0" and self.tail_in_fwd and self.fuse_k4 and self.h2
+                             and optimizer == "sgd" and not self.overlap_dw and not self.reduce_side)
         self.concurrent = {}
         if self.overlap_dw:
             k4 = "emb_pool_bwd_adam" if optimizer == "adam" else "emb_pool_bwd"
@@ -519,10 +528,11 @@ class DeepFMEngine:
             self.ev_small.record(self.side)
         self._small_pending = True
 
-    def _wgrad(self, i, x, dy, sc, dstW, dstb):
+    def _wgrad(self, i, x, dy, sc, dstW, dstb, main_only=False):
         if i == 0 and self.h2:
             ops.h2_wgrad_emb(self._ids_t[self.cur], self.row_base, self.table, self.tab_amax, self.dense_pad, self.dense_amax, dy,
-                             self.dh0_amax, sc, dstW, dstb, workspace=self.wg_ws[0], parts=1 if self._wgrad_reduce_deferred(i) else 3)
+                             self.dh0_amax, sc, dstW, dstb, workspace=self.wg_ws[0],
+                             parts=1 if (main_only or self._wgrad_reduce_deferred(i)) else 3)
         elif i == 0 and self.no_concat:
             # x = [embeddings of this batch's rows, dense features]: gathered from the tables (they are updated only by K4, later
             # on this stream) through the field-major ids
@@ -848,22 +858,28 @@ class DeepFMEngine:
         first-order bias.  The plane refresh waits for the dgrad."""
         lr = self.lr
         torch.cuda.current_stream().wait_event(self.ev_sorted)             # the plan's flags (long complete when prefetched)
-        self._k("linear_bwd_dw_L0", "mfma", fl, lambda: self._wgrad(0, x, dy, sc, dstW, dstb))
-        # The weight just moved: its planes follow on the side stream, BESIDE the dgrad, which keeps reading the previous W image and
-        # record (H2WeightPlanes(double_buffer=True): the refresh writes the other pair) -- the next forward waits for nothing.
+        fold = self.fold_reduces                  # the wgrad's reduce rides in the duplicate pass's launch: main launch only here
+        self._k("linear_bwd_dw_L0", "mfma", fl, lambda: self._wgrad(0, x, dy, sc, dstW, dstb, main_only=fold))
         w_old = self.wplanes[0].w
         early = self._early_issued
-        rs = self.side_r if early else self.side           # (without the early chain the hash + plan follow on `side`, behind the refresh)
-        self._refresh_stream = rs
-        self.ev_dw_done.record()
-        with torch.cuda.stream(rs):
-            rs.wait_event(self.ev_dw_done)
-            self.wplanes[0].refresh()
-            self.ev_planes.record(rs)
-        self._planes_pending = True
-        self._planes_pending_l0 = True
-        # the next batch's dense features (and, unless they went out at the start of the step, its hash + plan) behind the refresh: the
-        # wgrad was the last reader of dense_pad
+        rs = self.side_r if (early or fold) else self.side   # (without the early chain the hash + plan follow on `side`, behind the refresh)
+
+        def refresh_planes_behind():
+            # The weight just moved: its planes follow on the side stream.  The dgrad keeps reading the previous W image and record
+            # (H2WeightPlanes(double_buffer=True): the refresh writes the other pair) -- the next forward waits for ev_planes.
+            self._refresh_stream = rs
+            self.ev_dw_done.record()
+            with torch.cuda.stream(rs):
+                rs.wait_event(self.ev_dw_done)
+                self.wplanes[0].refresh()
+                self.ev_planes.record(rs)
+            self._planes_pending = True
+            self._planes_pending_l0 = True
+
+        if not fold:
+            refresh_planes_behind()                # BESIDE the dgrad
+        # the next batch's dense features (and, unless they went out at the start of the step, its hash + plan) behind the wgrad, the last
+        # reader of dense_pad: behind the refresh, or -- when W0 moves only in the duplicate pass's launch -- behind an event of their own
         mark = self._prefetch_mark()
         if early:
             self._prefetch_issue(mark)
@@ -877,7 +893,15 @@ class DeepFMEngine:
         k4 = lambda parts: ops.emb_pool_bwd_sorted(self.ids, self.row_base, self.plan, self.D, self.R, self.d_concat, self.d_logit, -lr,
                                                    self.table, self.lin_w, self.lin_bias, sum_x=self.sum_x, x_sorted=self.x_sorted,
                                                    parts=parts | 8, lin_old_t=self.lin_old_t, table_amax=self.tab_amax)
-        self._k("emb_pool_bwd_dups", "hbm", 0, lambda: k4(1))
+        if fold:
+            # the duplicate pass's launch carries the wgrad's reduce + SGD step of W0 / b0; the planes follow behind it
+            self._k("emb_pool_bwd_dups", "hbm", 0,
+                    lambda: ops.emb_pool_bwd_dups_apply(self.ids, self.row_base, self.plan, self.D, self.R, self.d_concat, self.d_logit, -lr,
+                                                        self.table, self.lin_w, self.lin_bias, self.sum_x, self.x_sorted, self.lin_old_t,
+                                                        self.tab_amax, self.wg_ws[0], self.B, sc, dstW, dstb, wg_h2=True, parts=1))
+            refresh_planes_behind()
+        else:
+            self._k("emb_pool_bwd_dups", "hbm", 0, lambda: k4(1))
         self._k("emb_hot_rows_apply", "hbm", 0, lambda: k4(2))
         if not early:
             self._prefetch_issue(mark)

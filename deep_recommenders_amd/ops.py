@@ -657,6 +657,24 @@ def emb_pool_bwd_sorted(ids, row_base, plan, D, num_rows, grad, d_fm_logit, scal
           "dr_emb_pool_bwd_sorted")
 
 
+def emb_pool_bwd_dups_apply(ids, row_base, plan, D, num_rows, grad, d_fm_logit, scale, dst_table, dst_lin, dst_bias, sum_x, x_sorted,
+                            lin_old_t, table_amax, wg_workspace, wg_R, wg_scale, dstW, dstb=None, wg_h2=True, parts=1):
+    """emb_pool_bwd_sorted(parts | 8) whose first launch also applies the first layer's wgrad (dr_emb_pool_bwd_dups_apply): extra blocks
+    behind the duplicate pass run the fixed-order reduce of the product that part 1 of h2_wgrad_emb (or of bf3_wgrad_emb: wg_h2=False)
+    left in wg_workspace -- dstW += wg_scale * sum of the partials, dstb likewise.  parts: 1 or 3 (| 8 is implied)."""
+    ids = _c(ids, torch.int64)
+    B, F = ids.shape
+    wg_F, wg_N = dstW.shape
+    assert grad.stride(1) == 1 and dstW.stride(1) == 1
+    assert lin_old_t is None or (lin_old_t.shape == (F, B) and lin_old_t.is_contiguous() and lin_old_t.dtype == torch.float32)
+    check(lib().dr_emb_pool_bwd_dups_apply(ptr(ids), ptr(row_base), ptr(plan.rows), ptr(plan.slots), ptr(plan.flags), ptr(plan.dup_heads),
+                                           ptr(plan.dup_count), B, F, D, int(num_rows), ptr(grad), grad.stride(0), ptr(sum_x),
+                                           ptr(d_fm_logit), float(scale), ptr(dst_table), ptr(dst_lin), ptr(dst_bias), ptr(x_sorted),
+                                           ptr(lin_old_t), int(parts) | 8, ptr(table_amax), ptr(wg_workspace), wg_workspace.numel() * 4,
+                                           int(wg_R), wg_F, wg_N, 1 if wg_h2 else 0, float(wg_scale), ptr(dstW), dstW.stride(0), ptr(dstb),
+                                           stream_ptr()), "dr_emb_pool_bwd_dups_apply")
+
+
 def h2_dgrad_emb_sgd(dy, dy_amax, w: "H2Planes", ids_t, plan, row_base, table, lin_w, lin_old_t, sum_x, d_fm_logit, scale, d_concat,
                      table_amax=None):
     """First-layer dgrad + K4's unique-row pass in one launch (dr_h2_dgrad_emb_sgd): the rows of `table` (and `lin_w`) that exactly one

@@ -792,6 +792,19 @@ int dr_h2_wgrad_emb(const int32_t* ids_t, int64_t R, int32_t nf, const int64_t* 
                     const uint32_t* table_amax, const float* dense_pad, const uint32_t* dense_amax, const float* dy, int64_t ld_dy,
                     const uint32_t* dy_amax, int32_t F, int32_t N, float scale, float* dstW, int64_t ld_w, float* dstb, void* workspace,
                     int64_t workspace_bytes, int32_t parts, dr_stream_t stream);
+/* dr_emb_pool_bwd_dups_apply = dr_emb_pool_bwd_sorted(parts = 1 | 8 or 3 | 8) whose first launch carries extra "rider" blocks behind the
+ * duplicate pass's own: ordinary independent blocks (no launch, stream, event or grid-wide wait of their own) that run part 2 of the
+ * wgrad (wg_R, wg_F, wg_N) whose part 1 left its product in wg_workspace earlier on this stream: dstW += wg_scale * sum of the
+ * partials, dstb likewise (may be NULL), bit for bit.  wg_h2 != 0: the product came from an f16x2 call (dr_h2_wgrad_emb / dr_h2_wgrad);
+ * the scales are taken from the amax words that call saved in the workspace, never from the live records.  DR_EINVAL for a null or
+ * short wg_workspace before anything is launched. */
+int dr_emb_pool_bwd_dups_apply(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows, const int32_t* sorted_slots,
+                               const uint8_t* unique_flags, const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
+                               int32_t D, int64_t num_rows, const float* grad, int64_t ld_grad, const float* sum_x,
+                               const float* d_fm_logit, float scale, float* dst_table, float* dst_lin, float* dst_bias, float* x_sorted,
+                               const float* lin_old_t, int32_t parts, uint32_t* table_amax, void* wg_workspace,
+                               int64_t wg_workspace_bytes, int64_t wg_R, int32_t wg_F, int32_t wg_N, int32_t wg_h2, float wg_scale,
+                               float* dstW, int64_t ld_w, float* dstb, dr_stream_t stream);
 
 
 /* ------------------------------------------------------------------------------------------
