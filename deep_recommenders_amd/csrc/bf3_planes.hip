@@ -1,6 +1,7 @@
 // PLANES family: fp32 GEMMs on operands that are pre-split on BOTH sides, and the kernels that make and read planes (split, join,
 // amax records, the f16x2 weight split).  Operand format and LDS images: bf3_rs_core.h.
 #include "bf3_rs_core.h"
+#include "tn_rs_reduce.h"
 
 namespace {
 
@@ -621,30 +622,9 @@ __global__ __launch_bounds__(256) void h2_split_both_kernel(const float* __restr
                                                             _Float16* __restrict__ w, int64_t w_ps, int64_t w_ld,
                                                             _Float16* __restrict__ wt, int64_t wt_ps, int64_t wt_ld,
                                                             const uint32_t* __restrict__ parts, int32_t nparts, uint32_t* __restrict__ amax) {
-    uint32_t m = (int)threadIdx.x < nparts ? parts[threadIdx.x] : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    __shared__ uint32_t wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = max(max(wm[0], wm[1]), max(wm[2], wm[3]));
-    if (blockIdx.x == 0 && threadIdx.x == 0) amax[0] = m;               // the record the GEMMs read (they run behind this kernel)
-    float sc, inv;
-    h2_scale_of(m, sc, inv);
-    h2_mode_on();
-    const int64_t total = R * (int64_t)C, stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * total; i += stride) {
-        // consecutive threads: consecutive DESTINATION elements, first of the plain image, then of the transposed one
-        int64_t r, c, off;
-        _Float16* dst;
-        int64_t ps;
-        if (i < total) { r = i / C; c = i - r * C; off = r * w_ld + c; dst = w; ps = w_ps; }
-        else { const int64_t j = i - total; c = j / R; r = j - c * R; off = c * wt_ld + r; dst = wt; ps = wt_ps; }
-        const float v = src[r * ld + c] * sc;
-        const _Float16 h = (_Float16)v;
-        dst[off] = h;
-        dst[ps + off] = (_Float16)(v - (float)h);
-    }
+    // (the body lives in tn_rs_reduce.h: the rider blocks behind K4's hot-row launch run the same text)
+    h2_split_both_block(H2RefreshRide{src, ld, R, C, w, w_ps, w_ld, wt, wt_ps, wt_ld, parts, nparts, amax},
+                        (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
 }
 
 // planes -> fp32 (tests, debugging): dst[r][c] = (p2 + p1) + p0

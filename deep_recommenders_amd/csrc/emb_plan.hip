@@ -663,7 +663,7 @@ namespace {
 // kernel.  Returns DR_OK + *done = false when the geometry is not the fused front's (the caller then runs the plain entry points).
 int plan_small_front(const int64_t* raw, const uint64_t* col_buckets, int64_t* ids_out, int32_t* ids_t, const int64_t* ids, int64_t B,
                      int32_t F, const int64_t* row_base, int64_t num_rows, uint64_t* rows_y, uint64_t* keys_x, uint32_t* ghist,
-                     uint32_t* tot, Ctrl* ctrl, int32_t* dup_count, hipStream_t s) {
+                     uint32_t* tot, Ctrl* ctrl, int32_t* dup_count, hipStream_t s, int parts) {
     const int64_t n64 = B * F;
     const int32_t n = (int32_t)n64;
     // row * 256 / num_rows as a multiply-shift; floor, so that row * mul >> 32 <= 255 for every row < num_rows
@@ -677,17 +677,19 @@ int plan_small_front(const int64_t* raw, const uint64_t* col_buckets, int64_t* i
     if (chunk > 0x7fffffff) return DR_EINVAL;
     const bool trans = ids_t != nullptr;
     const size_t lds = (size_t)8 * (raw ? 3 : 1) * F + (trans ? (size_t)4 * 64 * (F + 1) : 0);
-    if (raw) {
+    // the front kernel that hashes raw keys is the one launch that writes ids_out / ids_t: parts & 1; everything else is parts & 2
+    if (raw && (parts & 1)) {
         if (trans)
             hipLaunchKernelGGL((plan_front_kernel<true, true>), dim3(nbf), dim3(256), lds, s, raw, B, F, col_buckets, ids_out, ids_t, row_base,
                                (uint64_t)num_rows, mul, (int32_t)sub, rows_y, ghist);
         else
             hipLaunchKernelGGL((plan_front_kernel<true, false>), dim3(nbf), dim3(256), lds, s, raw, B, F, col_buckets, ids_out, ids_t,
                                row_base, (uint64_t)num_rows, mul, (int32_t)sub, rows_y, ghist);
-    } else {
+    } else if (!raw && (parts & 2)) {
         hipLaunchKernelGGL((plan_front_kernel<false, false>), dim3(nbf), dim3(256), lds, s, ids, B, F, col_buckets, ids_out, ids_t, row_base,
                            (uint64_t)num_rows, mul, (int32_t)sub, rows_y, ghist);
     }
+    if (!(parts & 2)) return DR_OK;
     hipLaunchKernelGGL((radix_scan_kernel<true>), dim3(RADIX), dim3(256), 0, s, ghist, (int32_t)nbf, tot, ctrl, dup_count);
     hipLaunchKernelGGL(plan_scatter_kernel, dim3(nbs), dim3(LG_T), 0, s, rows_y, keys_x, n, mul, (int32_t)chunk, ghist, (int32_t)nbf, tot);
     return DR_OK;
@@ -695,7 +697,8 @@ int plan_small_front(const int64_t* raw, const uint64_t* col_buckets, int64_t* i
 
 int sort_slots_impl(const int64_t* raw, const uint64_t* col_buckets, int32_t* ids_t, const int64_t* ids, int64_t B, int32_t F,
                     const int64_t* row_base, int64_t num_rows, int64_t* sorted_rows, int32_t* sorted_slots, uint8_t* unique_flags,
-                    int32_t* dup_heads, int32_t* dup_count, void* workspace, int64_t workspace_bytes, dr_stream_t stream) {
+                    int32_t* dup_heads, int32_t* dup_count, void* workspace, int64_t workspace_bytes, dr_stream_t stream,
+                    int parts = 3) {
     if (B < 0 || F <= 0 || num_rows <= 0) return DR_EINVAL;
     const int64_t n64 = B * F;
     if (n64 == 0) return DR_OK;
@@ -722,15 +725,19 @@ int sort_slots_impl(const int64_t* raw, const uint64_t* col_buckets, int32_t* id
     const bool claimable = n64 <= (1 << 24) && num_rows < 0x7fffffffLL;
     // K1 inside the front kernel: its LDS holds the per-field constants and (for the field-major ids) a 64 x (F + 1) tile
     const bool fused_front = raw != nullptr && claimable && F <= 64;
-    if (raw && !fused_front) {
+    if (raw && !fused_front && (parts & 1)) {
         int rc = dr_hash_bucket_i64(raw, B, F, col_buckets, const_cast<int64_t*>(ids), stream);
         if (rc == DR_OK && ids_t) rc = dr_ids_transpose_i32(ids, B, F, ids_t, stream);
         if (rc != DR_OK) return rc;
     }
     if (claimable) {
         int rc = plan_small_front(fused_front ? raw : nullptr, col_buckets, const_cast<int64_t*>(ids), fused_front ? ids_t : nullptr, ids, B,
-                                  F, row_base, num_rows, rows_y, keys_x, ghist, tot, ctrl, dup_count, s);
+                                  F, row_base, num_rows, rows_y, keys_x, ghist, tot, ctrl, dup_count, s, parts);
         if (rc != DR_OK) return rc;
+        if (!(parts & 2)) {
+            DR_CHECK_LAUNCH();
+            return DR_OK;
+        }
         // (dynamic LDS beyond 64 KB needs the opt-in)
         static const hipError_t lds_optin = hipFuncSetAttribute(reinterpret_cast<const void*>(plan_lds_claim_kernel),
                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 4 << LDS_TAB_MAX_LOG);
@@ -747,6 +754,7 @@ int sort_slots_impl(const int64_t* raw, const uint64_t* col_buckets, int32_t* id
         DR_CHECK_LAUNCH();
         return DR_OK;
     }
+    if (!(parts & 2)) return DR_OK;
     // geometry beyond the composite key: the chip-wide LSD radix sort of all n slots; the final pass must land in the output arrays
     if (hipMemsetAsync(dup_count, 0, 2 * sizeof(int32_t), s) != hipSuccess) return DR_ELAUNCH;
     const unsigned bits = bits_for((uint64_t)num_rows);            // the sentinel == num_rows needs these bits too
@@ -789,4 +797,17 @@ extern "C" int dr_hash_sort_slots(const int64_t* keys, int64_t B, int32_t F, con
     if (!keys || !col_buckets || !ids_out) return DR_EINVAL;
     return sort_slots_impl(keys, col_buckets, ids_t_out, ids_out, B, F, row_base, num_rows, sorted_rows, sorted_slots, unique_flags,
                            dup_heads, dup_count, workspace, workspace_bytes, stream);
+}
+
+// dr_hash_sort_slots issued in two parts on one stream, so that a caller can record an event between them: parts & 1 = every launch
+// that writes ids_out / ids_t_out (the fused front kernel; in the fallback geometries dr_hash_bucket_i64 + dr_ids_transpose_i32), parts & 2
+// = the rest of the plan, which reads what part 1 left (ids_out, and behind the fused front kernel the composite keys in sorted_rows and
+// the histogram in the workspace: nothing may touch them in between).  parts == 3 is dr_hash_sort_slots, launch for launch.
+extern "C" int dr_hash_sort_slots_parts(const int64_t* keys, int64_t B, int32_t F, const uint64_t* col_buckets, int64_t* ids_out,
+                                        int32_t* ids_t_out, const int64_t* row_base, int64_t num_rows, int64_t* sorted_rows,
+                                        int32_t* sorted_slots, uint8_t* unique_flags, int32_t* dup_heads, int32_t* dup_count,
+                                        void* workspace, int64_t workspace_bytes, int32_t parts, dr_stream_t stream) {
+    if (!keys || !col_buckets || !ids_out || parts < 1 || parts > 3) return DR_EINVAL;
+    return sort_slots_impl(keys, col_buckets, ids_t_out, ids_out, B, F, row_base, num_rows, sorted_rows, sorted_slots, unique_flags,
+                           dup_heads, dup_count, workspace, workspace_bytes, stream, parts);
 }

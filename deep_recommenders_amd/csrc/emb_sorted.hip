@@ -424,8 +424,12 @@ __global__ DR_K4_LB void emb_bwd_sorted_kernel(BwdSortedArgs a, AdamArgs ad, int
 // workspace earlier on this stream.  The riders share nothing with the other blocks (the dense weight, not the tables), so nothing
 // orders them inside the launch; the duplicate blocks stay first in the grid so that hot rows start early.  The duplicate pass is a
 // chain of dependent round trips in 2049 nearly empty blocks, the riders stream: together they take the longer of the two.
+// amax_parts (may be null): every rider also stores max |dst value it wrote| there, one word per rider with a plain store -- between
+// them the riders write all of dst, so the maximum of THIS launch's words is the weight's new amax record (a maximum: the same bits
+// for any partition).  The hot-row launch behind this one reads them (emb_bwd_hot_apply_kernel's riders).
 template <int LPR>
-__global__ __launch_bounds__(256) void emb_bwd_dups_apply_kernel(BwdSortedArgs a, drrs::TnRsApply ap, int grid_d) {
+__global__ __launch_bounds__(256) void emb_bwd_dups_apply_kernel(BwdSortedArgs a, drrs::TnRsApply ap, int grid_d,
+                                                                 uint32_t* __restrict__ amax_parts) {
     const int bid = blockIdx.x;
     if (bid < grid_d)
         emb_bwd_dups_body<LPR, false>(bid, grid_d, a.rows, a.slots, a.n, a.dup_heads, a.dup_count, a.F, a.D, a.num_rows, a.grad, a.ld,
@@ -433,8 +437,15 @@ __global__ __launch_bounds__(256) void emb_bwd_dups_apply_kernel(BwdSortedArgs a
                                       a.det != 0, a.amax);
     else if (bid == grid_d) {
         if (a.lin_bias != nullptr && a.d_fm_logit != nullptr) dr_block_sum_axpy(a.d_fm_logit, a.B, a.scale, a.lin_bias);
-    } else
-        drrs::tn_rs_reduce_ride(ap, bid - grid_d - 1, (int)gridDim.x - grid_d - 1, threadIdx.x);
+    } else {
+        const int rider = bid - grid_d - 1;
+        uint32_t m = drrs::tn_rs_reduce_ride(ap, rider, (int)gridDim.x - grid_d - 1, threadIdx.x);
+        if (amax_parts != nullptr) {                                      // (kernel-uniform: every thread of the block gets here)
+            __shared__ uint32_t wm[4];
+            m = drrs::block_max_256(m, wm, threadIdx.x);
+            if (threadIdx.x == 0) amax_parts[rider] = m;
+        }
+    }
 }
 
 // Second half of the deterministic hot-row update (SGD with x_sorted given): for every row whose slots span more than one piece,
@@ -447,15 +458,22 @@ __global__ __launch_bounds__(256) void emb_bwd_dups_apply_kernel(BwdSortedArgs a
 // first-order sum strides the segment with 64 lanes and is reduced by a fixed butterfly.  (A first version walked each hot row
 // with one lane group and a loop-carried `rows[j] == k` test: 275 dependent round trips for the hottest row of a Zipf batch,
 // +300 us per step.)
+// Blocks [grid_h, gridDim.x) are riders of a deferred plane refresh (tn_rs_reduce.h): the dense weight that the riders of the launch in
+// FRONT of this one stepped, and the per-rider maxima they stored, are final by stream order -- no hand-off inside the launch.  They
+// share nothing with the hot rows' blocks.  grid_h == gridDim.x: no riders; grid_h == 0: riders only (no parked pieces to combine).
 template <int LPR>
-__global__ __launch_bounds__(256) void emb_bwd_hot_apply_kernel(BwdSortedArgs a) {
+__global__ __launch_bounds__(256) void emb_bwd_hot_apply_kernel(BwdSortedArgs a, drrs::H2RefreshRide rf, int grid_h) {
+    if ((int)blockIdx.x >= grid_h) {
+        drrs::h2_split_both_block(rf, (int)blockIdx.x - grid_h, (int)gridDim.x - grid_h, threadIdx.x);
+        return;
+    }
     constexpr int NS = DR_WAVE / LPR;
     const int lane = threadIdx.x & 63, grp = lane / LPR, sub = lane % LPR;
     const int D = a.D, F = a.F;
     const bool dvalid = sub < (D >> 2);
     const int subc = dvalid ? sub : (D >> 2) - 1;
     const bool any_lin = a.lin_w != nullptr && (a.d_fm_logit != nullptr || a.slot_lin != nullptr);
-    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    const int64_t nwaves = (int64_t)grid_h * (blockDim.x >> 6);
     const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int64_t nheads = a.dup_count[0], n = a.dup_count[1];
     float wmax = 0.f;
@@ -558,7 +576,8 @@ static int bwd_sorted_impl(const int64_t* ids, const int64_t* row_base, const in
                            int64_t ld_grad, const float* concat, int64_t ld_concat, const float* sum_x,
                            const float* d_fm_logit, const float* slot_lin_grad, float scale, float* dst_table,
                            float* dst_lin, float* dst_bias, const AdamArgs* adam, float* x_sorted, dr_stream_t stream,
-                           int parts, const float* lin_old_t, uint32_t* table_amax, const drrs::TnRsApply* apply = nullptr) {
+                           int parts, const float* lin_old_t, uint32_t* table_amax, const drrs::TnRsApply* apply = nullptr,
+                           const drrs::H2RefreshRide* refresh = nullptr) {
     if (B < 0 || F <= 0 || F > 64 || D < 4 || D > 256 || (D & 3) || num_rows <= 0) return DR_EINVAL;
     const int64_t n = B * F;
     if (n == 0) return DR_OK;
@@ -591,10 +610,11 @@ static int bwd_sorted_impl(const int64_t* ids, const int64_t* row_base, const in
 #endif
     // riders of a deferred dense apply: one per logical reduce block, at most 1024 (a rider loops over what is left)
     const int nlb = apply != nullptr ? drrs::tn_rs_reduce_blocks(apply->F, apply->N, apply->vec) : 0;
-    const int riders = nlb < 1024 ? nlb : 1024;
+    const int riders = nlb < drrs::H2_REFRESH_MAX_PARTS ? nlb : drrs::H2_REFRESH_MAX_PARTS;
 #define LAUNCH(L, ADAM_)                                                                                              \
     { if (apply != nullptr) {                                                                                         \
-        hipLaunchKernelGGL((emb_bwd_dups_apply_kernel<L>), dim3(grid_d + 1 + riders), dim3(256), 0, dr_s(stream), ba, *apply, grid_d);     \
+        hipLaunchKernelGGL((emb_bwd_dups_apply_kernel<L>), dim3(grid_d + 1 + riders), dim3(256), 0, dr_s(stream), ba, *apply, grid_d,      \
+                           refresh != nullptr ? const_cast<uint32_t*>(refresh->parts) : nullptr);                     \
     } else {                                                                                                          \
         constexpr int NS_ = 64 / L;                                                                                   \
         constexpr int U_ = K4_U_OVERRIDE > 0 ? K4_U_OVERRIDE : (NS_ >= 16 ? 2 : 4);                                   \
@@ -617,10 +637,19 @@ static int bwd_sorted_impl(const int64_t* ids, const int64_t* row_base, const in
 #undef CALL
 #undef LAUNCH
     DR_CHECK_LAUNCH();
-    if (det && (parts & 2)) {
+    if ((det || refresh != nullptr) && (parts & 2)) {
         // deterministic hot rows: the pieces parked their sums in x_sorted, their owners add them up now (nothing to do when no row
-        // has more than CH slots: the kernel scans the head list and exits)
-#define HOT(L) hipLaunchKernelGGL((emb_bwd_hot_apply_kernel<L>), dim3(1024), dim3(256), 0, dr_s(stream), ba)
+        // has more than CH slots: the kernel scans the head list and exits).  Behind them the riders of a deferred plane refresh, as many
+        // blocks as dr_h2_refresh_weight's second launch; they reduce the words of the `riders` blocks of part 1.
+        const int grid_h = det ? 1024 : 0;
+        drrs::H2RefreshRide rf{};
+        int riders_s = 0;
+        if (refresh != nullptr) {
+            rf = *refresh;
+            rf.nparts = riders;
+            riders_s = dr_grid_for(2 * rf.R * (int64_t)rf.C, 256, 2048);
+        }
+#define HOT(L) hipLaunchKernelGGL((emb_bwd_hot_apply_kernel<L>), dim3(grid_h + riders_s), dim3(256), 0, dr_s(stream), ba, rf, grid_h)
         switch (lpr) {
             case 1: HOT(1); break;
             case 2: HOT(2); break;
@@ -678,6 +707,31 @@ extern "C" int dr_emb_pool_bwd_dups_apply(const int64_t* ids, const int64_t* row
                                           int32_t wg_N, int32_t wg_h2, float wg_scale, float* dstW, int64_t ld_w, float* dstb,
                                           dr_stream_t stream) {
     if (parts != 9 && parts != 11) return DR_EINVAL;
+    return dr_emb_pool_bwd_dups_apply_refresh(ids, row_base, sorted_rows, sorted_slots, unique_flags, dup_heads, dup_count, B, F, D, num_rows,
+                                              grad, ld_grad, sum_x, d_fm_logit, scale, dst_table, dst_lin, dst_bias, x_sorted, lin_old_t, parts,
+                                              table_amax, wg_workspace, wg_workspace_bytes, wg_R, wg_F, wg_N, wg_h2, wg_scale, dstW, ld_w, dstb,
+                                              nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr, stream);
+}
+
+// dr_emb_pool_bwd_dups_apply with the plane refresh of the weight it steps riding along (w_planes == NULL: none, the call above):
+// part 1's riders store max |dstW value written| per rider in amax_parts (plain stores), part 2 -- the hot rows' launch -- carries riders
+// that reduce the words of THAT launch, store the record w_amax and write both plane images of dstW [wg_F, wg_N]: the record and the
+// planes of dr_h2_refresh_weight(dstW) behind this call, bit for bit, without its two launches.  parts: 9, 10 or 11 (10: the hot rows'
+// launch alone, behind a call with 9 on the same stream).  Part 2 is launched for the riders even where the hot rows have nothing to do.
+extern "C" int dr_emb_pool_bwd_dups_apply_refresh(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
+                                                  const int32_t* sorted_slots, const uint8_t* unique_flags, const int32_t* dup_heads,
+                                                  const int32_t* dup_count, int64_t B, int32_t F, int32_t D, int64_t num_rows,
+                                                  const float* grad, int64_t ld_grad, const float* sum_x, const float* d_fm_logit, float scale,
+                                                  float* dst_table, float* dst_lin, float* dst_bias, float* x_sorted, const float* lin_old_t,
+                                                  int32_t parts, uint32_t* table_amax, void* wg_workspace, int64_t wg_workspace_bytes,
+                                                  int64_t wg_R, int32_t wg_F, int32_t wg_N, int32_t wg_h2, float wg_scale, float* dstW,
+                                                  int64_t ld_w, float* dstb, void* w_planes, int64_t w_plane_stride, int64_t w_ld,
+                                                  void* wt_planes, int64_t wt_plane_stride, int64_t wt_ld, uint32_t* w_amax,
+                                                  uint32_t* amax_parts, dr_stream_t stream) {
+    if (parts != 9 && parts != 11 && !(parts == 10 && w_planes != nullptr)) return DR_EINVAL;
+    if (w_planes != nullptr && (!wt_planes || !w_amax || !amax_parts || w_ld < wg_N || wt_ld < wg_F || w_plane_stride <= 0 ||
+                                wt_plane_stride <= 0))
+        return DR_EINVAL;
     if (wg_R <= 0 || wg_F <= 0 || wg_N <= 0 || !wg_workspace || !dstW || ld_w < wg_N) return DR_EINVAL;
     if (wg_workspace_bytes < dr_bf3_wgrad_workspace_bytes(wg_R, wg_F, wg_N)) return DR_EINVAL;
     if (B <= 0) return DR_EINVAL;                              // (an empty batch launches nothing: the apply would be lost)
@@ -685,9 +739,12 @@ extern "C" int dr_emb_pool_bwd_dups_apply(const int64_t* ids, const int64_t* row
     int64_t per;
     drrs::tn_rs_plan(wg_R, wg_F, wg_N, split, per, Fp, Np);
     const drrs::TnRsApply ap = drrs::tn_rs_apply_of(wg_workspace, split, wg_F, wg_N, Fp, Np, wg_h2 != 0, wg_scale, dstW, ld_w, dstb);
+    // (nparts is filled in by the launcher: the rider count of part 1, at most H2_REFRESH_MAX_PARTS)
+    const drrs::H2RefreshRide rf{dstW, ld_w, wg_F, wg_N, static_cast<_Float16*>(w_planes), w_plane_stride, w_ld,
+                                 static_cast<_Float16*>(wt_planes), wt_plane_stride, wt_ld, amax_parts, 0, w_amax};
     return bwd_sorted_impl(ids, row_base, sorted_rows, sorted_slots, unique_flags, dup_heads, dup_count, B, F, D, num_rows, grad, ld_grad,
                            nullptr, 0, sum_x, d_fm_logit, nullptr, scale, dst_table, dst_lin, dst_bias, nullptr, x_sorted, stream, parts,
-                           lin_old_t, table_amax, &ap);
+                           lin_old_t, table_amax, &ap, w_planes != nullptr ? &rf : nullptr);
 }
 
 // dst_lin[row_base[f] + ids[b, f]] += scale * (slot_lin_grad ? slot_lin_grad[b, f] : d_fm_logit[b])  for every slot whose row no other

@@ -245,7 +245,8 @@ class DeepFMEngine:
         self.prefetch_after_fwd = _pe == "2" and self.fuse_k3      # "2": behind the first GEMM, beside the tower tail
         # Fewer cross-stream packets in front of K4 (rocprofv3 showed a 31 us gap there against 11 - 13 us between the other
         # dependent kernels): the side chain is ordered behind the plane refresh instead of an event of its own, and the wait for
-        # a PREFETCHED plan -- long complete by then -- sits in front of the first-layer wgrad.
+        # a PREFETCHED plan -- long complete by then -- sits in front of the first-layer wgrad (in the fused backward, since the chain's
+        # tail may run beside the next forward: in front of the dgrad + K4, see ids_event_early below).
         # The early prefetch is ONE C call whose first kernel is K1 + field-major ids + composite keys + histogram (dr_hash_sort_slots).
         self._plan_prefetched = False
         if sorted_bwd:
@@ -322,8 +323,19 @@ class DeepFMEngine:
         # the words the main kernel saved in the workspace, not from the table's record, which K4 has raised by then.  Same partials,
         # same summation order: bit-identical steps (tests/test_gpu_folded_reduces.py).  DR_FOLD_REDUCES=0: the reduce as a launch of
         # its own behind the wgrad.  (The tower tail's reduce riding in the wgrad's main launch was measured too: DESIGN.md 3.5.)
-        self.fold_reduces = (os.environ.get("DR_FOLD_REDUCES", "1") != "0" and self.tail_in_fwd and self.fuse_k4 and self.h2
+        # "2" (default): the plane refresh rides too.  The riders that step W0 store max |W0| per rider; rider blocks behind the hot rows'
+        # launch reduce those words, store the record and write both images (ops.emb_pool_bwd_dups_apply(refresh=...)).  The refresh as two
+        # launches on a side stream behind the duplicate pass completed at about the hot rows' end, and the next forward started 18 - 25 us
+        # behind that cross-stream event instead of at the in-stream boundary.  Same record, same planes, and no ev_planes
+        # on this path.  "1": the refresh on the side stream as before.
+        _fr = os.environ.get("DR_FOLD_REDUCES", "2")
+        self.fold_reduces = (_fr != "0" and self.tail_in_fwd and self.fuse_k4 and self.h2
                              and optimizer == "sgd" and not self.overlap_dw and not self.reduce_side)
+        self.fold_planes = self.fold_reduces and _fr != "1"
+        # The next forward needs only ids / ids_t of the prefetched batch, which the chain's FIRST kernel writes: the early chain is issued
+        # in two parts with _ev_hashed between them, and the fused backward waits for _ev_sorted in front of the plan's first reader (the
+        # dgrad + K4) instead of in front of the wgrad.  DR_IDS_EVENT=0: both events behind the whole chain, the wait in front of the wgrad.
+        self.ids_event_early = os.environ.get("DR_IDS_EVENT", "1") != "0"
         self.concurrent = {}
         if self.overlap_dw:
             k4 = "emb_pool_bwd_adam" if optimizer == "adam" else "emb_pool_bwd"
@@ -447,10 +459,20 @@ class DeepFMEngine:
         with torch.cuda.stream(self.side):
             self.side.wait_event(self.ev_fwd0)
             # K1, the field-major ids and the plan as one chain of 6 launches (round 6: dr_hash_sort_slots; rounds 3 - 5: 27)
+            def chain(parts):
+                ops.hash_sort_slots(nk, self.col_buckets, self.row_base, self.R, self._ids[nxt],
+                                    self._ids_t[nxt] if self.no_concat else None, self._plans[nxt], parts=parts)
+
+            def chain_in_parts():
+                # the forward's event behind the launches that write the ids (hundreds of us before it is waited for: a free wait); the
+                # plan's tail may run on beside the next forward.  Buffer `nxt` is written by this stream alone, in stream order.
+                chain(1)
+                self._ev_hashed[nxt].record(self.side)
+                chain(2)
             self._k("next_batch: hash_sort_slots(side stream, overlapped)", "overlap", self.B * self.F * 52,
-                    lambda: ops.hash_sort_slots(nk, self.col_buckets, self.row_base, self.R, self._ids[nxt],
-                                                self._ids_t[nxt] if self.no_concat else None, self._plans[nxt]))
-            self._ev_hashed[nxt].record(self.side)
+                    chain_in_parts if self.ids_event_early else (lambda: chain(3)))
+            if not self.ids_event_early:
+                self._ev_hashed[nxt].record(self.side)
             self._ev_sorted[nxt].record(self.side)
         self._early_issued = True
 
@@ -574,7 +596,10 @@ class DeepFMEngine:
         else:
             if pref_tok is not None:
                 # a prefetch was issued for OTHER keys and is discarded: its side-stream copy of that batch's dense features into
-                # concat / dense_pad must be behind us before this forward writes its own
+                # concat / dense_pad must be behind us before this forward writes its own.  _ev_hashed, not _ev_sorted: the
+                # late prefetch records it behind that copy; the early chain copies on a stream of its own into the OTHER dense_pad.  The
+                # discarded chain's tail may still be writing _plans[cur ^ 1]: nothing on this stream touches that buffer -- this batch's
+                # own sort (_launch_sort) and the next chain are queued on `side` behind it.
                 torch.cuda.current_stream().wait_event(self._ev_hashed[self.cur ^ 1])
             self._k("hash_bucket_i64", "hbm", B * F * 16,
                     lambda: ops.hash_bucket_i64(keys, self.col_buckets, out=self.ids))                # K1
@@ -857,7 +882,8 @@ class DeepFMEngine:
         fused SGD step moves W0 but not the planes the dgrad reads) -> dgrad + K4's unique rows -> K4's duplicate pass, hot rows and
         first-order bias.  The plane refresh waits for the dgrad."""
         lr = self.lr
-        torch.cuda.current_stream().wait_event(self.ev_sorted)             # the plan's flags (long complete when prefetched)
+        if not self.ids_event_early:
+            torch.cuda.current_stream().wait_event(self.ev_sorted)         # the plan's flags (long complete when prefetched)
         fold = self.fold_reduces                  # the wgrad's reduce rides in the duplicate pass's launch: main launch only here
         self._k("linear_bwd_dw_L0", "mfma", fl, lambda: self._wgrad(0, x, dy, sc, dstW, dstb, main_only=fold))
         w_old = self.wplanes[0].w
@@ -883,6 +909,10 @@ class DeepFMEngine:
         mark = self._prefetch_mark()
         if early:
             self._prefetch_issue(mark)
+        if self.ids_event_early:
+            # the plan's first reader follows (the wgrad reads ids_t, not the plan).  The chain's tail may have run beside this step's
+            # forward: in front of the wgrad its event could be fresh, here it has had a wgrad's length to complete.
+            torch.cuda.current_stream().wait_event(self.ev_sorted)
         if not self._k4_det:
             ops.emb_snapshot_sorted_rows(self.plan, self.table, self.R, self.x_sorted)
         # bytes this kernel must move: SURVEY 8(d)'s K4 figure minus the 4FD read of d_concat that no longer exists, plus the dgrad's dy
@@ -894,15 +924,20 @@ class DeepFMEngine:
                                                    self.table, self.lin_w, self.lin_bias, sum_x=self.sum_x, x_sorted=self.x_sorted,
                                                    parts=parts | 8, lin_old_t=self.lin_old_t, table_amax=self.tab_amax)
         if fold:
-            # the duplicate pass's launch carries the wgrad's reduce + SGD step of W0 / b0; the planes follow behind it
-            self._k("emb_pool_bwd_dups", "hbm", 0,
-                    lambda: ops.emb_pool_bwd_dups_apply(self.ids, self.row_base, self.plan, self.D, self.R, self.d_concat, self.d_logit, -lr,
-                                                        self.table, self.lin_w, self.lin_bias, self.sum_x, self.x_sorted, self.lin_old_t,
-                                                        self.tab_amax, self.wg_ws[0], self.B, sc, dstW, dstb, wg_h2=True, parts=1))
-            refresh_planes_behind()
+            # the duplicate pass's launch carries the wgrad's reduce + SGD step of W0 / b0; the planes follow behind it -- as riders of the
+            # hot rows' launch (fold_planes: the bookkeeping of refresh() here, no stream, event or launch), or on the side stream
+            tgt = self.wplanes[0].hand_off() if self.fold_planes else None
+            dups = lambda parts: ops.emb_pool_bwd_dups_apply(self.ids, self.row_base, self.plan, self.D, self.R, self.d_concat, self.d_logit,
+                                                             -lr, self.table, self.lin_w, self.lin_bias, self.sum_x, self.x_sorted,
+                                                             self.lin_old_t, self.tab_amax, self.wg_ws[0], self.B, sc, dstW, dstb, wg_h2=True,
+                                                             parts=parts, refresh=tgt)
+            self._k("emb_pool_bwd_dups", "hbm", 0, lambda: dups(1))
+            if tgt is None:
+                refresh_planes_behind()
         else:
+            tgt = None
             self._k("emb_pool_bwd_dups", "hbm", 0, lambda: k4(1))
-        self._k("emb_hot_rows_apply", "hbm", 0, lambda: k4(2))
+        self._k("emb_hot_rows_apply", "hbm", 0, (lambda: dups(2)) if tgt is not None else (lambda: k4(2)))
         if not early:
             self._prefetch_issue(mark)
         self._k4_fused_done = True

@@ -598,9 +598,11 @@ def emb_sort_slots(ids, row_base, num_rows, plan=None):
     return plan
 
 
-def hash_sort_slots(keys, col_buckets, row_base, num_rows, ids_out, ids_t_out=None, plan=None):
+def hash_sort_slots(keys, col_buckets, row_base, num_rows, ids_out, ids_t_out=None, plan=None, parts=3):
     """hash_bucket_i64(keys -> ids_out) + ids_transpose_i32(ids_out -> ids_t_out, optional) + emb_sort_slots(ids_out) as one chain whose
-    first kernel does the work of the first four (dr_hash_sort_slots): same outputs, bit for bit."""
+    first kernel does the work of the first four (dr_hash_sort_slots): same outputs, bit for bit.
+    parts (dr_hash_sort_slots_parts): 1 = the launches that write ids_out / ids_t_out, 2 = the rest of the plan (same stream, same
+    arguments, nothing touching the plan in between), 3 = both."""
     keys = _c(keys, torch.int64)
     B, F = keys.shape
     assert ids_out.shape == (B, F) and ids_out.dtype == torch.int64 and ids_out.is_contiguous()
@@ -608,6 +610,12 @@ def hash_sort_slots(keys, col_buckets, row_base, num_rows, ids_out, ids_t_out=No
         assert ids_t_out.shape == (F, B) and ids_t_out.dtype == torch.int32 and ids_t_out.is_contiguous()
     if plan is None or plan.n < B * F:
         plan = SortPlan(B * F, keys.device)
+    if parts != 3:
+        check(lib().dr_hash_sort_slots_parts(ptr(keys), B, F, ptr(col_buckets), ptr(ids_out), ptr(ids_t_out), ptr(row_base), int(num_rows),
+                                             ptr(plan.rows), ptr(plan.slots), ptr(plan.flags), ptr(plan.dup_heads), ptr(plan.dup_count),
+                                             ptr(plan.workspace), plan.workspace.numel(), int(parts), stream_ptr()),
+              "dr_hash_sort_slots_parts")
+        return plan
     check(lib().dr_hash_sort_slots(ptr(keys), B, F, ptr(col_buckets), ptr(ids_out), ptr(ids_t_out), ptr(row_base), int(num_rows),
                                    ptr(plan.rows), ptr(plan.slots), ptr(plan.flags), ptr(plan.dup_heads), ptr(plan.dup_count),
                                    ptr(plan.workspace), plan.workspace.numel(), stream_ptr()), "dr_hash_sort_slots")
@@ -658,15 +666,27 @@ def emb_pool_bwd_sorted(ids, row_base, plan, D, num_rows, grad, d_fm_logit, scal
 
 
 def emb_pool_bwd_dups_apply(ids, row_base, plan, D, num_rows, grad, d_fm_logit, scale, dst_table, dst_lin, dst_bias, sum_x, x_sorted,
-                            lin_old_t, table_amax, wg_workspace, wg_R, wg_scale, dstW, dstb=None, wg_h2=True, parts=1):
+                            lin_old_t, table_amax, wg_workspace, wg_R, wg_scale, dstW, dstb=None, wg_h2=True, parts=1, refresh=None):
     """emb_pool_bwd_sorted(parts | 8) whose first launch also applies the first layer's wgrad (dr_emb_pool_bwd_dups_apply): extra blocks
     behind the duplicate pass run the fixed-order reduce of the product that part 1 of h2_wgrad_emb (or of bf3_wgrad_emb: wg_h2=False)
-    left in wg_workspace -- dstW += wg_scale * sum of the partials, dstb likewise.  parts: 1 or 3 (| 8 is implied)."""
+    left in wg_workspace -- dstW += wg_scale * sum of the partials, dstb likewise.  parts: 1 or 3 (| 8 is implied).
+    refresh: what H2WeightPlanes(dstW).hand_off() returned -- the plane refresh of dstW rides along (dr_emb_pool_bwd_dups_apply_refresh):
+    the amax words in part 1, record + both images in part 2, the hot rows' launch, which may then also be called alone (parts=2)."""
     ids = _c(ids, torch.int64)
     B, F = ids.shape
     wg_F, wg_N = dstW.shape
     assert grad.stride(1) == 1 and dstW.stride(1) == 1
     assert lin_old_t is None or (lin_old_t.shape == (F, B) and lin_old_t.is_contiguous() and lin_old_t.dtype == torch.float32)
+    if refresh is not None:
+        w, wt, amax, words = refresh
+        assert (w.rows, w.cols) == (wg_F, wg_N) and (wt.rows, wt.cols) == (wg_N, wg_F) and words.numel() >= 1024
+        check(lib().dr_emb_pool_bwd_dups_apply_refresh(
+            ptr(ids), ptr(row_base), ptr(plan.rows), ptr(plan.slots), ptr(plan.flags), ptr(plan.dup_heads), ptr(plan.dup_count), B, F, D,
+            int(num_rows), ptr(grad), grad.stride(0), ptr(sum_x), ptr(d_fm_logit), float(scale), ptr(dst_table), ptr(dst_lin), ptr(dst_bias),
+            ptr(x_sorted), ptr(lin_old_t), int(parts) | 8, ptr(table_amax), ptr(wg_workspace), wg_workspace.numel() * 4, int(wg_R), wg_F,
+            wg_N, 1 if wg_h2 else 0, float(wg_scale), ptr(dstW), dstW.stride(0), ptr(dstb), ptr(w.buf), w.plane_stride, w.ld, ptr(wt.buf),
+            wt.plane_stride, wt.ld, ptr(amax), ptr(words), stream_ptr()), "dr_emb_pool_bwd_dups_apply_refresh")
+        return
     check(lib().dr_emb_pool_bwd_dups_apply(ptr(ids), ptr(row_base), ptr(plan.rows), ptr(plan.slots), ptr(plan.flags), ptr(plan.dup_heads),
                                            ptr(plan.dup_count), B, F, D, int(num_rows), ptr(grad), grad.stride(0), ptr(sum_x),
                                            ptr(d_fm_logit), float(scale), ptr(dst_table), ptr(dst_lin), ptr(dst_bias), ptr(x_sorted),
@@ -1523,7 +1543,24 @@ class H2WeightPlanes:
         self.w = H2Planes(K, N, W.device, self.amax)
         self._w_alt = H2Planes(K, N, W.device, h2_record(W.device)) if double_buffer else None
         self._parts = None
+        self._ride_words = None
         self.refresh()
+
+    def _swap(self):
+        if self._w_alt is not None:
+            self.w, self._w_alt = self._w_alt, self.w
+            self.amax = self.w.amax
+            self.wt.amax = self.amax
+
+    def hand_off(self):
+        """refresh()'s bookkeeping without its launches: the image swap, the record pointers and the version stamp, for a caller whose own
+        launch on the current stream writes the record and both images (ops.emb_pool_bwd_dups_apply(refresh=...)) before anything reads
+        them.  Returns (w, wt, record, 1024 words of scratch for that launch)."""
+        if self._ride_words is None:
+            self._ride_words = torch.zeros(1024, dtype=torch.int32, device=self.W.device)
+        self._swap()
+        self._ver = self.W._version
+        return self.w, self.wt, self.amax, self._ride_words
 
     def refresh(self):
         # record + both images in two launches (dr_h2_refresh_weight: no memset, no atomic pass; same record, same planes as
@@ -1531,10 +1568,7 @@ class H2WeightPlanes:
         if self._parts is None:
             self._parts = torch.zeros(256, dtype=torch.int32, device=self.W.device)
         K, N = self.W.shape
-        if self._w_alt is not None:
-            self.w, self._w_alt = self._w_alt, self.w
-            self.amax = self.w.amax
-            self.wt.amax = self.amax
+        self._swap()
         check(lib().dr_h2_refresh_weight(ptr(self.W), self.W.stride(0), K, N, ptr(self.w.buf), self.w.plane_stride, self.w.ld,
                                          ptr(self.wt.buf), self.wt.plane_stride, self.wt.ld, ptr(self.amax), ptr(self._parts),
                                          stream_ptr()), "dr_h2_refresh_weight")

@@ -197,6 +197,14 @@ int dr_hash_sort_slots(const int64_t* keys, int64_t B, int32_t F, const uint64_t
                        int32_t* ids_t_out, const int64_t* row_base, int64_t num_rows, int64_t* sorted_rows,
                        int32_t* sorted_slots, uint8_t* unique_flags, int32_t* dup_heads, int32_t* dup_count, void* workspace,
                        int64_t workspace_bytes, dr_stream_t stream);
+/* dr_hash_sort_slots issued in two parts on ONE stream, for a caller that records an event between them (the next forward needs only the
+ * ids; the plan has one reader, K4).  parts & 1: every launch that writes ids_out / ids_t_out (the fused front kernel; in the fallback
+ * geometries dr_hash_bucket_i64 + dr_ids_transpose_i32).  parts & 2: the rest of the plan; it reads what part 1 left in ids_out, sorted_rows
+ * and the workspace, which nothing may touch in between.  parts == 3: dr_hash_sort_slots, launch for launch. */
+int dr_hash_sort_slots_parts(const int64_t* keys, int64_t B, int32_t F, const uint64_t* col_buckets, int64_t* ids_out,
+                             int32_t* ids_t_out, const int64_t* row_base, int64_t num_rows, int64_t* sorted_rows,
+                             int32_t* sorted_slots, uint8_t* unique_flags, int32_t* dup_heads, int32_t* dup_count, void* workspace,
+                             int64_t workspace_bytes, int32_t parts, dr_stream_t stream);
 int dr_emb_pool_bwd_sorted(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
                            const int32_t* sorted_slots, const uint8_t* unique_flags,
                            const int32_t* dup_heads, const int32_t* dup_count, int64_t B, int32_t F,
@@ -805,6 +813,22 @@ int dr_emb_pool_bwd_dups_apply(const int64_t* ids, const int64_t* row_base, cons
                                const float* lin_old_t, int32_t parts, uint32_t* table_amax, void* wg_workspace,
                                int64_t wg_workspace_bytes, int64_t wg_R, int32_t wg_F, int32_t wg_N, int32_t wg_h2, float wg_scale,
                                float* dstW, int64_t ld_w, float* dstb, dr_stream_t stream);
+/* dr_emb_pool_bwd_dups_apply with the f16x2 plane refresh of the weight it steps riding along, without a launch or a stream of its own:
+ * the riders of part 1 also store max |dstW value written| in amax_parts (one uint32 per rider, <= 1024, plain stores); part 2 -- the hot
+ * rows' launch -- carries rider blocks that reduce the words of that launch, store the record w_amax and write both plane images of dstW
+ * [wg_F, wg_N] (w_planes [2][wg_F][w_ld], wt_planes [2][wg_N][wt_ld]): what dr_h2_refresh_weight(dstW, ...) behind the call gives, bit for
+ * bit.  Stream order makes dstW and the words final for part 2: no hand-off inside a launch.  parts: 9, 10 (part 2 alone, behind a call
+ * with 9 on the same stream) or 11; part 2 is launched for its riders even when no hot row exists.  w_planes == NULL: no refresh (parts 9
+ * or 11), dr_emb_pool_bwd_dups_apply itself.  amax_parts: 1024 uint32 of scratch. */
+int dr_emb_pool_bwd_dups_apply_refresh(const int64_t* ids, const int64_t* row_base, const int64_t* sorted_rows,
+                                       const int32_t* sorted_slots, const uint8_t* unique_flags, const int32_t* dup_heads,
+                                       const int32_t* dup_count, int64_t B, int32_t F, int32_t D, int64_t num_rows, const float* grad,
+                                       int64_t ld_grad, const float* sum_x, const float* d_fm_logit, float scale, float* dst_table,
+                                       float* dst_lin, float* dst_bias, float* x_sorted, const float* lin_old_t, int32_t parts,
+                                       uint32_t* table_amax, void* wg_workspace, int64_t wg_workspace_bytes, int64_t wg_R, int32_t wg_F,
+                                       int32_t wg_N, int32_t wg_h2, float wg_scale, float* dstW, int64_t ld_w, float* dstb,
+                                       void* w_planes, int64_t w_plane_stride, int64_t w_ld, void* wt_planes, int64_t wt_plane_stride,
+                                       int64_t wt_ld, uint32_t* w_amax, uint32_t* amax_parts, dr_stream_t stream);
 
 
 /* ------------------------------------------------------------------------------------------
