@@ -8,3 +8,6 @@ from deep_recommenders_amd.keras.models.retrieval.skipgram import DeepWalk
 from deep_recommenders_amd.keras.models.retrieval.eges import EGES
 from deep_recommenders_amd.keras.models.retrieval.eges import graph_from_sessions
 from deep_recommenders_amd.keras.models.retrieval.airbnb import Airbnb
+from deep_recommenders_amd.keras.models.retrieval.graphsage import SAGEConv
+from deep_recommenders_amd.keras.models.retrieval.graphsage import GraphSAGE
+from deep_recommenders_amd.keras.models.retrieval.graphsage import PinSage

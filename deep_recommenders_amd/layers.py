@@ -686,6 +686,74 @@ def aggregate(adj, X):
     return _DenseAggFn.apply(X, adj)
 
 
+class SampledBlock:
+    """One layer of a sampled mini-batch: adj, a SparseAdjacency [n_dst, n_src] whose rows sum to 1, over the nodes src_ids int64
+    [n_src] (on the device); its first n_dst entries are the block's destination nodes, so h[:n_dst] are their own rows."""
+    __slots__ = ("adj", "src_ids", "n_dst")
+
+    def __init__(self, adj, src_ids, n_dst):
+        self.adj, self.src_ids, self.n_dst = adj, src_ids, n_dst
+
+    @property
+    def n_src(self):
+        return self.adj.shape[1]
+
+
+def _layer_seed(seed, k):
+    """the seed of layer k's draws: layers must not share one (a node's sample is a function of (seed, node))"""
+    return (int(seed) + 0x9E3779B97F4A7C15 * (k + 1)) & (2 ** 64 - 1)
+
+
+def sample_blocks(adjacency, seeds, fanouts, seed, importance=None, add_self=False):
+    """The blocks of a mini-batch of seed nodes for a len(fanouts)-layer network, outermost (input) layer first: blocks[k] aggregates
+    layer k's input rows, blocks[0].src_ids are the nodes whose raw features are read and blocks[-1]'s destinations are the seeds.
+    Layer k keeps up to fanouts[k] neighbours per node: uniformly without replacement (dr_neighbor_sample, GraphSAGE), or, with
+    importance = dict(num_walks=R, walk_length=L), the most visited nodes of R random walks of L nodes from it, weighted by their visit
+    counts (dr_random_walk + dr_walk_neighbors, PinSage).  add_self puts every destination into its own row (the `gcn` aggregator).
+    The whole chain -- sample, frontier, block CSR, per layer, innermost first -- runs on the device over buffers of the largest size
+    the fanouts allow; ONE device-to-host copy per call, at the end, reads every layer's counts (destinations, sources, entries) and
+    the blocks are views of those buffers.  The result is a function of (seed, seeds, graph) alone.  No gradient reaches a block."""
+    if not isinstance(adjacency, SparseAdjacency):
+        raise TypeError("sample_blocks: adjacency must be a SparseAdjacency (build it once per graph)")
+    fanouts = [int(f) for f in fanouts]
+    if not fanouts:
+        raise ValueError("sample_blocks: fanouts must name at least one layer")
+    for f in fanouts:
+        if not 1 <= f <= ops.SAMPLE_MAX_FANOUT:
+            raise ValueError("sample_blocks: every fanout must be in [1, %d], got %s" % (ops.SAMPLE_MAX_FANOUT, fanouts))
+    R = Lw = None
+    if importance is not None:
+        R, Lw = int(importance["num_walks"]), int(importance["walk_length"])
+        if R < 1 or Lw < 2 or R * (Lw - 1) > ops.WALK_MAX_VISITS:
+            raise ValueError("sample_blocks: importance needs num_walks >= 1, walk_length >= 2 and num_walks (walk_length - 1) <= %d, got %s"
+                             % (ops.WALK_MAX_VISITS, dict(importance)))
+    dst = torch.as_tensor(seeds)
+    if dst.dtype != torch.int64 or dst.dim() != 1:
+        raise ValueError("sample_blocks: seeds must be int64 [B], got %s %s" % (dst.dtype, tuple(dst.shape)))
+    dst = dst.to(adjacency.device).contiguous()
+    n_rows = adjacency.shape[0]
+    made = []
+    for k in reversed(range(len(fanouts))):
+        s = _layer_seed(seed, k)
+        if importance is None:
+            nbr, cnt = ops.neighbor_sample(adjacency.row_ptr, adjacency.col, n_rows, dst, fanouts[k], s)
+            weight = None
+        else:
+            walks = ops.random_walk(adjacency.row_ptr, adjacency.col, n_rows, dst.repeat_interleave(R), Lw, s)
+            nbr, weight, cnt = ops.walk_neighbors(walks.view(-1, R, Lw), fanouts[k])
+        src, counts, local = ops.frontier_build(dst, nbr, id_bound=n_rows)
+        row_ptr, col, val = ops.block_csr(cnt, local, weight, add_self=add_self, n_valid=counts[:1])
+        made.append((src, counts, row_ptr, col, val))
+        dst = src
+    sizes = torch.cat([torch.cat((counts, row_ptr[-1:])) for _, counts, row_ptr, _, _ in made]).cpu().tolist()    # the one read-back
+    blocks = []
+    for j, (src, _, row_ptr, col, val) in enumerate(made):
+        n_dst, n_src, nnz = sizes[3 * j: 3 * j + 3]
+        adj = SparseAdjacency._from_device(row_ptr[:n_dst + 1], col[:nnz], val[:nnz], (n_dst, n_src))
+        blocks.append(SampledBlock(adj, src[:n_src], n_dst))
+    return blocks[::-1]
+
+
 class _SoftmaxRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

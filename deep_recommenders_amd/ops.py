@@ -3171,3 +3171,121 @@ def eges_embed(side_table, row_base, side_ids, att=None, att_ids=None, out=None)
     _status(lib().dr_eges_embed(ptr(side_table), D, ptr(row_base), ptr(side_ids), S, ptr(att), ld_att, ptr(att_ids), n, ptr(out), ld_out,
                                 stream_ptr()), "dr_eges_embed")
     return out
+
+
+# ---- sampled graph blocks: GraphSAGE / PinSage (csrc/neighbor_sample.hip) ----------------------------------------------------------------
+SAMPLE_LONG_ROW = 512      # DR_SAMPLE_LONG_ROW: a row with more edges is selected by a whole block (radix select), a shorter one by a wave
+SAMPLE_MAX_FANOUT = 64     # the largest fanout of dr_neighbor_sample / dr_block_csr and the largest T of dr_walk_neighbors
+WALK_MAX_VISITS = 1024     # dr_walk_neighbors: R (L - 1) at most
+
+
+def _block_one_device(family, dev, **tensors):
+    """every tensor a sampling call is handed lives on one device"""
+    for what, t in tensors.items():
+        if t is not None and t.device != dev:
+            raise ValueError("%s: %s is on %s, the call's first tensor on %s; one call takes tensors of one device" % (family, what, t.device, dev))
+
+
+def _fanout_arg(family, what, fanout):
+    fanout = int(fanout)
+    if not 1 <= fanout <= SAMPLE_MAX_FANOUT:
+        raise ValueError("%s: %s must be in [1, %d], got %d" % (family, what, SAMPLE_MAX_FANOUT, fanout))
+    return fanout
+
+
+def neighbor_sample(row_ptr, col, n_rows, nodes, fanout, seed):
+    """(nbr int64 [n, fanout], cnt int32 [n]) of dr_neighbor_sample over the CSR graph (row_ptr int64 [n_rows + 1], col int32 [nnz]):
+    up to `fanout` neighbours of every node of nodes int64 [n], uniformly without replacement, in CSR order, -1 to the end of the row.
+    A node outside [0, n_rows) (-1 is the padding of a node list) has none.  The sample of a node depends on (seed, node) alone."""
+    n_rows = int(n_rows)
+    fanout = _fanout_arg("neighbor_sample", "fanout", fanout)
+    row_ptr = _dense_arg(row_ptr, "neighbor_sample: row_ptr", torch.int64, shape=(n_rows + 1,))
+    if col.dim() != 1:
+        raise ValueError("neighbor_sample: col must be int32 [nnz], got %s %s" % (col.dtype, tuple(col.shape)))
+    col = _dense_arg(col, "neighbor_sample: col", torch.int32)
+    if nodes.dim() != 1:
+        raise ValueError("neighbor_sample: nodes must be int64 [n], got %s %s" % (nodes.dtype, tuple(nodes.shape)))
+    nodes = _dense_arg(nodes, "neighbor_sample: nodes", torch.int64)
+    _block_one_device("neighbor_sample", row_ptr.device, col=col, nodes=nodes)
+    n = nodes.numel()
+    nbr = torch.empty((n, fanout), dtype=torch.int64, device=nodes.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=nodes.device)
+    if n == 0:
+        return nbr, cnt
+    _status(lib().dr_neighbor_sample(ptr(row_ptr), ptr(col) if col.numel() else None, n_rows, ptr(nodes), n, fanout,
+                                     int(seed) & (2 ** 64 - 1), ptr(nbr), ptr(cnt), stream_ptr()), "dr_neighbor_sample")
+    return nbr, cnt
+
+
+def walk_neighbors(walks, num_neighbors):
+    """(nbr int64 [n, T], weight fp32 [n, T], cnt int32 [n]) of dr_walk_neighbors: walks int64 [n, R, L] holds R walks of L nodes from
+    each of n starts (random_walk over the starts repeated R times, viewed [n, R, L]); the T = num_neighbors most visited ids of each
+    start, by (visits descending, id ascending), with their visit counts as weights; -1 / 0 to the end of a row."""
+    T = _fanout_arg("walk_neighbors", "num_neighbors", num_neighbors)
+    if walks.dim() != 3:
+        raise ValueError("walk_neighbors: walks must be int64 [n, R, L], got %s %s" % (walks.dtype, tuple(walks.shape)))
+    walks = _dense_arg(walks, "walk_neighbors: walks", torch.int64)
+    n, R, L = walks.shape
+    if R < 1 or L < 1 or R * (L - 1) > WALK_MAX_VISITS:
+        raise ValueError("walk_neighbors: walks [n, R, L] needs R >= 1, L >= 1 and R (L - 1) <= %d, got R = %d, L = %d" % (WALK_MAX_VISITS, R, L))
+    nbr = torch.empty((n, T), dtype=torch.int64, device=walks.device)
+    weight = torch.empty((n, T), dtype=torch.float32, device=walks.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=walks.device)
+    if n == 0:
+        return nbr, weight, cnt
+    _status(lib().dr_walk_neighbors(ptr(walks), n, R, L, T, ptr(nbr), ptr(weight), ptr(cnt), stream_ptr()), "dr_walk_neighbors")
+    return nbr, weight, cnt
+
+
+def frontier_build(dst, nbr, id_bound=0):
+    """(src int64 [n_dst + m], counts int64 [2] on the device, local int32 like nbr) of dr_frontier_build: dst int64 [n_dst] is a node
+    list (valid ids first, -1 padding after them), nbr int64 (any shape, m elements, -1 = none) the neighbours sampled for it.
+    src = dst's valid prefix, then the ids of nbr that dst does not hold in ascending order, then -1; counts = (valid dst entries, valid
+    src entries); local = where each nbr entry sits in src (-1 for none).  id_bound > 0 promises ids < id_bound (fewer sort passes).
+    Nothing is read back: src is the next layer's dst."""
+    if dst.dim() != 1:
+        raise ValueError("frontier_build: dst must be int64 [n_dst], got %s %s" % (dst.dtype, tuple(dst.shape)))
+    dst = _dense_arg(dst, "frontier_build: dst", torch.int64)
+    nbr = _dense_arg(nbr, "frontier_build: nbr", torch.int64)
+    _block_one_device("frontier_build", dst.device, nbr=nbr)
+    n_dst, m = dst.numel(), nbr.numel()
+    if n_dst + m >= 2 ** 31:
+        raise ValueError("frontier_build: dst and nbr together must stay below 2^31 entries, got %d" % (n_dst + m))
+    dev = dst.device
+    src = torch.empty((n_dst + m,), dtype=torch.int64, device=dev)
+    counts = torch.zeros((2,), dtype=torch.int64, device=dev)
+    local = torch.empty(nbr.shape, dtype=torch.int32, device=dev)
+    if n_dst + m == 0:
+        return src, counts, local
+    ws = torch.empty(max(1, lib().dr_frontier_workspace_bytes(n_dst, m)), dtype=torch.uint8, device=dev)
+    _status(lib().dr_frontier_build(ptr(dst) if n_dst else None, n_dst, ptr(nbr) if m else None, m, int(id_bound), ptr(src), ptr(counts),
+                                    ptr(local) if m else None, ptr(ws), ws.numel(), stream_ptr()), "dr_frontier_build")
+    return src, counts, local
+
+
+def block_csr(cnt, local, weight=None, add_self=False, n_valid=None):
+    """(row_ptr int64 [n_dst + 1], col int32, val fp32, both [n_dst (fanout + add_self)]) of dr_block_csr: the CSR of a sampled block
+    from cnt int32 [n_dst] and local int32 [n_dst, fanout] (frontier_build's), rows normalised to sum 1 (the mean; with weight fp32
+    [n_dst, fanout] the weighted mean; add_self puts the row's own index first at weight 1).  n_valid: a one-element int64 device tensor,
+    the number of rows that are not padding (rows beyond it are empty); None: all.  Only the first row_ptr[n_dst] entries of col / val
+    are written."""
+    if local.dim() != 2:
+        raise ValueError("block_csr: local must be int32 [n_dst, fanout], got %s %s" % (local.dtype, tuple(local.shape)))
+    n_dst, fanout = local.shape
+    fanout = _fanout_arg("block_csr", "fanout (local.shape[1])", fanout)
+    local = _dense_arg(local, "block_csr: local", torch.int32)
+    cnt = _dense_arg(cnt, "block_csr: cnt", torch.int32, shape=(n_dst,))
+    weight = _dense_arg(weight, "block_csr: weight", torch.float32, shape=(n_dst, fanout))
+    n_valid = _dense_arg(n_valid, "block_csr: n_valid", torch.int64, numel=1)
+    dev = local.device
+    _block_one_device("block_csr", dev, cnt=cnt, weight=weight, n_valid=n_valid)
+    extra = 1 if add_self else 0
+    row_ptr = torch.zeros((n_dst + 1,), dtype=torch.int64, device=dev)
+    col = torch.empty((max(1, n_dst * (fanout + extra)),), dtype=torch.int32, device=dev)
+    val = torch.empty((max(1, n_dst * (fanout + extra)),), dtype=torch.float32, device=dev)
+    if n_dst == 0:
+        return row_ptr, col[:0], val[:0]
+    ws = torch.empty(max(1, lib().dr_block_csr_workspace_bytes(n_dst)), dtype=torch.uint8, device=dev)
+    _status(lib().dr_block_csr(ptr(cnt), ptr(local), ptr(weight), n_dst, fanout, extra, ptr(n_valid), ptr(row_ptr), ptr(col), ptr(val),
+                               ptr(ws), ws.numel(), stream_ptr()), "dr_block_csr")
+    return row_ptr, col, val

@@ -1286,6 +1286,58 @@ int dr_softmax_rows_bwd(const float* y, int64_t ld_y, const float* dy, int64_t l
 int dr_cce_prob_rows(const float* p, int64_t ld_p, const float* labels, int64_t ld_labels, int64_t B, int32_t C,
                      const float* sample_weight, float* row_loss, float* grad, int64_t ld_grad, dr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sampled graph blocks: GraphSAGE (Hamilton et al., NeurIPS 2017) and PinSage (Ying et al., KDD 2018), which the reference's README
+ * lists and ships no code for; csrc/neighbor_sample.hip.  Integer kernels (one fp32 division per edge in dr_block_csr), counter-based
+ * on dr_mix32 (spelled out at dr_attn_fwd): an output is a function of (seed, inputs) alone, never of the launch, the grid or the run.
+ * The graph is a CSR as dr_csr_spmm takes it (row_ptr int64 [n_rows + 1], col int32).  Node lists are int64 with -1 for "none".
+ *   dr_neighbor_sample   nbr [n, fanout] int64, cnt [n] int32.  For i < n: v = nodes[i]; v < 0 or v >= n_rows: cnt[i] = 0, the row of
+ *                     nbr is all -1 and nothing is dereferenced.  Otherwise lo = row_ptr[v], hi = row_ptr[v + 1], deg = hi - lo.
+ *                       deg <= fanout: nbr[i, :] = col[lo .. hi) in CSR order, then -1; cnt[i] = deg.
+ *                       deg >  fanout: edge e in [lo, hi) has the key (uint64(dr_mix32(seed, e)) << 32) | uint64(e - lo); the fanout
+ *                                      edges with the smallest keys are taken (the keys are distinct: the set is unique) and col[e] of
+ *                                      them is written in ascending e; cnt[i] = fanout.
+ *                     Uniform without replacement under a uniform hash; the sample of v does not depend on where v sits in nodes.
+ *                     1 <= fanout <= 64.  Rows of up to DR_SAMPLE_LONG_ROW (512) edges are selected by one wave, longer ones by a
+ *                     whole block (a radix select on the hash): the same result either way.  col may be NULL for a graph without edges.
+ *   dr_walk_neighbors PinSage's importance neighbours.  walks [n, R, L] int64 is dr_random_walk's output for every node repeated R
+ *                     times as start (walks[i, r, 0] is the node).  For start i: every id in walks[i, :, 1:] that is >= 0 and differs
+ *                     from walks[i, 0, 0] is a visit; the distinct visited ids are ordered by (visits descending, id ascending) and the
+ *                     first T of them are written to nbr [n, T] int64 with weight [n, T] fp32 = visits (a small integer, exact); the
+ *                     rest of both rows is -1 and 0; cnt[i] = the number kept.  R (L - 1) <= 1024, 1 <= T <= 64, R >= 1, L >= 1.
+ *   dr_frontier_build the next layer's node list.  dst [n_dst] int64: valid ids (>= 0) form a prefix, -1 a suffix of padding.
+ *                     nbr [m] int64, -1 = none.  id_bound > 0 is the caller's promise that every id is < id_bound (the number of graph
+ *                     nodes: it sets the number of sort passes; an id >= id_bound in nbr is treated as none); id_bound <= 0: any id
+ *                     < 2^63 - 1.  Outputs: counts [2] int64 on the device, src [n_dst + m] int64, local [m] int32.
+ *                       counts[0] = the number of valid dst entries; src[0 .. counts[0]) = that prefix verbatim;
+ *                       src[counts[0] .. counts[1]) = the distinct ids of nbr that occur nowhere in dst, in ascending id order;
+ *                       src[counts[1] ..) = -1;  local[j] = the index in src of nbr[j] -- for an id that dst holds several times, the
+ *                       lowest such index -- and -1 where nbr[j] is none.
+ *                     No host reads: src is a valid `nodes` / `dst` of the next layer.  n_dst + m < 2^31.  workspace >=
+ *                     dr_frontier_workspace_bytes(n_dst, m) bytes.  m == 0 with n_dst > 0 still writes src and counts.
+ *   dr_block_csr      the CSR of one block.  cnt [n_dst] int32 (clamped to [0, fanout]), local [n_dst, fanout] int32, weight
+ *                     [n_dst, fanout] fp32 or NULL (all 1).  n_valid: a device pointer to the number of valid rows (dr_frontier_build's
+ *                     counts[0] of the layer whose src these rows are), or NULL for n_dst.  len(r) = cnt[r] + add_self for r < *n_valid,
+ *                     0 beyond; row_ptr [n_dst + 1] int64 = the exclusive scan of len.  Row r holds, with add_self, first (r, weight 1),
+ *                     then (local[r, k], w_k) for k < cnt[r] in that order, w_k = weight[r, k] or 1;  S = the fp32 sum of the row's
+ *                     weights taken in that order starting from 0 (with add_self: from the self weight 1);  val = w / S, one fp32
+ *                     division per entry.  col / val need room for n_dst (fanout + add_self) entries.  add_self is 0 or 1;
+ *                     1 <= fanout <= 64; workspace >= dr_block_csr_workspace_bytes(n_dst) bytes.
+ *   A size of 0 (n, or n_dst + m, or n_dst) is DR_OK and launches nothing; a negative size, a NULL required pointer, a parameter outside
+ *   its range or a workspace that is too small is DR_EINVAL.
+ * ---------------------------------------------------------------------------------------- */
+int dr_neighbor_sample(const int64_t* row_ptr, const int32_t* col, int64_t n_rows, const int64_t* nodes, int64_t n, int32_t fanout,
+                       uint64_t seed, int64_t* nbr, int32_t* cnt, dr_stream_t stream);
+int dr_walk_neighbors(const int64_t* walks, int64_t n, int32_t R, int32_t L, int32_t T, int64_t* nbr, float* weight, int32_t* cnt,
+                      dr_stream_t stream);
+int64_t dr_frontier_workspace_bytes(int64_t n_dst, int64_t m);
+int dr_frontier_build(const int64_t* dst, int64_t n_dst, const int64_t* nbr, int64_t m, int64_t id_bound, int64_t* src, int64_t* counts,
+                      int32_t* local, void* workspace, int64_t workspace_bytes, dr_stream_t stream);
+int64_t dr_block_csr_workspace_bytes(int64_t n_dst);
+int dr_block_csr(const int32_t* cnt, const int32_t* local, const float* weight, int64_t n_dst, int32_t fanout, int32_t add_self,
+                 const int64_t* n_valid, int64_t* row_ptr, int32_t* col, float* val, void* workspace, int64_t workspace_bytes,
+                 dr_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------
  * Transformer package (keras/models/nlp/ of the reference), csrc/attention.hip.
  *
