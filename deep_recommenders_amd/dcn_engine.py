@@ -29,40 +29,46 @@ class DCNDense:
     (ops.get_gemm_split(): "f16x2" -- three matrix instructions per fragment pair, every activation operand with its amax record: x0's
     from one dr_h2_amax pass, every later one from the epilogue of the kernel that produces it -- or "bf16x3")."""
 
-    def __init__(self, cross_W, cross_b, Ws, bs, batch, in_dim, ld, diag_scale, device, grads=None, k=None):
+    def __init__(self, cross_W, cross_b, Ws, bs, batch, in_dim, ld, diag_scale, device, grads=None, k=None, prims=None):
+        """prims: None = the HIP kernels (ops); anything else (the CPU tests' oracle-backed primitives) provides linear_fwd /
+        linear_bwd_dx / linear_bwd_dw / cross_fwd / cross_combine_bwd / bce_fwd_bwd, and every product then runs in the plain family:
+        no planes, no workspaces, no call into the library."""
         self.cross_W, self.cross_b, self.Ws, self.bs = list(cross_W), list(cross_b), list(Ws), list(bs)
         self.B, self.in_dim, self.ld, self.diag = batch, in_dim, ld, diag_scale
         self.grads = grads
+        self.p = prims if prims is not None else ops
         self._k = k if k is not None else (lambda name, bound, work, fn: fn())
         B = batch
         units = [W.shape[1] for W in self.Ws]
         self.acts = [1] * (len(units) - 1) + [0]
         f32 = dict(dtype=torch.float32, device=device)
-        wide_cross = ops.planes_worthwhile(B, in_dim, in_dim)
+        native = prims is None and torch.device(device).type == "cuda"
+        wide_cross = native and ops.planes_worthwhile(B, in_dim, in_dim)
+        wide = [native and u > 1 and ops.planes_worthwhile(B, W.shape[0], W.shape[1]) for W, u in zip(self.Ws, units)]
         self.h2 = wide_cross and ops.get_gemm_split() == "f16x2"
         self.h2_all_wide = self.h2                               # (bench.py: every planes GEMM of this engine is priced as f16x2)
         WP = ops.H2WeightPlanes if self.h2 else ops.WeightPlanes
-        self.cross_planes = [WP(W) if wide_cross else None for W in self.cross_W]
-        self.wplanes = [WP(W) if u > 1 and ops.planes_worthwhile(B, W.shape[0], W.shape[1]) else None
-                        for W, u in zip(self.Ws, units)]
-        if self.h2:
-            rec = lambda: ops.h2_record(device)
-            self.x_amax = [rec() for _ in range(len(self.cross_W) + 1)]   # x_0 .. x_L
-            self.h_amax = [rec() for _ in units]                          # MLP activations h_i
-            self.dh_amax = [rec() for _ in units]                         # their gradients (dy of layer i)
-            self.dp_amax = rec()                                          # d_prod of the cross layer being differentiated
+        # wide layers: the register-split wgrad (dr_bf3_wgrad / dr_h2_wgrad) on the same condition as the planes forward / dgrad
+        self.wg_ws = [ops.bf3_wgrad_workspace(B, W.shape[0], W.shape[1], device) if wd else None for W, wd in zip(self.Ws, wide)]
+        self.cross_wg_ws = ops.bf3_wgrad_workspace(B, in_dim, in_dim, device) if wide_cross else None
+        self.cross_planes = [WP(W, wgrad_ws=self.cross_wg_ws) if wide_cross else None for W in self.cross_W]
+        self.wplanes = [WP(W, wgrad_ws=ws) if wd else None for W, wd, ws in zip(self.Ws, wide, self.wg_ws)]
+        # the GEMM family of every product, decided here once: the planes object, or the plain family on `prims`
+        dw_ws = lambda K, N: ops.linear_bwd_dw_workspace(B, K, N, device) if native else None
+        cross_ws = None if wide_cross else dw_ws(in_dim, in_dim)
+        self.cross_gemm = [wp if wp is not None else ops.PlainWeight(W, prims, cross_ws) for W, wp in zip(self.cross_W, self.cross_planes)]
+        self.gemm = [wp if wp is not None else ops.PlainWeight(W, prims, dw_ws(*W.shape)) for W, wp in zip(self.Ws, self.wplanes)]
+        rec = (lambda: ops.h2_record(device)) if self.h2 else (lambda: None)
+        self.x_amax = [rec() for _ in range(len(self.cross_W) + 1)]   # x_0 .. x_L
+        self.h_amax = [rec() for _ in units]                          # MLP activations h_i
+        self.dh_amax = [rec() for _ in units]                         # their gradients (dy of layer i)
+        self.dp_amax = rec()                                          # d_prod of the cross layer being differentiated
         self.hs = [torch.empty((B, _pad4(u)), **f32)[:, :u] for u in units]
         self.dhs = [torch.empty((B, _pad4(u)), **f32)[:, :u] for u in units[:-1]]
         self.d_top = torch.zeros((B, ld), **f32)
         self.zero_logit = torch.zeros(B, **f32)
         self.prob, self.d_logit, self.loss = torch.empty(B, **f32), torch.empty(B, **f32), torch.zeros(1, **f32)
         self.ws = torch.empty(1024, **f32)
-        self.dw_ws = [ops.linear_bwd_dw_workspace(B, W.shape[0], W.shape[1], device) for W in self.Ws]
-        self.cross_ws = ops.linear_bwd_dw_workspace(B, in_dim, in_dim, device)
-        # wide layers: the register-split wgrad (dr_bf3_wgrad / dr_h2_wgrad) on the same condition as the planes forward / dgrad
-        self.wg_ws = [ops.bf3_wgrad_workspace(B, W.shape[0], W.shape[1], device) if wp is not None else None
-                      for W, wp in zip(self.Ws, self.wplanes)]
-        self.cross_wg_ws = ops.bf3_wgrad_workspace(B, in_dim, in_dim, device) if wide_cross else None
 
     def planes(self):
         return [wp for wp in list(self.cross_planes) + list(self.wplanes) if wp is not None]
@@ -83,132 +89,69 @@ class DCNDense:
 
     def step(self, x0_buf, labels, lr):
         """x0_buf [B, ld] (columns >= in_dim zero) -> d loss / d x0 as a [B, in_dim] view; loss in self.loss (mean over the B rows)."""
-        B, n_in = self.B, self.in_dim
+        B, n_in, p = self.B, self.in_dim, self.p
         inplace = self.grads is None
         sc = -lr if inplace else 1.0
         gcW, gcb, gW, gb = (self.cross_W, self.cross_b, self.Ws, self.bs) if inplace else self.grads
         x0 = x0_buf[:, :n_in]
-        h2 = self.h2
-        if h2:
+        if self.h2:
             self._k("h2_amax_x0", "hbm", 4.0 * B * n_in, lambda: ops.h2_amax(x0, self.x_amax[0]))
         xs, prods = [x0], []
         fl_c = 2.0 * B * n_in * n_in
-        for l, (W, b) in enumerate(zip(self.cross_W, self.cross_b)):
-            if h2:
-                out, prod = self._k("cross_fwd_L%d" % l, "mfma", fl_c,
-                                    lambda x=xs[-1], b=b, l=l: ops.h2_cross_fwd(x0, x, self.x_amax[l], self.cross_planes[l].wt, b, self.diag,
-                                                                                want_prod=True, out_amax=self.x_amax[l + 1]))
-            elif self.cross_planes[l] is not None:
-                out, prod = self._k("cross_fwd_L%d" % l, "mfma", fl_c,
-                                    lambda x=xs[-1], b=b, l=l: ops.bf3_cross_fwd(x0, x, self.cross_planes[l].wt, b, self.diag, want_prod=True))
-            else:
-                out, prod = self._k("cross_fwd_L%d" % l, "mfma", fl_c,
-                                    lambda x=xs[-1], W=W, b=b: ops.cross_fwd(x0, x, W, b, self.diag, want_prod=True))
+        for l, (g, b) in enumerate(zip(self.cross_gemm, self.cross_b)):
+            out, prod, _ = self._k("cross_fwd_L%d" % l, "mfma", fl_c,
+                                   lambda x=xs[-1], g=g, b=b, l=l: g.cross_fwd(x0, x, self.x_amax[l], b, self.diag, True,
+                                                                               out_amax=self.x_amax[l + 1]))
             xs.append(out)
             prods.append(prod)
-        x = xs[-1]
-        xam = self.x_amax[-1] if h2 else None                 # record of the current MLP input (None: not known)
-        for i, (W, b) in enumerate(zip(self.Ws, self.bs)):
-            if h2 and self.wplanes[i] is not None:
-                if xam is None:
-                    xam = ops.h2_amax(x, self.h_amax[i - 1])
-                self._k("linear_fwd_L%d" % i, "mfma", 2.0 * B * W.shape[0] * W.shape[1],
-                        lambda x=x, b=b, i=i, xam=xam: ops.h2_linear_nt(x, xam, self.wplanes[i].wt, bias=b, act=self.acts[i], out=self.hs[i],
-                                                                        out_amax=self.h_amax[i]))
-                xam = self.h_amax[i]
-                x = self.hs[i]
-                continue
-            xam = None
-            if self.wplanes[i] is not None:
-                self._k("linear_fwd_L%d" % i, "mfma", 2.0 * B * W.shape[0] * W.shape[1],
-                        lambda x=x, b=b, i=i: ops.bf3_linear_nt(x, self.wplanes[i].wt, bias=b, act=self.acts[i], out=self.hs[i]))
-            else:
-                self._k("linear_fwd_L%d" % i, "mfma", 2.0 * B * W.shape[0] * W.shape[1],
-                        lambda x=x, W=W, b=b, i=i: ops.linear_fwd(x, W, b, self.acts[i], out=self.hs[i]))
+        x, xam = xs[-1], self.x_amax[-1]                      # the current MLP input and its record (None: not known)
+        for i, (g, b) in enumerate(zip(self.gemm, self.bs)):
+            if g.wants_amax and xam is None:
+                xam = ops.h2_amax(x, self.h_amax[i - 1])
+            xam = self._k("linear_fwd_L%d" % i, "mfma", 2.0 * B * g.W.shape[0] * g.W.shape[1],
+                          lambda x=x, g=g, b=b, i=i, xam=xam: g.fwd(x, xam, b, self.acts[i], self.hs[i], out_amax=self.h_amax[i]))
             x = self.hs[i]
-        ops.bce_fwd_bwd(self.zero_logit, labels, ops.LOSS_SIGMOID_CE, workspace=self.ws, logits_b=self.hs[-1],
-                        out=(self.prob, self.d_logit, self.loss))
+        p.bce_fwd_bwd(self.zero_logit, labels, ops.LOSS_SIGMOID_CE, workspace=self.ws, logits_b=self.hs[-1],
+                      out=(self.prob, self.d_logit, self.loss))
         # ---- backward: MLP ---------------------------------------------------------------------------------------------
         dy = self.d_logit.reshape(-1, 1)
         dyam = None                                           # record of dy (None: not known, built by a pass when a GEMM wants it)
         for i in range(len(self.Ws) - 1, -1, -1):
-            xin = xs[-1] if i == 0 else self.hs[i - 1]
-            W = self.Ws[i]
-            fl = 2.0 * B * W.shape[0] * W.shape[1]
+            g = self.gemm[i]
+            fl = 2.0 * B * g.W.shape[0] * g.W.shape[1]
             if i > 0:
-                dx, rs = self.dhs[i - 1], (self.hs[i - 1] if self.acts[i - 1] else None)
+                xin, xinam = self.hs[i - 1], self.h_amax[i - 1]
+                dx, rs, dxam = self.dhs[i - 1], (self.hs[i - 1] if self.acts[i - 1] else None), self.dh_amax[i - 1]
             else:
-                dx, rs = self.d_top[:, :n_in], None
-            if h2 and self.wplanes[i] is not None:
-                if dyam is None:
-                    dyam = ops.h2_amax(dy, self.dh_amax[i])
-                xinam = self.x_amax[-1] if i == 0 else self.h_amax[i - 1]
-                dxam = self.dh_amax[i - 1] if i > 0 else None
-                self._k("linear_bwd_dx_L%d" % i, "mfma", fl,
-                        lambda dy=dy, rs=rs, dx=dx, i=i, dyam=dyam, dxam=dxam: ops.h2_linear_nt(dy, dyam, self.wplanes[i].w, mask=rs, out=dx,
-                                                                                                out_amax=dxam))
-                self._k("linear_bwd_dw_L%d" % i, "mfma", fl,
-                        lambda xin=xin, dy=dy, i=i, dyam=dyam, xinam=xinam: ops.h2_wgrad(xin, xinam, dy, dyam, sc, gW[i], gb[i],
-                                                                                          workspace=self.wg_ws[i]))
-                if inplace:
-                    self.wplanes[i].refresh()
-                dy, dyam = dx, dxam
-                continue
-            dyam = None
-            if self.wplanes[i] is not None:
-                self._k("linear_bwd_dx_L%d" % i, "mfma", fl,
-                        lambda dy=dy, rs=rs, dx=dx, i=i: ops.bf3_linear_nt(dy, self.wplanes[i].w, mask=rs, out=dx))
-            else:
-                self._k("linear_bwd_dx_L%d" % i, "mfma", fl, lambda dy=dy, W=W, rs=rs, dx=dx: ops.linear_bwd_dx(dy, W, relu_src=rs, out=dx))
-            if self.wg_ws[i] is not None:
-                self._k("linear_bwd_dw_L%d" % i, "mfma", fl,
-                        lambda xin=xin, dy=dy, i=i: ops.bf3_wgrad(xin, dy, sc, gW[i], gb[i], workspace=self.wg_ws[i]))
-            else:
-                self._k("linear_bwd_dw_L%d" % i, "mfma", fl,
-                        lambda xin=xin, dy=dy, i=i: ops.linear_bwd_dw(xin, dy, sc, gW[i], gb[i], workspace=self.dw_ws[i]))
-            if self.wplanes[i] is not None and inplace:
-                self.wplanes[i].refresh()
-            dy = dx
+                xin, xinam = xs[-1], self.x_amax[-1]
+                dx, rs, dxam = self.d_top[:, :n_in], None, None
+            if g.wants_amax and dyam is None:
+                dyam = ops.h2_amax(dy, self.dh_amax[i])
+            dxam = self._k("linear_bwd_dx_L%d" % i, "mfma", fl,
+                           lambda g=g, dy=dy, dyam=dyam, rs=rs, dx=dx, dxam=dxam: g.dgrad(dy, dyam, rs, dx, out_amax=dxam))
+            self._k("linear_bwd_dw_L%d" % i, "mfma", fl,
+                    lambda g=g, xin=xin, xinam=xinam, dy=dy, dyam=dyam, i=i: g.wgrad(xin, xinam, dy, dyam, sc, gW[i], gb[i]))
+            if inplace:
+                g.refresh()
+            dy, dyam = dx, dxam
         # ---- backward: cross stack.  d_out of layer l -> (d_x0 +=, d_x_l), W_l / b_l updated (or their gradients accumulated) -----
         d_out = self.d_top[:, :n_in]
         d_x0 = torch.zeros((B, self.ld), dtype=torch.float32, device=d_out.device)[:, :n_in]
+        dp_kw = {"d_prod_amax": self.dp_amax} if self.h2 else {}
         for l in range(len(self.cross_W) - 1, -1, -1):
-            if self.diag == 0.0:
-                # d_x = d_out + d_prod W^T: the dgrad below ACCUMULATES into the d_out buffer itself (d_out's last reader is the
-                # combine kernel) -- no zero-filled d_x, no read-modify-write of it in the combine pass: -1.3 GB per layer
-                d_x = d_out
-                d_prod = self._k("cross_combine_bwd_L%d" % l, "hbm", 6.0 * 4 * B * n_in,
-                                 lambda l=l, d_out=d_out: ops.cross_combine_bwd(x0, prods[l], d_out, 0.0, d_x0, None,
-                                                                                d_prod_amax=self.dp_amax if h2 else None))
-            else:
-                d_x = torch.zeros((B, self.ld), dtype=torch.float32, device=d_out.device)[:, :n_in]
-                d_prod = self._k("cross_combine_bwd_L%d" % l, "hbm", 6.0 * 4 * B * n_in,
-                                 lambda l=l, d_out=d_out, d_x=d_x: ops.cross_combine_bwd(x0, prods[l], d_out, self.diag, d_x0, d_x,
-                                                                                         d_prod_amax=self.dp_amax if h2 else None))
-            if h2:
-                self._k("cross_bwd_dx_L%d" % l, "mfma", fl_c,
-                        lambda d_prod=d_prod, l=l, d_x=d_x: ops.h2_linear_nt(d_prod, self.dp_amax, self.cross_planes[l].w, accumulate=True, out=d_x))
-                self._k("cross_bwd_dw_L%d" % l, "mfma", fl_c,
-                        lambda l=l, d_prod=d_prod: ops.h2_wgrad(xs[l], self.x_amax[l], d_prod, self.dp_amax, sc, gcW[l], gcb[l],
-                                                                workspace=self.cross_wg_ws))
-                if inplace:
-                    self.cross_planes[l].refresh()
-                d_out = d_x
-                continue
-            if self.cross_planes[l] is not None:
-                self._k("cross_bwd_dx_L%d" % l, "mfma", fl_c,
-                        lambda d_prod=d_prod, l=l, d_x=d_x: ops.bf3_linear_nt(d_prod, self.cross_planes[l].w, accumulate=True, out=d_x))
-            else:
-                self._k("cross_bwd_dx_L%d" % l, "mfma", fl_c,
-                        lambda d_prod=d_prod, l=l, d_x=d_x: ops.linear_bwd_dx(d_prod, self.cross_W[l], None, accumulate=True, out=d_x))
-            if self.cross_wg_ws is not None:
-                self._k("cross_bwd_dw_L%d" % l, "mfma", fl_c,
-                        lambda l=l, d_prod=d_prod: ops.bf3_wgrad(xs[l], d_prod, sc, gcW[l], gcb[l], workspace=self.cross_wg_ws))
-            else:
-                self._k("cross_bwd_dw_L%d" % l, "mfma", fl_c,
-                        lambda l=l, d_prod=d_prod: ops.linear_bwd_dw(xs[l], d_prod, sc, gcW[l], gcb[l], workspace=self.cross_ws))
-            if self.cross_planes[l] is not None and inplace:
-                self.cross_planes[l].refresh()
+            g = self.cross_gemm[l]
+            # diag == 0: d_x = d_out + d_prod W^T: the dgrad below ACCUMULATES into the d_out buffer itself (d_out's last reader is the
+            # combine kernel) -- no zero-filled d_x, no read-modify-write of it in the combine pass: -1.3 GB per layer
+            d_x = d_out if self.diag == 0.0 else torch.zeros((B, self.ld), dtype=torch.float32, device=d_out.device)[:, :n_in]
+            d_prod = self._k("cross_combine_bwd_L%d" % l, "hbm", 6.0 * 4 * B * n_in,
+                             lambda l=l, d_out=d_out, d_x=d_x: p.cross_combine_bwd(x0, prods[l], d_out, self.diag, d_x0,
+                                                                                   None if d_x is d_out else d_x, **dp_kw))
+            self._k("cross_bwd_dx_L%d" % l, "mfma", fl_c,
+                    lambda g=g, d_prod=d_prod, d_x=d_x: g.dgrad(d_prod, self.dp_amax, None, d_x, accumulate=True))
+            self._k("cross_bwd_dw_L%d" % l, "mfma", fl_c,
+                    lambda g=g, l=l, d_prod=d_prod: g.wgrad(xs[l], self.x_amax[l], d_prod, self.dp_amax, sc, gcW[l], gcb[l]))
+            if inplace:
+                g.refresh()
             d_out = d_x
         d_x0.add_(d_out)                                     # the first layer's x IS x0
         return d_x0

@@ -110,12 +110,10 @@ class DeepFMEngine:
         # Wide layers: forward and dgrad on pre-split weights (dr_bf3_linear_nt: the activation operand stays fp32 and is split
         # in registers, only the weight is staged through the LDS): 360 -> 264 us forward, 400 -> 306 us dgrad at the first layer
         # of config 3.  The planes are refreshed after every update of the weight.  Other layers: the in-kernel-split GEMMs.
-        self.wplanes = [ops.WeightPlanes(W) if (u > 1 and ops.planes_worthwhile(B, W.shape[0], W.shape[1])) else None
-                        for W, u in zip(self.Ws, units)]
-        self.dw_ws = [ops.linear_bwd_dw_workspace(B, W.shape[0], W.shape[1], device) for W in self.Ws]
+        wide = [u > 1 and ops.planes_worthwhile(B, W.shape[0], W.shape[1]) for W, u in zip(self.Ws, units)]
         # wide layers: the register-split wgrad (dr_bf3_wgrad) on the same condition as the planes forward / dgrad
-        self.wg_ws = [ops.bf3_wgrad_workspace(B, W.shape[0], W.shape[1], device) if wp is not None else None
-                      for W, wp in zip(self.Ws, self.wplanes)]
+        self.wg_ws = [ops.bf3_wgrad_workspace(B, W.shape[0], W.shape[1], device) if wd else None for W, wd in zip(self.Ws, wide)]
+        self.wplanes = [ops.WeightPlanes(W, wgrad_ws=ws) if wd else None for W, wd, ws in zip(self.Ws, wide, self.wg_ws)]
         # last hidden layer (<= 32 units, relu) + Dense(1) + loss + Dense(1) backward fused into one GEMM epilogue
         nl = len(self.Ws)
         self.fuse_head = nl >= 2 and self.Ws[-1].shape[1] == 1 and self.Ws[-2].shape[1] <= 32 and self.acts[-2] == 1
@@ -203,14 +201,18 @@ class DeepFMEngine:
         # "adam_tf" (whose catch-up kernel also writes table rows) stays on bf16x3.
         self.h2 = (ops.get_gemm_split() == "f16x2" and self.no_concat and self.wplanes[0] is not None
                    and not self.adam_tf and os.environ.get("DR_OVERLAP_DW", "0") != "1")
+        self.tab_amax = self.dh0_amax = None                 # (records exist in the f16x2 mode only)
         if self.h2:
             # (two W images: the fused dgrad + K4 of step s reads the old one while the refresh behind step s's wgrad writes the other)
-            self.wplanes[0] = ops.H2WeightPlanes(self.Ws[0], double_buffer=True)
+            self.wplanes[0] = ops.H2WeightPlanes(self.Ws[0], double_buffer=True, wgrad_ws=self.wg_ws[0])
             self.tab_amax = ops.h2_amax(self.table)
             self._tab_ver = (self.table.data_ptr(), self.table._version)
             self._dense_amaxs = [ops.h2_record(device) for _ in range(2)] if self._dense_pads is not None else None
             self.dh0_amax = ops.h2_record(device)
             self._amax_scratch = ops.h2_record(device)
+        # the GEMM family of each layer's products, decided here once: its planes object, else the plain family
+        self.gemm = [wp if wp is not None else ops.PlainWeight(W, dw_ws=ops.linear_bwd_dw_workspace(B, W.shape[0], W.shape[1], device))
+                     for W, wp in zip(self.Ws, self.wplanes)]
         # The tower tail as the EPILOGUE of the fused first layer (dr_h2_emb_linear_tail_fwd): with a [256, H <= 32] tower a wave of that
         # GEMM ends its main loop holding complete rows of h0, so the 256 -> H -> 1 forward, the loss and the backward down to d h0 run
         # on the accumulators -- h0 (67 MB at config 3) is not read back, and the tail's launch and its dependent boundary are gone.
@@ -550,20 +552,16 @@ class DeepFMEngine:
             self.ev_small.record(self.side)
         self._small_pending = True
 
-    def _wgrad(self, i, x, dy, sc, dstW, dstb, main_only=False):
-        if i == 0 and self.h2:
-            ops.h2_wgrad_emb(self._ids_t[self.cur], self.row_base, self.table, self.tab_amax, self.dense_pad, self.dense_amax, dy,
-                             self.dh0_amax, sc, dstW, dstb, workspace=self.wg_ws[0],
-                             parts=1 if (main_only or self._wgrad_reduce_deferred(i)) else 3)
-        elif i == 0 and self.no_concat:
+    def _wgrad(self, i, x, dy, sc, dstW, dstb, main_only=False, parts=None):
+        if i == 0 and self.no_concat:
             # x = [embeddings of this batch's rows, dense features]: gathered from the tables (they are updated only by K4, later
-            # on this stream) through the field-major ids
-            ops.bf3_wgrad_emb(self._ids_t[self.cur], self.row_base, self.table, self.dense_pad, dy, sc, dstW, dstb,
-                              workspace=self.wg_ws[0], parts=1 if self._wgrad_reduce_deferred(i) else 3)
-        elif self.wg_ws[i] is not None:
-            ops.bf3_wgrad(x, dy, sc, dstW, dstb, workspace=self.wg_ws[i])
+            # on this stream) through the field-major ids.  parts 1: the split-K GEMM, 2: its reduce (given: the deferred one)
+            if parts is None:
+                parts = 1 if (main_only or self._wgrad_reduce_deferred(i)) else 3
+            self.gemm[0].wgrad_emb(self._ids_t[self.cur], self.row_base, self.table, self.tab_amax, self.dense_pad, self.dense_amax, dy,
+                                   self.dh0_amax, sc, dstW, dstb, parts)
         else:
-            ops.linear_bwd_dw(x, dy, sc, dstW, dstb, workspace=self.dw_ws[i])
+            self.gemm[i].wgrad(x, None, dy, None, sc, dstW, dstb)
 
     # ------------------------------------------------------------------------------------------
     def forward(self, keys: torch.Tensor, dense: Optional[torch.Tensor], labels: Optional[torch.Tensor],
@@ -673,26 +671,17 @@ class DeepFMEngine:
             if i == 0 and fused_l0:
                 # K3 + first Dense in one launch: the GEMM gathers its activation operand from the tables, writes concat and the
                 # FM terms on the way (the dense features were placed in concat above)
-                if self.h2:
-                    self._k("emb_linear_fwd_L0", "mfma", 2.0 * B * W.shape[0] * W.shape[1],
-                            lambda b=b: ops.h2_emb_linear_fwd(self.ids, self.row_base, self.V, self.table, self.tab_amax, self.lin_w, self.lin_bias,
-                                                              self.dense_pad, self.dense_amax, None, self.in_dim, self.wplanes[0].wt, b,
-                                                              self.acts[0], self.sum_x, self.fm_logit, self.hs[0], lin_vals_t=self.lin_old_t))
-                else:
-                    self._k("emb_linear_fwd_L0", "mfma", 2.0 * B * W.shape[0] * W.shape[1],
-                            lambda b=b: ops.bf3_emb_linear_fwd(self.ids, self.row_base, self.V, self.table, self.lin_w, self.lin_bias,
-                                                               self.dense_pad, None if self.no_concat else self.concat, self.in_dim,
-                                                               self.wplanes[0].wt, b, self.acts[0], self.sum_x, self.fm_logit, self.hs[0],
-                                                               lin_vals_t=self.lin_old_t))
+                self._k("emb_linear_fwd_L0", "mfma", 2.0 * B * W.shape[0] * W.shape[1],
+                        lambda b=b: self.gemm[0].emb_linear_fwd(self.ids, self.row_base, self.V, self.table, self.tab_amax, self.lin_w,
+                                                                self.lin_bias, self.dense_pad, self.dense_amax,
+                                                                None if self.no_concat else self.concat, self.in_dim, b, self.acts[0],
+                                                                self.sum_x, self.fm_logit, self.hs[0], lin_vals_t=self.lin_old_t))
                 self._lin_old_valid = self.lin_old_t is not None
                 if self._in_train_step and self.prefetch_after_fwd:
                     self._prefetch_early()
-            elif self.wplanes[i] is not None:
-                self._k("linear_fwd_L%d" % i, "mfma", 2.0 * B * W.shape[0] * W.shape[1],
-                        lambda x=x, b=b, i=i: ops.bf3_linear_nt(x, self.wplanes[i].wt, bias=b, act=self.acts[i], out=self.hs[i]))
             else:
                 self._k("linear_fwd_L%d" % i, "mfma", 2.0 * B * W.shape[0] * W.shape[1],
-                        lambda x=x, W=W, b=b, i=i: ops.linear_fwd(x, W, b, self.acts[i], out=self.hs[i]))
+                        lambda x=x, b=b, i=i: self.gemm[i].fwd(x, None, b, self.acts[i], self.hs[i]))
             x = self.hs[i]
         self._head_done = head
         self._tail_done = False
@@ -789,17 +778,11 @@ class DeepFMEngine:
                 dy = None
                 continue
             # dx first (uses the pre-update W), then the wgrad (with the fused SGD step unless Adam)
-            if i == 0 and self.h2:
-                if not (n > 1 and self.narrow_ws[1] is not None):
-                    ops.h2_amax(dy, self.dh0_amax)       # (layer 1's backward was not the narrow kernel that leaves the record)
-                self._k("linear_bwd_dx_L%d" % i, "mfma", fl,
-                        lambda dy=dy, rs=rs, dx=dx, i=i: ops.h2_linear_nt(dy, self.dh0_amax, self.wplanes[i].w, mask=rs, out=dx))
-            elif self.wplanes[i] is not None:
-                self._k("linear_bwd_dx_L%d" % i, "mfma", fl,
-                        lambda dy=dy, rs=rs, dx=dx, i=i: ops.bf3_linear_nt(dy, self.wplanes[i].w, mask=rs, out=dx))
-            else:
-                self._k("linear_bwd_dx_L%d" % i, "mfma", fl,
-                        lambda dy=dy, W=W, rs=rs, dx=dx: ops.linear_bwd_dx(dy, W, relu_src=rs, out=dx))
+            if i == 0 and self.h2 and not (n > 1 and self.narrow_ws[1] is not None):
+                ops.h2_amax(dy, self.dh0_amax)           # (layer 1's backward was not the narrow kernel that leaves the record)
+            # (only layer 0 is ever in the f16x2 family: its dy comes with the d h0 record)
+            self._k("linear_bwd_dx_L%d" % i, "mfma", fl,
+                    lambda dy=dy, rs=rs, dx=dx, i=i: self.gemm[i].dgrad(dy, self.dh0_amax if i == 0 else None, rs, dx))
             if i == 0 and self.sorted_bwd and self._plan_prefetched:
                 # the wait for a prefetched plan, long complete by now, goes here: no cross-stream packet in front of K4
                 torch.cuda.current_stream().wait_event(self.ev_sorted)
@@ -825,13 +808,9 @@ class DeepFMEngine:
                     self._refresh_stream = self.side
                     with torch.cuda.stream(self.side):
                         self.side.wait_event(self.ev_dw_done)
-                        if self._wgrad_reduce_deferred(i) and self.h2:
-                            ops.h2_wgrad_emb(self._ids_t[self.cur], self.row_base, self.table, self.tab_amax, self.dense_pad, self.dense_amax,
-                                             dy, self.dh0_amax, sc, dstW, dstb, workspace=self.wg_ws[0], parts=2)
-                        elif self._wgrad_reduce_deferred(i):
+                        if self._wgrad_reduce_deferred(i):
                             # the split-K reduce (+ fused SGD step) of the GEMM just launched: nothing on the training stream reads W
-                            ops.bf3_wgrad_emb(self._ids_t[self.cur], self.row_base, self.table, self.dense_pad, dy, sc, dstW, dstb,
-                                              workspace=self.wg_ws[0], parts=2)
+                            self._wgrad(i, x, dy, sc, dstW, dstb, parts=2)
                         self.wplanes[i].refresh()
                         self.ev_planes.record(self.side)
                     self._planes_pending = True

@@ -1338,14 +1338,45 @@ def bf3_wgrad(x, dy, scale, dstW, dstb=None, workspace=None):
 
 class WeightPlanes:
     """Both pre-split forms of a Dense kernel W [K, N]: `wt` = W^T planes (rows N: the forward's B operand) and `w` = W planes
-    (rows K: the dgrad's B operand).  refresh() after every update of W (two dr_bf3_split launches)."""
+    (rows K: the dgrad's B operand).  refresh() after every update of W (two dr_bf3_split launches).
 
-    def __init__(self, W):
+    One of the three GEMM families of a weight (WeightPlanes, H2WeightPlanes, PlainWeight): fwd / dgrad / wgrad / cross_fwd (and, on the
+    two planes families, the first layer's emb_linear_fwd / wgrad_emb / linear_nt_pack) take the same arguments in every family and
+    are direct calls of that family's kernels.  Amax records: a family with wants_amax False ignores the record arguments; a method
+    returns the record it left for its output, or None.  wgrad_ws: the bf3_wgrad_workspace the wgrads run in (None: one per call)."""
+    wants_amax = False
+
+    def __init__(self, W, wgrad_ws=None):
         K, N = W.shape
         self.W = W
+        self.wgrad_ws = wgrad_ws
         self.wt = Planes(N, K, W.device)
         self.w = Planes(K, N, W.device)
         self.refresh()
+
+    def fwd(self, x, x_amax, bias, act, out, out_amax=None):
+        bf3_linear_nt(x, self.wt, bias=bias, act=act, out=out)
+
+    def dgrad(self, dy, dy_amax, mask, out, accumulate=False, out_amax=None):
+        bf3_linear_nt(dy, self.w, mask=mask, accumulate=accumulate, out=out)
+
+    def wgrad(self, x, x_amax, dy, dy_amax, scale, dstW, dstb):
+        bf3_wgrad(x, dy, scale, dstW, dstb, workspace=self.wgrad_ws)
+
+    def cross_fwd(self, x0, x, x_amax, b, diag, want_prod, out_amax=None):
+        """-> (out, prod, the record left for out)"""
+        return bf3_cross_fwd(x0, x, self.wt, b, diag, want_prod=want_prod) + (None,)
+
+    def emb_linear_fwd(self, ids, row_base, field_rows_max, table, table_amax, lin_w, lin_bias, dense_pad, dense_amax, concat, K, bias, act,
+                       sum_x, fm_logit, out, lin_vals_t=None):
+        bf3_emb_linear_fwd(ids, row_base, field_rows_max, table, lin_w, lin_bias, dense_pad, concat, K, self.wt, bias, act, sum_x, fm_logit,
+                           out, lin_vals_t=lin_vals_t)
+
+    def wgrad_emb(self, ids_t, row_base, table, table_amax, dense_pad, dense_amax, dy, dy_amax, scale, dstW, dstb, parts):
+        bf3_wgrad_emb(ids_t, row_base, table, dense_pad, dy, scale, dstW, dstb, workspace=self.wgrad_ws, parts=parts)
+
+    def linear_nt_pack(self, dy, dy_amax, pos, d_fm_logit, out_rows, out_lin, bias_sum, sum_x, x):
+        bf3_linear_nt_pack(dy, self.w, pos, d_fm_logit, out_rows, out_lin, bias_sum, sum_x=sum_x, x=x)
 
     def refresh(self):
         bf3_split(self.W, self.wt, transpose=True)
@@ -1532,12 +1563,15 @@ def h2_wgrad_emb(ids_t, row_base, table, table_amax, dense_pad, dense_amax, dy, 
 class H2WeightPlanes:
     """WeightPlanes in the f16x2 mode: W^T and W as two fp16 planes each, one amax record; refresh() = dr_h2_amax + two dr_h2_split."""
 
-    def __init__(self, W, double_buffer=False):
+    wants_amax = True       # every activation operand comes with its record; out_amax (a record) receives the output's
+
+    def __init__(self, W, double_buffer=False, wgrad_ws=None):
         """double_buffer: refresh() writes the W image (`w`) and the record into a SECOND buffer pair and then makes them current, so a
         kernel still reading the previous `w` (with the previous record) may run beside the refresh -- the caller keeps the H2Planes
         object it took before calling refresh().  `wt` is single: nothing may read it while a refresh runs."""
         K, N = W.shape
         self.W = W
+        self.wgrad_ws = wgrad_ws
         self.amax = h2_record(W.device)
         self.wt = H2Planes(N, K, W.device, self.amax)
         self.w = H2Planes(K, N, W.device, self.amax)
@@ -1577,6 +1611,61 @@ class H2WeightPlanes:
     def ensure_fresh(self):
         if self.W._version != self._ver:
             self.refresh()
+
+    def fwd(self, x, x_amax, bias, act, out, out_amax=None):
+        h2_linear_nt(x, x_amax, self.wt, bias=bias, act=act, out=out, out_amax=out_amax)
+        return out_amax
+
+    def dgrad(self, dy, dy_amax, mask, out, accumulate=False, out_amax=None):
+        h2_linear_nt(dy, dy_amax, self.w, mask=mask, accumulate=accumulate, out=out, out_amax=out_amax)
+        return out_amax
+
+    def wgrad(self, x, x_amax, dy, dy_amax, scale, dstW, dstb):
+        h2_wgrad(x, x_amax, dy, dy_amax, scale, dstW, dstb, workspace=self.wgrad_ws)
+
+    def cross_fwd(self, x0, x, x_amax, b, diag, want_prod, out_amax=None):
+        return h2_cross_fwd(x0, x, x_amax, self.wt, b, diag, want_prod=want_prod, out_amax=out_amax) + (out_amax,)
+
+    def emb_linear_fwd(self, ids, row_base, field_rows_max, table, table_amax, lin_w, lin_bias, dense_pad, dense_amax, concat, K, bias, act,
+                       sum_x, fm_logit, out, lin_vals_t=None):
+        h2_emb_linear_fwd(ids, row_base, field_rows_max, table, table_amax, lin_w, lin_bias, dense_pad, dense_amax, concat, K, self.wt, bias,
+                          act, sum_x, fm_logit, out, lin_vals_t=lin_vals_t)
+
+    def wgrad_emb(self, ids_t, row_base, table, table_amax, dense_pad, dense_amax, dy, dy_amax, scale, dstW, dstb, parts):
+        h2_wgrad_emb(ids_t, row_base, table, table_amax, dense_pad, dense_amax, dy, dy_amax, scale, dstW, dstb, workspace=self.wgrad_ws,
+                     parts=parts)
+
+    def linear_nt_pack(self, dy, dy_amax, pos, d_fm_logit, out_rows, out_lin, bias_sum, sum_x, x):
+        h2_linear_nt_pack(dy, dy_amax, self.w, pos, d_fm_logit, out_rows, out_lin, bias_sum, sum_x=sum_x, x=x)
+
+
+class PlainWeight:
+    """The third GEMM family of a weight W [K, N] (see WeightPlanes): no planes, the dr_linear_* / dr_cross_fwd kernels split both
+    operands themselves.  `prims`: whatever provides linear_fwd / linear_bwd_dx / linear_bwd_dw / cross_fwd (default: this module;
+    the CPU tests pass oracle-backed ones).  dw_ws: the linear_bwd_dw workspace (None: fp32 atomics -- and off the GPU)."""
+    wants_amax = False
+
+    def __init__(self, W, prims=None, dw_ws=None):
+        self.W, self.dw_ws = W, dw_ws
+        self._fwd, self._bwd_dx, self._bwd_dw, self._cross = ((linear_fwd, linear_bwd_dx, linear_bwd_dw, cross_fwd) if prims is None else
+                                                              (prims.linear_fwd, prims.linear_bwd_dx, prims.linear_bwd_dw, getattr(prims, "cross_fwd", None)))
+
+    def refresh(self):
+        pass
+
+    ensure_fresh = refresh
+
+    def fwd(self, x, x_amax, bias, act, out, out_amax=None):
+        self._fwd(x, self.W, bias, act, out=out)
+
+    def dgrad(self, dy, dy_amax, mask, out, accumulate=False, out_amax=None):
+        self._bwd_dx(dy, self.W, relu_src=mask, accumulate=accumulate, out=out)
+
+    def wgrad(self, x, x_amax, dy, dy_amax, scale, dstW, dstb):
+        self._bwd_dw(x, dy, scale, dstW, dstb, workspace=self.dw_ws)
+
+    def cross_fwd(self, x0, x, x_amax, b, diag, want_prod, out_amax=None):
+        return tuple(self._cross(x0, x, self.W, b, diag, want_prod=want_prod)) + (None,)
 
 
 def planes_worthwhile(M, K, N):

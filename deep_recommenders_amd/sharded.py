@@ -576,11 +576,11 @@ class ShardedDeepFMEngine:
             self.head_ws = ops.tower_head_workspace(B, device) if self.fuse_head else None
             self.narrow_ws = [ops.linear_bwd_narrow_workspace(B, Wt.shape[0], Wt.shape[1], device) if self.narrow[i] else None
                               for i, Wt in enumerate(self.Ws)]
-            self.dw_ws = [ops.linear_bwd_dw_workspace(B, Wt.shape[0], Wt.shape[1], device) for Wt in self.Ws]
+            dw_ws = [ops.linear_bwd_dw_workspace(B, Wt.shape[0], Wt.shape[1], device) for Wt in self.Ws]
         else:
             self.head_ws = None
             self.narrow_ws = [None] * nl
-            self.dw_ws = [None] * nl
+            dw_ws = [None] * nl
         self.comm = torch.cuda.Stream(device=device) if self._cuda else None   # every exchange + the owner-side updates
         # micro-batches per step (see train_step); needs the fused head (per-slice loss normalisation) and slices the
         # narrow kernel accepts
@@ -610,10 +610,9 @@ class ShardedDeepFMEngine:
         # the dgrad of a micro-batch and the wgrad over the whole rank batch.  The forward stays on the in-kernel-split GEMM below
         # 65 536 rows: its 256-row tiles number 128 at a 32 768-row micro-batch, half a machine (267 us either way, measured).
         use_planes = self._cuda and self.p is HipPrims
-        self.wplanes = [ops.WeightPlanes(Wt) if (use_planes and ops.planes_worthwhile(Bm, Wt.shape[0], Wt.shape[1])) else None
-                        for Wt in self.Ws]
-        self.wg_ws = [ops.bf3_wgrad_workspace(B, Wt.shape[0], Wt.shape[1], device) if self.wplanes[i] is not None else None
-                      for i, Wt in enumerate(self.Ws)]
+        wide = [use_planes and ops.planes_worthwhile(Bm, Wt.shape[0], Wt.shape[1]) for Wt in self.Ws]
+        self.wg_ws = [ops.bf3_wgrad_workspace(B, Wt.shape[0], Wt.shape[1], device) if wd else None for Wt, wd in zip(self.Ws, wide)]
+        self.wplanes = [ops.WeightPlanes(Wt, wgrad_ws=ws) if wd else None for Wt, wd, ws in zip(self.Ws, wide, self.wg_ws)]
         self.planes_fwd_rows = 65536
         # K3 inside the first layer's GEMM, over the RECEIVED rows: the register-split kernel gathers its activation operand by
         # LDS-DMA and does not care where the rows live -- table := the receive buffer, ids := each slot's position in it, one
@@ -637,8 +636,10 @@ class ShardedDeepFMEngine:
         # it the bound for the rows any rank may receive in the next step (on the communication stream, long before those rows
         # arrive).  d h0's record comes out of the narrow backward per micro-batch.  DR_GEMM_SPLIT=bf16x3: the six-product mode.
         self.h2 = (self.fuse_k3 and ops.get_gemm_split() == "f16x2" and not (self.fuse_head and nl - 2 == 0))
+        self.tab_amax = self.dense_amax = self.dh0_amax_all = self.x_amax_all = None       # (records exist in the f16x2 mode only)
+        self.dh0_amax = [None] * mb
         if self.h2:
-            self.wplanes[0] = ops.H2WeightPlanes(self.Ws[0])
+            self.wplanes[0] = ops.H2WeightPlanes(self.Ws[0], wgrad_ws=self.wg_ws[0])
             self.tab_amax_local = ops.h2_amax(self.table)
             # (two buffers for the global bound: the all-reduce behind step t's last update fills the one step t + 1 will read, while
             # step t's wgrad -- whose rows were fetched before that update -- still reads the other)
@@ -652,6 +653,11 @@ class ShardedDeepFMEngine:
             self.dh0_amax = [ops.h2_record(device) for _ in range(mb)]
             self.dh0_amax_all = ops.h2_record(device)
             self.x_amax_all = ops.h2_record(device)
+        # The GEMM family of each layer's products: its planes object, else the plain family on the primitives.  Two objects per weight:
+        # the dgrad / wgrad use the planes wherever they exist, the (unfused) forward only from planes_fwd_rows rows (see above).
+        plain = [ops.PlainWeight(Wt, self.p, ws) for Wt, ws in zip(self.Ws, dw_ws)]
+        self.gemm = [wp if wp is not None else pl for wp, pl in zip(self.wplanes, plain)]
+        self.gemm_fwd = self.gemm if Bm >= self.planes_fwd_rows else plain
         # DR_SH_TRACK_AMAX=1 (tests): the bookkeeping of the table bound -- local running record, the all-reduce(MAX) behind the step's last
         # owner-side update, the two-buffer swap -- WITHOUT the f16x2 kernels, so that the N > 1 control flow of the mode runs wherever
         # the engine runs (world-size-2 gloo on CPU with the oracle-backed primitives: the record is recomputed from the shard with
@@ -925,18 +931,11 @@ class ShardedDeepFMEngine:
                 if t is not None:
                     t.record_stream(stream)
             Wt, b = self.Ws[0], self.bs[0]
-            if h2:
-                self._k("emb_linear_fwd_L0", "mfma", 2.0 * Bm * Wt.shape[0] * Wt.shape[1],
-                        lambda: ops.h2_emb_linear_fwd(
-                            routes[m].pos, self.ex._zero_base, rows_m.shape[0], rows_m, self.tab_amax, lin_m, self.lin_bias,
-                            self.dense_pad[sl] if self.dense_pad is not None else None, self.dense_amax, self.concat[sl], self.in_dim,
-                            self.wplanes[0].wt, b, self.acts[0], self.sum_x[sl], self.fm_logit[sl], self.hs[0][sl]))
-                return
             self._k("emb_linear_fwd_L0", "mfma", 2.0 * Bm * Wt.shape[0] * Wt.shape[1],
-                    lambda: ops.bf3_emb_linear_fwd(
-                        routes[m].pos, self.ex._zero_base, rows_m.shape[0], rows_m, lin_m, self.lin_bias,
-                        self.dense_pad[sl] if self.dense_pad is not None else None, self.concat[sl], self.in_dim,
-                        self.wplanes[0].wt, b, self.acts[0], self.sum_x[sl], self.fm_logit[sl], self.hs[0][sl]))
+                    lambda: self.gemm[0].emb_linear_fwd(
+                        routes[m].pos, self.ex._zero_base, rows_m.shape[0], rows_m, self.tab_amax, lin_m, self.lin_bias,
+                        self.dense_pad[sl] if self.dense_pad is not None else None, self.dense_amax, self.concat[sl], self.in_dim,
+                        b, self.acts[0], self.sum_x[sl], self.fm_logit[sl], self.hs[0][sl]))
 
         # The fused first layer of a micro-batch is 256-row tiles x ONE column tile: B / M / 256 blocks, i.e. half of the 256 CUs at
         # M = 2 -- and a persistent block owns its CU (160 KB of LDS), so each launch takes as long as the full batch's.  The later
@@ -972,13 +971,9 @@ class ShardedDeepFMEngine:
                 if i == 0 and fused_l0:
                     if ev_fwd[m] is None:
                         fused_first_layer(m, sl, main)
-                elif self.wplanes[i] is not None and Bm >= self.planes_fwd_rows:
-                    self._k("linear_fwd_L%d" % i, "mfma", 2.0 * Bm * Wt.shape[0] * Wt.shape[1],
-                            lambda x=x, b=b, i=i, sl=sl: ops.bf3_linear_nt(x, self.wplanes[i].wt, bias=b, act=self.acts[i],
-                                                                           out=self.hs[i][sl]))
                 else:
                     self._k("linear_fwd_L%d" % i, "mfma", 2.0 * Bm * Wt.shape[0] * Wt.shape[1],
-                            lambda x=x, Wt=Wt, b=b, i=i, sl=sl: p.linear_fwd(x, Wt, b, self.acts[i], out=self.hs[i][sl]))
+                            lambda x=x, b=b, i=i, sl=sl: self.gemm_fwd[i].fwd(x, None, b, self.acts[i], self.hs[i][sl]))
                 x = self.hs[i][sl]
             tail_done = False
             if self.fuse_tail:
@@ -1028,18 +1023,12 @@ class ShardedDeepFMEngine:
                 if i == 0 and fuse_pack:
                     # the gradient of every slot straight into the send layout (dgrad epilogue = dr_emb_pack_grads)
                     g_rows, g_lin = self.ex.pack_buffers(routes[m])
-                    if h2:
-                        if not (n_layers > 1 and self.narrow[1]):
-                            ops.h2_amax(dy, self.dh0_amax[m])        # (layer 1's backward was not the narrow kernel that leaves the record)
-                        self._k("linear_bwd_dx_L0", "mfma", 2.0 * Bm * self.Ws[0].shape[0] * self.Ws[0].shape[1],
-                                lambda dy=dy, sl=sl, m=m, g_rows=g_rows, g_lin=g_lin: ops.h2_linear_nt_pack(
-                                    dy, self.dh0_amax[m], self.wplanes[0].w, routes[m].pos, self.d_logit[sl], g_rows, g_lin, self.g_lin_bias,
-                                    sum_x=self.sum_x[sl], x=self.concat[sl]))
-                    else:
-                        self._k("linear_bwd_dx_L0", "mfma", 2.0 * Bm * self.Ws[0].shape[0] * self.Ws[0].shape[1],
-                                lambda dy=dy, sl=sl, m=m, g_rows=g_rows, g_lin=g_lin: ops.bf3_linear_nt_pack(
-                                    dy, self.wplanes[0].w, routes[m].pos, self.d_logit[sl], g_rows, g_lin, self.g_lin_bias,
-                                    sum_x=self.sum_x[sl], x=self.concat[sl]))
+                    if h2 and not (n_layers > 1 and self.narrow[1]):
+                        ops.h2_amax(dy, self.dh0_amax[m])            # (layer 1's backward was not the narrow kernel that leaves the record)
+                    self._k("linear_bwd_dx_L0", "mfma", 2.0 * Bm * self.Ws[0].shape[0] * self.Ws[0].shape[1],
+                            lambda dy=dy, sl=sl, m=m, g_rows=g_rows, g_lin=g_lin: self.gemm[0].linear_nt_pack(
+                                dy, self.dh0_amax[m], routes[m].pos, self.d_logit[sl], g_rows, g_lin, self.g_lin_bias,
+                                self.sum_x[sl], self.concat[sl]))
                     if m == 0:
                         dw_todo.append(i)
                     continue
@@ -1050,17 +1039,11 @@ class ShardedDeepFMEngine:
                                                                                      workspace=self.narrow_ws[i],
                                                                                      **({"dx_amax": self.dh0_amax[m]} if (h2 and i == 1) else {})))
                 else:
-                    if i == 0 and h2:
-                        if not (n_layers > 1 and self.narrow[1]):
-                            ops.h2_amax(dy, self.dh0_amax[m])        # (layer 1's backward was not the narrow kernel that leaves the record)
-                        self._k("linear_bwd_dx_L%d" % i, "mfma", 2.0 * Bm * self.Ws[i].shape[0] * self.Ws[i].shape[1],
-                                lambda dy=dy, i=i, rs=rs, dx=dx, m=m: ops.h2_linear_nt(dy, self.dh0_amax[m], self.wplanes[i].w, mask=rs, out=dx))
-                    elif self.wplanes[i] is not None:
-                        self._k("linear_bwd_dx_L%d" % i, "mfma", 2.0 * Bm * self.Ws[i].shape[0] * self.Ws[i].shape[1],
-                                lambda dy=dy, i=i, rs=rs, dx=dx: ops.bf3_linear_nt(dy, self.wplanes[i].w, mask=rs, out=dx))
-                    else:
-                        self._k("linear_bwd_dx_L%d" % i, "mfma", 2.0 * Bm * self.Ws[i].shape[0] * self.Ws[i].shape[1],
-                                lambda dy=dy, i=i, rs=rs, dx=dx: p.linear_bwd_dx(dy, self.Ws[i], relu_src=rs, out=dx))
+                    if i == 0 and h2 and not (n_layers > 1 and self.narrow[1]):
+                        ops.h2_amax(dy, self.dh0_amax[m])            # (layer 1's backward was not the narrow kernel that leaves the record)
+                    # (only layer 0 is ever in the f16x2 family here: its dy comes with the micro-batch's d h0 record)
+                    self._k("linear_bwd_dx_L%d" % i, "mfma", 2.0 * Bm * self.Ws[i].shape[0] * self.Ws[i].shape[1],
+                            lambda dy=dy, i=i, rs=rs, dx=dx, m=m: self.gemm[i].dgrad(dy, self.dh0_amax[m] if i == 0 else None, rs, dx))
                     if m == 0:
                         dw_todo.append(i)
                 dy = dx
@@ -1108,15 +1091,9 @@ class ShardedDeepFMEngine:
                     torch.maximum(self.dh0_amax[0], self.dh0_amax[1], out=self.dh0_amax_all)
                     for r in self.dh0_amax[2:]:
                         torch.maximum(self.dh0_amax_all, r, out=self.dh0_amax_all)
-                self._k("linear_bwd_dw_L%d" % i, "mfma", 2.0 * B * self.Ws[i].shape[0] * self.Ws[i].shape[1],
-                        lambda xin=xin, dyi=dyi, i=i: ops.h2_wgrad(xin, self.x_amax_all, dyi, self.dh0_amax_all, 1.0, self.gWs[i], self.gbs[i],
-                                                                   workspace=self.wg_ws[i]))
-            elif self.wg_ws[i] is not None:
-                self._k("linear_bwd_dw_L%d" % i, "mfma", 2.0 * B * self.Ws[i].shape[0] * self.Ws[i].shape[1],
-                        lambda xin=xin, dyi=dyi, i=i: ops.bf3_wgrad(xin, dyi, 1.0, self.gWs[i], self.gbs[i], workspace=self.wg_ws[i]))
-            else:
-                self._k("linear_bwd_dw_L%d" % i, "mfma", 2.0 * B * self.Ws[i].shape[0] * self.Ws[i].shape[1],
-                        lambda xin=xin, dyi=dyi, i=i: p.linear_bwd_dw(xin, dyi, 1.0, self.gWs[i], self.gbs[i], workspace=self.dw_ws[i]))
+            xam, dyam = (self.x_amax_all, self.dh0_amax_all) if i == 0 else (None, None)
+            self._k("linear_bwd_dw_L%d" % i, "mfma", 2.0 * B * self.Ws[i].shape[0] * self.Ws[i].shape[1],
+                    lambda xin=xin, dyi=dyi, i=i, xam=xam, dyam=dyam: self.gemm[i].wgrad(xin, xam, dyi, dyam, 1.0, self.gWs[i], self.gbs[i]))
         if not prefetched:
             # Second half of the next batch's routing (id exchange + owner-side plan: ~50 launches for two micro-batches).  Issued
             # HERE, after the last gradient exchange / K4 and the wgrads have been handed to the GPU: in front of them (round 2)
@@ -1217,25 +1194,20 @@ class ShardedDCNEngine:
             for r0 in range(0, F * rps, 1 << 24):
                 self.table[r0:r0 + (1 << 24)].normal_(0.0, std, generator=gt).clamp_(-2 * std, 2 * std)
         self.x0 = torch.zeros((B, ld), **f32)
-        self.zero_logit = torch.zeros(B, **f32)
-        self.prob, self.d_logit, self.loss = torch.empty(B, **f32), torch.empty(B, **f32), torch.zeros(1, **f32)
-        self.ws = torch.empty(1024, **f32)
         self._cuda = torch.device(device).type == "cuda"
         self.mb = 1
         # The dense half -- cross stack, MLP, loss and their backward -- is dcn_engine.DCNDense, the SAME object the single-GPU DCNEngine
         # runs (round 5): wide GEMMs on pre-split weights in the operand split the library reports ("f16x2" by default; x0's amax record
         # comes from a pass over the rows this rank received, so no record has to travel with the exchange), gradients accumulated
-        # into the all-reduce bucket instead of applied in place.  The generic in-kernel-split path below remains for primitives other
-        # than HipPrims (the oracle-backed ones of the gloo tests).
-        self.core = None
-        if self._cuda and self.p is HipPrims:
-            from .dcn_engine import DCNDense
-            self.core = DCNDense(self.cross_W, self.cross_b, self.Ws, self.bs, B, self.in_dim, ld, diag_scale, device,
-                                 grads=(self.g_cross_W, self.g_cross_b, self.gWs, self.gbs))
-            self.loss = self.core.loss
+        # into the all-reduce bucket instead of applied in place.  With primitives other than HipPrims (the oracle-backed ones of the
+        # gloo tests) the same object runs every product in the plain family on those primitives.
+        from .dcn_engine import DCNDense
+        self.core = DCNDense(self.cross_W, self.cross_b, self.Ws, self.bs, B, self.in_dim, ld, diag_scale, device,
+                             grads=(self.g_cross_W, self.g_cross_b, self.gWs, self.gbs), prims=None if self.p is HipPrims else self.p)
+        self.prob, self.d_logit, self.loss = self.core.prob, self.core.d_logit, self.core.loss
 
-    h2 = property(lambda self: bool(self.core is not None and self.core.h2))
-    h2_all_wide = property(lambda self: bool(self.core is not None and self.core.h2_all_wide))
+    h2 = property(lambda self: bool(self.core.h2))
+    h2_all_wide = property(lambda self: bool(self.core.h2_all_wide))
 
     def enable_kernel_events(self, on):           # bench.py contract; the sharded DCN step reports no per-kernel rows
         pass
@@ -1244,8 +1216,7 @@ class ShardedDCNEngine:
         return {}
 
     def train_step(self, keys, dense, labels, next_keys=None):
-        p, F, D, B, W, lr, n_in, ld = self.p, self.F, self.D, self.B, self.world, self.lr, self.in_dim, self.ld
-        f32 = dict(dtype=torch.float32, device=self.x0.device)
+        p, F, D, W, lr, ld = self.p, self.F, self.D, self.world, self.lr, self.ld
         # ---- embeddings: route, owner-side gather, rows back, K3 over the received rows -------------------------------------------
         route = self.ex.route(keys, hashed=True)
         got_rows, _ = self.ex.fetch(route, self.table, None)
@@ -1253,57 +1224,11 @@ class ShardedDCNEngine:
                        ld_concat=ld, concat=self.x0, want_sum_x=False, want_fm=False)
         if self.Nd:
             self.x0[:, F * D:F * D + self.Nd].copy_(dense)
-        x0 = self.x0[:, :n_in]
-        if self.core is not None:
-            # cross stack + MLP + loss + backward on the shared dense core; every weight gradient goes into the bucket
-            self.core.ensure_fresh()
-            self.flat_grads.zero_()
-            d_x0 = self.core.step(self.x0, labels, lr)
-            return self._finish_step(route, d_x0)
-        # ---- forward: cross stack, MLP, loss (mean over the rank's batch; the 1 / W of the global mean is folded into the step) --
-        xs, prods = [x0], []
-        for Wc, bc in zip(self.cross_W, self.cross_b):
-            out, prod = p.cross_fwd(x0, xs[-1], Wc, bc, self.diag, want_prod=True)
-            xs.append(out)
-            prods.append(prod)
-        hs, x = [], xs[-1]
-        for i, (Wm, bm) in enumerate(zip(self.Ws, self.bs)):
-            h = torch.empty((B, _pad4(Wm.shape[1])), **f32)[:, :Wm.shape[1]]
-            x = p.linear_fwd(x, Wm, bm, self.acts[i], out=h)
-            hs.append(x)
-        p.bce_fwd_bwd(self.zero_logit, labels, ops.LOSS_SIGMOID_CE, workspace=self.ws, logits_b=hs[-1],
-                      out=(self.prob, self.d_logit, self.loss))
-        # ---- backward: MLP, then the cross stack; every weight gradient goes into the bucket --------------------------------------
+        # cross stack + MLP + loss (mean over the rank's batch; the 1 / W of the global mean is folded into the step) + backward on the
+        # shared dense core; every weight gradient goes into the bucket
+        self.core.ensure_fresh()
         self.flat_grads.zero_()
-        dy = self.d_logit.reshape(-1, 1)
-        d_top = torch.zeros((B, ld), **f32)[:, :n_in]
-        for i in range(len(self.Ws) - 1, -1, -1):
-            xin = xs[-1] if i == 0 else hs[i - 1]
-            if i > 0:
-                dx = torch.empty((B, _pad4(xin.shape[1])), **f32)[:, :xin.shape[1]]
-                rs = hs[i - 1] if self.acts[i - 1] else None
-            else:
-                dx, rs = d_top, None
-            p.linear_bwd_dx(dy, self.Ws[i], relu_src=rs, out=dx)
-            p.linear_bwd_dw(xin, dy, 1.0, self.gWs[i], self.gbs[i])
-            dy = dx
-        d_out = d_top
-        d_x0 = torch.zeros((B, ld), **f32)[:, :n_in]
-        for l in range(len(self.cross_W) - 1, -1, -1):
-            if self.diag == 0.0:         # the dgrad accumulates into the d_out buffer itself (see dcn_engine.DCNEngine)
-                d_x = d_out
-                d_prod = p.cross_combine_bwd(x0, prods[l], d_out, 0.0, d_x0, None)
-            else:
-                d_x = torch.zeros((B, ld), **f32)[:, :n_in]
-                d_prod = p.cross_combine_bwd(x0, prods[l], d_out, self.diag, d_x0, d_x)
-            p.linear_bwd_dx(d_prod, self.cross_W[l], None, accumulate=True, out=d_x)
-            p.linear_bwd_dw(xs[l], d_prod, 1.0, self.g_cross_W[l], self.g_cross_b[l])
-            d_out = d_x
-        d_x0.add_(d_out)                                  # the first layer's x IS x0
-        return self._finish_step(route, d_x0)
-
-    def _finish_step(self, route, d_x0):
-        p, W, lr = self.p, self.world, self.lr
+        d_x0 = self.core.step(self.x0, labels, lr)
         # ---- C4: the replicated weights' gradients (asynchronous: the embedding gradients travel meanwhile) ------------------------
         work = self.tr.allreduce(self.flat_grads, async_op=True) if not self.ex.local else None
         # ---- C3: embedding-row gradients to their owners + sorted scatter with the SGD step --------------------------------------------
@@ -1312,6 +1237,5 @@ class ShardedDCNEngine:
         if work is not None:
             work.wait()
         p.axpy(-lr / W, self.flat_grads, self.flat_params)
-        if self.core is not None:
-            self.core.refresh_planes()                   # the weights just moved: their planes follow
+        self.core.refresh_planes()                       # the weights just moved: their planes follow
         return self.loss

@@ -109,6 +109,92 @@ def test_h2_linear_nt_epilogues_and_edges(ops):
         ops.h2_linear_nt(torch.zeros((8, 64), device="cuda"), None, ops.H2WeightPlanes(torch.ones((64, 128), device="cuda")).wt)
 
 
+@pytest.mark.parametrize("M,K,N", [(515, 300, 257), (1000, 83, 40)])
+@pytest.mark.parametrize("family", ["plain", "bf16x3", "f16x2"])
+def test_gemm_family_methods_are_the_direct_calls(ops, family, M, K, N):
+    """PlainWeight / WeightPlanes / H2WeightPlanes: fwd (bias + ReLU), dgrad (mask; accumulate into a preset buffer), wgrad (with a bias
+    destination) and, on the planes families, cross_fwd are bit-equal to the direct ops.* call of the family on cloned operands and
+    destinations.  The record a method returns: None for plain and bf16x3, the out_amax buffer -- max |out| as float bits -- for f16x2."""
+    g = torch.Generator(device="cuda").manual_seed(M + N)
+    rnd = lambda r, c, s=1.0: torch.randn((r, (c + 3) // 4 * 4), device="cuda", generator=g)[:, :c] * s
+    x, W, b = rnd(M, K), rnd(K, N, 0.1), torch.randn((N,), device="cuda", generator=g)
+    dy, mask, preset = rnd(M, N, 1e-3), rnd(M, K), rnd(M, K)
+    dW0, db0 = rnd(K, N), torch.zeros((N,), device="cuda")
+    Wd = W.clone()                                        # the direct calls' own copy of the weight (and planes of it)
+    if family == "plain":
+        fam = ops.PlainWeight(W, dw_ws=ops.linear_bwd_dw_workspace(M, K, N, "cuda"))
+        ws = ops.linear_bwd_dw_workspace(M, K, N, "cuda")
+        direct = dict(fwd=lambda o, r: ops.linear_fwd(x.clone(), Wd, b.clone(), 1, out=o),
+                      dgrad=lambda o, r, acc: ops.linear_bwd_dx(dy.clone(), Wd, relu_src=None if acc else mask.clone(), accumulate=acc, out=o),
+                      wgrad=lambda dW, db: ops.linear_bwd_dw(x.clone(), dy.clone(), -0.5, dW, db, workspace=ws))
+    elif family == "bf16x3":
+        fam, wp = ops.WeightPlanes(W, wgrad_ws=ops.bf3_wgrad_workspace(M, K, N, "cuda")), ops.WeightPlanes(Wd)
+        ws = ops.bf3_wgrad_workspace(M, K, N, "cuda")
+        direct = dict(fwd=lambda o, r: ops.bf3_linear_nt(x.clone(), wp.wt, bias=b.clone(), act=1, out=o),
+                      dgrad=lambda o, r, acc: ops.bf3_linear_nt(dy.clone(), wp.w, mask=None if acc else mask.clone(), accumulate=acc, out=o),
+                      wgrad=lambda dW, db: ops.bf3_wgrad(x.clone(), dy.clone(), -0.5, dW, db, workspace=ws))
+    else:
+        fam, wp = ops.H2WeightPlanes(W, wgrad_ws=ops.bf3_wgrad_workspace(M, K, N, "cuda")), ops.H2WeightPlanes(Wd)
+        ws = ops.bf3_wgrad_workspace(M, K, N, "cuda")
+        direct = dict(fwd=lambda o, r: ops.h2_linear_nt(x.clone(), ops.h2_amax(x), wp.wt, bias=b.clone(), act=1, out=o, out_amax=r),
+                      dgrad=lambda o, r, acc: ops.h2_linear_nt(dy.clone(), ops.h2_amax(dy), wp.w, mask=None if acc else mask.clone(),
+                                                               accumulate=acc, out=o, out_amax=r),
+                      wgrad=lambda dW, db: ops.h2_wgrad(x.clone(), ops.h2_amax(x), dy.clone(), ops.h2_amax(dy), -0.5, dW, db, workspace=ws))
+    assert fam.wants_amax == (family == "f16x2")
+    xa, dya = (ops.h2_amax(x), ops.h2_amax(dy)) if fam.wants_amax else (None, None)
+
+    def check_record(ret, rec, out, what):
+        if family == "f16x2":
+            assert ret is rec and int(rec.item()) == _amax_bits(out), what
+        else:
+            assert ret is None and int(rec.item()) == 0x7f000000, what          # (the record argument is ignored)
+
+    def recs():
+        return [ops.h2_record("cuda").fill_(0x7f000000) for _ in range(2)]
+
+    # fwd: bias + ReLU
+    (o1, o2), (r1, r2) = [rnd(M, N) for _ in range(2)], recs()
+    ret = fam.fwd(x, xa, b, 1, o1, out_amax=r1)
+    direct["fwd"](o2, r2)
+    assert torch.equal(o1, o2) and (o1 == 0).any() and (o1 > 0).any()
+    check_record(ret, r1, o1, "fwd")
+    # dgrad with the ReLU' mask; dgrad accumulating into a preset buffer
+    for acc in (False, True):
+        (o1, o2), (r1, r2) = [preset.clone() for _ in range(2)], recs()
+        ret = fam.dgrad(dy, dya, None if acc else mask, o1, accumulate=acc, out_amax=r1)
+        direct["dgrad"](o2, r2, acc)
+        assert torch.equal(o1, o2) and not torch.equal(o1, preset), acc
+        if not acc:
+            assert (o1[mask <= 0] == 0).all() and (o1[mask > 0] != 0).any()
+        check_record(ret, r1, o1, "dgrad accumulate=%s" % acc)
+    # wgrad into a preset weight destination, with a bias destination (zero: see the plain family's bound below)
+    (dW1, dW2), (db1, db2) = [dW0.clone() for _ in range(2)], [db0.clone() for _ in range(2)]
+    assert fam.wgrad(x, xa, dy, dya, -0.5, dW1, db1) is None
+    direct["wgrad"](dW2, db2)
+    assert torch.equal(dW1, dW2) and not torch.equal(dW1, dW0) and not torch.equal(db1, db0)
+    if family == "plain":
+        # dr_linear_bwd_dw combines the bias column sums of its split-K blocks by fp32 atomics, workspace or not: two direct calls differ in
+        # the last bits.  The bound tests/test_gpu_kernels.py puts on that sum (1e-5 * sqrt(M) * 4: unit-normal dy, scale 1, a zero
+        # destination) scales with dy (here 1e-3 x unit-normal) and the scale (0.5)
+        assert (db1 - db2).abs().max().item() <= 4e-5 * M ** 0.5 * 0.5 * 1e-3
+    else:
+        assert torch.equal(db1, db2)
+    # cross_fwd (square weight) on the planes families, with the product
+    if family != "plain" and (M, K) == (515, 300):
+        Wc, x0 = rnd(K, K, 0.05), rnd(M, K)
+        bc = torch.randn((K,), device="cuda", generator=g)
+        r1, r2 = recs()
+        if family == "bf16x3":
+            out, prod, ret = ops.WeightPlanes(Wc).cross_fwd(x0, x, xa, bc, 0.3, True, out_amax=r1)
+            out2, prod2 = ops.bf3_cross_fwd(x0.clone(), x.clone(), ops.WeightPlanes(Wc.clone()).wt, bc.clone(), 0.3, want_prod=True)
+        else:
+            out, prod, ret = ops.H2WeightPlanes(Wc).cross_fwd(x0, x, xa, bc, 0.3, True, out_amax=r1)
+            out2, prod2 = ops.h2_cross_fwd(x0.clone(), x.clone(), ops.h2_amax(x), ops.H2WeightPlanes(Wc.clone()).wt, bc.clone(), 0.3,
+                                           want_prod=True, out_amax=r2)
+        assert torch.equal(out, out2) and torch.equal(prod, prod2)
+        check_record(ret, r1, out, "cross_fwd")
+
+
 @pytest.mark.parametrize("M,K,N", [(3000, 1677, 256), (5000, 300, 257), (777, 96, 130)])
 def test_h2_wgrad_against_fp64(ops, M, K, N):
     g = torch.Generator(device="cuda").manual_seed(K)
