@@ -1436,3 +1436,22 @@ def skipgram_pairs(seqs, window):
     ok = inside[None, :, :] & (partner >= 0) & (center >= 0)
     minus = torch.full_like(partner, -1)
     return torch.where(ok, center, minus).reshape(-1), torch.where(ok, partner, minus).reshape(-1)
+
+
+# ---- sampled softmax (csrc/sampled_softmax.hip) ---------------------------------------------------------------------------------------------
+def sampled_softmax(u, table, labels, sampled, log_q_true=None, log_q_sampled=None, sample_weight=None, remove_accidental_hits=True,
+                    row_scale=1.0):
+    """(loss_rows [B], d_u [B, D], d_true [B, D], d_sampled [S, D]) of tf.nn.sampled_softmax_loss with num_true = 1 and NO per-class bias
+    (the paper's softmax has none; TensorFlow's users pass zeros): loss_i = w_i (log(exp(t_i) + sum_j exp(s_ij)) - t_i), t_i =
+    u_i . table[labels_i] - log_q_true_i, s_ij = u_i . table[sampled_j] - log_q_sampled_j over the S classes `sampled` that the whole
+    batch shares, an accidental hit (sampled_j == labels_i) left out.  A training-step op like ops.sgns_fwd with row_scale, computed on
+    u.detach(): the three buffers are the gradients of row_scale * sum(loss_rows); the caller continues with u.backward(d_u) and hands
+    d_true (ids labels [B, 1]) and d_sampled (ids sampled [S, 1]) to sgns_apply_rows.  A row with labels_i < 0 is padding (loss 0, zero
+    gradient rows, its u_i never read as a value); a sampled id < 0 is left out.  No [B, S] tensor is written."""
+    ud, td = u.detach(), table.detach()
+    ws = ops.sampled_softmax_workspace(ud.shape[0], sampled.shape[0], td.shape[1], td.device) if ud.dim() == 2 and td.dim() == 2 else None
+    true_logit, row_lse, loss_rows, _ = ops.sampled_softmax_fwd(ud, td, labels, sampled, log_q_true, log_q_sampled, sample_weight,
+                                                                remove_accidental_hits, workspace=ws)
+    d_u, d_true, d_sampled = ops.sampled_softmax_bwd(ud, td, labels, sampled, true_logit, row_lse, log_q_sampled, sample_weight,
+                                                     remove_accidental_hits, row_scale, workspace=ws)
+    return loss_rows, d_u, d_true, d_sampled

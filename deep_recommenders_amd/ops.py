@@ -3378,3 +3378,126 @@ def block_csr(cnt, local, weight=None, add_self=False, n_valid=None):
     _status(lib().dr_block_csr(ptr(cnt), ptr(local), ptr(weight), n_dst, fanout, extra, ptr(n_valid), ptr(row_ptr), ptr(col), ptr(val),
                                ptr(ws), ws.numel(), stream_ptr()), "dr_block_csr")
     return row_ptr, col, val
+
+
+# ---- sampled softmax (csrc/sampled_softmax.hip): YoutubeNet's training loss ------------------------------------------------------------
+SAMPLED_SOFTMAX_TILE = 64           # DR_SAMPLED_SOFTMAX_TILE: rows / columns of a tile
+SAMPLED_SOFTMAX_COL_GROUP = 128     # DR_SAMPLED_SOFTMAX_COL_GROUP: a column segment has at least this many columns ...
+SAMPLED_SOFTMAX_MAX_GROUPS = 8      # DR_SAMPLED_SOFTMAX_MAX_GROUPS: ... and there are at most this many
+SAMPLED_SOFTMAX_SPLIT_TILES = 128   # DR_SAMPLED_SOFTMAX_SPLIT_TILES: up to this many row tiles every segment has a block of its own
+SAMPLED_SOFTMAX_ROW_CHUNK = 128     # DR_SAMPLED_SOFTMAX_ROW_CHUNK: a d_sampled partial covers at least this many rows ...
+SAMPLED_SOFTMAX_MAX_CHUNKS = 64     # DR_SAMPLED_SOFTMAX_MAX_CHUNKS: ... and there are at most this many
+
+
+def sampled_softmax_col_groups(B, S, D):
+    """blocks per row tile of the row-owning kernels (1, or the number of column segments): dr_sampled_softmax_col_groups"""
+    n = lib().dr_sampled_softmax_col_groups(int(B), int(S), int(D))
+    if n < 0:
+        _status(n, "dr_sampled_softmax_col_groups")
+    return n
+
+
+def sampled_softmax_row_chunks(B, S, D):
+    """number of d_sampled partials of the column-owning sweep: dr_sampled_softmax_row_chunks"""
+    n = lib().dr_sampled_softmax_row_chunks(int(B), int(S), int(D))
+    if n < 0:
+        _status(n, "dr_sampled_softmax_row_chunks")
+    return n
+
+
+def sampled_softmax_workspace_bytes(B, S, D):
+    """dr_sampled_softmax_workspace_bytes: host arithmetic, no device"""
+    n = lib().dr_sampled_softmax_workspace_bytes(int(B), int(S), int(D))
+    if n < 0:
+        _status(n, "dr_sampled_softmax_workspace_bytes")
+    return n
+
+
+def sampled_softmax_workspace(B, S, D, device):
+    return torch.empty(max(16, sampled_softmax_workspace_bytes(B, S, D)), dtype=torch.uint8, device=device)
+
+
+def _ssm_vec(t, n, what, dtype=torch.float32):
+    if t is None:
+        return None
+    if t.dtype != dtype or t.numel() != n:
+        raise ValueError("sampled_softmax: %s must be %s with %d values, got %s %s" % (what, dtype, n, t.dtype, tuple(t.shape)))
+    return t.reshape(n).contiguous()
+
+
+def _ssm_args(u, table, labels, sampled, log_q_true, log_q_sampled, sample_weight):
+    """validates the domain of dr_sampled_softmax_*; returns (B, S, V, D, ld_u, labels, sampled, log_q_true, log_q_sampled, sample_weight)"""
+    if table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
+        raise ValueError("sampled_softmax: table must be contiguous fp32 [V, D] (a view is refused: its rows are read in place by id), "
+                         "got %s %s with strides %s" % (table.dtype, tuple(table.shape), tuple(table.stride())))
+    V, D = table.shape
+    if D % 4 != 0 or not 4 <= D <= 256:
+        raise ValueError("sampled_softmax: D must be a multiple of 4 in [4, 256] (the slab's domain), got %d" % D)
+    if not 1 <= V < 2 ** 31:
+        raise ValueError("sampled_softmax: needs 1 <= V < 2^31 classes, got %d" % V)
+    ld_u = _row_pitch("sampled_softmax", u, D, "u")
+    B = u.shape[0]
+    if labels.dtype != torch.int64 or labels.numel() != B:
+        raise ValueError("sampled_softmax: labels must be int64 [%d], got %s %s" % (B, labels.dtype, tuple(labels.shape)))
+    if sampled.dtype != torch.int64 or sampled.dim() != 1:
+        raise ValueError("sampled_softmax: sampled must be int64 [S], got %s %s" % (sampled.dtype, tuple(sampled.shape)))
+    S = sampled.shape[0]
+    if not 1 <= S < 2 ** 31:
+        raise ValueError("sampled_softmax: needs 1 <= S < 2^31 sampled classes, got %d" % S)
+    for t, what in ((u, "u"), (labels, "labels"), (sampled, "sampled"), (log_q_true, "log_q_true"), (log_q_sampled, "log_q_sampled"),
+                    (sample_weight, "sample_weight")):
+        if t is not None and t.device != table.device:
+            raise ValueError("sampled_softmax: %s is on %s, the table on %s" % (what, t.device, table.device))
+    return (B, S, V, D, ld_u, labels.reshape(B).contiguous(), sampled.contiguous(), _ssm_vec(log_q_true, B, "log_q_true"),
+            _ssm_vec(log_q_sampled, S, "log_q_sampled"), _ssm_vec(sample_weight, B, "sample_weight"))
+
+
+def sampled_softmax_fwd(u, table, labels, sampled, log_q_true=None, log_q_sampled=None, sample_weight=None, remove_accidental_hits=True,
+                        want_scores=False, workspace=None):
+    """(true_logit [B], row_lse [B], row_loss [B], scores [B, S] | None) of dr_sampled_softmax_fwd: tf.nn.sampled_softmax_loss with
+    num_true = 1 and no bias.  u fp32 [B, D], possibly a view with a row pitch (a multiple of 4); table contiguous fp32 [V, D]; labels
+    int64 [B] (< 0: a padding row, loss 0); sampled int64 [S] shared by the batch (< 0: the column is left out).  Labels and sampled
+    ids must be < V: not checked on the device.  want_scores is for tests and diagnosis: the only [B, S] tensor of the family."""
+    B, S, V, D, ld_u, labels, sampled, log_q_true, log_q_sampled, sample_weight = _ssm_args(u, table, labels, sampled, log_q_true,
+                                                                                             log_q_sampled, sample_weight)
+    dev = table.device
+    true_logit = torch.empty((B,), dtype=torch.float32, device=dev)
+    row_lse = torch.empty((B,), dtype=torch.float32, device=dev)
+    row_loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, S), dtype=torch.float32, device=dev) if want_scores else None
+    if B == 0:
+        return true_logit, row_lse, row_loss, scores
+    if workspace is None:
+        workspace = sampled_softmax_workspace(B, S, D, dev)
+    _status(lib().dr_sampled_softmax_fwd(ptr(u), ld_u, ptr(table), V, D, ptr(labels), B, ptr(sampled), S, ptr(log_q_true),
+                                         ptr(log_q_sampled), ptr(sample_weight), 1 if remove_accidental_hits else 0, ptr(true_logit),
+                                         ptr(row_lse), ptr(row_loss), ptr(scores), ptr(workspace), workspace.numel(), stream_ptr()),
+            "dr_sampled_softmax_fwd")
+    return true_logit, row_lse, row_loss, scores
+
+
+def sampled_softmax_bwd(u, table, labels, sampled, true_logit, row_lse, log_q_sampled=None, sample_weight=None,
+                        remove_accidental_hits=True, row_scale=1.0, d_u=None, workspace=None):
+    """(d_u [B, D], d_true [B, D], d_sampled [S, D]) of dr_sampled_softmax_bwd: the gradients of row_scale * sum_i row_loss[i] from the
+    forward's true_logit and row_lse, the scores recomputed.  d_true with ids labels [B, 1] and d_sampled with ids sampled [S, 1] are
+    what K4 takes; d_u may be given as a view with a row pitch and is written at that pitch."""
+    B, S, V, D, ld_u, labels, sampled, _, log_q_sampled, sample_weight = _ssm_args(u, table, labels, sampled, None, log_q_sampled,
+                                                                                  sample_weight)
+    dev = table.device
+    true_logit, row_lse = _ssm_vec(true_logit, B, "true_logit"), _ssm_vec(row_lse, B, "row_lse")
+    if d_u is None:
+        d_u = torch.empty((B, D), dtype=torch.float32, device=dev)
+    ld_du = _row_pitch("sampled_softmax", d_u, D, "d_u")
+    if d_u.shape[0] != B:
+        raise ValueError("sampled_softmax: d_u must have %d rows, got %d" % (B, d_u.shape[0]))
+    d_true = torch.empty((B, D), dtype=torch.float32, device=dev)
+    d_sampled = torch.empty((S, D), dtype=torch.float32, device=dev)
+    if B == 0:
+        return d_u, d_true, d_sampled.zero_()
+    if workspace is None:
+        workspace = sampled_softmax_workspace(B, S, D, dev)
+    _status(lib().dr_sampled_softmax_bwd(ptr(u), ld_u, ptr(table), V, D, ptr(labels), B, ptr(sampled), S, ptr(log_q_sampled),
+                                         ptr(sample_weight), 1 if remove_accidental_hits else 0, float(row_scale), ptr(true_logit),
+                                         ptr(row_lse), ptr(d_u), ld_du, ptr(d_true), ptr(d_sampled), ptr(workspace), workspace.numel(),
+                                         stream_ptr()), "dr_sampled_softmax_bwd")
+    return d_u, d_true, d_sampled

@@ -1453,6 +1453,66 @@ int64_t dr_confusion_hist_workspace_bytes(int64_t n, int32_t num_thresholds);
 int dr_confusion_hist_update(const float* pred, const float* labels, const float* weights, int64_t n, const float* thresholds,
                              int32_t T, int32_t from_logits, double* hist, void* workspace, dr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sampled softmax (csrc/sampled_softmax.hip): the training loss of YoutubeNet (Covington et al., RecSys 2016), which the reference's
+ * README lists and ships no code for.  The arithmetic is TensorFlow's tf.nn.sampled_softmax_loss (_compute_sampled_logits + softmax
+ * cross-entropy) with num_true = 1 and NO per-class bias (the paper's softmax has none; TensorFlow's users pass zeros).  All fp32.
+ *   u [B, D] at the row pitch ld_u; table [V, D] dense, read in place by id (no [S, D] copy); labels int64 [B]; sampled int64 [S], shared
+ *   by the whole batch; log_q_true [B], log_q_sampled [S], sample_weight [B] (w_i; each may be NULL: 0, 0, 1).
+ *     t_i     = u_i . table[labels_i] - log_q_true_i
+ *     s_ij    = u_i . table[sampled_j] - log_q_sampled_j
+ *     keep_ij = sampled_j >= 0 and not (remove_accidental_hits and sampled_j == labels_i)
+ *     lse_i   = log(exp(t_i) + sum_{j kept} exp(s_ij))
+ *     loss_i  = w_i (lse_i - t_i)
+ *   TensorFlow adds -FLT_MAX to an accidental hit, whose exp is 0 in fp32 beside the finite true logit: leaving the entry out is the
+ *   same arithmetic.  An accidental hit masks one (i, j) entry; the column's row is still read by the other examples.
+ *   A row with labels_i < 0 is padding: u_i is replaced by zeros on load (a NaN in it reaches no output), true_logit, row_lse and
+ *   row_loss are 0 and so are its gradient rows.  A sampled id < 0 leaves its column out of every row and its d_sampled row is 0.  No
+ *   id < 0 is turned into an address.  Labels and sampled ids must be < V: this is NOT checked on the device.
+ *   dr_sampled_softmax_fwd   writes true_logit [B] (t_i), row_lse [B], row_loss [B] and, unless NULL, scores [B, S] dense (s_ij, -inf at
+ *                            left-out entries; a padding row's are those of u_i = 0) -- for tests and diagnosis, never for training.
+ *                            Without it nothing of size B * S is written: online softmax over 64-column tiles.
+ *   dr_sampled_softmax_bwd   from the saved true_logit and row_lse, the gradients of row_scale * sum_i loss_i, the scores recomputed:
+ *                              g_i = row_scale w_i (exp(t_i - lse_i) - 1),  G_ij = row_scale w_i exp(s_ij - lse_i)  (0 where left out)
+ *                              d_u [B, D] at the pitch ld_du  = g_i table[labels_i] + sum_j G_ij table[sampled_j]
+ *                              d_true [B, D] dense            = g_i u_i            what K4 takes as d_concat for ids labels [B, 1]
+ *                              d_sampled [S, D] dense         = sum_i G_ij u_i     what K4 takes as d_concat for ids sampled [S, 1]
+ *                            Two sweeps: a row-owning one (d_u, d_true) over all column tiles, a column-owning one (d_sampled) over a
+ *                            chunk of the batch, the chunk partials added in chunk order.  Four products for the two of the
+ *                            mathematics; no float atomics, no B * S tensor, bit-identical from run to run.
+ *   Every product is v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation), the true logit included: a sampled id equal to
+ *   the label scores the bits of the true logit.  The columns are cut into dr_sampled_softmax_col_groups' segments -- a function of S
+ *   alone: min(DR_SAMPLED_SOFTMAX_MAX_GROUPS, ceil(S / DR_SAMPLED_SOFTMAX_COL_GROUP)), evened out over whole tiles -- every segment
+ *   starts from fresh accumulators and the segments are combined in ascending order, whether one block walks them all (more than
+ *   DR_SAMPLED_SOFTMAX_SPLIT_TILES row tiles) or each has a block of its own: true_logit, row_lse, row_loss, d_u and d_true of a row
+ *   depend on that row and `sampled` alone, not on B or the other rows.  dr_sampled_softmax_col_groups returns the number of blocks per
+ *   row tile (1 or the segment count), dr_sampled_softmax_row_chunks the number of d_sampled partials (<= DR_SAMPLED_SOFTMAX_MAX_CHUNKS,
+ *   at least DR_SAMPLED_SOFTMAX_ROW_CHUNK rows each): pure functions of (B, S, D), no device query.
+ *   workspace: 16-byte aligned, dr_sampled_softmax_workspace_bytes(B, S, D) bytes (the same for both entry points): the (max, sum)
+ *   pairs, the d_u partials of the split form and the d_sampled partials; nothing that grows like B * S.
+ *   Domain: D % 4 == 0, 4 <= D <= 256, 1 <= S < 2^31, 1 <= V < 2^31, B >= 0; u, table, d_u, d_true, d_sampled 16-byte aligned, ld_u and
+ *   ld_du multiples of 4 and >= D.  Anything else or a NULL required pointer is DR_ESHAPE / DR_EINVAL before a launch (the three
+ *   sizing functions return the negative status).  B == 0 is DR_OK with nothing written.
+ * ---------------------------------------------------------------------------------------- */
+#define DR_SAMPLED_SOFTMAX_TILE 64
+#define DR_SAMPLED_SOFTMAX_COL_GROUP 128
+#define DR_SAMPLED_SOFTMAX_MAX_GROUPS 8
+#define DR_SAMPLED_SOFTMAX_SPLIT_TILES 128
+#define DR_SAMPLED_SOFTMAX_ROW_CHUNK 128
+#define DR_SAMPLED_SOFTMAX_MAX_CHUNKS 64
+int64_t dr_sampled_softmax_workspace_bytes(int64_t B, int64_t S, int32_t D);
+int32_t dr_sampled_softmax_col_groups(int64_t B, int64_t S, int32_t D);
+int32_t dr_sampled_softmax_row_chunks(int64_t B, int64_t S, int32_t D);
+int dr_sampled_softmax_fwd(const float* u, int64_t ld_u, const float* table, int64_t V, int32_t D, const int64_t* labels, int64_t B,
+                           const int64_t* sampled, int64_t S, const float* log_q_true, const float* log_q_sampled,
+                           const float* sample_weight, int32_t remove_accidental_hits, float* true_logit, float* row_lse,
+                           float* row_loss, float* scores, void* workspace, int64_t workspace_bytes, dr_stream_t stream);
+int dr_sampled_softmax_bwd(const float* u, int64_t ld_u, const float* table, int64_t V, int32_t D, const int64_t* labels, int64_t B,
+                           const int64_t* sampled, int64_t S, const float* log_q_sampled, const float* sample_weight,
+                           int32_t remove_accidental_hits, float row_scale, const float* true_logit, const float* row_lse, float* d_u,
+                           int64_t ld_du, float* d_true, float* d_sampled, void* workspace, int64_t workspace_bytes,
+                           dr_stream_t stream);
+
 /* dr_clock_stamp: dst[0] = the device's constant-rate wall clock (100 MHz ticks) when a one-thread kernel reaches the head of
  * `stream`.  Measurement plumbing with no reference counterpart: bench.py brackets the sharded step's cross-stream waits with two
  * stamps to report the EXPOSED part of the exchange (HIP timing events around a wait serialise the step). */
