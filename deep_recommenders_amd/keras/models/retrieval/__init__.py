@@ -6,6 +6,7 @@ from deep_recommenders_amd.keras.models.retrieval.skipgram import SkipGram
 from deep_recommenders_amd.keras.models.retrieval.skipgram import Item2Vec
 from deep_recommenders_amd.keras.models.retrieval.skipgram import DeepWalk
 from deep_recommenders_amd.keras.models.retrieval.youtubenet import YoutubeNet
+from deep_recommenders_amd.keras.models.retrieval.ebr import EBR
 from deep_recommenders_amd.keras.models.retrieval.eges import EGES
 from deep_recommenders_amd.keras.models.retrieval.eges import graph_from_sessions
 from deep_recommenders_amd.keras.models.retrieval.airbnb import Airbnb

@@ -1455,3 +1455,32 @@ def sampled_softmax(u, table, labels, sampled, log_q_true=None, log_q_sampled=No
     d_u, d_true, d_sampled = ops.sampled_softmax_bwd(ud, td, labels, sampled, true_logit, row_lse, log_q_sampled, sample_weight,
                                                      remove_accidental_hits, row_scale, workspace=ws)
     return loss_rows, d_u, d_true, d_sampled
+
+
+# ---- margin ranking loss (csrc/margin_rank.hip) -----------------------------------------------------------------------------------------------
+def margin_rank(q, pos, neg=None, pos_ids=None, neg_ids=None, sample_weight=None, margin=0.2, metric="cosine", num_hard_negatives=0,
+                row_scale=1.0):
+    """(row_loss [B], row_active int32 [B], d_q [B, D], d_pos [B, D], d_neg [S, D] | None) of EBR's triplet loss: loss_i =
+    w_i sum_{j in N(i)} max(0, margin - s(q_i, pos_i) + s(q_i, neg_j)), s the cosine (metric "dot": the dot product) and N(i) the kept
+    negatives of row i, or its num_hard_negatives highest-scoring ones (online hard-negative mining).  neg=None is in-batch: the
+    negatives of a row are the pos rows of the others; the part of the gradient that reaches pos as a negative is then already added,
+    d_pos = d_pos + 1 * d_neg elementwise, and None is returned for d_neg.  A training-step op like sampled_softmax, computed on
+    detached inputs: the buffers are the gradients of row_scale * sum(row_loss) with respect to the RAW q, pos and neg (the L2
+    normalisation is inside the kernels); the caller continues with torch.autograd.backward([q, pos], [d_q, d_pos]).  A row with
+    pos_ids_i < 0 is padding (loss 0, zero gradient rows, its q_i never read as a value); a negative with id < 0 is left out; with
+    both id arrays a negative carrying the row's pos id is left out.  No [B, S] tensor is written."""
+    qd, pd = q.detach(), pos.detach()
+    nd = None if neg is None else neg.detach()
+    _, K = ops.margin_rank_options(qd.shape[-1], metric, num_hard_negatives)
+    ws = None
+    if qd.dim() == 2 and (nd is None or nd.dim() == 2) and qd.shape[0] > 0:
+        ws = ops.margin_rank_workspace(qd.shape[0], qd.shape[0] if nd is None else nd.shape[0], qd.shape[1], K, qd.device)
+    pos_score, row_loss, row_active, hard_idx, _ = ops.margin_rank_fwd(qd, pd, nd, pos_ids, neg_ids, sample_weight, margin, metric, K,
+                                                                       workspace=ws)
+    d_q, d_pos, d_neg = ops.margin_rank_bwd(qd, pd, nd, pos_score, hard_idx, pos_ids, neg_ids, sample_weight, margin, metric, K,
+                                            row_scale, workspace=ws)
+    if nd is None:
+        if d_pos.numel() > 0:
+            ops.axpy(1.0, d_neg, d_pos)
+        d_neg = None
+    return row_loss, row_active, d_q, d_pos, d_neg

@@ -3501,3 +3501,158 @@ def sampled_softmax_bwd(u, table, labels, sampled, true_logit, row_lse, log_q_sa
                                          ptr(row_lse), ptr(d_u), ld_du, ptr(d_true), ptr(d_sampled), ptr(workspace), workspace.numel(),
                                          stream_ptr()), "dr_sampled_softmax_bwd")
     return d_u, d_true, d_sampled
+
+
+# ---- margin ranking loss with hard-negative mining (csrc/margin_rank.hip): EBR's training loss ----------------------------------------
+MARGIN_RANK_TILE = 64               # DR_MARGIN_RANK_TILE: rows / columns of a tile
+MARGIN_RANK_COL_GROUP = 128         # DR_MARGIN_RANK_COL_GROUP: a column segment has at least this many columns ...
+MARGIN_RANK_MAX_GROUPS = 8          # DR_MARGIN_RANK_MAX_GROUPS: ... and there are at most this many
+MARGIN_RANK_SPLIT_TILES = 128       # DR_MARGIN_RANK_SPLIT_TILES: up to this many row tiles every segment has a block of its own
+MARGIN_RANK_ROW_CHUNK = 128         # DR_MARGIN_RANK_ROW_CHUNK: a d_neg partial covers at least this many rows ...
+MARGIN_RANK_MAX_CHUNKS = 64         # DR_MARGIN_RANK_MAX_CHUNKS: ... and there are at most this many
+MARGIN_RANK_MAX_HARD = 8            # DR_MARGIN_RANK_MAX_HARD: the longest hard-negative list
+MARGIN_RANK_EPS = 1e-12             # tf.math.l2_normalize's epsilon
+MARGIN_RANK_METRICS = {"dot": 0, "cosine": 1}
+
+
+def _mr_plan(fn, name, B, S, D):
+    n = fn(int(B), int(S), int(D))
+    if n < 0:
+        _status(n, name)
+    return n
+
+
+def margin_rank_col_groups(B, S, D):
+    """blocks per row tile of the row-owning kernels (1, or the number of column segments): dr_margin_rank_col_groups"""
+    return _mr_plan(lib().dr_margin_rank_col_groups, "dr_margin_rank_col_groups", B, S, D)
+
+
+def margin_rank_col_segments(B, S, D):
+    """number of column segments, a function of S alone: dr_margin_rank_col_segments"""
+    return _mr_plan(lib().dr_margin_rank_col_segments, "dr_margin_rank_col_segments", B, S, D)
+
+
+def margin_rank_row_chunks(B, S, D):
+    """number of d_neg partials of the column-owning sweep: dr_margin_rank_row_chunks"""
+    return _mr_plan(lib().dr_margin_rank_row_chunks, "dr_margin_rank_row_chunks", B, S, D)
+
+
+def margin_rank_workspace_bytes(B, S, D, num_hard=0):
+    """dr_margin_rank_workspace_bytes: host arithmetic, no device"""
+    n = lib().dr_margin_rank_workspace_bytes(int(B), int(S), int(D), int(num_hard))
+    if n < 0:
+        _status(n, "dr_margin_rank_workspace_bytes")
+    return n
+
+
+def margin_rank_workspace(B, S, D, num_hard, device):
+    return torch.empty(max(16, margin_rank_workspace_bytes(B, S, D, num_hard)), dtype=torch.uint8, device=device)
+
+
+def margin_rank_options(D, metric, num_hard):
+    """the host-side domain of the options, shared with the EBR model: (metric code, num_hard); ValueError otherwise"""
+    if int(D) % 4 != 0 or not 4 <= int(D) <= 256:
+        raise ValueError("margin_rank: D must be a multiple of 4 in [4, 256], got %d" % int(D))
+    if metric not in MARGIN_RANK_METRICS:
+        raise ValueError("margin_rank: metric must be one of %s, got %r" % (sorted(MARGIN_RANK_METRICS), metric))
+    if int(num_hard) != num_hard or not 0 <= int(num_hard) <= MARGIN_RANK_MAX_HARD:
+        raise ValueError("margin_rank: num_hard must be an integer in [0, %d], got %r" % (MARGIN_RANK_MAX_HARD, num_hard))
+    return MARGIN_RANK_METRICS[metric], int(num_hard)
+
+
+def _mr_vec(t, n, what, dtype, dev):
+    if t is None:
+        return None
+    if t.dtype != dtype or t.numel() != n:
+        raise ValueError("margin_rank: %s must be %s with %d values, got %s %s" % (what, dtype, n, t.dtype, tuple(t.shape)))
+    if t.device != dev:
+        raise ValueError("margin_rank: %s is on %s, q on %s" % (what, t.device, dev))
+    return t.reshape(n).contiguous()
+
+
+def _mr_args(q, pos, neg, pos_ids, neg_ids, sample_weight, metric, num_hard):
+    """validates the domain of dr_margin_rank_*; returns (B, S, D, ld_q, ld_p, ld_n, neg, in_batch, pos_ids, neg_ids, sample_weight,
+    metric code, num_hard)"""
+    if q.dim() != 2:
+        raise ValueError("margin_rank: q must be fp32 [B, D], got %s" % (tuple(q.shape),))
+    B, D = q.shape
+    code, K = margin_rank_options(D, metric, num_hard)
+    ld_q = _row_pitch("margin_rank", q, D, "q")
+    ld_p = _row_pitch("margin_rank", pos, D, "pos")
+    if pos.shape[0] != B:
+        raise ValueError("margin_rank: pos must have %d rows, got %d" % (B, pos.shape[0]))
+    in_batch = neg is None
+    if in_batch:
+        neg, neg_ids = pos, (pos_ids if neg_ids is None else neg_ids)
+    ld_n = _row_pitch("margin_rank", neg, D, "neg")
+    S = neg.shape[0]
+    if not in_batch and not 1 <= S < 2 ** 31:
+        raise ValueError("margin_rank: needs 1 <= S < 2^31 negatives, got %d" % S)
+    dev = q.device
+    for t, what in ((pos, "pos"), (neg, "neg")):
+        if t.device != dev:
+            raise ValueError("margin_rank: %s is on %s, q on %s" % (what, t.device, dev))
+    return (B, S, D, ld_q, ld_p, ld_n, neg, in_batch, _mr_vec(pos_ids, B, "pos_ids", torch.int64, dev),
+            _mr_vec(neg_ids, S, "neg_ids", torch.int64, dev), _mr_vec(sample_weight, B, "sample_weight", torch.float32, dev), code, K)
+
+
+def margin_rank_fwd(q, pos, neg=None, pos_ids=None, neg_ids=None, sample_weight=None, margin=0.2, metric="cosine", num_hard=0,
+                    want_scores=False, workspace=None):
+    """(pos_score [B], row_loss [B], row_active int32 [B], hard_idx int32 [B, num_hard] | None, scores [B, S] | None) of
+    dr_margin_rank_fwd: loss_i = w_i sum_{j in N(i)} max(0, margin - s(q_i, pos_i) + s(q_i, neg_j)), s the cosine (or the dot product),
+    N(i) the kept negatives of row i or its num_hard highest-scoring ones.  q, pos fp32 [B, D] and neg fp32 [S, D], each possibly a view
+    with a row pitch (a multiple of 4); neg=None is in-batch: the negatives of row i are the pos rows of the other rows (and neg_ids
+    defaults to pos_ids).  pos_ids int64 [B] (< 0: a padding row, loss 0), neg_ids int64 [S] (< 0: the negative is left out and never
+    read); with both given a negative whose id equals the row's pos id is left out.  want_scores is for tests and diagnosis: the only
+    [B, S] tensor of the family."""
+    B, S, D, ld_q, ld_p, ld_n, neg, in_batch, pos_ids, neg_ids, sample_weight, code, K = _mr_args(q, pos, neg, pos_ids, neg_ids,
+                                                                                                 sample_weight, metric, num_hard)
+    dev = q.device
+    pos_score = torch.empty((B,), dtype=torch.float32, device=dev)
+    row_loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    row_active = torch.empty((B,), dtype=torch.int32, device=dev)
+    hard_idx = torch.empty((B, K), dtype=torch.int32, device=dev) if K > 0 else None
+    scores = torch.empty((B, S), dtype=torch.float32, device=dev) if want_scores else None
+    if B == 0:
+        return pos_score, row_loss, row_active, hard_idx, scores
+    if workspace is None:
+        workspace = margin_rank_workspace(B, S, D, K, dev)
+    _status(lib().dr_margin_rank_fwd(ptr(q), ld_q, ptr(pos), ld_p, ptr(neg), ld_n, D, B, S, ptr(pos_ids), ptr(neg_ids),
+                                     ptr(sample_weight), float(margin), code, 1 if in_batch else 0, K, MARGIN_RANK_EPS, ptr(pos_score),
+                                     ptr(row_loss), ptr(row_active), ptr(hard_idx), ptr(scores), ptr(workspace), workspace.numel(),
+                                     stream_ptr()), "dr_margin_rank_fwd")
+    return pos_score, row_loss, row_active, hard_idx, scores
+
+
+def margin_rank_bwd(q, pos, neg, pos_score, hard_idx, pos_ids=None, neg_ids=None, sample_weight=None, margin=0.2, metric="cosine",
+                    num_hard=0, row_scale=1.0, d_q=None, workspace=None):
+    """(d_q [B, D], d_pos [B, D], d_neg [S, D]) of dr_margin_rank_bwd: the gradients of row_scale * sum_i row_loss[i] with respect to
+    the raw rows (the normalisation differentiated inside) from the forward's pos_score and hard_idx, the scores recomputed.  neg=None
+    is in-batch: d_neg [B, D] is then the part that reaches pos as the other rows' negative, and the caller adds d_pos + d_neg.  d_q may
+    be given as a view with a row pitch and is written at that pitch."""
+    B, S, D, ld_q, ld_p, ld_n, neg, in_batch, pos_ids, neg_ids, sample_weight, code, K = _mr_args(q, pos, neg, pos_ids, neg_ids,
+                                                                                                 sample_weight, metric, num_hard)
+    dev = q.device
+    pos_score = _mr_vec(pos_score, B, "pos_score", torch.float32, dev)
+    if K > 0:
+        if hard_idx is None:
+            raise ValueError("margin_rank: num_hard = %d needs the forward's hard_idx" % K)
+        hard_idx = _mr_vec(hard_idx, B * K, "hard_idx", torch.int32, dev)
+    else:
+        hard_idx = None
+    if d_q is None:
+        d_q = torch.empty((B, D), dtype=torch.float32, device=dev)
+    ld_dq = _row_pitch("margin_rank", d_q, D, "d_q")
+    if d_q.shape[0] != B:
+        raise ValueError("margin_rank: d_q must have %d rows, got %d" % (B, d_q.shape[0]))
+    d_pos = torch.empty((B, D), dtype=torch.float32, device=dev)
+    d_neg = torch.empty((S, D), dtype=torch.float32, device=dev)
+    if B == 0:
+        return d_q, d_pos, d_neg.zero_()
+    if workspace is None:
+        workspace = margin_rank_workspace(B, S, D, K, dev)
+    _status(lib().dr_margin_rank_bwd(ptr(q), ld_q, ptr(pos), ld_p, ptr(neg), ld_n, D, B, S, ptr(pos_ids), ptr(neg_ids),
+                                     ptr(sample_weight), float(margin), code, 1 if in_batch else 0, K, MARGIN_RANK_EPS, float(row_scale),
+                                     ptr(pos_score), ptr(hard_idx), ptr(d_q), ld_dq, ptr(d_pos), ptr(d_neg), ptr(workspace),
+                                     workspace.numel(), stream_ptr()), "dr_margin_rank_bwd")
+    return d_q, d_pos, d_neg

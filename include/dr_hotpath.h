@@ -1513,6 +1513,76 @@ int dr_sampled_softmax_bwd(const float* u, int64_t ld_u, const float* table, int
                            int64_t ld_du, float* d_true, float* d_sampled, void* workspace, int64_t workspace_bytes,
                            dr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Margin ranking loss with hard-negative mining (csrc/margin_rank.hip): the training loss of EBR (Huang et al., "Embedding-based
+ * Retrieval in Facebook Search", KDD 2020), which the reference's README lists and ships no code for -- a triplet loss over cosine
+ * similarities against a negative matrix that the whole batch shares ("in-batch": the positives of the other rows), optionally
+ * restricted to each row's num_hard hardest negatives (the paper's online hard-negative mining).  A sibling of the sampled softmax
+ * above: the same tiles (csrc/dr_score_tile.h), no [B, S] tensor, scores recomputed in the backward.  All fp32.
+ *   q [B, D] at the pitch ld_q; pos [B, D] at ld_p; neg [S, D] at ld_n (it may be the buffer of pos with S == B); pos_ids int64 [B],
+ *   neg_ids int64 [S], sample_weight [B] (w_i), each may be NULL.  metric 0 (dot): x^ = x.  metric 1 (cosine): x^ = x r_x,
+ *   r_x = (max(sum x^2, eps))^(-1/2) -- tf.math.l2_normalize with its epsilon (1e-12).
+ *     t_i     = q^_i . p^_i                    s_ij = q^_i . n^_j
+ *     valid_i = pos_ids == NULL or pos_ids_i >= 0
+ *     keep_ij = valid_i and not (in_batch and j == i) and (neg_ids == NULL or neg_ids_j >= 0)
+ *               and not (both id arrays given and neg_ids_j == pos_ids_i)
+ *     N(i)    = all kept j (num_hard == 0) | the num_hard kept j of largest s_ij, ties to the smaller j (fewer if fewer are kept)
+ *     h_ij    = margin - t_i + s_ij            loss_i = w_i sum_{j in N(i)} max(0, h_ij)       (h_ij == 0 is inactive)
+ *   A padding row (valid_i false) has q_i replaced by zeros on load (a NaN in it reaches nothing; its pos row is not read for t_i);
+ *   pos_score, row_loss, row_active and its d_q / d_pos rows are 0, its hard_idx -1.  A negative with id < 0 is never read and its
+ *   d_neg row is 0.  No id is turned into an address: the ids are only compared.
+ *   dr_margin_rank_fwd   writes pos_score [B] (t_i), row_loss [B], row_active int32 [B] (the number of j in N(i) with h_ij > 0), with
+ *                        num_hard > 0 hard_idx int32 [B, num_hard] (falling score, -1 padded) and, unless NULL, scores [B, S] dense
+ *                        (s_ij, -inf where not kept) -- for tests and diagnosis.  Without it nothing of size B * S is written.
+ *   dr_margin_rank_bwd   from the forward's pos_score and hard_idx, the scores recomputed, the gradients of row_scale * sum_i loss_i
+ *                        with respect to the RAW rows (the normalisation is differentiated inside):
+ *                          a_ij = row_scale w_i [j in N(i) and h_ij > 0]    c_i = sum_j a_ij    e_i = sum_j a_ij s_ij    f_j = sum_i a_ij s_ij
+ *                          d_q [B, D] at ld_dq = r_qi [ sum_j a_ij n^_j - c_i p^_i - pi_qi (e_i - c_i t_i) q^_i ]
+ *                          d_pos [B, D] dense  = -c_i r_pi ( q^_i - pi_pi t_i p^_i )
+ *                          d_neg [S, D] dense  = r_nj [ sum_i a_ij q^_i - pi_nj f_j n^_j ]
+ *                        pi_x = 1 if sum x^2 >= eps else 0 (a zero row has cosine 0 with everything and gets the unprojected
+ *                        gradient); metric dot is r = 1, pi = 0.  "j in N(i)" is "j is among hard_idx[i, :]" (num_hard compares, no
+ *                        second selection).  All three are overwritten; in in-batch use the caller adds d_pos + d_neg.
+ *   Every product is v_mfma_f32_16x16x4_f32 on the raw rows; the inverse norms (a prologue writes them to the workspace) multiply the
+ *   score tile, (raw r_q) r_n, and the weights a_ij r_nj / a_ij r_qi of the second product.  Order of every sum: as the sampled
+ *   softmax -- column segments that are a function of S alone (min(DR_MARGIN_RANK_MAX_GROUPS, ceil(S / DR_MARGIN_RANK_COL_GROUP)),
+ *   evened out over whole tiles), fresh accumulators per segment, segments combined in ascending order whether one block walks them
+ *   all (more than DR_MARGIN_RANK_SPLIT_TILES row tiles) or each has a block of its own; a row's pos_score, row_loss, row_active,
+ *   hard_idx, d_q and d_pos depend on that row and the negatives alone, not on B or the other rows.  dr_margin_rank_col_segments returns
+ *   the number of segments, dr_margin_rank_col_groups the number of blocks per row tile (1 or the segment count): pure functions of
+ *   (B, S, D), no device query.  d_neg and f_j are summed over dr_margin_rank_row_chunks' chunks of the batch (<=
+ *   DR_MARGIN_RANK_MAX_CHUNKS, at least DR_MARGIN_RANK_ROW_CHUNK rows each), the partials added in chunk order.  The top-k is a sorted (score, j) list per row,
+ *   carried across the tiles of a segment and merged in segment order; its order is total, so the selected set does not depend on
+ *   the segmentation.  The hinge terms of a row are summed in column order in both modes, so num_hard >= the number of kept columns
+ *   gives the bits of num_hard == 0.  No float atomics, no waiting between workgroups; bit-identical from run to run.
+ *   workspace: 16-byte aligned, dr_margin_rank_workspace_bytes(B, S, D, num_hard) bytes (the same for both entry points).
+ *   Domain: D % 4 == 0, 4 <= D <= 256, 1 <= S < 2^31, B >= 0, 0 <= num_hard <= DR_MARGIN_RANK_MAX_HARD, metric 0 | 1, in_batch needs
+ *   S == B; q, pos, neg, d_q, d_pos, d_neg, workspace 16-byte aligned, ld_q, ld_p, ld_n, ld_dq multiples of 4 and >= D.  Anything
+ *   else or a NULL required pointer is DR_ESHAPE / DR_EINVAL before a launch (the three sizing functions return the negative status).
+ *   B == 0 is DR_OK with nothing written.
+ * ---------------------------------------------------------------------------------------- */
+#define DR_MARGIN_RANK_TILE 64
+#define DR_MARGIN_RANK_COL_GROUP 128
+#define DR_MARGIN_RANK_MAX_GROUPS 8
+#define DR_MARGIN_RANK_SPLIT_TILES 128
+#define DR_MARGIN_RANK_ROW_CHUNK 128
+#define DR_MARGIN_RANK_MAX_CHUNKS 64
+#define DR_MARGIN_RANK_MAX_HARD 8
+int64_t dr_margin_rank_workspace_bytes(int64_t B, int64_t S, int32_t D, int32_t num_hard);
+int32_t dr_margin_rank_col_groups(int64_t B, int64_t S, int32_t D);
+int32_t dr_margin_rank_col_segments(int64_t B, int64_t S, int32_t D);
+int32_t dr_margin_rank_row_chunks(int64_t B, int64_t S, int32_t D);
+int dr_margin_rank_fwd(const float* q, int64_t ld_q, const float* pos, int64_t ld_p, const float* neg, int64_t ld_n, int32_t D, int64_t B,
+                       int64_t S, const int64_t* pos_ids, const int64_t* neg_ids, const float* sample_weight, float margin,
+                       int32_t metric, int32_t in_batch, int32_t num_hard, float eps, float* pos_score, float* row_loss,
+                       int32_t* row_active, int32_t* hard_idx, float* scores, void* workspace, int64_t workspace_bytes,
+                       dr_stream_t stream);
+int dr_margin_rank_bwd(const float* q, int64_t ld_q, const float* pos, int64_t ld_p, const float* neg, int64_t ld_n, int32_t D, int64_t B,
+                       int64_t S, const int64_t* pos_ids, const int64_t* neg_ids, const float* sample_weight, float margin,
+                       int32_t metric, int32_t in_batch, int32_t num_hard, float eps, float row_scale, const float* pos_score,
+                       const int32_t* hard_idx, float* d_q, int64_t ld_dq, float* d_pos, float* d_neg, void* workspace,
+                       int64_t workspace_bytes, dr_stream_t stream);
+
 /* dr_clock_stamp: dst[0] = the device's constant-rate wall clock (100 MHz ticks) when a one-thread kernel reaches the head of
  * `stream`.  Measurement plumbing with no reference counterpart: bench.py brackets the sharded step's cross-stream waits with two
  * stamps to report the EXPOSED part of the exchange (HIP timing events around a wait serialise the step). */
