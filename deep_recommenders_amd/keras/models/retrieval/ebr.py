@@ -7,8 +7,8 @@ Training is the paper's triplet loss on cosine similarities, L = sum_j max(0, ma
 documents of the batch as negatives ("random negatives" come for free), optionally over each query's num_hard_negatives highest-scoring
 in-batch negatives (the paper's online hard-negative mining): dr_margin_rank_fwd / _bwd (csrc/margin_rank.hip), which fold the L2
 normalisation in and return gradients with respect to the raw tower outputs.  Serving goes through the indices the package has:
-BruteForce, or Faiss (IVF-Flat on csrc/ivf.hip) with normalize=True.  Not built: product quantisation / IVF-PQ, offline hard-negative
-mining from an index, the embedding ensemble."""
+BruteForce, Faiss (IVF-Flat on csrc/ivf.hip) or FaissIVFPQ (the paper's IVF-PQ, csrc/ivf_pq.hip), the two IVF kinds with normalize=True.
+Not built: offline hard-negative mining from an index, the embedding ensemble."""
 import contextlib
 
 import torch
@@ -16,7 +16,7 @@ from torch import nn
 
 from deep_recommenders_amd import layers as L
 from deep_recommenders_amd import ops
-from deep_recommenders_amd.keras.models.retrieval.factorized_top_k import BruteForce, Faiss
+from deep_recommenders_amd.keras.models.retrieval.factorized_top_k import BruteForce, Faiss, FaissIVFPQ
 
 _ACT = {"relu": 1, None: 0, "linear": 0, "sigmoid": 2, "tanh": 3}
 
@@ -188,13 +188,17 @@ class EBR(nn.Module):
         return ops.rows_scale(x, ops.rowdot(x, x), mode=1) if self.metric == "cosine" else x
 
     def index(self, document_inputs, identifiers=None, k=10, kind="brute_force", **faiss_kwargs):
-        """indexes the documents' vectors as the towers are now: "brute_force" (exact; unit vectors for the cosine) or "faiss"
-        (IVF-Flat, normalize=True for the cosine; nlist, nprobe, niter, seed as Faiss takes them)"""
-        if kind not in ("brute_force", "faiss"):
-            raise ValueError("EBR: kind must be 'brute_force' or 'faiss', got %r" % (kind,))
+        """indexes the documents' vectors as the towers are now: "brute_force" (exact; unit vectors for the cosine), "faiss"
+        (IVF-Flat, normalize=True for the cosine; nlist, nprobe, niter, seed as Faiss takes them) or "ivfpq" (IVF-PQ, normalize=True
+        for the cosine; nlist, nprobe, m, refine, niter, pq_niter, seed as FaissIVFPQ takes them)"""
+        if kind not in ("brute_force", "faiss", "ivfpq"):
+            raise ValueError("EBR: kind must be 'brute_force', 'faiss' or 'ivfpq', got %r" % (kind,))
         with torch.no_grad():
             d = self.document_vectors(document_inputs)
-            if kind == "faiss":
+            if kind == "ivfpq":
+                self._serving = (FaissIVFPQ(k=int(k), normalize=self.metric == "cosine", **faiss_kwargs).index(d.contiguous(), identifiers),
+                                 kind)
+            elif kind == "faiss":
                 self._serving = (Faiss(k=int(k), normalize=self.metric == "cosine", **faiss_kwargs).index(d.contiguous(), identifiers), kind)
             else:
                 self._serving = (BruteForce(k=int(k)).index(self._unit(d), identifiers), kind)
@@ -207,7 +211,7 @@ class EBR(nn.Module):
         with torch.no_grad():
             q = self.query_vectors(query_inputs)
             idx, kind = self._serving
-            return idx.call(q.contiguous() if kind == "faiss" else self._unit(q), int(k))
+            return idx.call(q.contiguous() if kind in ("faiss", "ivfpq") else self._unit(q), int(k))
 
     def get_config(self):
         """the constructor's arguments; the columns as (key, num_buckets, dimension) records, enough to rebuild identity / hashed

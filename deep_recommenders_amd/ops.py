@@ -993,6 +993,114 @@ def ivf_scan(q, probes, blk_off, packed, packed_ids, k):
     return s, i
 
 
+PQ_KSUB = 256                       # codewords per sub-quantiser (one byte per code)
+PQ_MAX_K = 128                      # drtk::KMAX
+
+
+def pq_check(D, m):
+    """validates the domain of dr_pq_encode / dr_ivfpq_scan; returns (D, m, dsub) as ints"""
+    D, m = int(D), int(m)
+    if m % 4 != 0 or not 4 <= m <= 64:
+        raise ValueError("ivfpq: the number of sub-quantisers m must be a multiple of 4 in [4, 64], got m = %d" % m)
+    if not 1 <= D <= 1024:
+        raise ValueError("ivfpq: the dimension D must lie in [1, 1024], got D = %d" % D)
+    if D % m != 0:
+        raise ValueError("ivfpq: D must be a multiple of m, got D = %d, m = %d" % (D, m))
+    if D // m > 64:
+        raise ValueError("ivfpq: a sub-vector holds D / m <= 64 components (its codebook slice sits in LDS), got D = %d, m = %d, "
+                         "D / m = %d" % (D, m, D // m))
+    return D, m, D // m
+
+
+def _pq_k(k, what):
+    k = int(k)
+    if not 1 <= k <= PQ_MAX_K:
+        raise ValueError("ivfpq: %s must lie in [1, %d], got %d" % (what, PQ_MAX_K, k))
+    return k
+
+
+def _pq_mat(t, what, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError("%s must be a 2-d %s tensor, got %s" % (what, dtype, tuple(t.shape) if hasattr(t, "shape") else type(t)))
+    return _dense_arg(t, what, dtype=dtype)
+
+
+def pq_encode(x, codebooks, assign=None, centroids=None):
+    """codes int32 [N, m / 4] (code j of a vector in bits 8 * (j % 4) of word j / 4) of x [N, D] against codebooks [m, 256, D / m]:
+    the nearest codeword of every sub-vector of x - centroids[assign] (assign / centroids None: of x itself).  dr_pq_encode."""
+    if not isinstance(codebooks, torch.Tensor) or codebooks.dim() != 3 or codebooks.shape[1] != PQ_KSUB:
+        raise ValueError("pq_encode: codebooks must be fp32 [m, %d, D / m], got %s" % (PQ_KSUB, tuple(getattr(codebooks, "shape", ()))))
+    x = _pq_mat(x, "pq_encode: x")
+    N, D = x.shape
+    m = codebooks.shape[0]
+    D, m, dsub = pq_check(D, m)
+    codebooks = _dense_arg(codebooks, "pq_encode: codebooks", shape=(m, PQ_KSUB, dsub))
+    if (assign is None) != (centroids is None):
+        raise ValueError("pq_encode: assign and centroids come together (both None: x is the residual)")
+    nlist = 0
+    if assign is not None:
+        centroids = _pq_mat(centroids, "pq_encode: centroids")
+        nlist = centroids.shape[0]
+        if centroids.shape[1] != D or nlist < 1:
+            raise ValueError("pq_encode: centroids must be fp32 [nlist >= 1, %d], got %s" % (D, tuple(centroids.shape)))
+        assign = _dense_arg(assign, "pq_encode: assign", dtype=torch.int64, numel=N)
+    codes = torch.empty((N, m // 4), dtype=torch.int32, device=x.device)
+    check(lib().dr_pq_encode(ptr(x), ptr(assign), ptr(centroids), nlist, ptr(codebooks), N, D, m, ptr(codes), stream_ptr()),
+          "dr_pq_encode")
+    return codes
+
+
+def ivfpq_scan(q, probes, probe_scores, blk_off, packed_codes, packed_rows, codebooks, k):
+    """(scores [Bq, k], rows [Bq, k] int64): the ADC top k of each query over its probed lists (dr_ivfpq_scan).  probes / probe_scores
+    [Bq, nprobe] as ops.topk_mips(q, centroids, nprobe) returns them (a probe < 0 is skipped); packed_codes (int32 words, or the fp32
+    view ops.ivf_pack returns), packed_rows and blk_off in ops.ivf_pack's layout; codebooks [m, 256, D / m]."""
+    if not isinstance(codebooks, torch.Tensor) or codebooks.dim() != 3 or codebooks.shape[1] != PQ_KSUB:
+        raise ValueError("ivfpq_scan: codebooks must be fp32 [m, %d, D / m], got %s" % (PQ_KSUB, tuple(getattr(codebooks, "shape", ()))))
+    q = _pq_mat(q, "ivfpq_scan: q")
+    Bq, D = q.shape
+    m = codebooks.shape[0]
+    D, m, dsub = pq_check(D, m)
+    k = _pq_k(k, "k")
+    codebooks = _dense_arg(codebooks, "ivfpq_scan: codebooks", shape=(m, PQ_KSUB, dsub))
+    probes = _pq_mat(probes, "ivfpq_scan: probes", dtype=torch.int64)
+    nprobe = probes.shape[1]
+    if probes.shape[0] != Bq or nprobe < 1:
+        raise ValueError("ivfpq_scan: probes must be int64 [%d, nprobe >= 1], got %s" % (Bq, tuple(probes.shape)))
+    probe_scores = _dense_arg(probe_scores, "ivfpq_scan: probe_scores", shape=(Bq, nprobe))
+    blk_off = _dense_arg(blk_off, "ivfpq_scan: blk_off", dtype=torch.int64)
+    if blk_off.dim() != 1 or blk_off.numel() < 2:
+        raise ValueError("ivfpq_scan: blk_off must be int64 [nlist + 1], got %s" % (tuple(blk_off.shape),))
+    if packed_codes.dtype not in (torch.int32, torch.float32) or not packed_codes.is_contiguous() or \
+            packed_codes.numel() % (64 * (m // 4)) != 0:
+        raise ValueError("ivfpq_scan: packed_codes must be contiguous int32 (or fp32-viewed) words, a whole number of 64-vector blocks "
+                         "of m / 4 = %d words, got %s with %d elements" % (m // 4, packed_codes.dtype, packed_codes.numel()))
+    packed_rows = _dense_arg(packed_rows, "ivfpq_scan: packed_rows", dtype=torch.int64, numel=packed_codes.numel() // (m // 4))
+    s, i = topk_state(Bq, k, q.device)
+    check(lib().dr_ivfpq_scan(ptr(q), ptr(probes), ptr(probe_scores), ptr(blk_off), ptr(packed_codes), ptr(packed_rows), ptr(codebooks),
+                              Bq, D, m, nprobe, k, ptr(s), ptr(i), stream_ptr()), "dr_ivfpq_scan")
+    return s, i
+
+
+def rerank_topk(q, cand, rows, k):
+    """(scores [Bq, k], rows [Bq, k] int64): the exact fp32 inner products of q [Bq, D] with cand[rows[b, t]] (rows [Bq, kin <= 128]
+    int64, entries < 0: none), top k by score descending, ties to the lower row (dr_rerank_topk)."""
+    q = _pq_mat(q, "rerank_topk: q")
+    cand = _pq_mat(cand, "rerank_topk: cand")
+    Bq, D = q.shape
+    if cand.shape[1] != D or not 1 <= D <= 1024:
+        raise ValueError("rerank_topk: q [Bq, D] and cand [N, D] share D in [1, 1024], got %s and %s" % (tuple(q.shape), tuple(cand.shape)))
+    rows = _pq_mat(rows, "rerank_topk: rows", dtype=torch.int64)
+    kin = rows.shape[1]
+    if rows.shape[0] != Bq:
+        raise ValueError("rerank_topk: rows must be int64 [%d, kin], got %s" % (Bq, tuple(rows.shape)))
+    _pq_k(kin, "kin (the width of rows)")
+    k = _pq_k(k, "k")
+    s, i = topk_state(Bq, k, q.device)
+    check(lib().dr_rerank_topk(ptr(q), ptr(cand), ptr(rows), Bq, cand.shape[0], D, kin, k, ptr(s), ptr(i), stream_ptr()),
+          "dr_rerank_topk")
+    return s, i
+
+
 def topk_merge(sa, ia, sb, ib, k):
     Bq = sa.shape[0]
     out = topk_state(Bq, k, sa.device)

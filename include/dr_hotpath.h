@@ -538,6 +538,30 @@ int dr_ivf_pack(const float* cand, int64_t N, int32_t D, const int64_t* order, c
 int dr_ivf_scan(const float* q, int64_t Bq, int32_t D, const int64_t* probes, int32_t nprobe,
                 const int64_t* blk_off, const float* packed, const int64_t* packed_ids, int32_t k,
                 float* out_scores, int64_t* out_index, dr_stream_t stream);
+/* ------------------------------------------------------------------------------------------
+ * IVF-PQ (csrc/ivf_pq.hip): the index EBR serves from (Huang et al., KDD 2020, section 4) -- IVF lists of product-quantised
+ * residuals, inner product.  256 codewords per sub-quantiser, m sub-quantisers, dsub = D / m.
+ * Domain of all three: m % 4 == 0, 4 <= m <= 64, D % m == 0, D / m <= 64, D <= 1024, 1 <= k <= 128, nprobe >= 1, kin <= 128.
+ *   dr_pq_encode:   codes_out[i, j / 4] bits 8 * (j % 4) = the codeword of codebooks[j] ([m, 256, dsub]) nearest to sub-vector j of
+ *                   x[i] - centroids[assign[i]] (squared L2 summed over ascending d in fp32, no fused multiply-add; ties to the
+ *                   lower code).  assign and centroids both NULL: x is the residual already (the assignment step of codebook
+ *                   training).  An assign outside [0, nlist) encodes as zeros.
+ *   dr_ivfpq_scan:  packed_codes[(blk * (m/4) + w) * 64 + lane] = word w of the vector in slot (blk, lane) of dr_ivf_pack's layout,
+ *                   packed_rows its candidate row (-1: padding).  score = probe_scores[q, p] + sum_j LUT[j][code_j] added in
+ *                   ascending j, LUT[j][c] = fmaf chain of q_j . codebooks[j][c] over ascending d from 0 (built in LDS per query).
+ *                   Top k by score descending, ties to the lower row; a probe < 0 is skipped; fewer than k members leave
+ *                   (-inf, -1).  Bit-identical from run to run and independent of the batch.
+ *   dr_rerank_topk: exact fp32 inner products of q[b] with cand[rows[b, t]] (rows < 0 or >= N: none), top k with the row numbers,
+ *                   score descending, ties to the lower row.
+ * ---------------------------------------------------------------------------------------- */
+int dr_pq_encode(const float* x, const int64_t* assign, const float* centroids, int32_t nlist, const float* codebooks,
+                 int64_t N, int32_t D, int32_t m, uint32_t* codes_out, dr_stream_t stream);
+int dr_ivfpq_scan(const float* q, const int64_t* probes, const float* probe_scores, const int64_t* blk_off,
+                  const uint32_t* packed_codes, const int64_t* packed_rows, const float* codebooks, int64_t Bq,
+                  int32_t D, int32_t m, int32_t nprobe, int32_t k, float* out_scores, int64_t* out_rows,
+                  dr_stream_t stream);
+int dr_rerank_topk(const float* q, const float* cand, const int64_t* rows, int64_t Bq, int64_t N, int32_t D, int32_t kin,
+                   int32_t k, float* out_scores, int64_t* out_rows, dr_stream_t stream);
 int dr_topk_merge(const float* sa, const int64_t* ia, int32_t ka, const float* sb, const int64_t* ib,
                   int32_t kb, int64_t Bq, int32_t k, float* out_scores, int64_t* out_index,
                   dr_stream_t stream);
