@@ -12,7 +12,7 @@ The host never holds the tables: the rows the two batches touch are gathered fro
 (b) a sample of untouched rows must be bit-identical to their initial values.  That makes the full-size table (V = 10 M per
 field, 66.6 GB: the bench's own) testable, not only V = 1 M.
 
-Tolerances (written where they are used): ids bit-exact; loss 1e-5 relative (north_star); parameters compared through their
+Tolerances (written where they are used, the shared ones in tests/engine_oracle.py): ids bit-exact; loss 1e-5 relative (north_star); parameters compared through their
 UPDATE (after - before) so that a wrong or missing gradient cannot hide behind the size of the weights: |d_gpu - d_cpu| <=
 2 ulp(weight) + 2e-3 * |d_cpu| + 1e-3 * rms(d_cpu) for SGD; 2 % of one Adam step for Adam (as in test_gpu_models.py).
 The SGD tests use lr = 1.0 instead of bench.py's 0.01: the learning rate is a scalar the kernels multiply by, and at 0.01 a row's
@@ -28,6 +28,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import tf_semantics as O
 from oracle import torch_ref as T
+from engine_oracle import _assert_update, _check_adam_step, _CompactOracle, _device_relu_masks
 
 F, D, ND, B, DNN = 26, 64, 13, 65536, [256, 32]
 
@@ -55,185 +56,6 @@ def _oracle_ids(keys, V):
     return np.stack([O.hash_bucket_i64(k[:, f], V) for f in range(F)], axis=1)
 
 
-def _ulp(x):
-    return np.spacing(np.abs(x).astype(np.float32)).astype(np.float64)
-
-
-def _assert_update(name, before, after, want_after, rel=2e-3, outliers=1e-4):
-    """after - before (device) against want_after - before (oracle), see the module docstring.
-
-    `outliers`: fraction of elements allowed outside the tight tolerance, each still bounded by half its update + 2 rms.
-    Two fp32 implementations of a ReLU network cannot agree on every element: a hidden unit whose pre-activation is within
-    rounding of zero (a few of the 16.7 M per step) is "on" on one side and "off" on the other, which switches one of the
-    ~128 active terms of that example's 1664 input gradients (first seen at 5e-6 of the table elements, errors of ~0.5 % of
-    the update).  A wrong kernel moves every element, not 1e-5 of them."""
-    b64 = before.astype(np.float64)
-    d_gpu, d_cpu = after.astype(np.float64) - b64, want_after.astype(np.float64) - b64
-    rms = float(np.sqrt(np.mean(d_cpu * d_cpu)))
-    assert rms > 0, name + ": the oracle update is identically zero (test is vacuous)"
-    err = np.abs(d_gpu - d_cpu)
-    tol = 2 * np.maximum(_ulp(before), _ulp(want_after)) + rel * np.abs(d_cpu) + 1e-3 * rms
-    bad = err > tol
-    frac = float(bad.mean())
-    assert frac <= outliers, "%s: %.2e of %d elements off (allowed %.0e); worst |err| %.3e at update %.3e (rms update %.3e)" % (
-        name, frac, bad.size, outliers, float(err[bad].max()), float(np.abs(d_cpu)[bad].max()), rms)
-    if bad.any():
-        assert bool((err[bad] <= 0.5 * np.abs(d_cpu)[bad] + 2 * rms).all()), "%s: an outlier is not ReLU-tie sized: |err| %.3e (rms %.3e)" % (
-            name, float(err[bad].max()), rms)
-
-
-def _assert_close_adam(name, got, want, lr, outliers, mean_tol=2e-3):
-    """Adam at this batch size is an amplifier: on step t the update is lr * g / (|g| + eps'), eps' = eps / sqrt(1 - beta2^t)
-    ~ 3e-7, and the gradients of a 65 536-example mean are 1e-8 .. 1e-5 -- for |g| < ~1e-6 a change of 1e-8 in g moves the
-    update by more than 2 % of a step.  fp32 rounding is far below that, a ReLU tie (see _assert_update) is not: one hidden
-    unit switched for one example shifts that example's 1664 embedding-gradient elements by ~0.5 % and, through dy, a whole
-    1677-element column of the first layer's weight gradient by ~1e-7.  So: all but `outliers` of the elements within 2 % of a
-    step (measured: 4e-4 of the table rows, 7e-3 of W0 with ~1e2 ties per step), the MEAN difference within 0.2 % of a step,
-    nothing off by more than one whole step.  A wrong gradient or update rule moves the mean by tens of per cent."""
-    err = np.abs(got.astype(np.float64) - want.astype(np.float64))
-    frac = float((err > 2e-2 * lr).mean())
-    assert frac <= outliers, "%s: %.2e of %d elements differ by more than 2 %% of an Adam step (allowed %.0e)" % (name, frac, err.size, outliers)
-    assert float(err.mean()) <= mean_tol * lr, "%s: mean difference %.3e of a step" % (name, float(err.mean()) / lr)
-    assert float(err.max()) <= 1.0 * lr, "%s: worst difference %.3e exceeds one Adam step" % (name, float(err.max()))
-
-
-class _CompactOracle:
-    """DeepFM training steps on the rows a set of batches touches (oracle/torch_ref.py math, torch autograd for the gradients,
-    [TF] B15 Adam from the same module)."""
-
-    def __init__(self, eng, ids_list, V, optimizer, lr):
-        base = np.arange(F, dtype=np.int64)[None, :] * V
-        rows = [i + base for i in ids_list]
-        self.U = np.unique(np.concatenate([r.reshape(-1) for r in rows]))
-        self.cidx = [torch.from_numpy(np.searchsorted(self.U, r)) for r in rows]
-        Ud = torch.from_numpy(self.U).cuda()
-        self.Ud = Ud
-        self.table = eng.table[Ud].cpu()
-        self.lin = eng.lin_w[Ud].cpu()
-        self.bias = eng.lin_bias.cpu().clone()
-        self.Ws = [w.cpu().clone().contiguous() for w in eng.Ws]
-        self.bs = [b.cpu().clone() for b in eng.bs]
-        self.table0, self.lin0 = self.table.clone(), self.lin.clone()
-        self.Ws0, self.bs0, self.bias0 = [w.clone() for w in self.Ws], [b.clone() for b in self.bs], self.bias.clone()
-        self.opt, self.lr, self.t = optimizer, lr, 0
-        if optimizer == "adam":
-            z = torch.zeros_like
-            self.mt, self.vt, self.ml, self.vl = z(self.table), z(self.table), z(self.lin), z(self.lin)
-            self.mb, self.vb = z(self.bias), z(self.bias)
-            self.mW, self.vW = [z(w) for w in self.Ws], [z(w) for w in self.Ws]
-            self.mB, self.vB = [z(b) for b in self.bs], [z(b) for b in self.bs]
-
-    def resync_from(self, eng):
-        """Adopt the device's state -- touched table rows, first-order weights, bias, dense parameters and (Adam) every moment -- so that
-        the next step starts from IDENTICAL state on both sides (compare first, then call this)."""
-        Ud = self.Ud
-        self.table, self.lin = eng.table[Ud].cpu(), eng.lin_w[Ud].cpu()
-        self.bias = eng.lin_bias.cpu().clone()
-        self.Ws = [w.cpu().clone().contiguous() for w in eng.Ws]
-        self.bs = [b.cpu().clone() for b in eng.bs]
-        if self.opt == "adam":
-            self.mt, self.vt = eng.m_table[Ud].cpu(), eng.v_table[Ud].cpu()
-            self.ml, self.vl = eng.m_lin[Ud].cpu().clone(), eng.v_lin[Ud].cpu().clone()
-            fm, fv = eng.flat_m.cpu(), eng.flat_v.cpu()
-            self.mb, self.vb = fm[eng._bias_off:eng._bias_off + 1].clone(), fv[eng._bias_off:eng._bias_off + 1].clone()
-            self.mW = [fm[wo:wo + k * pu].view(k, pu)[:, :u].clone().contiguous() for wo, k, pu, u, bo in eng._views]
-            self.vW = [fv[wo:wo + k * pu].view(k, pu)[:, :u].clone().contiguous() for wo, k, pu, u, bo in eng._views]
-            self.mB = [fm[bo:bo + u].clone() for wo, k, pu, u, bo in eng._views]
-            self.vB = [fv[bo:bo + u].clone() for wo, k, pu, u, bo in eng._views]
-
-    def step(self, i, dense, labels, relu_masks=None):
-        """relu_masks: the device's ReLU decisions of this step (oracle/torch_ref.py dnn: tie-aware comparison); the units where
-        they differ from the oracle's own are recorded in self.ties and must be ties (T.check_ties)."""
-        cidx = self.cidx[i]
-        emb = self.table[cidx].requires_grad_(True)                      # [B, F, D]  single-valued fields: x = the row ([TF] B5)
-        lw = self.lin[cidx].requires_grad_(True)
-        bias = self.bias.clone().requires_grad_(True)
-        ks = [k.clone().requires_grad_(True) for k in self.Ws]
-        bs = [b.clone().requires_grad_(True) for b in self.bs]
-        x = torch.cat([emb.reshape(B, F * D), dense], 1)
-        self.ties = []
-        # (Adam amplifies fp32 noise in the gradients -- d step / d g is up to lr / eps' = 3e4 where |g| ~ 3e-7, see _assert_close_adam --
-        # so two sides that each carry their OWN state drift apart by ~1e-5 rms in the pre-activations after one step.  Round 5 widened
-        # the tie width 20 x for step 2; since round 6 the oracle adopts the device's parameters and moments after every step
-        # (resync_from), each step is a one-step comparison from identical state, and a tie is a tie at the step-1 width)
-        eps = 1e-5
-        logit = T.fm_second_order(emb) + lw.sum(1) + bias + T.dnn(x, ks, bs, relu_masks=relu_masks, ties=self.ties, tie_eps=eps).squeeze(1)   # deepfm.py:36-47
-        loss = T.sigmoid_cross_entropy(labels, logit)                                        # train_fm_on_movielens_estimator.py:46
-        grads = torch.autograd.grad(loss, [emb, lw, bias] + ks + bs)
-        gt = torch.zeros_like(self.table).index_add_(0, cidx.reshape(-1), grads[0].reshape(-1, D))
-        gl = torch.zeros_like(self.lin).index_add_(0, cidx.reshape(-1), grads[1].reshape(-1))
-        n = len(ks)
-        self.t += 1
-        self.last_gW, self.last_gb = [g_.detach().clone() for g_ in grads[3:3 + n]], [g_.detach().clone() for g_ in grads[3 + n:3 + 2 * n]]
-        # smallest |gradient| an element has seen over the steps: Adam's sensitivity to gradient round-off (see _run_deepfm)
-        mins = [g_.detach().abs() for g_ in list(grads[3:3 + n]) + list(grads[3 + n:3 + 2 * n])]
-        self.min_abs_g = mins if self.t == 1 else [torch.minimum(a, b_) for a, b_ in zip(self.min_abs_g, mins)]
-        with torch.no_grad():
-            if self.opt == "sgd":
-                self.table -= self.lr * gt
-                self.lin -= self.lr * gl
-                self.bias -= self.lr * grads[2]
-                for j in range(n):
-                    self.Ws[j] -= self.lr * grads[3 + j]
-                    self.bs[j] -= self.lr * grads[3 + n + j]
-            else:
-                touched = torch.unique(cidx.reshape(-1))
-                T.adam_rows_step(self.table, gt, touched, self.mt, self.vt, self.lr, self.t)
-                T.adam_rows_step(self.lin, gl, touched, self.ml, self.vl, self.lr, self.t)
-                T.adam_dense_step(self.bias, grads[2], self.mb, self.vb, self.lr, self.t)
-                for j in range(n):
-                    T.adam_dense_step(self.Ws[j], grads[3 + j], self.mW[j], self.vW[j], self.lr, self.t)
-                    T.adam_dense_step(self.bs[j], grads[3 + n + j], self.mB[j], self.vB[j], self.lr, self.t)
-        return float(loss.detach())
-
-
-def _device_relu_masks(eng):
-    """The ReLU decisions the device made in the step that just ran, one bool [B, units] per hidden layer: h > 0 of the stored
-    activations; the fused head (last hidden layer + Dense(1) + loss in one GEMM epilogue) never stores its h, there the decision is
-    read off the gradient it wrote: d_h = d_logit * w2 * (h > 0) with d_logit != 0 and w2 != 0 (both asserted)."""
-    torch.cuda.synchronize()
-    n_hidden = len(eng.Ws) - 1
-    masks = []
-    for i in range(n_hidden):
-        if eng._head_done and i == n_hidden - 1:
-            assert bool((eng.d_logit != 0).all()) and bool((eng.Ws[-1] != 0).all())
-            masks.append((eng.dhs[-1] != 0).cpu())
-        else:
-            masks.append((eng.hs[i] > 0).cpu())
-    return masks
-
-
-def _check_adam_step(eng, orc, lr, step):
-    """One Adam step of the device against one Adam step of the oracle FROM THE SAME STATE (the oracle was re-synchronised after the
-    previous step): the step-1 tolerances apply to every step -- all but 3e-3 of the table rows / first-order weights and 1e-2 of the
-    dense weights whose |g| >= 1e-5 within 2 % of a step, mean difference within 0.2 % of a step, nothing off by more than one step
-    (an element whose gradient is ~0 may take +lr on one side and -lr on the other: 2 lr) -- and the gradients themselves directly."""
-    torch.cuda.synchronize()
-    got_t, got_l = eng.table[orc.Ud].cpu().numpy(), eng.lin_w[orc.Ud].cpu().numpy()
-    _assert_close_adam("step %d table rows" % step, got_t, orc.table.numpy(), lr, 3e-3)
-    _assert_close_adam("step %d first-order weights" % step, got_l, orc.lin.numpy(), lr, 3e-3)
-    _assert_close_adam("step %d first-order bias" % step, eng.lin_bias.cpu().numpy(), orc.bias.numpy(), lr, 0.0)
-    nW = len(orc.Ws)
-    for j in range(nW):
-        # the dense gradients (the engine's Adam bucket holds this step's): the direct check.  A ReLU tie moves a whole column of W0's
-        # gradient by ~1e-7, hence the rms-relative floor.
-        for nm, got, want in (("gW%d" % j, eng.gWs[j], orc.last_gW[j]), ("gb%d" % j, eng.gbs[j], orc.last_gb[j])):
-            got, want = got.cpu().numpy().astype(np.float64), want.numpy().astype(np.float64)
-            rms = float(np.sqrt(np.mean(want * want)))
-            bad = np.abs(got - want) > 1e-3 * np.abs(want) + 2e-2 * rms
-            assert float(bad.mean()) <= 1e-3, "step %d %s: %.2e of the gradient elements off (rms %.3e, worst %.3e)" % (
-                step, nm, float(bad.mean()), rms, float(np.abs(got - want).max()))
-        # the updated weights.  A step moves an element by ~ lr * g / (|g| + 3e-7): where |g| is within an order of magnitude of 3e-7 a
-        # 1e-8 difference in g -- fp32 summation order -- moves the step by per cents; those elements are covered by the gradient check,
-        # the update itself is compared where this step's |g| >= 1e-5
-        for nm, got, want, g_ in (("W%d" % j, eng.Ws[j], orc.Ws[j], orc.last_gW[j]), ("b%d" % j, eng.bs[j], orc.bs[j], orc.last_gb[j])):
-            sel = (g_.abs() >= 1e-5).numpy()
-            if sel.sum() >= 16:
-                _assert_close_adam("step %d %s" % (step, nm), got.cpu().numpy()[sel], want.numpy()[sel], lr, 1e-2, mean_tol=2e-3)
-            err = np.abs(got.cpu().numpy().astype(np.float64) - want.numpy().astype(np.float64))
-            assert float(err.max()) <= 2.05 * lr, "step %d %s: worst difference %.3e exceeds what one Adam step can differ by" % (step, nm, float(err.max()))
-
-
 def _make_engine(V, optimizer, lr, overlap=None):
     from deep_recommenders_amd.engine import DeepFMEngine
     old = os.environ.get("DR_OVERLAP_DW")
@@ -259,7 +81,7 @@ def _run_deepfm(V, optimizer, kind, lr, steps=2):
     assert ops.linear_bwd_narrow_supported(B, 256, 32) and eng.narrow_ws[1] is not None
     batches = _batches(steps, kind, seed=1234)
     ids_list = [_oracle_ids(k, V) for k, _, _ in batches]
-    orc = _CompactOracle(eng, ids_list, V, optimizer, lr)
+    orc = _CompactOracle(eng, ids_list, optimizer, lr)
     # untouched rows: a sample outside the touched set, must stay bit-identical
     g = torch.Generator().manual_seed(5)
     cand = torch.randint(0, F * V, (40000,), generator=g).numpy()

@@ -68,19 +68,22 @@ def _run(ops, s, fused, lr=0.05):
         k4(1)
         k4(2)
     torch.cuda.synchronize()
-    return table, lin, bias, tab_am.clone(), plan
+    return table, lin, bias, tab_am.clone(), plan, d_concat
 
 
-@pytest.mark.parametrize("B,F,V,H,n_dense,skew,missing", [
+SHAPES = [
     (1024, 6, 5000, 64, 0, False, 0.0),          # interior row tiles, 1.5 column tiles
     (1000, 5, 300, 96, 13, False, 0.05),         # ragged last row tile, many shared rows, missing ids, dense columns behind the embeddings
     (2500, 9, 200000, 256, 13, False, 0.0),      # mostly unique rows, K = 256 (the bench layer's width), 3 column tiles
     (3000, 4, 4000, 32, 0, True, 0.02),          # Zipf-like ids: hot rows through the duplicate pass
-])
+]
+
+
+@pytest.mark.parametrize("B,F,V,H,n_dense,skew,missing", SHAPES)
 def test_fused_dgrad_k4_is_bit_identical_to_dgrad_then_k4(ops, B, F, V, H, n_dense, skew, missing):
     s = _setup(ops, B, F, V, H, n_dense, seed=B + F, skew=skew, missing=missing)
-    t0, l0, b0, a0, plan = _run(ops, s, fused=False)
-    t1, l1, b1, a1, _ = _run(ops, s, fused=True)
+    t0, l0, b0, a0, plan, _ = _run(ops, s, fused=False)
+    t1, l1, b1, a1, _, _ = _run(ops, s, fused=True)
     uniq = int(plan.flags[:B * F].sum().item())
     assert 0 < uniq <= B * F
     assert not torch.equal(t0, s["table"])                                  # the step did move the table
@@ -90,23 +93,59 @@ def test_fused_dgrad_k4_is_bit_identical_to_dgrad_then_k4(ops, B, F, V, H, n_den
     assert torch.equal(a1, a0)                                              # the table's amax record as K4 leaves it
 
 
-def test_fused_dgrad_k4_against_fp64(ops):
-    """... and the pair itself against a float64 restatement of the update (unique rows only -- where the fused epilogue acts)."""
-    s = _setup(ops, 1500, 7, 100000, 128, 13, seed=3)
+@pytest.mark.parametrize("B,F,V,H,n_dense,skew,missing", SHAPES + [(1500, 7, 100000, 128, 13, False, 0.0)])
+def test_fused_dgrad_k4_against_fp64(ops, B, F, V, H, n_dense, skew, missing):
+    """... and the whole backward -- fused dgrad + unique rows, duplicate pass, hot rows -- against a float64 restatement of the update:
+    EVERY touched row and first-order weight (the gradient summed over all slots that share the row, x read before the update, a
+    missing id contributing nothing), every other row bit-identical, the first-order bias against -lr sum(dl), and what the launch
+    leaves in d_concat for the duplicate pass (the rows of the slots that are not unique) against dy W^T.  The fused launch documents
+    d_concat as [M, >= 64 F]: it does not write the dense features' columns (nothing trains them), so those are compared on the
+    unfused dgrad, which does.
+    Bounds: 2e-6 max |want| on rows (and, relative to max |dx|, on d_concat), 1e-7 on first-order weights; the bias is one fp32 sum of
+    B terms: B 2^-24 lr sum |dl|, the worst case of any summation order."""
+    s = _setup(ops, B, F, V, H, n_dense, seed=B + F, skew=skew, missing=missing)
     lr = 0.05
-    t1, l1, _, _, plan = _run(ops, s, fused=True, lr=lr)
-    B, F = s["ids"].shape
+    t1, l1, b1, _, plan, dc = _run(ops, s, fused=True, lr=lr)
+    D, R, in_dim = 64, s["R"], s["in_dim"]
     flags = plan.flags[:B * F].reshape(B, F).bool()
-    dx = (s["dy"].double() @ s["W"].double().t())[:, :F * 64].reshape(B, F, 64)
-    idc = s["ids"] + s["row_base"][None, :]
+    valid = s["ids"] >= 0
+    assert bool((valid & ~flags).any()) and bool(flags.any()) and (missing == 0.0 or bool((~valid).any()))
+    idc = s["ids"].clamp_min(0) + s["row_base"][None, :]
+    dx_all = s["dy"].double() @ s["W"].double().t()
+    dx = dx_all[:, :F * D].reshape(B, F, D)
+    dl = s["dl"].double()
     x = s["table"][idc].double()
-    g = dx + s["dl"].double()[:, None, None] * (s["sum_x"].double()[:, None, :] - x)
-    want = x - lr * g
-    got = t1[idc].double()
-    err = ((got - want).abs() * flags[..., None]).max().item()
+    g = (dx + dl[:, None, None] * (s["sum_x"].double()[:, None, :] - x)) * valid[..., None]
+    G = torch.zeros((R, D), dtype=torch.float64, device="cuda").index_add_(0, idc.reshape(-1), g.reshape(-1, D))
+    GL = torch.zeros(R, dtype=torch.float64, device="cuda").index_add_(0, idc.reshape(-1), (dl[:, None] * valid).reshape(-1))
+    rows = torch.unique(idc[valid])
+    cnt = torch.bincount(idc[valid], minlength=R)
+    assert not skew or int(cnt.max()) > 32                                  # (the skewed case does reach the parked-pieces path)
+    want = s["table"][rows].double() - lr * G[rows]
+    err = (t1[rows].double() - want).abs().max().item()
+    print("rows: worst |err| %.3e, bound %.3e" % (err, 2e-6 * want.abs().max().item()))
     assert err <= 2e-6 * want.abs().max().item()
-    wl = s["lin"][idc].double() - lr * s["dl"].double()[:, None]
-    assert ((l1[idc].double() - wl).abs() * flags).max().item() <= 1e-7
+    wl = s["lin"][rows].double() - lr * GL[rows]
+    err_l = (l1[rows].double() - wl).abs().max().item()
+    print("first-order weights: worst |err| %.3e, bound 1e-7" % err_l)
+    assert err_l <= 1e-7
+    rest = torch.ones(R, dtype=torch.bool, device="cuda")
+    rest[rows] = False
+    assert torch.equal(t1[rest], s["table"][rest]) and torch.equal(l1[rest], s["lin"][rest]), "a row no slot looked up changed"
+    want_b = -lr * dl.sum().item()
+    tol_b = B * 2.0 ** -24 * lr * dl.abs().sum().item()
+    print("first-order bias: |err| %.3e, bound %.3e" % (abs(b1.item() - want_b), tol_b))
+    assert abs(b1.item() - want_b) <= tol_b
+    scale = dx_all.abs().max().item()
+    got = dc[:, :F * D].reshape(B, F, D)[~flags].double()
+    err_d = (got - dx[~flags]).abs().max().item()
+    print("d_concat rows of the non-unique slots: worst |err| %.3e, bound %.3e" % (err_d, 2e-6 * scale))
+    assert err_d <= 2e-6 * scale
+    if n_dense:
+        dc0 = _run(ops, s, fused=False, lr=lr)[5]
+        err_n = (dc0[:, F * D:in_dim].double() - dx_all[:, F * D:]).abs().max().item()
+        print("d_concat dense columns (unfused dgrad): worst |err| %.3e, bound %.3e" % (err_n, 2e-6 * scale))
+        assert err_n <= 2e-6 * scale
 
 
 @pytest.mark.parametrize("V,zipf", [(3000, False), (200000, False), (50000, True)])

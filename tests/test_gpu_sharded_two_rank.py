@@ -33,7 +33,7 @@ DEDUP = dict(F=5, V=503, D=64, B=4096, Nd=3, units=[128, 16], lr=0.05, key_max=1
 
 def _assert_close(name, got, want, before=None, rel=2e-3):
     """parameters after N steps: |got - want| <= rel * |want - before| + a few ulp + 1e-3 rms(update) for all but 1e-4 of the
-    elements (ReLU ties, see tests/test_gpu_benchcfg.py::_assert_update); without `before`: plain allclose."""
+    elements (ReLU ties, see tests/engine_oracle.py::_assert_update); without `before`: plain allclose."""
     got, want = got.double().numpy(), want.double().numpy()
     if before is None:
         np.testing.assert_allclose(got, want, rtol=2e-5, atol=2e-6, err_msg=name)
@@ -90,7 +90,7 @@ def test_two_ranks_one_gpu_deepfm_adam_equals_oracle(tmp_path):
         assert abs(got - lo) <= 1e-5 * abs(lo), (t, got, lo)
 
     def close(name, got, want):
-        # Adam divides by sqrt(v): tolerances are fractions of one step (see tests/test_gpu_benchcfg.py::_assert_close_adam)
+        # Adam divides by sqrt(v): tolerances are fractions of one step (see tests/engine_oracle.py::_assert_close_adam)
         err = (got.double() - want.double()).abs().numpy()
         assert float((err > 2e-2 * lr).mean()) <= 2e-2, "%s: %.2e of the elements off by > 2 %% of a step" % (name, float((err > 2e-2 * lr).mean()))
         assert float(err.mean()) <= 2e-3 * lr and float(err.max()) <= lr, "%s: mean %.3e max %.3e of a step" % (name, err.mean() / lr, err.max() / lr)

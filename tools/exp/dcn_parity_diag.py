@@ -16,6 +16,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import test_gpu_benchcfg as tb                       # noqa: E402
+from engine_oracle import _ulp                     # noqa: E402
 from deep_recommenders_amd import ops               # noqa: E402
 
 
@@ -24,7 +25,7 @@ def report(name, before, after, want, rel=1e-2):
     d_gpu, d_cpu = after.astype(np.float64) - b64, want.astype(np.float64) - b64
     rms = float(np.sqrt(np.mean(d_cpu * d_cpu)))
     err = np.abs(d_gpu - d_cpu)
-    tol = 2 * np.maximum(tb._ulp(before), tb._ulp(want)) + rel * np.abs(d_cpu) + 1e-3 * rms
+    tol = 2 * np.maximum(_ulp(before), _ulp(want)) + rel * np.abs(d_cpu) + 1e-3 * rms
     bad = err > tol
     line = "  %-12s off %.2e of %d   rms err / rms update %.2e   max err / rms %.2e" % (
         name, bad.mean(), bad.size, float(np.sqrt(np.mean(err * err))) / rms, float(err.max()) / rms)
