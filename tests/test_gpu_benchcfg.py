@@ -28,6 +28,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import tf_semantics as O
 from oracle import torch_ref as T
+from dcn_oracle import _dcn_step_vs_oracle, make_engine as _make_dcn_engine
 from engine_oracle import _assert_update, _check_adam_step, _CompactOracle, _device_relu_masks
 
 F, D, ND, B, DNN = 26, 64, 13, 65536, [256, 32]
@@ -257,63 +258,17 @@ def test_deepfm_bench_config_overlap_on_off_agree():
         _assert_update(name + " (overlap off vs on)", b0, a1, a0, rel=1e-4, outliers=1e-4)
 
 
-def _dcn_step_vs_oracle(Bd, V, tie_aware=True):
-    """One DCNEngine step at bench.py --model dcn's shapes against the float64 oracle (T.cross / T.dnn under autograd).  Returns
-    (loss_device, loss_oracle, ties, [(name, before, after_device, after_oracle), ...]); see the test below."""
-    from deep_recommenders_amd.dcn_engine import DCNEngine
-    lr = 1.0
-    eng = DCNEngine(F, V, D, 3, [1024, 512, 256], Bd, num_dense=ND, lr=lr, seed=11)
-    g = torch.Generator(device="cuda")
-    g.manual_seed(3)
-    with torch.no_grad():
-        for b in eng.cross_b:
-            b.normal_(0, 0.05, generator=g)
-        eng.bs[-1].fill_(0.03)          # see test_gpu_models.py::test_dcn_engine_train_step_matches_oracle (loss kink at logit 0)
+def _dcn_bench_step(Bd, V, tie_aware=True):
+    """One DCNEngine step at bench.py --model dcn's shapes against the float64 oracle (tests/dcn_oracle.py: T.cross / T.dnn under
+    autograd).  Returns (loss_device, loss_oracle, ties, [(name, before, after_device, after_oracle), ...]); see the test below."""
+    eng, g = _make_dcn_engine(F, V, D, ND, 3, [1024, 512, 256], Bd, 0.0, lr=1.0, seed=11, gen_seed=3)
     keys = torch.randint(0, 10**16, (Bd, F), device="cuda", generator=g)
     dense = torch.log1p(torch.randn((Bd, ND), device="cuda", generator=g).abs())
     labels = (torch.rand(Bd, device="cuda", generator=g) < 0.25).float()
-    k = keys.cpu().numpy()
-    ids = np.stack([O.hash_bucket_i64(k[:, f], V) for f in range(F)], axis=1)
-    rows = ids + np.arange(F, dtype=np.int64)[None, :] * V
-    U = np.unique(rows.reshape(-1))
-    cidx = torch.from_numpy(np.searchsorted(U, rows))
-    Ud = torch.from_numpy(U).cuda()
-    t0 = eng.table[Ud].cpu()
-    cW0 = [w.cpu().clone() for w in eng.cross_W]
-    cb0 = [b.cpu().clone() for b in eng.cross_b]
-    Ws0 = [w.cpu().clone() for w in eng.Ws]
-    bs0 = [b.cpu().clone() for b in eng.bs]
-    loss = float(eng.train_step(keys, dense, labels).item())
-    np.testing.assert_array_equal(eng.ids.cpu().numpy(), ids)
-    dd = torch.float64
-    emb = t0.to(dd)[cidx].requires_grad_(True)
-    cW = [w.to(dd).requires_grad_(True) for w in cW0]
-    cb = [b.to(dd).requires_grad_(True) for b in cb0]
-    Ws = [w.to(dd).requires_grad_(True) for w in Ws0]
-    bs = [b.to(dd).requires_grad_(True) for b in bs0]
-    x0 = torch.cat([emb.reshape(Bd, F * D), dense.cpu().to(dd)], 1)
-    x = x0
-    for W, b in zip(cW, cb):
-        x = T.cross(x0, x, W, b, 0.0)                                            # dcn.py:81-88
-    # tie-aware: the fp64 oracle takes the ReLU branches the device took (its stored activations h > 0); every unit where that
-    # differs from the oracle's own z > 0 must be within 1e-5 rms(z) of zero (T.check_ties, asserted by the caller)
-    torch.cuda.synchronize()
-    masks, ties = ([(h > 0).cpu() for h in eng.hs[:-1]] if tie_aware else None), []
-    x = T.dnn(x, Ws, bs, relu_masks=masks, ties=ties).reshape(-1)
-    lo = T.sigmoid_cross_entropy(labels.cpu().to(dd), x)
-    grads = torch.autograd.grad(lo, [emb] + cW + cb + Ws + bs)
-    gt = torch.zeros((len(U), D), dtype=dd).index_add_(0, cidx.reshape(-1), grads[0].reshape(-1, D))
-    out = [("table rows", t0.numpy(), eng.table[Ud].cpu().numpy(), (t0.to(dd) - lr * gt).float().numpy())]
-    n, m = 3, len(Ws)
-    for j in range(n):
-        out.append(("cross W%d" % j, cW0[j].numpy(), eng.cross_W[j].cpu().numpy(), (cW0[j].to(dd) - lr * grads[1 + j]).float().numpy()))
-        out.append(("cross b%d" % j, cb0[j].numpy(), eng.cross_b[j].cpu().numpy(), (cb0[j].to(dd) - lr * grads[1 + n + j]).float().numpy()))
-    for j in range(m):
-        out.append(("mlp W%d" % j, Ws0[j].numpy(), eng.Ws[j].cpu().numpy(), (Ws0[j].to(dd) - lr * grads[1 + 2 * n + j]).float().numpy()))
-        out.append(("mlp b%d" % j, bs0[j].numpy(), eng.bs[j].cpu().numpy(), (bs0[j].to(dd) - lr * grads[1 + 2 * n + m + j]).float().numpy()))
+    loss, want, ties, out, _ = _dcn_step_vs_oracle(eng, keys, dense, labels, tie_aware=tie_aware)
     del eng
     torch.cuda.empty_cache()
-    return loss, lo.item(), ties, out
+    return loss, want, ties, out
 
 
 @pytest.mark.parametrize("Bd,V", [(8192, 200_000), (65536, 10_000_000)])
@@ -324,7 +279,7 @@ def test_dcn_bench_config_matches_oracle(Bd, V):
     the touched rows are gathered to the host and the oracle trains that compact table.
     Oracle in float64 (T.cross / dense layers under autograd), as in test_gpu_models.py, tie-aware (oracle/torch_ref.py dnn): no
     allowance for ReLU ties in the tolerances below (round 4 had widened the table rows' to 1e-3)."""
-    loss, want, ties, params = _dcn_step_vs_oracle(Bd, V)
+    loss, want, ties, params = _dcn_bench_step(Bd, V)
     T.check_ties(ties)
     print("ReLU ties resolved the device's way: %s" % [(t["layer"], t["disagree"], t["worst_abs_z"]) for t in ties])
     assert abs(loss - want) <= 1e-5 * abs(want), (loss, want)

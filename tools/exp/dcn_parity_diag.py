@@ -46,7 +46,7 @@ def main():
         ops.set_gemm_split(split)
         for rep in range(2):
             for tie_aware in ((False, True) if rep == 0 else (True,)):
-                loss, want, ties, params = tb._dcn_step_vs_oracle(Bd, V, tie_aware=tie_aware)
+                loss, want, ties, params = tb._dcn_bench_step(Bd, V, tie_aware=tie_aware)
                 print("split %s run %d tie_aware %s: loss %.9f oracle %.9f (rel %.2e); ties %s" % (
                     split, rep, tie_aware, loss, want, abs(loss - want) / abs(want),
                     [(t["layer"], t["disagree"], "%.2e" % t["worst_abs_z"], "%.2e" % t["rms_z"], t["examples"][:8]) for t in ties]), flush=True)
