@@ -94,14 +94,16 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
     // per-lane byte offset inside a k-tile's rows (32-bit) + a wave-uniform row pointer per load: one address register, the
     // row stepping stays on the scalar unit
     const unsigned xoff = (unsigned)((16 * hi * g.ldx + fcol) * 4), yoff = (unsigned)((16 * hi * g.ldy + ncol) * 4);
-    auto load_raw = [&](float (&dst)[16], const float* base, int64_t ld, unsigned voff, int64_t r0) {
-        if (r0 + BK <= r_end) {                                         // (wave-uniform) a full k-tile: no checks
+    // (elements [e0, e1): all 16, or one k-step's 8 where the main loop re-issues an operand in pieces; known_full: the caller
+    // knows that the k-tile is a full one, and the other arm is not even compiled in)
+    auto load_raw = [&](float (&dst)[16], const float* base, int64_t ld, unsigned voff, int64_t r0, int e0 = 0, int e1 = 16, bool known_full = false) {
+        if (known_full || r0 + BK <= r_end) {                           // (wave-uniform) a full k-tile: no checks
             const char* rowp = reinterpret_cast<const char*>(base + r0 * ld);
 #pragma unroll
-            for (int e = 0; e < 16; ++e) dst[e] = *reinterpret_cast<const float*>(rowp + (int64_t)e * ld * 4 + voff);
+            for (int e = e0; e < e1; ++e) dst[e] = *reinterpret_cast<const float*>(rowp + (int64_t)e * ld * 4 + voff);
         } else {                                                        // the slice's last, partial k-tile (or past its end)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
+            for (int e = e0; e < e1; ++e) {
                 const int64_t r = r0 + 16 * hi + e;
                 const bool ok = r < r_end;
                 const float v = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base + (ok ? r : r_end - 1) * ld) +
@@ -163,25 +165,33 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
         const int64_t r = r0 + id_lane < g.R ? r0 + id_lane : g.R - 1;
         return idrow[r];
     };
-    auto load_gather = [&](float (&dst)[16], int ids_of_tile, int64_t r0) {
-        const bool full = r0 + BK <= r_end;                             // (wave-uniform) all but a slice's last k-tile
-        unsigned off[16];
+    // the byte offsets of elements [e0, e1) of the k-tile at r0 (whose ids are ids_of_tile), then the loads themselves: two steps, so
+    // that the main loop can put the next id load between them
+    auto gather_offsets = [&](unsigned (&off)[16], int ids_of_tile, int64_t r0, int e0, int e1, bool known_full = false) {
+        const bool full = known_full || r0 + BK <= r_end;               // (wave-uniform) all but a slice's last k-tile
         if (w_field) {                                                  // (wave-uniform; ONE branch, not one per load)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) off[e] = (unsigned)gather_id(ids_of_tile, e) * gpitch;
+            for (int e = e0; e < e1; ++e) off[e] = (unsigned)gather_id(ids_of_tile, e) * gpitch;
         } else {                                                        // dense_pad: R rows of 128 bytes, below 4 GB; no columns: 0
             const unsigned o0 = (unsigned)(r0 + 16 * hi) * gpitch;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) off[e] = o0 + (unsigned)e * gpitch;
+            for (int e = e0; e < e1; ++e) off[e] = o0 + (unsigned)e * gpitch;
         }
         if (!full) {
             const int nv = (int)(r_end - r0 < BK ? r_end - r0 : BK) - 16 * hi;     // this lane half's rows inside the slice (<= 0: none)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) off[e] = e < nv ? off[e] : 0xFFFFFF00u;
+            for (int e = e0; e < e1; ++e) off[e] = e < nv ? off[e] : 0xFFFFFF00u;
         }
+    };
+    auto gather_issue = [&](float (&dst)[16], const unsigned (&off)[16], int e0, int e1) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e)
+        for (int e = e0; e < e1; ++e)
             dst[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(grsrc, (int)(off[e] + gcol), 0, DR_NT_WGRAD_GATHER ? 2 : 0));
+    };
+    auto load_gather = [&](float (&dst)[16], int ids_of_tile, int64_t r0) {
+        unsigned off[16];
+        gather_offsets(off, ids_of_tile, r0, 0, 16);
+        gather_issue(dst, off, 0, 16);
     };
     bf16x8 fa[2][3];
     bf16x8 fb[4][3];                                                    // group q uses buffer q & 3, read two groups ahead
@@ -215,48 +225,19 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
 #pragma unroll
         for (int k = 0; k < 16; ++k) acc[tt][k] = 0.f;
 
-    // ---- prologue: B(0) into stage 0, A(0) and B(1) into registers -------------------------------------------------------------
-    load_raw(yb, g.Y, g.ldy, yoff, r_begin);
-    stage_b(0);
-    if (GATHER) {
-        idv = load_ids(r_begin);
-        load_gather(xa, idv, r_begin);
-        idv = load_ids(r_begin + BK);
-    } else {
-        load_raw(xa, g.X, g.ldx, xoff, r_begin);
-    }
-    load_raw(yb, g.Y, g.ldy, yoff, r_begin + BK);                       // (all zeros when nk == 1)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    read_b(0, 0, 0);
-    read_b(1, 0, 1);
-
-    for (int kt = 0; kt < nk; ++kt) {
-        const int stage = kt & 1;
-        // A of this k-tile -> bf16 terms; B of the next k-tile -> the other stage (its readers passed the barrier at the end of
-        // the previous step); the loads of the k-tile after that go into flight
-        {
-            float v[8];
+    auto split_a = [&](int s) {                                         // k-step s of xa -> its terms
+        float v[8];
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = xa[8 * s + j];
-                if constexpr (H2) h2_split8v(v, h2_sx, fa[s][0], fa[s][1]);
-                else rs_split8v(v, fa[s][0], fa[s][1], fa[s][2]);
-            }
-        }
-        if (kt + 1 < nk) stage_b(stage ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (GATHER) {
-            // (the loads stay between these two scheduling barriers, in front of the MFMA loop's fragment reads)
-            load_gather(xa, idv, r_begin + (int64_t)(kt + 1) * BK);
-            idv = load_ids(r_begin + (int64_t)(kt + 2) * BK);
-        } else {
-            load_raw(xa, g.X, g.ldx, xoff, r_begin + (int64_t)(kt + 1) * BK);
-        }
-        load_raw(yb, g.Y, g.ldy, yoff, r_begin + (int64_t)(kt + 2) * BK);
-        __builtin_amdgcn_sched_barrier(0);
+        for (int j = 0; j < 8; ++j) v[j] = xa[8 * s + j];
+        if constexpr (H2) h2_split8v(v, h2_sx, fa[s][0], fa[s][1]);
+        else rs_split8v(v, fa[s][0], fa[s][1], fa[s][2]);
+    };
+    // The 16 MFMA groups of the k-tile in `stage` (groups 0 and 1 are in fb already); more: another k-tile follows in the other stage.
+    // before_group(q) is the place of whatever a caller interleaves with the groups.
+    auto mma_groups = [&](int stage, bool more, auto&& before_group) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
+            before_group(q);
             if (q < 14) {
                 rs_wait_frag<NPL, NPL>(fb[q & 3]);                     // the next group's NPL reads may fly
                 read_b((q + 2) & 3, stage, q + 2);
@@ -265,14 +246,145 @@ __global__ __launch_bounds__(512, 2) void bf3_gemm_tn_rs_kernel(TnRsArgs g) {
                 // have retired (lgkmcnt(0) covers both): publish
                 rs_wait_frag<NPL, 0>(fb[2]);
                 asm volatile("s_barrier" ::: "memory");
-                if (kt + 1 < nk) read_b(0, stage ^ 1, 0);
+                if (more) read_b(0, stage ^ 1, 0);
             } else {
-                if (kt + 1 < nk) read_b(1, stage ^ 1, 1);
+                if (more) read_b(1, stage ^ 1, 1);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int term = 0; term < RS_TERMS<H2>; ++term) acc[q & 7] = rs_mma_term<H2>(term, fa[q >> 3], fb[q & 3], acc[q & 7]);
             __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    if constexpr (!H2) {
+        // ---- prologue: B(0) into stage 0, A(0) and B(1) into registers ---------------------------------------------------------
+        load_raw(yb, g.Y, g.ldy, yoff, r_begin);
+        stage_b(0);
+        if (GATHER) {
+            idv = load_ids(r_begin);
+            load_gather(xa, idv, r_begin);
+            idv = load_ids(r_begin + BK);
+        } else {
+            load_raw(xa, g.X, g.ldx, xoff, r_begin);
+        }
+        load_raw(yb, g.Y, g.ldy, yoff, r_begin + BK);                   // (all zeros when nk == 1)
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        read_b(0, 0, 0);
+        read_b(1, 0, 1);
+        for (int kt = 0; kt < nk; ++kt) {
+            const int stage = kt & 1;
+            // A of this k-tile -> bf16 terms; B of the next k-tile -> the other stage (its readers passed the barrier at the end of
+            // the previous step); the loads of the k-tile after that go into flight
+            split_a(0);
+            split_a(1);
+            if (kt + 1 < nk) stage_b(stage ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (GATHER) {
+                // (the loads stay between these two scheduling barriers, in front of the MFMA loop's fragment reads)
+                load_gather(xa, idv, r_begin + (int64_t)(kt + 1) * BK);
+                idv = load_ids(r_begin + (int64_t)(kt + 2) * BK);
+            } else {
+                load_raw(xa, g.X, g.ldx, xoff, r_begin + (int64_t)(kt + 1) * BK);
+            }
+            load_raw(yb, g.Y, g.ldy, yoff, r_begin + (int64_t)(kt + 2) * BK);
+            __builtin_amdgcn_sched_barrier(0);
+            mma_groups(stage, kt + 1 < nk, [](int) {});
+        }
+    } else {
+        // f16x2 mode (the registers of the third plane are free).  Every operand register set is consumed where its first reader
+        // needs it and re-issued at once, at THREE points of a step, so that a block never has all of its loads retired at the same
+        // time -- its eight waves run in one phase, and with one consume-all / issue-all point per step the CU had nothing in flight
+        // once per k-tile.  k-step 0 of x at the top, k-step 1 in front of MFMA group Q_A1 (its first reader is group 8), dy in front
+        // of group Q_B (its image is published by the barrier of group 14).  Issue order: x k-step 0, ids, x k-step 1, dy; at the
+        // three waits 24 / 24 / 16 younger loads stay in flight (+ the id load).
+        // The waits are the compiler's, and they come out exact only while NO load result is consumed under a branch on any path
+        // into the loop: the select of load_raw's partial arm drains everything there, and every wait behind the join inherits the
+        // drained path (measured in the ISA: vmcnt(8) where 24 were possible).  So the pipelined loop runs over the slice's FULL
+        // k-tiles only, its loads are all of the unchecked kind (a prefetch past the last full k-tile reads that one again and is
+        // never consumed), and a partial last k-tile gets a step of its own behind the loop.  Same products in the same order.
+        constexpr int Q_A1 = 5, Q_B = 10;                               // (3 - 6 and 10 - 12 measured: within 3 us of one another)
+        const int nfull = (int)((r_end - r_begin) / BK);                // nk == nfull, or nfull + 1 with a partial last k-tile
+        if (nfull > 0) {
+            const int64_t r_last = r_begin + (int64_t)(nfull - 1) * BK;
+            int64_t r1 = nfull > 1 ? r_begin + BK : r_last;             // the k-tile after this step's, and the one after that
+            int64_t r2 = nfull > 2 ? r_begin + 2 * BK : r_last;
+            // ---- prologue: B(0) into stage 0, A(0) and B(1) into registers, in the loop's issue order --------------------------
+            load_raw(yb, g.Y, g.ldy, yoff, r_begin, 0, 16, true);
+            stage_b(0);
+            if (GATHER) {
+                idv = load_ids(r_begin);
+                unsigned off[16];
+                gather_offsets(off, idv, r_begin, 0, 16, true);
+                gather_issue(xa, off, 0, 8);
+                __builtin_amdgcn_sched_barrier(0);
+                idv = load_ids(r1);
+                __builtin_amdgcn_sched_barrier(0);
+                gather_issue(xa, off, 8, 16);
+            } else {
+                load_raw(xa, g.X, g.ldx, xoff, r_begin, 0, 16, true);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            load_raw(yb, g.Y, g.ldy, yoff, r1, 0, 16, true);
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            read_b(0, 0, 0);
+            read_b(1, 0, 1);
+            for (int kt = 0; kt < nfull; ++kt) {
+                const int stage = kt & 1;
+                const bool more = kt + 1 < nfull;
+                split_a(0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (GATHER) {
+                    unsigned off[16];
+                    gather_offsets(off, idv, r1, 0, 8, true);
+                    gather_issue(xa, off, 0, 8);
+                } else {
+                    load_raw(xa, g.X, g.ldx, xoff, r1, 0, 8, true);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                mma_groups(stage, more, [&](int q) {
+                    if (q == Q_A1) {
+                        split_a(1);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (GATHER) {
+                            unsigned off[16];
+                            gather_offsets(off, idv, r1, 8, 16, true);  // (the last readers of this id register)
+                            idv = load_ids(r2);
+                            gather_issue(xa, off, 8, 16);
+                        } else {
+                            load_raw(xa, g.X, g.ldx, xoff, r1, 8, 16, true);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if (q == Q_B) {
+                        if (more) stage_b(stage ^ 1);                   // (its readers passed the barrier of the previous step)
+                        __builtin_amdgcn_sched_barrier(0);
+                        load_raw(yb, g.Y, g.ldy, yoff, r2, 0, 16, true);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
+                r1 = r2;
+                r2 = r2 < r_last ? r2 + BK : r_last;
+            }
+        }
+        if (nk > nfull) {
+            // ---- the slice's last, partial k-tile: rows past the end are zeros (load_raw's checks, the gather's range check) ------
+            const int stage = nfull & 1;                                // (last read two barriers ago)
+            const int64_t r0 = r_begin + (int64_t)nfull * BK;
+            load_raw(yb, g.Y, g.ldy, yoff, r0);
+            if (GATHER) {
+                idv = load_ids(r0);
+                load_gather(xa, idv, r0);
+            } else {
+                load_raw(xa, g.X, g.ldx, xoff, r0);
+            }
+            stage_b(stage);
+            split_a(0);
+            split_a(1);
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            read_b(0, stage, 0);
+            read_b(1, stage, 1);
+            mma_groups(stage, false, [](int) {});
         }
     }
     // ---- epilogue: partial tile (padded workspace: unconditional stores); C/D layout: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 hi
