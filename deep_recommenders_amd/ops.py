@@ -3039,6 +3039,240 @@ def ffm_gather_bwd(ids, row_base, table, F, k, d_inter, d_rows=None):
     return d_rows
 
 
+# ---- NFM: the Bi-Interaction pooling (csrc/bi_interaction.hip) ----------------------------------------------------------------------------
+def _bi_dims(F, D):
+    """validates the domain of dr_bi_interact_*; returns (F, D) as ints"""
+    F, D = int(F), int(D)
+    if D % 4 != 0 or not 4 <= D <= 256:
+        raise ValueError("bi_interaction: the row width D must be a multiple of 4 in [4, 256], got %d" % D)
+    if not 1 <= F <= 1024:
+        raise ValueError("bi_interaction: needs 1 <= F <= 1024 fields, got F = %d" % F)
+    return F, D
+
+
+def _bi_rows(t, F, D, what):
+    """(t as [B, F * D], its row stride) of a fp32 matrix of rows with unit column stride; [B, F, D] contiguous is taken as it is"""
+    cols = F * D
+    if t.dtype != torch.float32:
+        raise ValueError("bi_interaction: %s must be fp32, got %s" % (what, t.dtype))
+    if t.dim() == 3:
+        if tuple(t.shape[1:]) != (F, D) or not t.is_contiguous():
+            raise ValueError("bi_interaction: a 3-d %s must be contiguous [B, %d, %d], got %s" % (what, F, D, tuple(t.shape)))
+        t = t.reshape(t.shape[0], cols)
+    return t, _row_pitch("bi_interaction", t, cols, what)
+
+
+def _bi_out(t, B, D, what, device):
+    """(t, its row stride) of an [B, D] fp32 output or gradient; allocated when None"""
+    if t is None:
+        t = torch.empty((B, D), dtype=torch.float32, device=device)
+    if t.dim() != 2 or t.shape[0] != B:
+        raise ValueError("bi_interaction: %s must be fp32 [%d, %d], got %s %s" % (what, B, D, t.dtype, tuple(t.shape)))
+    return t, _row_pitch("bi_interaction", t, D, what)
+
+
+def _bi_gather_args(ids, row_base, table, F, D, lin_w=None, lin_bias=None):
+    F, D = _bi_dims(F, D)
+    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[1] != F:
+        raise ValueError("bi_interaction: ids must be int64 [B, %d] (one id per field), got %s %s" % (F, ids.dtype, tuple(ids.shape)))
+    if row_base.dtype != torch.int64 or row_base.numel() != F:
+        raise ValueError("bi_interaction: row_base must be int64 [%d], got %s %s" % (F, row_base.dtype, tuple(row_base.shape)))
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != D or not table.is_contiguous():
+        raise ValueError("bi_interaction: table must be contiguous fp32 [R, %d], got %s %s" % (D, table.dtype, tuple(table.shape)))
+    lin_w = _dense_arg(lin_w, "bi_interaction: lin_w", numel=table.shape[0])
+    lin_bias = _dense_arg(lin_bias, "bi_interaction: lin_bias", numel=1)
+    return F, D, ids.contiguous(), row_base.contiguous(), lin_w, lin_bias
+
+
+def bi_interaction_fwd(rows, F, D, out=None):
+    """out [B, D] of dr_bi_interact_fwd: 0.5 ((sum_f e_f)^2 - sum_f e_f^2) over the F rows of every example.  rows: [B, F, D] contiguous,
+    or [B, F * D] with any row stride that is a multiple of 4 (the slab's concat, in place).  out: a buffer to overwrite."""
+    F, D = _bi_dims(F, D)
+    rows, ld = _bi_rows(rows, F, D, "rows")
+    B = rows.shape[0]
+    out, ld_out = _bi_out(out, B, D, "out", rows.device)
+    if B == 0:
+        return out
+    _status(lib().dr_bi_interact_fwd(ptr(rows), ld, B, F, D, ptr(out), ld_out, stream_ptr()), "dr_bi_interact_fwd")
+    return out
+
+
+def bi_interaction_bwd(rows, F, D, d_out, d_rows=None):
+    """d_rows [B, F * D] of dr_bi_interact_bwd: d_rows[b, f, :] = d_out[b, :] * (sum_g e_g - e_f).  d_rows: a buffer to overwrite (only
+    its first F * D columns are written)."""
+    F, D = _bi_dims(F, D)
+    rows, ld = _bi_rows(rows, F, D, "rows")
+    B = rows.shape[0]
+    d_out, ld_do = _bi_out(d_out, B, D, "d_out", rows.device)
+    if d_rows is None:
+        d_rows = torch.empty((B, F * D), dtype=torch.float32, device=rows.device)
+    d_rows, ld_d = _bi_rows(d_rows, F, D, "d_rows")
+    if d_rows.shape[0] != B:
+        raise ValueError("bi_interaction: d_rows must have %d rows, got %s" % (B, tuple(d_rows.shape)))
+    if B == 0:
+        return d_rows
+    _status(lib().dr_bi_interact_bwd(ptr(rows), ld, ptr(d_out), ld_do, B, F, D, ptr(d_rows), ld_d, stream_ptr()), "dr_bi_interact_bwd")
+    return d_rows
+
+
+def bi_interaction_gather_fwd(ids, row_base, table, F, D, lin_w=None, lin_bias=None, out=None):
+    """(out [B, D], first_order [B] | None) of dr_bi_interact_gather_fwd for single-valued fields: the rows table[row_base[f] + ids[b, f]]
+    are read from the table and written nowhere; an id < 0 is a row of zeros.  first_order = lin_bias + sum_f lin_w[row] when lin_w is
+    given."""
+    F, D, ids, row_base, lin_w, lin_bias = _bi_gather_args(ids, row_base, table, F, D, lin_w, lin_bias)
+    B = ids.shape[0]
+    out, ld_out = _bi_out(out, B, D, "out", ids.device)
+    first = torch.empty((B,), dtype=torch.float32, device=ids.device) if lin_w is not None else None
+    if B == 0:
+        return out, first
+    _status(lib().dr_bi_interact_gather_fwd(ptr(ids), B, F, ptr(row_base), ptr(table), D, ptr(lin_w), ptr(lin_bias), ptr(out), ld_out,
+                                                ptr(first), stream_ptr()), "dr_bi_interact_gather_fwd")
+    return out, first
+
+
+def bi_interaction_gather_bwd(ids, row_base, table, F, D, d_out, d_rows=None):
+    """d_rows [B, F * D] of dr_bi_interact_gather_bwd, from the table and d_out: what emb_pool_bwd takes as d_concat."""
+    F, D, ids, row_base, _, _ = _bi_gather_args(ids, row_base, table, F, D)
+    B = ids.shape[0]
+    d_out, ld_do = _bi_out(d_out, B, D, "d_out", ids.device)
+    if d_rows is None:
+        d_rows = torch.empty((B, F * D), dtype=torch.float32, device=ids.device)
+    d_rows, ld_d = _bi_rows(d_rows, F, D, "d_rows")
+    if d_rows.shape[0] != B:
+        raise ValueError("bi_interaction: d_rows must have %d rows, got %s" % (B, tuple(d_rows.shape)))
+    if B == 0:
+        return d_rows
+    _status(lib().dr_bi_interact_gather_bwd(ptr(ids), B, F, ptr(row_base), ptr(table), D, ptr(d_out), ld_do, ptr(d_rows), ld_d,
+                                                stream_ptr()), "dr_bi_interact_gather_bwd")
+    return d_rows
+
+
+# ---- LS-PLM: the bag sum and the mixture head (csrc/lsplm.hip) ----------------------------------------------------------------------------
+def _lsplm_dims(F, m):
+    """validates the domain of dr_lsplm_*; returns (F, m) as ints"""
+    F, m = int(F), int(m)
+    if m % 2 != 0 or not 2 <= m <= 128:
+        raise ValueError("lsplm: the number of regions m must be even and in [2, 128], got %d" % m)
+    if not 1 <= F <= 1024:
+        raise ValueError("lsplm: needs 1 <= F <= 1024 fields, got F = %d" % F)
+    return F, m
+
+
+def _lsplm_pool_args(ids, F, col_start, row_base, table, m, bias):
+    """validates the inputs of the pooling; returns (F, m, ids, C, col_start, row_base, bias)"""
+    F, m = _lsplm_dims(F, m)
+    if ids.dtype != torch.int64 or ids.dim() != 2:
+        raise ValueError("lsplm: ids must be int64 [B, C], got %s %s" % (ids.dtype, tuple(ids.shape)))
+    C = int(ids.shape[1])
+    if col_start is None:
+        if C != F:
+            raise ValueError("lsplm: without col_start every field is single-valued and ids must be [B, %d], got %s" % (F, tuple(ids.shape)))
+    else:
+        if col_start.dtype != torch.int32 or col_start.numel() != F + 1:
+            raise ValueError("lsplm: col_start must be int32 [%d], got %s %s" % (F + 1, col_start.dtype, tuple(col_start.shape)))
+        if C < F:
+            raise ValueError("lsplm: ids [B, C] needs C >= F = %d columns, got C = %d" % (F, C))
+        col_start = col_start.contiguous()
+    if row_base.dtype != torch.int64 or row_base.numel() != F:
+        raise ValueError("lsplm: row_base must be int64 [%d], got %s %s" % (F, row_base.dtype, tuple(row_base.shape)))
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 2 * m or not table.is_contiguous():
+        raise ValueError("lsplm: table must be contiguous fp32 [R, %d] (2 m columns: gate | expert), got %s %s"
+                         % (2 * m, table.dtype, tuple(table.shape)))
+    bias = _dense_arg(bias, "lsplm: bias", numel=2 * m)
+    if bias is None:
+        raise ValueError("lsplm: bias [%d] is required" % (2 * m))
+    return F, m, ids.contiguous(), C, col_start, row_base.contiguous(), bias
+
+
+def _lsplm_vec(t, B, what):
+    if t is None:
+        return None
+    if t.dtype != torch.float32 or t.numel() != B:
+        raise ValueError("lsplm: %s must be fp32 with one value per example (%d), got %s %s" % (what, B, t.dtype, tuple(t.shape)))
+    return t.reshape(B).contiguous()
+
+
+def _lsplm_mat(t, B, cols, what, device):
+    """(t, its row stride) of a [B, cols] fp32 buffer the kernel writes; allocated when None"""
+    if t is None:
+        t = torch.empty((B, cols), dtype=torch.float32, device=device)
+    if t.dim() != 2 or t.shape[0] != B:
+        raise ValueError("lsplm: %s must be fp32 [%d, %d], got %s %s" % (what, B, cols, t.dtype, tuple(t.shape)))
+    return t, _row_pitch("lsplm", t, cols, what)
+
+
+def lsplm_fwd(ids, F, col_start, row_base, table, m, bias, want_z=True, z=None):
+    """(p [B], q [B], z [B, 2 m] | None) of dr_lsplm_fwd: z = bias + the sum over the fields of the mean-pooled rows (K3's pooling; ids
+    [B, C] with col_start int32 [F + 1], or col_start None and ids [B, F]), p = sum_i softmax(z[:m])_i sigmoid(z[m + i]) and q = 1 - p
+    computed without the subtraction.  z: a buffer to overwrite."""
+    F, m, ids, C, col_start, row_base, bias = _lsplm_pool_args(ids, F, col_start, row_base, table, m, bias)
+    B = ids.shape[0]
+    ld_z = 0
+    if want_z or z is not None:
+        z, ld_z = _lsplm_mat(z, B, 2 * m, "z", ids.device)
+    p = torch.empty((B,), dtype=torch.float32, device=ids.device)
+    q = torch.empty((B,), dtype=torch.float32, device=ids.device)
+    if B == 0:
+        return p, q, z
+    _status(lib().dr_lsplm_fwd(ptr(ids), B, F, C, ptr(col_start), ptr(row_base), ptr(table), m, ptr(bias), ptr(z), ld_z, ptr(p), ptr(q),
+                               stream_ptr()), "dr_lsplm_fwd")
+    return p, q, z
+
+
+def lsplm_bwd(z, F, m, d_p, d_z=None, d_rows=None):
+    """(d_z [B, 2 m], d_rows [B, F * 2 m]) of dr_lsplm_bwd from the z that lsplm_fwd stored: d_z = d_p [pi (sg - p) ; pi sg (1 - sg)],
+    d_rows = F copies of it (emb_pool_bwd's d_concat with D = 2 m).  d_z, d_rows: buffers to overwrite."""
+    F, m = _lsplm_dims(F, m)
+    if z.dim() != 2:
+        raise ValueError("lsplm: z must be fp32 [B, %d], got %s" % (2 * m, tuple(z.shape)))
+    ld_z = _row_pitch("lsplm", z, 2 * m, "z")
+    B = z.shape[0]
+    d_p = _lsplm_vec(d_p, B, "d_p")
+    if d_p is None:
+        raise ValueError("lsplm: d_p [%d] is required" % B)
+    d_z, ld_dz = _lsplm_mat(d_z, B, 2 * m, "d_z", z.device)
+    d_rows, ld_d = _lsplm_mat(d_rows, B, F * 2 * m, "d_rows", z.device)
+    if B == 0:
+        return d_z, d_rows
+    _status(lib().dr_lsplm_bwd(ptr(z), ld_z, ptr(d_p), B, F, m, ptr(d_z), ld_dz, ptr(d_rows), ld_d, stream_ptr()), "dr_lsplm_bwd")
+    return d_z, d_rows
+
+
+def lsplm_loss_fwd(ids, F, col_start, row_base, table, m, bias, labels, sample_weight=None, row_scale=1.0, d_z=None, d_rows=None):
+    """(p, q, loss [B], d_z [B, 2 m], d_rows [B, F * 2 m]) of dr_lsplm_loss_fwd, the one-pass training form: loss = -wt (y log p +
+    (1 - y) log q) and the gradient of row_scale * loss with respect to z, bit for bit what lsplm_fwd + lsplm_bwd give for d_p =
+    (row_scale * wt) * (-y / p + (1 - y) / q)."""
+    F, m, ids, C, col_start, row_base, bias = _lsplm_pool_args(ids, F, col_start, row_base, table, m, bias)
+    B = ids.shape[0]
+    labels = _lsplm_vec(labels, B, "labels")
+    if labels is None:
+        raise ValueError("lsplm: labels [%d] are required" % B)
+    sample_weight = _lsplm_vec(sample_weight, B, "sample_weight")
+    d_z, ld_dz = _lsplm_mat(d_z, B, 2 * m, "d_z", ids.device)
+    d_rows, ld_d = _lsplm_mat(d_rows, B, F * 2 * m, "d_rows", ids.device)
+    p, q, loss = (torch.empty((B,), dtype=torch.float32, device=ids.device) for _ in range(3))
+    if B == 0:
+        return p, q, loss, d_z, d_rows
+    _status(lib().dr_lsplm_loss_fwd(ptr(ids), B, F, C, ptr(col_start), ptr(row_base), ptr(table), m, ptr(bias), ptr(labels),
+                                    ptr(sample_weight), float(row_scale), ptr(p), ptr(q), ptr(loss), ptr(d_z), ld_dz, ptr(d_rows), ld_d,
+                                    stream_ptr()), "dr_lsplm_loss_fwd")
+    return p, q, loss, d_z, d_rows
+
+
+def lsplm_bias_grad(d_z, m):
+    """d_bias [2 m] of dr_lsplm_bias_grad: the column sum of d_z [B, 2 m] in a fixed order (two stages, no float atomics)"""
+    _, m = _lsplm_dims(1, m)
+    if d_z.dim() != 2:
+        raise ValueError("lsplm: d_z must be fp32 [B, %d], got %s" % (2 * m, tuple(d_z.shape)))
+    ld = _row_pitch("lsplm", d_z, 2 * m, "d_z")
+    B = d_z.shape[0]
+    d_bias = torch.empty((2 * m,), dtype=torch.float32, device=d_z.device)
+    nbytes = int(lib().dr_lsplm_bias_grad_workspace_bytes(B, m))
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=d_z.device)
+    _status(lib().dr_lsplm_bias_grad(ptr(d_z), ld, B, m, ptr(d_bias), ptr(ws), ws.numel() * 4, stream_ptr()), "dr_lsplm_bias_grad")
+    return d_bias
+
+
 # ---- skip-gram with negative sampling (csrc/sgns.hip) and the samplers around it (csrc/sampling.hip) -----------------------------------
 SGNS_SKIP_EQUAL = 1     # DR_SGNS_SKIP_EQUAL
 

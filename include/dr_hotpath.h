@@ -1035,6 +1035,79 @@ int dr_ffm_gather_bwd(const int64_t* ids, int64_t B, int32_t F, const int64_t* r
                       const float* d_inter, float* d_rows, int64_t ld_d, dr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * NFM's Bi-Interaction pooling (He & Chua, SIGIR 2017; the reference's README lists NFM among its ranking models and ships no code for
+ * it), csrc/bi_interaction.hip.  All fp32.  e_f = field f's row (D floats), s = sum_f e_f, q = sum_f e_f * e_f (elementwise):
+ *   out[b, :]        = 0.5 * (s * s - q)             the vector K3 sums over d into fm_logit and never writes
+ *   d_rows[b, f, :]  = d_out[b, :] * (s - e_f)       s is recomputed in the backward; nothing is saved between the two
+ *   dr_bi_interact_fwd / _bwd                rows [B, F * D] at the pitch ld_rows: the slab's concat, read in place (multi-valued
+ *                                            fields that K3 has pooled, or a caller that already holds the rows).  out [B, D] at the
+ *                                            pitch ld_out, d_out at ld_do, d_rows [B, F * D] at ld_d: exactly D (F * D) columns are
+ *                                            written, nothing beyond them.
+ *   dr_bi_interact_gather_fwd / _gather_bwd  single-valued fields, ids [B, F]: row f of example b is table + (row_base[f] +
+ *                                            ids[b, f]) * D, read straight from the table and never written anywhere.  An id < 0 is a
+ *                                            row of zeros and is never dereferenced.  first_order[b] = lin_bias[0] + sum_f
+ *                                            lin_w[row_base[f] + ids[b, f]], added in field order (missing ids skipped), is written
+ *                                            when first_order and lin_w are both given; lin_bias NULL counts as 0.  lin_w, lin_bias
+ *                                            and first_order may be NULL.  d_rows [B, F * D] is what dr_emb_pool_bwd takes as
+ *                                            d_concat; for a missing slot the formula with e = 0 is written, K4 never applies it.
+ *   A group of D / 4 lanes owns an example, lane l the float4 at column 4 l of s and q; the fields are added in ascending order, so
+ *   the order is a function of (F, D) alone: no atomics, no workspace, no LDS, no cross-lane arithmetic.  Results are bit-identical
+ *   from run to run and an example's bits depend neither on its batch nor on its place in it.  The gather entry points run the same
+ *   arithmetic in the same order as the rows entry points: on K3's concat of single-valued fields out and d_rows agree bit for bit.
+ *   s * s and q are rounded separately before the difference: F = 1 gives exactly +0.0.  One launch each.
+ *   Domain: D % 4 == 0 and 4 <= D <= 256 (else DR_ESHAPE); 1 <= F <= 1024, every ld a multiple of 4 and >= its width, rows, table,
+ *   out, d_out and d_rows 16-byte aligned, required pointers non-NULL (else DR_EINVAL).  B == 0 is DR_OK and launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+int dr_bi_interact_fwd(const float* rows, int64_t ld_rows, int64_t B, int32_t F, int32_t D, float* out, int64_t ld_out,
+                       dr_stream_t stream);
+int dr_bi_interact_bwd(const float* rows, int64_t ld_rows, const float* d_out, int64_t ld_do, int64_t B, int32_t F, int32_t D,
+                       float* d_rows, int64_t ld_d, dr_stream_t stream);
+int dr_bi_interact_gather_fwd(const int64_t* ids, int64_t B, int32_t F, const int64_t* row_base, const float* table, int32_t D,
+                              const float* lin_w, const float* lin_bias, float* out, int64_t ld_out, float* first_order,
+                              dr_stream_t stream);
+int dr_bi_interact_gather_bwd(const int64_t* ids, int64_t B, int32_t F, const int64_t* row_base, const float* table, int32_t D,
+                              const float* d_out, int64_t ld_do, float* d_rows, int64_t ld_d, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * LS-PLM, the large-scale piece-wise linear model (Gai et al., Alibaba 2017; listed in the reference's README, no code there),
+ * csrc/lsplm.hip.  All fp32.  A table row is W = 2 m floats: the first m are the gate u, the last m the expert w.
+ *   z[b, :]  = bias[:] + sum_f mean over the valid ids of field f's bag of table[row_base[f] + id, :]
+ *              K3's pooling (ids [B, C], col_start [F + 1], or col_start NULL and C == F for single-valued fields; ids < 0 are
+ *              dropped, an empty bag adds nothing), so dr_emb_pool_bwd with D = W is its exact transpose.
+ *   pi = softmax(z[:m]) with the max subtracted;  sg_i = sigmoid(z[m + i]);  sn_i = sigmoid(-z[m + i])
+ *   p = sum_i pi_i sg_i;   q = sum_i pi_i sn_i  (1 - p, computed without the subtraction: sg and sn share one exponential)
+ *   dr_lsplm_fwd       z (optional, [B, W] at ld_z), p [B], q [B].
+ *   dr_lsplm_bwd       from the stored z and d_p [B]: d_z[b] = d_p[b] * [pi_i (sg_i - p) ; pi_i sg_i sn_i] ([B, W] at ld_dz) and d_rows
+ *                      [B, F * W] at ld_d = F copies of d_z[b], bit for bit: dr_emb_pool_bwd's d_concat (K4 divides by the bag count
+ *                      itself).  Either of d_z, d_rows may be NULL, not both.
+ *   dr_lsplm_loss_fwd  the one-pass training form: p, q, loss[b] = -wt_b (y log p + (1 - y) log q) (loss may be NULL), and d_z / d_rows
+ *                      = the gradient of row_scale * loss[b], i.e. dr_lsplm_bwd's with d_p = (row_scale * wt_b) * c, c = -y / p +
+ *                      (1 - y) / q.  A term whose coefficient y or 1 - y is exactly 0 is not evaluated (no 0 * inf); inside the log
+ *                      and the quotient p and q are floored at 1e-30.  sample_weight NULL: wt = 1.  p, q, d_z and d_rows carry the
+ *                      same bits as dr_lsplm_fwd followed by dr_lsplm_bwd on that d_p.
+ *   dr_lsplm_bias_grad d_bias[c] = sum_b d_z[b, c] (overwritten), rows summed in ascending order inside at most 256 chunks and the
+ *                      chunks in order (dr_sum_partials.h): no float atomics, bit-identical from run to run.  workspace: at least
+ *                      dr_lsplm_bias_grad_workspace_bytes(B, m) bytes.  B == 0 writes +0.0.
+ *   A power-of-two group of at least m / 2 lanes owns an example; lane l holds the columns 2 l, 2 l + 1 of the gate and of the expert.
+ *   The m-way max and sums are fixed-order xor butterflies inside the group.  No LDS, no atomics; fields in ascending order, a bag in
+ *   column order: bit-identical from run to run, and an example's bits depend neither on its batch nor on its place in it.
+ *   Domain: m even and 2 <= m <= 128 (else DR_ESHAPE); 1 <= F <= 1024, C >= F (C == F without col_start), every ld a multiple of 4 and
+ *   >= its width, table, bias, z, d_z and d_rows 16-byte aligned, required pointers non-NULL (else DR_EINVAL).  B == 0 is DR_OK and
+ *   launches nothing (dr_lsplm_bias_grad excepted).
+ * ---------------------------------------------------------------------------------------- */
+int dr_lsplm_fwd(const int64_t* ids, int64_t B, int32_t F, int32_t C, const int32_t* col_start, const int64_t* row_base,
+                 const float* table, int32_t m, const float* bias, float* z, int64_t ld_z, float* p, float* q, dr_stream_t stream);
+int dr_lsplm_bwd(const float* z, int64_t ld_z, const float* d_p, int64_t B, int32_t F, int32_t m, float* d_z, int64_t ld_dz,
+                 float* d_rows, int64_t ld_d, dr_stream_t stream);
+int dr_lsplm_loss_fwd(const int64_t* ids, int64_t B, int32_t F, int32_t C, const int32_t* col_start, const int64_t* row_base,
+                      const float* table, int32_t m, const float* bias, const float* labels, const float* sample_weight,
+                      float row_scale, float* p, float* q, float* loss, float* d_z, int64_t ld_dz, float* d_rows, int64_t ld_d,
+                      dr_stream_t stream);
+int64_t dr_lsplm_bias_grad_workspace_bytes(int64_t B, int32_t m);
+int dr_lsplm_bias_grad(const float* d_z, int64_t ld_dz, int64_t B, int32_t m, float* d_bias, void* workspace,
+                       int64_t workspace_bytes, dr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Skip-gram with negative sampling (Mikolov et al., NIPS 2013): the training step of Word2Vec, Item2Vec and DeepWalk, which the
  * reference's README lists and ships no code for; csrc/sgns.hip.  All fp32.  in_table [R_in, D] and out_table [R_out, D] dense.
  * Example b: c = centers[b], o_0 = contexts[b], o_1 .. o_K = negatives[b, :] ([B, K] dense int64), u = in_table[c], v_j = out_table[o_j],
