@@ -19,6 +19,7 @@
 // Determinism: the dK/dV sweep owns a key block and runs over all queries, the dQ sweep owns a query block and runs over all keys
 // (with the delta pass nine products instead of five); no float atomics, no waiting between workgroups; the dropout mask is regenerated from the hash.
 #include "dr_common.h"
+#include "dr_owner_rows.h"
 #include "dr_sum_partials.h"
 #include <math.h>
 #include <algorithm>
@@ -485,42 +486,16 @@ __global__ __launch_bounds__(256) void token_emb_fwd_kernel(const int64_t* __res
     }
 }
 
-// One block per position p of the id-sorted order; only the block at the first position of a run of equal ids works.  It owns
-// the run's table row: lane (rl, col) sums the run's positions p0 + rl, p0 + rl + RL, ... (the stable sort keeps them ascending),
-// the RL partial sums are added in rl order, and d_table[id] += sqrt(D) * sum -- a fixed order, no atomics.
+// One owner block per table row (dr_owner_rows.h): d_table[id] += sqrt(D) * the kept d_out rows of the id's positions / (1 - rate),
+// summed in a fixed order, no atomics.
 __global__ __launch_bounds__(256) void token_emb_bwd_kernel(const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ order, int64_t N,
                                                             int64_t V, int32_t D, int32_t CW, const float* __restrict__ d_out, int64_t ld_do,
                                                             float scale, uint32_t thresh, uint64_t seed, float inv_keep,
                                                             float* __restrict__ d_table) {
-    __shared__ float part[256];
-    const int64_t p0 = blockIdx.x;
-    const int64_t id = sorted_ids[p0];
-    if ((p0 > 0 && sorted_ids[p0 - 1] == id) || id < 0 || id >= V) return;
-    int64_t lo = p0, hi = N;             // first position whose id is larger
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sorted_ids[mid] <= id) lo = mid + 1; else hi = mid;
-    }
-    const int64_t p1 = lo;
-    const int RL = 256 / CW, col = threadIdx.x % CW, rl = threadIdx.x / CW;
-    for (int c0 = 0; c0 < D; c0 += CW) {
-        const int c = c0 + col;
-        float acc = 0.f;
-        if (c < D)
-            for (int64_t q = p0 + rl; q < p1; q += RL) {
-                const int64_t n = order[q];
-                const bool keep = thresh == 0u || dr_mix32(seed, (uint64_t)(n * D + c)) >= thresh;
-                if (keep) acc += d_out[n * ld_do + c] * inv_keep;
-            }
-        __syncthreads();
-        part[threadIdx.x] = acc;
-        __syncthreads();
-        if (rl == 0 && c < D) {
-            float sum = 0.f;
-            for (int k = 0; k < RL; ++k) sum += part[k * CW + col];
-            d_table[id * D + c] = fmaf(scale, sum, d_table[id * D + c]);
-        }
-    }
+    dr_owner_row_scatter(sorted_ids, order, N, V, D, CW, scale, d_table, [&](int64_t n, int c, float& acc) {
+        const bool keep = thresh == 0u || dr_mix32(seed, (uint64_t)(n * D + c)) >= thresh;
+        if (keep) acc += d_out[n * ld_do + c] * inv_keep;
+    });
 }
 
 }  // namespace
@@ -632,8 +607,7 @@ extern "C" int dr_token_embedding_bwd(const int64_t* sorted_ids, const int64_t* 
     if (N >= (int64_t)1 << 31) return DR_ESHAPE;
     if (N == 0) return DR_OK;
     if (!sorted_ids || !order || !d_out || !d_table) return DR_EINVAL;
-    int CW = 8;
-    while (CW < 64 && CW < D) CW <<= 1;
+    const int CW = dr_owner_row_cw(D);
     hipLaunchKernelGGL(token_emb_bwd_kernel, dim3((unsigned)N), dim3(256), 0, dr_s(stream), sorted_ids, order, N, V, D, CW, d_out, ld_do,
                        (float)sqrt((double)D), rate > 0.f ? dr_drop_thresh(rate) : 0u, seed, 1.f / (1.f - rate), d_table);
     DR_CHECK_LAUNCH();

@@ -16,6 +16,7 @@
 //             division per entry.
 // No float atomics and no float reductions across lanes; the only atomics are integer counts in LDS histograms (exact).
 #include "dr_common.h"
+#include "dr_rank_select.h"
 #include "dr_scan.h"
 #include <algorithm>
 
@@ -30,8 +31,6 @@ constexpr int MAX_FANOUT = 64;
 static_assert(SAMPLE_LONG_ROW >= MAX_FANOUT, "a long row must have more edges than any fanout");
 constexpr int SEL_BINS = 2048;     // radix select: 11 + 11 + 10 bits of the 32-bit hash
 constexpr int LONG_NODES = 16;     // nodes a block of sample_long_kernel looks at per pass
-
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return lane == 0 ? 0ull : (~0ull >> (64 - lane)); }
 
 // (lo, deg) of node i's row; deg = 0 for i >= n or a node outside [0, n_rows)
 __device__ __forceinline__ void row_of(const int64_t* __restrict__ row_ptr, int64_t n_rows, const int64_t* __restrict__ nodes, int64_t n,
@@ -54,7 +53,7 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const int64_t* __restr
     __shared__ uint32_t hs[4][SAMPLE_LONG_ROW];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     uint32_t* h = hs[w];
-    const uint64_t lt_mask = lanes_below(lane);
+    const uint64_t lt_mask = dr_lanes_below(lane);
     for (int64_t base = (int64_t)blockIdx.x * 4; base < n; base += (int64_t)gridDim.x * 4) {
         const int64_t i = base + w;
         int64_t lo, deg;
@@ -74,13 +73,7 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const int64_t* __restr
                 const int j = j0 + lane;
                 bool take = false;
                 if (j < d) {
-                    const uint32_t hj = h[j];
-                    int rank = 0;                              // keys below (hj, j): the hash decides, the index breaks a tie
-                    for (int k = 0; k < d; ++k) {
-                        const uint32_t hk = h[k];
-                        rank += (hk < hj || (hk == hj && k < j)) ? 1 : 0;
-                    }
-                    take = rank < fanout;
+                    take = dr_key_rank(h, d, h[j], j) < fanout;     // keys below (h[j], j): dr_rank_select.h
                 }
                 const uint64_t b = __ballot(take);
                 if (take) nbr[i * fanout + written + __popcll(b & lt_mask)] = (int64_t)col[lo + j];    // exactly fanout keys rank below fanout
@@ -319,7 +312,7 @@ __global__ __launch_bounds__(256) void radix64_scatter_kernel(const uint64_t* __
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     base_d[t] = offs[(int64_t)t * n_tiles + blockIdx.x];
     run[t] = 0;
-    const uint64_t lt_mask = lanes_below(lane);
+    const uint64_t lt_mask = dr_lanes_below(lane);
     for (int round = 0; round < RADIX_TILE / 256; ++round) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) wcnt[i][t] = 0;

@@ -160,21 +160,27 @@ class _Fm2Fn(torch.autograd.Function):
 
 class _MlpFn(torch.autograd.Function):
     """K7: a whole Dense tower.  acts[i] in {0: linear, 1: relu (fused into the GEMM epilogue; relu' is folded into the dx epilogue
-    of the layer above), 2: sigmoid, 3: tanh (dr_act_fwd on the linear output, dr_act_bwd through the saved output)}.
+    of the layer above), 2: sigmoid, 3: tanh (dr_act_fwd on the linear output, dr_act_bwd through the saved output), 4: exact GELU
+    (dr_gelu_fwd from the linear output z into a fresh buffer; z is kept, because GELU's derivative is no function of its output:
+    dr_gelu_bwd through z)}.
     args: x, acts tuple, then W0, b0, W1, b1, ..."""
 
     @staticmethod
     def forward(ctx, x, acts, *params):
         n = len(params) // 2
         hs = [x]
+        zs = []                          # the pre-activations of the GELU layers, in layer order
         h = x
         for i in range(n):
             h = ops.linear_fwd(h, params[2 * i], params[2 * i + 1], 1 if acts[i] == 1 else 0)
             if acts[i] in (2, 3):
                 ops.act_fwd_(h, acts[i])
+            elif acts[i] == 4:
+                zs.append(h)
+                h = ops.gelu_fwd(h)
             hs.append(h)
         ctx.acts = acts
-        ctx.save_for_backward(*hs, *params)
+        ctx.save_for_backward(*hs, *params, *zs)
         return h
 
     @staticmethod
@@ -183,12 +189,15 @@ class _MlpFn(torch.autograd.Function):
         acts = ctx.acts
         n = len(acts)
         saved = ctx.saved_tensors
-        hs, params = saved[:n + 1], saved[n + 1:]
+        hs, params, zs = saved[:n + 1], saved[n + 1:3 * n + 1], list(saved[3 * n + 1:])
         grads = [None] * (2 * n)
         dy = _rows(dy)
         for i in range(n - 1, -1, -1):
             W, b = params[2 * i], params[2 * i + 1]
-            if acts[i] in (2, 3) or (acts[i] == 1 and i == n - 1):
+            if acts[i] == 4:
+                # GELU's derivative through the saved pre-activation (the top layer's incoming gradient is the caller's: cloned)
+                dy = ops.gelu_bwd_(zs.pop(), dy.clone(memory_format=torch.contiguous_format) if i == n - 1 else dy)
+            elif acts[i] in (2, 3) or (acts[i] == 1 and i == n - 1):
                 # the activation's derivative through the saved output (a relu BELOW the top layer is folded into the dx GEMM)
                 dy = ops.act_bwd_(hs[i + 1], dy.clone(memory_format=torch.contiguous_format) if i == n - 1 else dy, acts[i])
             need_b = b is not None and ctx.needs_input_grad[3 + 2 * i]
@@ -1455,6 +1464,80 @@ def sampled_softmax(u, table, labels, sampled, log_q_true=None, log_q_sampled=No
     d_u, d_true, d_sampled = ops.sampled_softmax_bwd(ud, td, labels, sampled, true_logit, row_lse, log_q_sampled, sample_weight,
                                                      remove_accidental_hits, row_scale, workspace=ws)
     return loss_rows, d_u, d_true, d_sampled
+
+
+# ---- full-vocabulary cross-entropy over integer labels (csrc/bert.hip) ---------------------------------------------------------------------
+VOCAB_CE_BUFFER_BYTES = 256 << 20      # the default chunk_rows keeps the [chunk, pad4(V)] logits buffer at or below this
+VOCAB_CE_WORKSPACE_BYTES = 128 << 20   # the split-K partials of the table's gradient: the table's rows are taken in blocks that fit
+
+
+def vocab_cross_entropy(t, table, bias, labels, weight=None, smoothing=0.0, row_scale=1.0, denom=None, denom_eps=0.0, d_table=None,
+                        d_bias=None, chunk_rows=None):
+    """(loss_rows [M], d_t [M, D]) of the softmax cross-entropy of t @ table^T + bias against integer labels [M] (a masked-LM head
+    whose decoder is tied to the token table [V, D]), and d_table [V, D] / d_bias [V] += their gradients where given.  loss_r and the
+    gradient are dr_softmax_ce_ids': weight w_r, label smoothing, a negative label = padding; the buffers hold the gradients of
+    row_scale / (denom + denom_eps) * sum(loss_rows), denom a one-element DEVICE tensor (BERT's sum of the weights: no host read),
+    and loss_rows is NOT divided by it.  A training-step op on detached inputs, like sampled_softmax: the caller continues with
+    t.backward(d_t).  The [M, V] logits are never whole in memory: for each chunk of chunk_rows rows, in ascending order,
+    ops.scores_nt writes the chunk's logits into one reused buffer, ops.softmax_ce_ids turns them into the gradient in place, the
+    dx GEMM g @ table (ops.linear_fwd, the product tied_projection's backward runs) gives d_t's rows, ops.linear_bwd_dw
+    (deterministic split-K form) adds into d_table and ops.colsum_add into d_bias.  chunk_rows defaults to the largest value that
+    keeps the buffer at or below 256 MiB.
+    For a FIXED chunk_rows everything is bit-identical from run to run.  Across different chunk_rows only agreement within fp32
+    summation error is promised: d_table and d_bias are accumulated chunk by chunk, so their summation order follows the chunking
+    (loss_rows and d_t are per-row results and do not change)."""
+    td, tb = t.detach(), table.detach()
+    if td.dim() != 2 or tb.dim() != 2 or td.shape[1] != tb.shape[1] or td.dtype != torch.float32 or tb.dtype != torch.float32:
+        raise ValueError("vocab_cross_entropy: t must be fp32 [M, D] and table fp32 [V, D], got %s and %s" % (tuple(t.shape), tuple(table.shape)))
+    M, D = td.shape
+    V = tb.shape[0]
+    dev = td.device
+    if D % 4 != 0 or not tb.is_contiguous():
+        raise ValueError("vocab_cross_entropy: table must be contiguous with a width that is a multiple of 4, got %s" % (tuple(tb.shape),))
+    if td.stride(1) != 1 or td.stride(0) % 4 != 0 or td.stride(0) < D or td.data_ptr() % 16 != 0:
+        td = td.contiguous()                                  # rows the GEMMs read as float4
+    bias = bias.detach() if bias is not None else None
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (M,) or not labels.is_contiguous():
+        raise ValueError("vocab_cross_entropy: labels must be contiguous int64 [M]")
+    if weight is not None and (weight.dtype != torch.float32 or tuple(weight.shape) != (M,) or not weight.is_contiguous()):
+        raise ValueError("vocab_cross_entropy: weight must be contiguous fp32 [M]")
+    if d_table is not None and (d_table.dtype != torch.float32 or tuple(d_table.shape) != (V, D) or not d_table.is_contiguous()):
+        raise ValueError("vocab_cross_entropy: d_table must be contiguous fp32 [V, D]")
+    Vp = _pad4(V)
+    if chunk_rows is None:
+        chunk_rows = max(1, VOCAB_CE_BUFFER_BYTES // (4 * Vp))
+    chunk_rows = max(1, min(int(chunk_rows), max(M, 1)))
+    loss_rows = torch.empty(M, dtype=torch.float32, device=dev)
+    d_t = torch.empty((M, _pad4(D)), dtype=torch.float32, device=dev)[:, :D]
+    if M == 0:
+        return loss_rows, d_t
+    buf = torch.empty((chunk_rows, Vp), dtype=torch.float32, device=dev)
+    ws_dw, ws_cs, v_block = None, None, V
+    if d_table is not None:
+        # the deterministic dW keeps `split` partial [rows, D] products: the table's rows go in blocks (a function of the shapes
+        # alone) small enough for that workspace to stay at or below VOCAB_CE_WORKSPACE_BYTES, one buffer for every chunk and block
+        sizes = {chunk_rows, M % chunk_rows or chunk_rows}
+        need = lambda vb: max(ops.lib().dr_linear_bwd_dw_workspace_bytes(m, v, D) for m in sizes for v in {vb, V % vb or vb})   # noqa: E731
+        while v_block > 1024 and need(v_block) > VOCAB_CE_WORKSPACE_BYTES:
+            v_block = _pad4((v_block + 1) // 2)
+        ws_dw = torch.empty(max(1, need(v_block) // 4), dtype=torch.float32, device=dev)
+    if d_bias is not None:
+        ws_cs = ops.colsum_add_workspace(chunk_rows, V, dev)
+    for r0 in range(0, M, chunk_rows):
+        r1 = min(M, r0 + chunk_rows)
+        t_c = td[r0:r1]
+        g = buf[:r1 - r0, :V]
+        ops.scores_nt(t_c, tb, out=g)
+        ops.softmax_ce_ids(g, labels[r0:r1], bias, weight[r0:r1] if weight is not None else None, smoothing, row_scale, denom, denom_eps,
+                           row_loss=loss_rows[r0:r1])
+        ops.linear_fwd(g, tb, out=d_t[r0:r1])                        # d_t = g @ table, as tied_projection's backward
+        if d_table is not None:
+            for v0 in range(0, V, v_block):
+                v1 = min(V, v0 + v_block)
+                ops.linear_bwd_dw(g[:, v0:v1], t_c, 1.0, d_table[v0:v1], None, workspace=ws_dw)
+        if d_bias is not None:
+            ops.colsum_add(g, d_bias, ws_cs)
+    return loss_rows, d_t
 
 
 # ---- margin ranking loss (csrc/margin_rank.hip) -----------------------------------------------------------------------------------------------

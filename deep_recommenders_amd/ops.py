@@ -3998,3 +3998,187 @@ def margin_rank_bwd(q, pos, neg, pos_score, hard_idx, pos_ids=None, neg_ids=None
                                      ptr(pos_score), ptr(hard_idx), ptr(d_q), ld_dq, ptr(d_pos), ptr(d_neg), ptr(workspace),
                                      workspace.numel(), stream_ptr()), "dr_margin_rank_bwd")
     return d_q, d_pos, d_neg
+
+
+# ---- BERT (csrc/bert.hip) -----------------------------------------------------------------------------------------------------------------
+SOFTMAX_CE_IDS_LDS_COLS = 32768     # DR_SOFTMAX_CE_IDS_LDS_COLS: rows up to this width are staged in LDS
+MLM_MAX_LENGTH = 512                # dr_mlm_mask: one wave per sequence
+MLM_MAX_PREDICTIONS = 128
+
+
+def _bert_arg(t, what, dtype, shape=None):
+    """an argument the BERT kernels address densely and never copy: another dtype, shape or a view is a ValueError naming it"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)) or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s tensor%s, got %s" % (
+            what, dtype, " of shape %s" % (tuple(shape),) if shape is not None else "",
+            "%s %s with strides %s" % (t.dtype, tuple(t.shape), tuple(t.stride())) if isinstance(t, torch.Tensor) else type(t).__name__))
+    return t
+
+
+def _bert_rows(t, what):
+    """[M, N] fp32 with unit column stride and a row pitch >= N (one row has no pitch); ValueError naming the argument otherwise"""
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < 1 or (t.shape[1] > 1 and t.stride(1) != 1)
+            or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+        raise ValueError("%s must be fp32 [M, N] with unit column stride and a row stride >= N, got %s" % (
+            what, "%s %s with strides %s" % (t.dtype, tuple(t.shape), tuple(t.stride())) if isinstance(t, torch.Tensor) else type(t).__name__))
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def gelu_fwd(z, out=None):
+    """h [M, N] = z * Phi(z), the exact (erf) GELU of dr_gelu_fwd; z may be a view with a row pitch and is left as it is"""
+    ld_z = _bert_rows(z, "gelu_fwd: z")
+    M, N = z.shape
+    if out is None:
+        out = torch.empty((M, _pad4(N)), dtype=torch.float32, device=z.device)[:, :N]
+    ld_h = _bert_rows(out, "gelu_fwd: out")
+    if tuple(out.shape) != (M, N):
+        raise ValueError("gelu_fwd: out must be %s, got %s" % ((M, N), tuple(out.shape)))
+    check(lib().dr_gelu_fwd(ptr(z), ld_z, M, N, ptr(out), ld_h, stream_ptr()), "dr_gelu_fwd")
+    return out
+
+
+def gelu_bwd_(z, dy):
+    """in place: dy *= Phi(z) + z phi(z), the GELU's derivative through the saved pre-activation z"""
+    ld_z = _bert_rows(z, "gelu_bwd_: z")
+    ld_dy = _bert_rows(dy, "gelu_bwd_: dy")
+    if z.shape != dy.shape:
+        raise ValueError("gelu_bwd_: z %s and dy %s differ in shape" % (tuple(z.shape), tuple(dy.shape)))
+    check(lib().dr_gelu_bwd(ptr(z), ld_z, ptr(dy), ld_dy, z.shape[0], z.shape[1], stream_ptr()), "dr_gelu_bwd")
+    return dy
+
+
+def _bert_embed_args(ids, segment, tok, pos, seg, gamma, beta, rate):
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 2:
+        raise ValueError("bert_embed: ids must be an int64 [B, L] tensor")
+    B, L = ids.shape
+    _bert_arg(ids, "bert_embed: ids", torch.int64)
+    _bert_arg(segment, "bert_embed: segment", torch.int64, (B, L))
+    if not isinstance(tok, torch.Tensor) or tok.dim() != 2:
+        raise ValueError("bert_embed: tok must be an fp32 [V, D] tensor")
+    V, D = tok.shape
+    _bert_arg(tok, "bert_embed: tok", torch.float32)
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 2 or not isinstance(seg, torch.Tensor) or seg.dim() != 2:
+        raise ValueError("bert_embed: pos must be [max_position, D] and seg [T, D]")
+    _bert_arg(pos, "bert_embed: pos", torch.float32, (pos.shape[0], D))
+    _bert_arg(seg, "bert_embed: seg", torch.float32, (seg.shape[0], D))
+    _bert_arg(gamma, "bert_embed: gamma", torch.float32, (D,))
+    if beta is not None:
+        _bert_arg(beta, "bert_embed: beta", torch.float32, (D,))
+    if D % 4 != 0 or D < 4 or D > 1024 or L > pos.shape[0] or V < 1 or seg.shape[0] < 1:
+        raise ValueError("bert_embed: D %d must be a multiple of 4 in [4, 1024] and L %d <= max_position %d" % (D, L, pos.shape[0]))
+    if not 0.0 <= float(rate) < 1.0:
+        raise ValueError("bert_embed: rate must be in [0, 1), got %r" % (rate,))
+    return B, L, V, D, pos.shape[0], seg.shape[0]
+
+
+def bert_embed_fwd(ids, segment, tok, pos, seg, gamma, beta, eps=1e-12, rate=0.0, seed=0):
+    """(out [B, L, D], stats [B * L, 2]) of dr_bert_embed_fwd: dropout(LayerNorm(tok[ids] + pos[l] + seg[segment])); ids, segment int64
+    [B, L], tok [V, D], pos [max_position, D], seg [T, D]; an id or segment out of range reads as a zero row"""
+    B, L, V, D, P, T = _bert_embed_args(ids, segment, tok, pos, seg, gamma, beta, rate)
+    out = torch.empty((B, L, D), dtype=torch.float32, device=tok.device)
+    stats = torch.empty((B * L, 2), dtype=torch.float32, device=tok.device)
+    if B * L > 0:
+        _status(lib().dr_bert_embed_fwd(ptr(ids), ptr(segment), B * L, L, ptr(tok), V, ptr(pos), P, ptr(seg), T, ptr(gamma), ptr(beta), D,
+                                        float(eps), float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), D, ptr(stats), stream_ptr()),
+                "dr_bert_embed_fwd")
+    return out, stats
+
+
+def bert_embed_bwd(ids, segment, tok, pos, seg, gamma, stats, d_out, d_tok, rate=0.0, seed=0):
+    """(d_s [B * L, D], d_gamma [D], d_beta [D], d_pos [L, D], d_seg [T, D]) of dr_bert_embed_bwd, and d_tok [V, D] += the rows of d_s
+    summed per id in ascending position order.  Everything is summed in a fixed order (deterministic)."""
+    B, L, V, D, P, T = _bert_embed_args(ids, segment, tok, pos, seg, gamma, None, rate)
+    N = B * L
+    _bert_arg(stats, "bert_embed_bwd: stats", torch.float32, (N, 2))
+    _bert_arg(d_tok, "bert_embed_bwd: d_tok", torch.float32, (V, D))
+    if not isinstance(d_out, torch.Tensor) or d_out.dtype != torch.float32 or d_out.numel() != N * D:
+        raise ValueError("bert_embed_bwd: d_out must be fp32 with %d elements" % (N * D))
+    d_out = d_out.reshape(N, D)
+    ld_do = _bert_rows(d_out, "bert_embed_bwd: d_out") if N > 0 else D
+    dev = tok.device
+    d_s = torch.empty((N, D), dtype=torch.float32, device=dev)
+    d_gamma = torch.zeros(D, dtype=torch.float32, device=dev)
+    d_beta = torch.zeros(D, dtype=torch.float32, device=dev)
+    d_pos = torch.zeros((L, D), dtype=torch.float32, device=dev)
+    d_seg = torch.zeros((T, D), dtype=torch.float32, device=dev)
+    if N == 0:
+        return d_s, d_gamma, d_beta, d_pos, d_seg
+    sorted_ids, order = torch.sort(ids.reshape(-1), stable=True)     # plumbing: the order of the row owners' sums
+    nb = lib().dr_bert_embed_bwd_workspace_bytes(N, L, D, T)
+    ws = torch.empty(max(1, nb // 4), dtype=torch.float32, device=dev)
+    _status(lib().dr_bert_embed_bwd(ptr(ids), ptr(segment), ptr(sorted_ids), ptr(order), N, L, ptr(tok), V, ptr(pos), ptr(seg), T,
+                                    ptr(gamma), ptr(stats), D, ptr(d_out), ld_do, float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(d_s),
+                                    ptr(d_gamma), ptr(d_beta), ptr(d_tok), ptr(d_pos), ptr(d_seg), ptr(ws), ws.numel() * 4, stream_ptr()),
+            "dr_bert_embed_bwd")
+    return d_s, d_gamma, d_beta, d_pos, d_seg
+
+
+def softmax_ce_ids(logits, labels, bias=None, weight=None, smoothing=0.0, row_scale=1.0, denom=None, denom_eps=0.0, row_loss=None,
+                   _path=0):
+    """row_loss [M] of dr_softmax_ce_ids; logits [M, C] (a row pitch is honoured) are OVERWRITTEN with the gradient
+    row_scale * w / (denom + denom_eps) * (softmax(logits + bias) - (1 - smoothing) * onehot(labels) - smoothing / C).  labels int64 [M],
+    a negative one marks a padding row (loss 0, a zero gradient row, its logits never read); denom is a one-element DEVICE tensor.
+    _path (tests only): 1 forces the kernel that stages the row in LDS, 2 the one that re-reads it from memory."""
+    ld = _bert_rows(logits, "softmax_ce_ids: logits")
+    M, C = logits.shape
+    _bert_arg(labels, "softmax_ce_ids: labels", torch.int64, (M,))
+    if bias is not None:
+        _bert_arg(bias, "softmax_ce_ids: bias", torch.float32, (C,))
+    if weight is not None:
+        _bert_arg(weight, "softmax_ce_ids: weight", torch.float32, (M,))
+    if denom is not None:
+        _bert_arg(denom, "softmax_ce_ids: denom", torch.float32)
+        if denom.numel() != 1:
+            raise ValueError("softmax_ce_ids: denom must hold one element, got %s" % (tuple(denom.shape),))
+    if not 0.0 <= float(smoothing) < 1.0:
+        raise ValueError("softmax_ce_ids: smoothing must be in [0, 1), got %r" % (smoothing,))
+    if row_loss is None:
+        row_loss = torch.empty(M, dtype=torch.float32, device=logits.device)
+    else:
+        _bert_arg(row_loss, "softmax_ce_ids: row_loss", torch.float32, (M,))
+    _status(lib().dr_softmax_ce_ids(ptr(logits), ld, ptr(bias), ptr(labels), ptr(weight), M, C, float(smoothing), float(row_scale),
+                                    ptr(denom), float(denom_eps), ptr(row_loss), int(_path), stream_ptr()), "dr_softmax_ce_ids")
+    return row_loss
+
+
+def colsum_add_workspace(M, C, device):
+    return torch.empty(max(1, lib().dr_colsum_add_workspace_bytes(int(M), int(C)) // 4), dtype=torch.float32, device=device)
+
+
+def colsum_add(g, dst, workspace=None):
+    """dst [C] += the column sums of g [M, C] (a row pitch is honoured), in a fixed order: dr_colsum_add"""
+    ld = _bert_rows(g, "colsum_add: g")
+    M, C = g.shape
+    _bert_arg(dst, "colsum_add: dst", torch.float32, (C,))
+    if workspace is None or workspace.numel() * 4 < lib().dr_colsum_add_workspace_bytes(M, C):
+        workspace = colsum_add_workspace(M, C, g.device)
+    _status(lib().dr_colsum_add(ptr(g), ld, M, C, ptr(dst), ptr(workspace), workspace.numel() * 4, stream_ptr()), "dr_colsum_add")
+    return dst
+
+
+def mlm_prob_q16(prob):
+    """round(prob * 65536): the fixed-point masking probability dr_mlm_mask takes"""
+    if not 0.0 <= float(prob) <= 1.0:
+        raise ValueError("mlm_mask: prob must be in [0, 1], got %r" % (prob,))
+    return int(round(float(prob) * 65536))
+
+
+def mlm_mask(ids, vocab_size, num_special, mask_id, prob=0.15, max_predictions=20, seed=0):
+    """(out_ids [B, L], positions int32 [B, P], labels int64 [B, P]) of dr_mlm_mask: BERT's dynamic masking on the device, a function of
+    (seed, ids) alone.  Positions holding an id >= num_special are candidates; positions / labels are -1 beyond a row's count."""
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 2:
+        raise ValueError("mlm_mask: ids must be an int64 [B, L] tensor")
+    _bert_arg(ids, "mlm_mask: ids", torch.int64)
+    B, L = ids.shape
+    P = int(max_predictions)
+    if L > MLM_MAX_LENGTH or L < 1 or not 1 <= P <= MLM_MAX_PREDICTIONS:
+        raise ValueError("mlm_mask: 1 <= L <= %d and 1 <= max_predictions <= %d, got L %d, max_predictions %d"
+                         % (MLM_MAX_LENGTH, MLM_MAX_PREDICTIONS, L, P))
+    if not 0 <= int(num_special) < int(vocab_size):
+        raise ValueError("mlm_mask: 0 <= num_special < vocab_size, got %r, %r" % (num_special, vocab_size))
+    out_ids = torch.empty_like(ids)
+    positions = torch.empty((B, P), dtype=torch.int32, device=ids.device)
+    labels = torch.empty((B, P), dtype=torch.int64, device=ids.device)
+    _status(lib().dr_mlm_mask(ptr(ids), B, L, int(vocab_size), int(num_special), int(mask_id), mlm_prob_q16(prob), P,
+                              int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out_ids), ptr(positions), ptr(labels), stream_ptr()), "dr_mlm_mask")
+    return out_ids, positions, labels

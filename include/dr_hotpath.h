@@ -1680,6 +1680,78 @@ int dr_margin_rank_bwd(const float* q, int64_t ld_q, const float* pos, int64_t l
                        const int32_t* hard_idx, float* d_q, int64_t ld_dq, float* d_pos, float* d_neg, void* workspace,
                        int64_t workspace_bytes, dr_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * BERT (Devlin et al., NAACL 2019; the reference README's model list names it, its tree has no code for it), csrc/bert.hip.
+ * All fp32, on the caller's stream, no host synchronisation, no float atomics: every result is bit-identical from run to run, and
+ * a row's outputs do not depend on the batch around it (the column reductions d_gamma, d_beta, d_seg, d_pos and dr_colsum_add cut
+ * their chunks by the row index and are fixed for a given shape).
+ *
+ *   dr_gelu_fwd   h = z * Phi(z) over z [M, N] (row pitches ld_z, ld_h >= N, any N >= 1), Phi(z) = erfc(-z / sqrt 2) / 2: the exact
+ *                 GELU 0.5 z (1 + erf(z / sqrt 2)) without the cancellation of 1 + erf at negative z.  Saturated inputs give finite
+ *                 values: gelu(-88) = -0.0, gelu(88) = 88.  h may not alias z where the backward still needs z.
+ *   dr_gelu_bwd   in place on dy [M, N]: dy *= Phi(z) + z phi(z), phi(z) = exp(-z^2 / 2) / sqrt(2 pi), through the saved PRE-activation
+ *                 z (GELU is not monotonic, so dr_act_bwd's "derivative from the output" does not exist for it).
+ *   dr_bert_embed_fwd   s[n, :] = (tok[ids[n], :] + pos[n % L, :]) + seg[segment[n], :] for n < N = B*L, two fp32 additions in that
+ *                 order; out[n, :] = dropout(gamma * (s - mean) * rstd + beta), mean and the POPULATION variance over the D columns,
+ *                 rstd = 1 / sqrt(var + eps); dropout as dr_token_embedding_fwd: element n*D + c is kept iff dr_mix32(seed, n*D + c)
+ *                 >= (uint32)min(4294967040, rate * 2^32) [always when rate == 0] and kept values are scaled by 1 / (1 - rate).
+ *                 stats [N, 2] = (mean, rstd).  tok [V, D], pos [max_position, D], seg [T, D], gamma, beta [D], ids and segment int64
+ *                 [N]; an id outside [0, V) or a segment outside [0, T) reads as a zero row and is never turned into an address.
+ *                 Domain: D % 4 == 0, 4 <= D <= 1024, L <= max_position, N % L == 0, N < 2^31 (DR_ESHAPE otherwise); tables, gamma,
+ *                 beta and out 16-byte aligned, ld_out % 4 == 0 and >= D, rate in [0, 1) (DR_EINVAL otherwise).
+ *   dr_bert_embed_bwd   from d_out [N, D] (pitch ld_do), with s recomputed from the tables and the mask from the hash:
+ *                 d_s [N, D] (dense) = rstd * (g gamma - mean_c(g gamma) - xhat mean_c(g gamma xhat)), g = the kept d_out / (1 - rate);
+ *                 d_gamma [D] = sum_n g xhat and d_beta [D] = sum_n g, d_seg [T, D] = the sum of the d_s rows of each segment:
+ *                 OVERWRITTEN, two-stage sums (128-row chunks in ascending row order, then the chunks in order);
+ *                 d_pos [L, D] (the first L rows of the position table's gradient) = sum_b d_s[b*L + l, :]: OVERWRITTEN, two-stage
+ *                 (16-sequence chunks);
+ *                 d_tok [V, D] += the sum of d_s[n, :] over the positions with ids[n] == v in ascending n: one owner block per table
+ *                 row fed by sorted_ids / order (the ids sorted by a STABLE sort and its permutation, as dr_token_embedding_bwd, whose
+ *                 device code this shares).  workspace: dr_bert_embed_bwd_workspace_bytes(N, L, D, T) bytes, a function of the
+ *                 shapes alone.
+ *   dr_softmax_ce_ids   softmax cross-entropy over integer labels, IN PLACE: logits [M, C] (pitch ld >= C) are overwritten with the
+ *                 gradient.  z = logits + bias (bias [C] or NULL), lse = log sum_j exp z_j (max-shifted), label = labels[r] (int64),
+ *                 w = weight[r] (or 1), e = smoothing in [0, 1):
+ *                   row_loss[r] = w ((1 - e) (lse - z_label) + e (lse - mean_j z_j))               (NOT divided by the denominator)
+ *                   g[r, j]     = row_scale w / (denom ? denom[0] + denom_eps : 1) * (softmax_j - e / C - (1 - e) [j == label])
+ *                 denom is a DEVICE scalar (no host read).  A row with label < 0 is padding: loss 0, its gradient row exact +0.0, its
+ *                 logits never read (a NaN there reaches nothing).  label >= C breaks the contract (the row's result is unspecified;
+ *                 it is not checked).  One block owns a row: up to dr_softmax_ce_ids_lds_cols() = DR_SOFTMAX_CE_IDS_LDS_COLS columns
+ *                 the row is staged once in LDS, so the logits move once in and once out; a wider row is re-read from memory and
+ *                 gives the same bits.  path: 0 chooses by C; 1 / 2 force the staged / the re-reading kernel (tests only; 1 with a
+ *                 row too wide is DR_ESHAPE).  Rows are read as float4 when logits is 16-byte aligned and ld % 4 == 0.  Max and sums
+ *                 are fixed-order reductions.
+ *   dr_colsum_add       dst[j] += sum_r g[r, j] over g [M, C] (pitch ld), two-stage (32-row chunks, then the chunks in order): the
+ *                 bias gradient of the above.  workspace: dr_colsum_add_workspace_bytes(M, C) bytes.
+ *   dr_mlm_mask   BERT's dynamic masking, integer only and counter-based: a function of (seed, ids) alone.  Per row b of ids [B, L]:
+ *                 position l is a candidate iff ids[b, l] >= num_special; n = 0 without candidates, else
+ *                 min(P, max(1, (n_cand * prob_q16 + 32768) >> 16)), prob_q16 = round(prob * 65536) <= 65536.  Candidate l has the key
+ *                 (uint64(dr_mix32(seed, b*L + l)) << 32) | l; the n smallest keys are chosen and written in ascending l:
+ *                 positions int32 [B, P] = l, labels int64 [B, P] = the original id, both -1 beyond n.  out_ids = ids with the chosen
+ *                 positions replaced by r = dr_mix32(seed + 1, b*L + l) % 10: r < 8 -> mask_id; r == 8 -> num_special +
+ *                 dr_mix32(seed + 2, b*L + l) % (V - num_special); r == 9 -> unchanged.  One wave per row.  1 <= P <= 128,
+ *                 V > num_special >= 0 (DR_EINVAL otherwise); 1 <= L <= 512 (L > 512: DR_ESHAPE).
+ * ---------------------------------------------------------------------------------------- */
+int dr_gelu_fwd(const float* z, int64_t ld_z, int64_t M, int32_t N, float* h, int64_t ld_h, dr_stream_t stream);
+int dr_gelu_bwd(const float* z, int64_t ld_z, float* dy, int64_t ld_dy, int64_t M, int32_t N, dr_stream_t stream);
+int dr_bert_embed_fwd(const int64_t* ids, const int64_t* segment, int64_t N, int32_t L, const float* tok, int64_t V, const float* pos,
+                      int32_t max_position, const float* seg, int32_t T, const float* gamma, const float* beta, int32_t D, float eps,
+                      float rate, uint64_t seed, float* out, int64_t ld_out, float* stats, dr_stream_t stream);
+int64_t dr_bert_embed_bwd_workspace_bytes(int64_t N, int32_t L, int32_t D, int32_t T);
+int dr_bert_embed_bwd(const int64_t* ids, const int64_t* segment, const int64_t* sorted_ids, const int64_t* order, int64_t N, int32_t L,
+                      const float* tok, int64_t V, const float* pos, const float* seg, int32_t T, const float* gamma, const float* stats,
+                      int32_t D, const float* d_out, int64_t ld_do, float rate, uint64_t seed, float* d_s, float* d_gamma, float* d_beta,
+                      float* d_tok, float* d_pos, float* d_seg, float* workspace, int64_t workspace_bytes, dr_stream_t stream);
+int dr_softmax_ce_ids(float* logits, int64_t ld, const float* bias, const int64_t* labels, const float* weight, int64_t M, int32_t C,
+                      float smoothing, float row_scale, const float* denom, float denom_eps, float* row_loss, int32_t path,
+                      dr_stream_t stream);
+int32_t dr_softmax_ce_ids_lds_cols(void);
+int64_t dr_colsum_add_workspace_bytes(int64_t M, int32_t C);
+int dr_colsum_add(const float* g, int64_t ld, int64_t M, int32_t C, float* dst, float* workspace, int64_t workspace_bytes,
+                  dr_stream_t stream);
+int dr_mlm_mask(const int64_t* ids, int64_t B, int32_t L, int64_t V, int64_t num_special, int64_t mask_id, uint32_t prob_q16, int32_t P,
+                uint64_t seed, int64_t* out_ids, int32_t* positions, int64_t* labels, dr_stream_t stream);
+
 /* dr_clock_stamp: dst[0] = the device's constant-rate wall clock (100 MHz ticks) when a one-thread kernel reaches the head of
  * `stream`.  Measurement plumbing with no reference counterpart: bench.py brackets the sharded step's cross-stream waits with two
  * stamps to report the EXPOSED part of the exchange (HIP timing events around a wait serialise the step). */
