@@ -13,3 +13,7 @@ from deep_recommenders_amd.keras.models.retrieval.airbnb import Airbnb
 from deep_recommenders_amd.keras.models.retrieval.graphsage import SAGEConv
 from deep_recommenders_amd.keras.models.retrieval.graphsage import GraphSAGE
 from deep_recommenders_amd.keras.models.retrieval.graphsage import PinSage
+from deep_recommenders_amd.keras.models.retrieval.intentgc import IntentConv
+from deep_recommenders_amd.keras.models.retrieval.intentgc import IntentNet
+from deep_recommenders_amd.keras.models.retrieval.intentgc import IntentGC
+from deep_recommenders_amd.keras.models.retrieval.intentgc import translate_relations

@@ -763,6 +763,68 @@ def sample_blocks(adjacency, seeds, fanouts, seed, importance=None, add_self=Fal
     return blocks[::-1]
 
 
+class TypedBlock:
+    """One layer of a sampled mini-batch over R relations: adj, a SparseAdjacency [n_dst * R, n_src] whose virtual row v * R + r holds
+    the type-(r + 1) neighbours of destination v (row-normalised; empty when v has none of that type), over the nodes src_ids int64
+    [n_src]; the first n_dst of them are the destinations.  adj.spmm(h) viewed [n_dst, R, D] is the per-type mean, and
+    adj.transpose().spmm(d_agg) scatters all R gradients back in one launch."""
+    __slots__ = ("adj", "src_ids", "n_dst", "R")
+
+    def __init__(self, adj, src_ids, n_dst, R):
+        self.adj, self.src_ids, self.n_dst, self.R = adj, src_ids, n_dst, R
+
+    @property
+    def n_src(self):
+        return self.adj.shape[1]
+
+
+def sample_typed_blocks(adjacencies, seeds, fanouts, seed):
+    """sample_blocks over R relations of one node set (IntentGC's heterogeneous neighbourhoods): one TypedBlock per layer, outermost
+    first.  Layer k draws up to fanouts[k] neighbours of every destination from EACH relation (dr_neighbor_sample, seeded per (layer,
+    relation)), builds one frontier from all of them (one dr_frontier_build over nbr [n_dst, R * fanout]) and one CSR with a row per
+    (destination, relation) (one dr_block_csr over [n_dst * R, fanout]).  As sample_blocks: everything on the device, ONE read-back per
+    call, the result a function of (seed, seeds, graphs) alone; seeds may repeat."""
+    adjacencies = list(adjacencies)
+    if not adjacencies or not all(isinstance(a, SparseAdjacency) for a in adjacencies):
+        raise TypeError("sample_typed_blocks: adjacencies must be a non-empty list of SparseAdjacency (build each once per graph)")
+    R = len(adjacencies)
+    if R > ops.INTENT_MAX_TYPES:
+        raise ValueError("sample_typed_blocks: at most %d relations, got %d" % (ops.INTENT_MAX_TYPES, R))
+    n_rows = adjacencies[0].shape[0]
+    for a in adjacencies:
+        if a.shape != (n_rows, n_rows) or a.device != adjacencies[0].device:
+            raise ValueError("sample_typed_blocks: every relation must be [%d, %d] over the same nodes on one device, got %s on %s"
+                             % (n_rows, n_rows, a.shape, a.device))
+    fanouts = [int(f) for f in fanouts]
+    if not fanouts:
+        raise ValueError("sample_typed_blocks: fanouts must name at least one layer")
+    for f in fanouts:
+        if not 1 <= f <= ops.SAMPLE_MAX_FANOUT:
+            raise ValueError("sample_typed_blocks: every fanout must be in [1, %d], got %s" % (ops.SAMPLE_MAX_FANOUT, fanouts))
+    dst = torch.as_tensor(seeds)
+    if dst.dtype != torch.int64 or dst.dim() != 1:
+        raise ValueError("sample_typed_blocks: seeds must be int64 [B], got %s %s" % (dst.dtype, tuple(dst.shape)))
+    dst = dst.to(adjacencies[0].device).contiguous()
+    made = []
+    for k in reversed(range(len(fanouts))):
+        n = dst.numel()
+        drawn = [ops.neighbor_sample(a.row_ptr, a.col, n_rows, dst, fanouts[k], _layer_seed(seed, k * R + r))
+                 for r, a in enumerate(adjacencies)]
+        nbr = torch.cat([d[0] for d in drawn], dim=1)                       # [n, R * fanout]
+        cnt = torch.stack([d[1] for d in drawn], dim=1).contiguous()        # [n, R]
+        src, counts, local = ops.frontier_build(dst, nbr, id_bound=n_rows)
+        row_ptr, col, val = ops.block_csr(cnt.view(n * R), local.view(n * R, fanouts[k]), None, add_self=False, n_valid=counts[:1] * R)
+        made.append((src, counts, row_ptr, col, val))
+        dst = src
+    sizes = torch.cat([torch.cat((counts, row_ptr[-1:])) for _, counts, row_ptr, _, _ in made]).cpu().tolist()    # the one read-back
+    blocks = []
+    for j, (src, _, row_ptr, col, val) in enumerate(made):
+        n_dst, n_src, nnz = sizes[3 * j: 3 * j + 3]
+        adj = SparseAdjacency._from_device(row_ptr[:n_dst * R + 1], col[:nnz], val[:nnz], (n_dst * R, n_src))
+        blocks.append(TypedBlock(adj, src[:n_src], n_dst, R))
+    return blocks[::-1]
+
+
 class _SoftmaxRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

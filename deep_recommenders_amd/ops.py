@@ -4182,3 +4182,141 @@ def mlm_mask(ids, vocab_size, num_special, mask_id, prob=0.15, max_predictions=2
     _status(lib().dr_mlm_mask(ptr(ids), B, L, int(vocab_size), int(num_special), int(mask_id), mlm_prob_q16(prob), P,
                               int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out_ids), ptr(positions), ptr(labels), stream_ptr()), "dr_mlm_mask")
     return out_ids, positions, labels
+
+
+# ---- IntentGC: the vector-wise convolution over typed blocks (csrc/intent_conv.hip) -------------------------------------------------------
+INTENT_MAX_TYPES = 7        # R, the neighbour types of a typed block
+INTENT_MAX_FILTERS = 16     # L, the local filters of a layer
+
+
+def _intent_dims(R, D, L, act):
+    """validates the domain of dr_intent_*; returns (R, D, L, act) as ints"""
+    R, D, L = int(R), int(D), int(L)
+    if D % 4 != 0 or not 4 <= D <= 256:
+        raise ValueError("intent_conv: the row width D must be a multiple of 4 in [4, 256], got D = %d" % D)
+    if not 1 <= R <= INTENT_MAX_TYPES:
+        raise ValueError("intent_conv: needs 1 <= R <= %d neighbour types, got R = %d" % (INTENT_MAX_TYPES, R))
+    if not 1 <= L <= INTENT_MAX_FILTERS:
+        raise ValueError("intent_conv: needs 1 <= L <= %d filters, got L = %d" % (INTENT_MAX_FILTERS, L))
+    if act not in (0, 1):
+        raise ValueError("intent_conv: act must be 0 (linear) or 1 (relu), got %r" % (act,))
+    return R, D, L, int(act)
+
+
+def _intent_rows(t, rows, D, what, min_rows=False):
+    """the row pitch of an fp32 [rows, D] matrix the kernels take where it lies (a view with a pitch passes; nothing is copied): unit
+    column stride, a pitch that is a multiple of 4 floats and >= D, a 16-byte aligned base; ValueError naming `what` otherwise.
+    min_rows: at least `rows` rows (the source rows of a block, whose first n_dst are the destinations)."""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != D or (t.shape[0] < rows if min_rows else t.shape[0] != rows):
+        raise ValueError("intent_conv: %s must be fp32 [%s%d, %d], got %s %s" % (what, ">= " if min_rows else "", rows, D, t.dtype,
+                                                                                 tuple(t.shape)))
+    if t.stride(1) != 1 or (t.shape[0] > 1 and (t.stride(0) % 4 != 0 or t.stride(0) < D)):
+        raise ValueError("intent_conv: %s needs unit column stride and a row pitch that is a multiple of 4 and >= %d, got strides %s"
+                         % (what, D, tuple(t.stride())))
+    if t.data_ptr() % 16 != 0:
+        raise ValueError("intent_conv: %s must start at a 16-byte aligned address (a view that begins inside a row does not)" % what)
+    return t.stride(0) if t.shape[0] > 1 else D
+
+
+def _intent_filters(W, theta, R=None):
+    """(W [L, R + 1], theta [L], R, L) dense fp32"""
+    if W.dim() != 2 or W.shape[1] < 2 or (R is not None and W.shape[1] != int(R) + 1):
+        raise ValueError("intent_conv: W must be fp32 [L, R + 1]%s, got %s" % ("" if R is None else " with R = %d" % int(R), tuple(W.shape)))
+    L, R = int(W.shape[0]), int(W.shape[1]) - 1
+    W = _dense_arg(W, "intent_conv: W")
+    theta = _dense_arg(theta, "intent_conv: theta", numel=L)
+    if theta is None:
+        raise ValueError("intent_conv: theta [%d] is required" % L)
+    return W, theta, R, L
+
+
+def _intent_agg(agg, n_dst, R, D, what):
+    """agg / d_agg as the kernels address it: fp32 [n_dst, R, D] (or [n_dst * R, D]) contiguous, 16-byte aligned"""
+    if agg.dtype != torch.float32 or tuple(agg.shape) not in ((n_dst, R, D), (n_dst * R, D)):
+        raise ValueError("intent_conv: %s must be fp32 [%d, %d, %d], got %s %s" % (what, n_dst, R, D, agg.dtype, tuple(agg.shape)))
+    if not agg.is_contiguous() or agg.data_ptr() % 16 != 0:
+        raise ValueError("intent_conv: %s must be contiguous and 16-byte aligned, got strides %s" % (what, tuple(agg.stride())))
+    return agg
+
+
+def intent_conv_fwd(row_ptr, col, val, n_dst, R, h, W, theta, act=1, want_agg=False, out=None):
+    """(out [n_dst, D], agg [n_dst, R, D] | None) of dr_intent_conv_fwd over a typed block's CSR (row_ptr int64 [n_dst R + 1], col
+    int32, val fp32; virtual row v R + r holds the type-(r + 1) neighbours of destination v): a_0 = h[v], a_r the rows' sums, p_i =
+    sum_r W[i, r] a_r, out = act(sum_i theta_i relu(p_i)).  h fp32 [n_src, D] (its first n_dst rows are the destinations; a view with a
+    row pitch is read in place).  want_agg stores the aggregates for intent_conv_bwd.  out: a buffer to overwrite."""
+    n_dst = int(n_dst)
+    W, theta, R, L = _intent_filters(W, theta, R)
+    if h.dim() != 2:
+        raise ValueError("intent_conv: h must be fp32 [n_src, D], got %s" % (tuple(h.shape),))
+    R, D, L, act = _intent_dims(R, h.shape[1], L, act)
+    ld_h = _intent_rows(h, n_dst, D, "h", min_rows=True)
+    row_ptr = _dense_arg(row_ptr, "intent_conv: row_ptr", torch.int64, shape=(n_dst * R + 1,))
+    col = _dense_arg(col, "intent_conv: col", torch.int32)
+    val = _dense_arg(val, "intent_conv: val", torch.float32, numel=col.numel())
+    if out is None:
+        out = torch.empty((n_dst, D), dtype=torch.float32, device=h.device)
+    ld_out = _intent_rows(out, n_dst, D, "out")
+    agg = torch.empty((n_dst, R, D), dtype=torch.float32, device=h.device) if want_agg else None
+    if n_dst == 0:
+        return out, agg
+    _status(lib().dr_intent_conv_fwd(ptr(row_ptr), ptr(col) if col.numel() else None, ptr(val) if val.numel() else None, n_dst, R, ptr(h),
+                                     ld_h, D, ptr(W), ptr(theta), L, act, ptr(out), ld_out, ptr(agg), stream_ptr()), "dr_intent_conv_fwd")
+    return out, agg
+
+
+def intent_mix_fwd(h_self, agg, W, theta, act=1, out=None):
+    """out [n_dst, D] of dr_intent_mix_fwd: intent_conv_fwd's filters on aggregates that already exist (agg fp32 [n_dst, R, D], e.g.
+    adj.spmm(h) of a typed adjacency viewed so) and the destinations' own rows h_self [n_dst, D]; the same bits as the gathered form
+    gives from the same aggregates."""
+    W, theta, R, L = _intent_filters(W, theta)
+    if h_self.dim() != 2:
+        raise ValueError("intent_conv: h_self must be fp32 [n_dst, D], got %s" % (tuple(h_self.shape),))
+    n_dst = int(h_self.shape[0])
+    R, D, L, act = _intent_dims(R, h_self.shape[1], L, act)
+    ld_h = _intent_rows(h_self, n_dst, D, "h_self")
+    agg = _intent_agg(agg, n_dst, R, D, "agg")
+    if out is None:
+        out = torch.empty((n_dst, D), dtype=torch.float32, device=h_self.device)
+    ld_out = _intent_rows(out, n_dst, D, "out")
+    if n_dst == 0:
+        return out
+    _status(lib().dr_intent_mix_fwd(ptr(h_self), ld_h, ptr(agg), n_dst, R, D, ptr(W), ptr(theta), L, act, ptr(out), ld_out, stream_ptr()),
+            "dr_intent_mix_fwd")
+    return out
+
+
+def intent_conv_bwd_workspace(n_dst, D, R, L, device):
+    n = lib().dr_intent_conv_bwd_workspace_bytes(int(n_dst), int(D), int(R), int(L))
+    if n < 0:
+        raise ValueError("intent_conv: (n_dst, D, R, L) = %s is outside the kernel's domain" % ((n_dst, D, R, L),))
+    return torch.empty((max(4, n) // 4,), dtype=torch.float32, device=device)
+
+
+def intent_conv_bwd(h_self, agg, d_out, W, theta, act=1, out=None, d_self=None, workspace=None):
+    """(d_self [n_dst, D], d_agg [n_dst, R, D], d_W [L, R + 1], d_theta [L]) of dr_intent_conv_bwd from the destinations' rows, the
+    aggregates the forward stored, d_out [n_dst, D] and optionally the forward's out (otherwise recomputed).  d_self: a buffer to
+    overwrite, e.g. the top rows of the source gradient; d_agg goes through the transposed block (adj.transpose().spmm) to the rest."""
+    W, theta, R, L = _intent_filters(W, theta)
+    if h_self.dim() != 2:
+        raise ValueError("intent_conv: h_self must be fp32 [n_dst, D], got %s" % (tuple(h_self.shape),))
+    n_dst = int(h_self.shape[0])
+    R, D, L, act = _intent_dims(R, h_self.shape[1], L, act)
+    ld_h = _intent_rows(h_self, n_dst, D, "h_self")
+    agg = _intent_agg(agg, n_dst, R, D, "agg")
+    ld_do = _intent_rows(d_out, n_dst, D, "d_out")
+    ld_out = _intent_rows(out, n_dst, D, "out") if out is not None else 0
+    dev = h_self.device
+    if d_self is None:
+        d_self = torch.empty((n_dst, D), dtype=torch.float32, device=dev)
+    ld_ds = _intent_rows(d_self, n_dst, D, "d_self")
+    d_agg = torch.empty((n_dst, R, D), dtype=torch.float32, device=dev)
+    d_W = torch.zeros((L, R + 1), dtype=torch.float32, device=dev)
+    d_theta = torch.zeros((L,), dtype=torch.float32, device=dev)
+    if n_dst == 0:
+        return d_self, d_agg, d_W, d_theta
+    if workspace is None:
+        workspace = intent_conv_bwd_workspace(n_dst, D, R, L, dev)
+    _status(lib().dr_intent_conv_bwd(ptr(h_self), ld_h, ptr(agg), ptr(d_out), ld_do, ptr(out), ld_out, ptr(W), ptr(theta), n_dst, R, D, L,
+                                     act, ptr(d_self), ld_ds, ptr(d_agg), ptr(d_W), ptr(d_theta), ptr(workspace), workspace.numel() * 4,
+                                     stream_ptr()), "dr_intent_conv_bwd")
+    return d_self, d_agg, d_W, d_theta

@@ -1752,6 +1752,47 @@ int dr_colsum_add(const float* g, int64_t ld, int64_t M, int32_t C, float* dst, 
 int dr_mlm_mask(const int64_t* ids, int64_t B, int32_t L, int64_t V, int64_t num_special, int64_t mask_id, uint32_t prob_q16, int32_t P,
                 uint64_t seed, int64_t* out_ids, int32_t* positions, int64_t* labels, dr_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * IntentGC (Zhao et al., KDD 2019, arXiv:1907.12377; the reference README's model list names it, its tree has no code for it),
+ * csrc/intent_conv.hip: IntentNet's vector-wise convolution over R neighbour types and L local filters.  All fp32, on the caller's
+ * stream, no host synchronisation, no atomics: every result is bit-identical from run to run.
+ *
+ *   a_0 = h[v],  a_r = sum_k val[k] h[col[k]] over k in [row_ptr[v R + r - 1], row_ptr[v R + r])     (r = 1 .. R)
+ *   p_i = sum_{r = 0 .. R} W[i, r] a_r,  g_i = relu(p_i),  s = sum_{i < L} theta_i g_i,  out[v] = act(s)
+ *
+ * The CSR (row_ptr int64 [n_dst R + 1], col int32, val fp32) is a typed block: virtual row v R + r - 1 holds the type-r neighbours of
+ * destination v (layers.sample_typed_blocks; row-normalised, possibly empty) and the destinations are rows 0 .. n_dst - 1 of h.  W
+ * [L, R + 1] and theta [L] are dense; a_r, p_i, g_i, s are D-vectors and W[i, r], theta_i scalars.  act: 0 linear, 1 relu.
+ *
+ *   dr_intent_conv_fwd  gathers a_1 .. a_R as dr_csr_spmm gathers a row (ascending k, the same bits on any row that kernel does not
+ *                       split; here rows of ANY length are summed in ascending k, there is no split), applies the filters in registers
+ *                       and writes out [n_dst, D] (pitch ld_out).  agg non-NULL: also stores a_1 .. a_R as [n_dst, R, D], dense.
+ *   dr_intent_mix_fwd   the same body with a_r read from agg [n_dst, R, D] (pre-aggregated rows; adj.spmm's output over a whole
+ *                       graph) and a_0 from h_self (pitch ld_h): the same out bits from the same a_r bits.
+ *   dr_intent_conv_bwd  from h_self, agg, d_out (pitch ld_do) and optionally the forward's out (pitch ld_out; NULL: s is recomputed,
+ *                       the same bits): d_self [n_dst, D] (pitch ld_ds) = d_a_0, d_agg [n_dst, R, D] = d_a_r (the caller scatters it
+ *                       with the transposed block), d_W [L, R + 1] and d_theta [L], all OVERWRITTEN.
+ *                         ds = d_out * act'(s),  d_theta_i = sum_{v, c} ds g_i,  dp_i = [p_i > 0] theta_i ds,
+ *                         d_W[i, r] = sum_{v, c} dp_i a_r,  d_a_r = sum_i W[i, r] dp_i
+ *                       d_W / d_theta are two-stage sums: per-block partials in the workspace (lanes by a fixed butterfly, destinations
+ *                       in ascending order), then the blocks in order.  The grid is a function of (n_dst, D) alone.
+ *                       workspace: dr_intent_conv_bwd_workspace_bytes(n_dst, D, R, L) bytes (-1 outside the domain).
+ *   Order of every sum: p_i over ascending r, s and d_a_r over ascending i, each an fmaf chain from +0.
+ *   Domain: D % 4 == 0, 4 <= D <= 256, 1 <= R <= 7, 1 <= L <= 16 (DR_ESHAPE otherwise); act in {0, 1}, pitches multiples of 4 and
+ *   >= D, every matrix 16-byte aligned (DR_EINVAL otherwise).  Outside the domain nothing is launched; n_dst == 0 returns DR_OK and
+ *   launches nothing (d_W and d_theta are then not written).
+ * ---------------------------------------------------------------------------------------- */
+int dr_intent_conv_fwd(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n_dst, int32_t R, const float* h,
+                       int64_t ld_h, int32_t D, const float* W, const float* theta, int32_t L, int32_t act, float* out, int64_t ld_out,
+                       float* agg, dr_stream_t stream);
+int dr_intent_mix_fwd(const float* h_self, int64_t ld_h, const float* agg, int64_t n_dst, int32_t R, int32_t D, const float* W,
+                      const float* theta, int32_t L, int32_t act, float* out, int64_t ld_out, dr_stream_t stream);
+int64_t dr_intent_conv_bwd_workspace_bytes(int64_t n_dst, int32_t D, int32_t R, int32_t L);
+int dr_intent_conv_bwd(const float* h_self, int64_t ld_h, const float* agg, const float* d_out, int64_t ld_do, const float* out,
+                       int64_t ld_out, const float* W, const float* theta, int64_t n_dst, int32_t R, int32_t D, int32_t L, int32_t act,
+                       float* d_self, int64_t ld_ds, float* d_agg, float* d_W, float* d_theta, void* workspace,
+                       int64_t workspace_bytes, dr_stream_t stream);
+
 /* dr_clock_stamp: dst[0] = the device's constant-rate wall clock (100 MHz ticks) when a one-thread kernel reaches the head of
  * `stream`.  Measurement plumbing with no reference counterpart: bench.py brackets the sharded step's cross-stream waits with two
  * stamps to report the EXPOSED part of the exchange (HIP timing events around a wait serialise the step). */
