@@ -204,6 +204,92 @@ def _dense_arg(t, what, dtype=torch.float32, shape=None, numel=None, copy=True):
     return t.contiguous()
 
 
+# The argument checks the model-layer and retrieval families share.  Each raises a ValueError that names the family and the argument;
+# a family's own domain (its field counts, option codes, workspace sizes) stays with the family.
+def _slab_width(family, D, what="D", lo=4, hi=256):
+    """a row width the kernels vectorise over: a multiple of 4 in [lo, hi] ([4, 256] is the embedding slab's domain); returns it as an int"""
+    D = int(D)
+    if D % 4 != 0 or not lo <= D <= hi:
+        raise ValueError("%s: %s must be a multiple of 4 in [%d, %d], got %d" % (family, what, lo, hi, D))
+    return D
+
+
+def _vec_arg(family, t, n, what, dtype=torch.float32, none_ok=False, device=None):
+    """t as a contiguous [n] (a copy only where it is no such view already): one value per example, id or slot.  None passes where
+    none_ok; another dtype or element count, or (device given) another device, is a ValueError."""
+    if t is None and none_ok:
+        return None
+    if t.dtype != dtype or t.numel() != n:
+        raise ValueError("%s: %s must be %s with %d values (one value per example, id or slot), got %s %s"
+                         % (family, what, dtype, n, t.dtype, tuple(t.shape)))
+    if device is not None and t.device != device:
+        raise ValueError("%s: %s is on %s, the call's other tensors on %s" % (family, what, t.device, device))
+    return t.reshape(n).contiguous()
+
+
+def _ids_arg(family, t, what, cols=None, rows=None):
+    """int64 [rows, cols] ids (None: any number of rows / columns), returned contiguous"""
+    if t.dtype != torch.int64 or t.dim() != 2 or (cols is not None and t.shape[1] != cols) or (rows is not None and t.shape[0] != rows):
+        raise ValueError("%s: %s must be int64 [%s, %s], got %s %s" % (family, what, "B" if rows is None else rows,
+                                                                      "C" if cols is None else cols, t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def _table_arg(family, t, what, cols=None):
+    """a table whose rows the kernel reads in place by id: contiguous fp32 [R, cols] (cols None: any width); a view is refused"""
+    if t.dtype != torch.float32 or t.dim() != 2 or (cols is not None and t.shape[1] != cols) or not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous fp32 [R, %s], got %s %s with strides %s"
+                         % (family, what, "D" if cols is None else cols, t.dtype, tuple(t.shape), tuple(t.stride())))
+
+
+def _rows_arg(family, t, cols, what, shapes=(), rows=None, device=None):
+    """(t as [B, cols], its row pitch) of an fp32 matrix of rows a kernel reads or writes where it lies (_row_pitch's rule).  A
+    contiguous N-d tensor whose trailing shape is one of `shapes` is taken as [B, cols].  rows given: t must have that many rows, and a
+    None t is allocated [rows, cols] on `device`."""
+    if t is None and rows is not None:
+        t = torch.empty((rows, cols), dtype=torch.float32, device=device)
+    if t.dtype != torch.float32:
+        raise ValueError("%s: %s must be fp32, got %s" % (family, what, t.dtype))
+    if t.dim() > 2:
+        if tuple(t.shape[1:]) not in shapes or not t.is_contiguous():
+            raise ValueError("%s: a %d-d %s must be contiguous [B, ...] with trailing shape %s, got %s with strides %s"
+                             % (family, t.dim(), what, " or ".join(str(tuple(s)) for s in shapes) or "(%d,)" % cols, tuple(t.shape),
+                                tuple(t.stride())))
+        t = t.reshape(t.shape[0], cols)
+    if rows is not None and (t.dim() != 2 or t.shape[0] != rows):
+        raise ValueError("%s: %s must be fp32 [%d, %d], got %s %s" % (family, what, rows, cols, t.dtype, tuple(t.shape)))
+    return t, _row_pitch(family, t, cols, what)
+
+
+def _pitched(family, t, what, cols=None, rows=None, min_rows=False, mult4=False, aligned=False, tight_row=False):
+    """the row pitch of an fp32 [rows, cols] matrix (None: any number of rows; any width >= 1) that a kernel takes where it lies: nothing
+    is copied, and a layout outside the policy is a ValueError.  Always: unit column stride and, with more than one row, a pitch >= the
+    width.  mult4: that pitch is a multiple of 4 floats.  aligned: the base address is 16-byte aligned.  min_rows: `rows` or more rows
+    (the source rows of a block, whose first `rows` are the destinations).  One row has no pitch: its stride is handed on where that
+    is a legal pitch, and the width otherwise -- or always, with tight_row."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] < 1 if cols is None else t.shape[1] != cols) or \
+            (rows is not None and (t.shape[0] < rows if min_rows else t.shape[0] != rows)):
+        raise ValueError("%s: %s must be fp32 [%s%s, %s], got %s" % (
+            family, what, ">= " if min_rows else "", "M" if rows is None else rows, cols or "N >= 1",
+            "%s %s" % (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+    M, N = t.shape
+    ld = t.stride(0)
+    legal = ld >= N and not (mult4 and ld % 4)
+    if (N > 1 and t.stride(1) != 1) or (M > 1 and not legal):
+        raise ValueError("%s: %s needs unit column stride and a row pitch %s>= %d, got strides %s"
+                         % (family, what, "that is a multiple of 4 and " if mult4 else "", N, tuple(t.stride())))
+    if aligned and t.data_ptr() % 16 != 0:
+        raise ValueError("%s: %s must start at a 16-byte aligned address (a view that begins inside a row does not)" % (family, what))
+    return ld if M > 1 or (legal and not tight_row) else _pad4(N) if mult4 else N
+
+
+def _one_device(family, anchor, device, **tensors):
+    """every tensor one call is handed lives on one device: `device`, where the argument named `anchor` is"""
+    for what, t in tensors.items():
+        if t is not None and t.device != device:
+            raise ValueError("%s: %s is on %s, %s on %s; one call takes tensors of one device" % (family, what, t.device, anchor, device))
+
+
 def _vec_f32(b):
     """a bias / per-column vector the kernel reads densely (an expanded one has a 0 stride and a single element behind it)"""
     return None if b is None else _c(b, torch.float32)
@@ -878,7 +964,6 @@ class TopKIndex:
         # `cand` must be the caller's own fp32 tensor: staleness is detected through ITS version counter (a copy made here would
         # never see the caller's later writes; writes through raw pointers -- another library -- are not seen either: call rebuild())
         self.cand = _c(cand, torch.float32)
-        self.follows_caller = self.cand is cand
         N, D = self.cand.shape
         self.buf = None
         self._able = N > 0 and D % 4 == 0 and 4 <= D <= 512 and self.cand.is_cuda
@@ -1888,23 +1973,18 @@ def cin_pool_bwd(x0, x, W, act, out, d_out, d_pooled, want_bias=False, d_x0=None
 
 # ---- DLRM: the pairwise dot interaction (csrc/dot_interact.hip) ------------------------------------------------------------------------
 def _di_dims(dense, emb, F, D, self_interaction):
-    """validates the domain of dr_dot_interact_*; returns (emb as [B, F * D], B, N, c0, P)"""
-    F, D = int(F), int(D)
-    if D % 4 != 0 or not 4 <= D <= 256:
-        raise ValueError("dot_interact: D must be a multiple of 4 in [4, 256], got %d" % D)
+    """validates the domain of dr_dot_interact_*; returns (emb as [B, F * D], its row pitch, B, N, c0, P)"""
+    F, D = int(F), _slab_width("dot_interact", D)
     N = F + (0 if dense is None else 1)
     if F < 1 or not 2 <= N <= 64:
         raise ValueError("dot_interact: needs 2 <= N <= 64 vectors per example (F fields + the dense vector), got F = %d, N = %d" % (F, N))
-    if emb.dim() == 3:
-        if emb.shape[1:] != (F, D) or not emb.is_contiguous():
-            raise ValueError("dot_interact: a 3-d emb must be contiguous [B, %d, %d], got %s" % (F, D, tuple(emb.shape)))
-        emb = emb.reshape(emb.shape[0], F * D)
+    emb, ld_emb = _rows_arg("dot_interact", emb, F * D, "emb", ((F, D),))
     B = emb.shape[0]
     if dense is not None and dense.shape[0] != B:
         raise ValueError("dot_interact: dense and emb disagree on the batch size")
     c0 = 0 if dense is None else D
     P = N * (N + 1) // 2 if self_interaction else N * (N - 1) // 2
-    return emb, B, N, c0, P
+    return emb, ld_emb, B, N, c0, P
 
 
 def dot_interact_width(F, D, dense=True, self_interaction=False):
@@ -1917,8 +1997,7 @@ def dot_interact_fwd(dense, emb, F, D, self_interaction=False, out=None, ld_out=
     """out [B, c0 + P] (a view of a [B, ld_out] buffer, zero beyond c0 + P) of dr_dot_interact_fwd: dense [B, D] (or None) copied to the
     first D columns, then the row-major lower triangle of T T^T for T = [dense; emb's F rows].  emb: [B, F, D] contiguous, or
     [B, F * D] with any row stride that is a multiple of 4.  out: a [B, c0 + P] view to write into (its row stride is ld_out)."""
-    emb, B, N, c0, P = _di_dims(dense, emb, F, D, self_interaction)
-    ld_emb = _row_pitch("dot_interact", emb, F * D, "emb")
+    emb, ld_emb, B, N, c0, P = _di_dims(dense, emb, F, D, self_interaction)
     ld_dense = 0 if dense is None else _row_pitch("dot_interact", dense, D, "dense")
     if out is None:
         ld_out = _pad4(c0 + P) if ld_out is None else int(ld_out)
@@ -1938,8 +2017,7 @@ def dot_interact_fwd(dense, emb, F, D, self_interaction=False, out=None, ld_out=
 def dot_interact_bwd(dense, emb, F, D, d_out, self_interaction=False, d_dense=None, d_emb=None):
     """(d_dense [B, D] | None, d_emb [B, F * D]) of dr_dot_interact_bwd from d_out [B, c0 + P] (row stride a multiple of 4; columns
     beyond c0 + P are not read).  d_dense / d_emb: buffers to overwrite (only their first D / F * D columns are written)."""
-    emb, B, N, c0, P = _di_dims(dense, emb, F, D, self_interaction)
-    ld_emb = _row_pitch("dot_interact", emb, F * D, "emb")
+    emb, ld_emb, B, N, c0, P = _di_dims(dense, emb, F, D, self_interaction)
     ld_dense = 0 if dense is None else _row_pitch("dot_interact", dense, D, "dense")
     ld_dout = _row_pitch("dot_interact", d_out, c0 + P, "d_out")
     if d_emb is None:
@@ -1964,15 +2042,14 @@ def afm_num_pairs(F):
 
 
 def _afm_dims(emb, W, b, h, F):
-    """validates the domain of dr_afm_pool_* (include/dr_hotpath.h) without a device; returns (emb as [B, F * D], B, F, D, A, P)"""
+    """validates the domain of dr_afm_pool_* (include/dr_hotpath.h) without a device; returns (emb as [B, F * D], its row pitch, B, F, D,
+    A, P)"""
     F = int(F)
     if W.dim() != 2 or b.dim() != 1 or h.dim() != 1 or b.shape[0] != W.shape[1] or h.shape[0] != W.shape[1]:
         raise ValueError("afm_pool: W [D, A], b [A], h [A] expected, got %s, %s, %s" % (tuple(W.shape), tuple(b.shape), tuple(h.shape)))
     if any(t.dtype != torch.float32 for t in (emb, W, b, h)):
         raise ValueError("afm_pool: fp32 tensors only")
-    D, A = int(W.shape[0]), int(W.shape[1])
-    if D % 4 != 0 or not 4 <= D <= 256:
-        raise ValueError("afm_pool: D must be a multiple of 4 in [4, 256], got %d" % D)
+    D, A = _slab_width("afm_pool", W.shape[0]), int(W.shape[1])
     if not 1 <= A <= 128:
         raise ValueError("afm_pool: the attention factor A must be in [1, 128], got %d" % A)
     if not 2 <= F <= 64:
@@ -1985,20 +2062,14 @@ def _afm_dims(emb, W, b, h, F):
     PE, PW = 16 * DT + 4, 16 * AT + 4
     if 16 * DT * PW + 32 * AT + (P + 15) // 16 * 16 + 2 * F * PE + 16 * DT + 16 * PW + 16 * PE > 40000:
         raise ValueError("afm_pool: F = %d, D = %d, A = %d do not fit the LDS" % (F, D, A))
-    if emb.dim() == 3:
-        if tuple(emb.shape[1:]) != (F, D) or not emb.is_contiguous():
-            raise ValueError("afm_pool: a 3-d emb must be contiguous [B, %d, %d], got %s" % (F, D, tuple(emb.shape)))
-        emb = emb.reshape(emb.shape[0], F * D)
-    elif emb.dim() != 2 or emb.shape[1] != F * D:
-        raise ValueError("afm_pool: emb must be [B, %d, %d] or [B, %d], got %s" % (F, D, F * D, tuple(emb.shape)))
-    return emb, int(emb.shape[0]), F, D, A, P
+    emb, ld_emb = _rows_arg("afm_pool", emb, F * D, "emb", ((F, D),))
+    return emb, ld_emb, int(emb.shape[0]), F, D, A, P
 
 
 def afm_pool_fwd(emb, W, b, h, F, want_attention=False, out=None):
     """(out [B, D], lse [B], attn [B, P] | None) of dr_afm_pool_fwd.  emb: [B, F, D] contiguous, or [B, F * D] with any row stride that
     is a multiple of 4 (the slab's concat, read in place); W [D, A], b [A], h [A].  out: a [B, D] view to write into."""
-    emb, B, F, D, A, P = _afm_dims(emb, W, b, h, F)
-    ld_emb = _row_pitch("afm_pool", emb, F * D, "emb")
+    emb, ld_emb, B, F, D, A, P = _afm_dims(emb, W, b, h, F)
     if out is None:
         out = torch.empty((B, D), dtype=torch.float32, device=emb.device)
     ld_out = _row_pitch("afm_pool", out, D, "out")
@@ -2016,8 +2087,7 @@ def afm_pool_fwd(emb, W, b, h, F, want_attention=False, out=None):
 def afm_pool_bwd(emb, W, b, h, F, out, lse, d_out, d_emb=None, workspace=None):
     """(d_emb [B, F * D], dW [D, A], db [A], dh [A]) of dr_afm_pool_bwd from d_out [B, D], with out and lse of afm_pool_fwd.  d_emb: a
     [B, F * D] buffer to overwrite; workspace: fp32, at least dr_afm_pool_bwd_workspace_bytes(B, F, D, A) bytes (allocated when None)."""
-    emb, B, F, D, A, P = _afm_dims(emb, W, b, h, F)
-    ld_emb = _row_pitch("afm_pool", emb, F * D, "emb")
+    emb, ld_emb, B, F, D, A, P = _afm_dims(emb, W, b, h, F)
     ld_out = _row_pitch("afm_pool", out, D, "out")
     ld_dout = _row_pitch("afm_pool", d_out, D, "d_out")
     if lse.dtype != torch.float32 or tuple(lse.shape) != (B,) or not lse.is_contiguous():
@@ -2062,9 +2132,7 @@ def _pnn_dims(emb, W, F):
         emb = emb.reshape(emb.shape[0], F * emb.shape[2])
     elif emb.dim() != 2 or emb.shape[1] % F != 0:
         raise ValueError("pnn_outer: emb must be [B, %d, D] or [B, %d * D], got %s" % (F, F, tuple(emb.shape)))
-    D = int(emb.shape[1]) // F
-    if D % 4 != 0 or not 4 <= D <= 128:
-        raise ValueError("pnn_outer: D must be a multiple of 4 in [4, 128], got %d" % D)
+    D = _slab_width("pnn_outer", int(emb.shape[1]) // F, hi=128)
     if W.dim() != 2 or W.shape[0] != D * D:
         raise ValueError("pnn_outer: W must be [D * D, N] = [%d, N], got %s" % (D * D, tuple(W.shape)))
     N = int(W.shape[1])
@@ -2206,9 +2274,7 @@ def _gru_dims(xp, U):
     """validates the domain of dr_gru_seq_* (include/dr_hotpath.h) without a device; returns (B, T, H)"""
     if U.dim() != 2 or U.dtype != torch.float32 or U.shape[1] != 3 * U.shape[0]:
         raise ValueError("gru_seq: U must be fp32 [H, 3H], got %s %s" % (U.dtype, tuple(U.shape)))
-    H = int(U.shape[0])
-    if H % 4 != 0 or not 4 <= H <= 128:
-        raise ValueError("gru_seq: H must be a multiple of 4 in [4, 128], got %d" % H)
+    H = _slab_width("gru_seq", U.shape[0], "H", hi=128)
     if xp.dim() != 3 or xp.shape[2] != 3 * H:
         raise ValueError("gru_seq: xp must be [B, T, %d], got %s" % (3 * H, tuple(xp.shape)))
     B, T = int(xp.shape[0]), int(xp.shape[1])
@@ -2288,8 +2354,7 @@ def _seq_attn_dims(hs, q):
     if hs.dim() != 3 or q.dim() != 2 or q.dtype != torch.float32 or q.shape[0] != hs.shape[0] or q.shape[1] != hs.shape[2]:
         raise ValueError("seq_attn: hs [B, T, H] and q [B, H] fp32 expected, got %s and %s" % (tuple(hs.shape), tuple(q.shape)))
     B, T, H = (int(s) for s in hs.shape)
-    if H % 4 != 0 or not 4 <= H <= 128:
-        raise ValueError("seq_attn: H must be a multiple of 4 in [4, 128], got %d" % H)
+    _slab_width("seq_attn", H, "H", hi=128)
     if T < 1:
         raise ValueError("seq_attn: needs T >= 1 time steps, got %d" % T)
     return B, T, H
@@ -2931,9 +2996,7 @@ def din_pool_bwd(query, keys, mask, W, b, w_out, b_out, mode, act, d_out, d_scor
 # ---- FFM: the field-aware interaction (csrc/ffm.hip) -------------------------------------------------------------------------------------
 def _ffm_dims(F, k):
     """validates the domain of dr_ffm_*; returns (F, k) as ints"""
-    F, k = int(F), int(k)
-    if k % 4 != 0 or not 4 <= k <= 128:
-        raise ValueError("ffm: the latent size k must be a multiple of 4 in [4, 128], got %d" % k)
+    F, k = int(F), _slab_width("ffm", k, "the latent size k", hi=128)
     if not 2 <= F <= 64:
         raise ValueError("ffm: needs 2 <= F <= 64 fields, got F = %d" % F)
     if F * k > 256:
@@ -2948,33 +3011,11 @@ def ffm_row_width(F, k):
     return F * k
 
 
-def _ffm_rows(t, F, k, what):
-    """(t as [B, F * F * k], its row stride) of a fp32 matrix of gathered rows with unit column stride; ValueError unless the stride is a
-    multiple of 4 and >= F * F * k.  [B, F, F, k] and [B, F, F * k] contiguous are taken as they are."""
-    cols = F * F * k
-    if t.dtype != torch.float32:
-        raise ValueError("ffm: %s must be fp32, got %s" % (what, t.dtype))
-    if t.dim() in (3, 4):
-        if tuple(t.shape[1:]) not in ((F, F, k), (F, F * k)) or not t.is_contiguous():
-            raise ValueError("ffm: a %d-d %s must be contiguous [B, %d, %d, %d] or [B, %d, %d], got %s"
-                             % (t.dim(), what, F, F, k, F, F * k, tuple(t.shape)))
-        t = t.reshape(t.shape[0], cols)
-    if t.dim() != 2 or t.shape[1] != cols:
-        raise ValueError("ffm: %s must be [B, %d] (F * F * k columns), got %s" % (what, cols, tuple(t.shape)))
-    return t, _row_pitch("ffm", t, cols, what)                 # a single row's pitch is _pad4(cols) = cols: k is a multiple of 4
-
-
-def _ffm_vec(t, B, what):
-    if t.dtype != torch.float32 or t.numel() != B:
-        raise ValueError("ffm: %s must be fp32 with one value per example (%d), got %s %s" % (what, B, t.dtype, tuple(t.shape)))
-    return t.reshape(B).contiguous()
-
-
 def ffm_fwd(rows, F, k):
     """inter [B] of dr_ffm_fwd: sum over the pairs j < i of <A[i, j, :], A[j, i, :]> with A [F, F, k] the example's gathered rows.  rows:
     [B, F, F, k] or [B, F, F * k] contiguous, or [B, F * F * k] with any row stride that is a multiple of 4 (the slab's concat, in place)."""
     F, k = _ffm_dims(F, k)
-    rows, ld = _ffm_rows(rows, F, k, "rows")
+    rows, ld = _rows_arg("ffm", rows, F * F * k, "rows (F * F * k columns)", ((F, F, k), (F, F * k)))
     B = rows.shape[0]
     inter = torch.empty((B,), dtype=torch.float32, device=rows.device)
     if B == 0:
@@ -2987,12 +3028,10 @@ def ffm_bwd(rows, F, k, d_inter, d_rows=None):
     """d_rows [B, F * F * k] of dr_ffm_bwd: d_rows[b, i, j, :] = d_inter[b] * A[b, j, i, :], the diagonal blocks +0.0.  d_rows: a buffer to
     overwrite (only its first F * F * k columns are written)."""
     F, k = _ffm_dims(F, k)
-    rows, ld = _ffm_rows(rows, F, k, "rows")
+    rows, ld = _rows_arg("ffm", rows, F * F * k, "rows (F * F * k columns)", ((F, F, k), (F, F * k)))
     B = rows.shape[0]
-    d_inter = _ffm_vec(d_inter, B, "d_inter")
-    if d_rows is None:
-        d_rows = torch.empty((B, F * F * k), dtype=torch.float32, device=rows.device)
-    d_rows, ld_d = _ffm_rows(d_rows, F, k, "d_rows")
+    d_inter = _vec_arg("ffm", d_inter, B, "d_inter")
+    d_rows, ld_d = _rows_arg("ffm", d_rows, F * F * k, "d_rows (F * F * k columns)", ((F, F, k), (F, F * k)), rows=B, device=rows.device)
     if B == 0:
         return d_rows
     _status(lib().dr_ffm_bwd(ptr(rows), ld, ptr(d_inter), B, F, k, ptr(d_rows), ld_d, stream_ptr()), "dr_ffm_bwd")
@@ -3001,13 +3040,10 @@ def ffm_bwd(rows, F, k, d_inter, d_rows=None):
 
 def _ffm_gather_args(ids, row_base, table, F, k):
     F, k = _ffm_dims(F, k)
-    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[1] != F:
-        raise ValueError("ffm: ids must be int64 [B, %d] (one id per field), got %s %s" % (F, ids.dtype, tuple(ids.shape)))
-    if row_base.dtype != torch.int64 or row_base.numel() != F:
-        raise ValueError("ffm: row_base must be int64 [%d], got %s %s" % (F, row_base.dtype, tuple(row_base.shape)))
-    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != F * k or not table.is_contiguous():
-        raise ValueError("ffm: table must be contiguous fp32 [R, %d] (F * k columns), got %s %s" % (F * k, table.dtype, tuple(table.shape)))
-    return F, k, ids.contiguous(), row_base.contiguous()
+    ids = _ids_arg("ffm", ids, "ids", F)
+    row_base = _vec_arg("ffm", row_base, F, "row_base", torch.int64)
+    _table_arg("ffm", table, "table", F * k)
+    return F, k, ids, row_base
 
 
 def ffm_gather_fwd(ids, row_base, table, F, k, lin_w=None, lin_bias=None):
@@ -3028,10 +3064,8 @@ def ffm_gather_bwd(ids, row_base, table, F, k, d_inter, d_rows=None):
     """d_rows [B, F * F * k] of dr_ffm_gather_bwd, from the table and d_inter: what emb_pool_bwd takes as d_concat with D = F * k."""
     F, k, ids, row_base = _ffm_gather_args(ids, row_base, table, F, k)
     B = ids.shape[0]
-    d_inter = _ffm_vec(d_inter, B, "d_inter")
-    if d_rows is None:
-        d_rows = torch.empty((B, F * F * k), dtype=torch.float32, device=ids.device)
-    d_rows, ld_d = _ffm_rows(d_rows, F, k, "d_rows")
+    d_inter = _vec_arg("ffm", d_inter, B, "d_inter")
+    d_rows, ld_d = _rows_arg("ffm", d_rows, F * F * k, "d_rows (F * F * k columns)", ((F, F, k), (F, F * k)), rows=B, device=ids.device)
     if B == 0:
         return d_rows
     _status(lib().dr_ffm_gather_bwd(ptr(ids), B, F, ptr(row_base), ptr(table), k, ptr(d_inter), ptr(d_rows), ld_d, stream_ptr()),
@@ -3042,55 +3076,29 @@ def ffm_gather_bwd(ids, row_base, table, F, k, d_inter, d_rows=None):
 # ---- NFM: the Bi-Interaction pooling (csrc/bi_interaction.hip) ----------------------------------------------------------------------------
 def _bi_dims(F, D):
     """validates the domain of dr_bi_interact_*; returns (F, D) as ints"""
-    F, D = int(F), int(D)
-    if D % 4 != 0 or not 4 <= D <= 256:
-        raise ValueError("bi_interaction: the row width D must be a multiple of 4 in [4, 256], got %d" % D)
+    F, D = int(F), _slab_width("bi_interaction", D, "the row width D")
     if not 1 <= F <= 1024:
         raise ValueError("bi_interaction: needs 1 <= F <= 1024 fields, got F = %d" % F)
     return F, D
 
 
-def _bi_rows(t, F, D, what):
-    """(t as [B, F * D], its row stride) of a fp32 matrix of rows with unit column stride; [B, F, D] contiguous is taken as it is"""
-    cols = F * D
-    if t.dtype != torch.float32:
-        raise ValueError("bi_interaction: %s must be fp32, got %s" % (what, t.dtype))
-    if t.dim() == 3:
-        if tuple(t.shape[1:]) != (F, D) or not t.is_contiguous():
-            raise ValueError("bi_interaction: a 3-d %s must be contiguous [B, %d, %d], got %s" % (what, F, D, tuple(t.shape)))
-        t = t.reshape(t.shape[0], cols)
-    return t, _row_pitch("bi_interaction", t, cols, what)
-
-
-def _bi_out(t, B, D, what, device):
-    """(t, its row stride) of an [B, D] fp32 output or gradient; allocated when None"""
-    if t is None:
-        t = torch.empty((B, D), dtype=torch.float32, device=device)
-    if t.dim() != 2 or t.shape[0] != B:
-        raise ValueError("bi_interaction: %s must be fp32 [%d, %d], got %s %s" % (what, B, D, t.dtype, tuple(t.shape)))
-    return t, _row_pitch("bi_interaction", t, D, what)
-
-
 def _bi_gather_args(ids, row_base, table, F, D, lin_w=None, lin_bias=None):
     F, D = _bi_dims(F, D)
-    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[1] != F:
-        raise ValueError("bi_interaction: ids must be int64 [B, %d] (one id per field), got %s %s" % (F, ids.dtype, tuple(ids.shape)))
-    if row_base.dtype != torch.int64 or row_base.numel() != F:
-        raise ValueError("bi_interaction: row_base must be int64 [%d], got %s %s" % (F, row_base.dtype, tuple(row_base.shape)))
-    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != D or not table.is_contiguous():
-        raise ValueError("bi_interaction: table must be contiguous fp32 [R, %d], got %s %s" % (D, table.dtype, tuple(table.shape)))
+    ids = _ids_arg("bi_interaction", ids, "ids", F)
+    row_base = _vec_arg("bi_interaction", row_base, F, "row_base", torch.int64)
+    _table_arg("bi_interaction", table, "table", D)
     lin_w = _dense_arg(lin_w, "bi_interaction: lin_w", numel=table.shape[0])
     lin_bias = _dense_arg(lin_bias, "bi_interaction: lin_bias", numel=1)
-    return F, D, ids.contiguous(), row_base.contiguous(), lin_w, lin_bias
+    return F, D, ids, row_base, lin_w, lin_bias
 
 
 def bi_interaction_fwd(rows, F, D, out=None):
     """out [B, D] of dr_bi_interact_fwd: 0.5 ((sum_f e_f)^2 - sum_f e_f^2) over the F rows of every example.  rows: [B, F, D] contiguous,
     or [B, F * D] with any row stride that is a multiple of 4 (the slab's concat, in place).  out: a buffer to overwrite."""
     F, D = _bi_dims(F, D)
-    rows, ld = _bi_rows(rows, F, D, "rows")
+    rows, ld = _rows_arg("bi_interaction", rows, F * D, "rows", ((F, D),))
     B = rows.shape[0]
-    out, ld_out = _bi_out(out, B, D, "out", rows.device)
+    out, ld_out = _rows_arg("bi_interaction", out, D, "out", rows=B, device=rows.device)
     if B == 0:
         return out
     _status(lib().dr_bi_interact_fwd(ptr(rows), ld, B, F, D, ptr(out), ld_out, stream_ptr()), "dr_bi_interact_fwd")
@@ -3101,14 +3109,10 @@ def bi_interaction_bwd(rows, F, D, d_out, d_rows=None):
     """d_rows [B, F * D] of dr_bi_interact_bwd: d_rows[b, f, :] = d_out[b, :] * (sum_g e_g - e_f).  d_rows: a buffer to overwrite (only
     its first F * D columns are written)."""
     F, D = _bi_dims(F, D)
-    rows, ld = _bi_rows(rows, F, D, "rows")
+    rows, ld = _rows_arg("bi_interaction", rows, F * D, "rows", ((F, D),))
     B = rows.shape[0]
-    d_out, ld_do = _bi_out(d_out, B, D, "d_out", rows.device)
-    if d_rows is None:
-        d_rows = torch.empty((B, F * D), dtype=torch.float32, device=rows.device)
-    d_rows, ld_d = _bi_rows(d_rows, F, D, "d_rows")
-    if d_rows.shape[0] != B:
-        raise ValueError("bi_interaction: d_rows must have %d rows, got %s" % (B, tuple(d_rows.shape)))
+    d_out, ld_do = _rows_arg("bi_interaction", d_out, D, "d_out", rows=B, device=rows.device)
+    d_rows, ld_d = _rows_arg("bi_interaction", d_rows, F * D, "d_rows", ((F, D),), rows=B, device=rows.device)
     if B == 0:
         return d_rows
     _status(lib().dr_bi_interact_bwd(ptr(rows), ld, ptr(d_out), ld_do, B, F, D, ptr(d_rows), ld_d, stream_ptr()), "dr_bi_interact_bwd")
@@ -3121,7 +3125,7 @@ def bi_interaction_gather_fwd(ids, row_base, table, F, D, lin_w=None, lin_bias=N
     given."""
     F, D, ids, row_base, lin_w, lin_bias = _bi_gather_args(ids, row_base, table, F, D, lin_w, lin_bias)
     B = ids.shape[0]
-    out, ld_out = _bi_out(out, B, D, "out", ids.device)
+    out, ld_out = _rows_arg("bi_interaction", out, D, "out", rows=B, device=ids.device)
     first = torch.empty((B,), dtype=torch.float32, device=ids.device) if lin_w is not None else None
     if B == 0:
         return out, first
@@ -3134,12 +3138,8 @@ def bi_interaction_gather_bwd(ids, row_base, table, F, D, d_out, d_rows=None):
     """d_rows [B, F * D] of dr_bi_interact_gather_bwd, from the table and d_out: what emb_pool_bwd takes as d_concat."""
     F, D, ids, row_base, _, _ = _bi_gather_args(ids, row_base, table, F, D)
     B = ids.shape[0]
-    d_out, ld_do = _bi_out(d_out, B, D, "d_out", ids.device)
-    if d_rows is None:
-        d_rows = torch.empty((B, F * D), dtype=torch.float32, device=ids.device)
-    d_rows, ld_d = _bi_rows(d_rows, F, D, "d_rows")
-    if d_rows.shape[0] != B:
-        raise ValueError("bi_interaction: d_rows must have %d rows, got %s" % (B, tuple(d_rows.shape)))
+    d_out, ld_do = _rows_arg("bi_interaction", d_out, D, "d_out", rows=B, device=ids.device)
+    d_rows, ld_d = _rows_arg("bi_interaction", d_rows, F * D, "d_rows", ((F, D),), rows=B, device=ids.device)
     if B == 0:
         return d_rows
     _status(lib().dr_bi_interact_gather_bwd(ptr(ids), B, F, ptr(row_base), ptr(table), D, ptr(d_out), ld_do, ptr(d_rows), ld_d,
@@ -3161,44 +3161,21 @@ def _lsplm_dims(F, m):
 def _lsplm_pool_args(ids, F, col_start, row_base, table, m, bias):
     """validates the inputs of the pooling; returns (F, m, ids, C, col_start, row_base, bias)"""
     F, m = _lsplm_dims(F, m)
-    if ids.dtype != torch.int64 or ids.dim() != 2:
-        raise ValueError("lsplm: ids must be int64 [B, C], got %s %s" % (ids.dtype, tuple(ids.shape)))
+    ids = _ids_arg("lsplm", ids, "ids")
     C = int(ids.shape[1])
     if col_start is None:
         if C != F:
             raise ValueError("lsplm: without col_start every field is single-valued and ids must be [B, %d], got %s" % (F, tuple(ids.shape)))
     else:
-        if col_start.dtype != torch.int32 or col_start.numel() != F + 1:
-            raise ValueError("lsplm: col_start must be int32 [%d], got %s %s" % (F + 1, col_start.dtype, tuple(col_start.shape)))
+        col_start = _vec_arg("lsplm", col_start, F + 1, "col_start", torch.int32)
         if C < F:
             raise ValueError("lsplm: ids [B, C] needs C >= F = %d columns, got C = %d" % (F, C))
-        col_start = col_start.contiguous()
-    if row_base.dtype != torch.int64 or row_base.numel() != F:
-        raise ValueError("lsplm: row_base must be int64 [%d], got %s %s" % (F, row_base.dtype, tuple(row_base.shape)))
-    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 2 * m or not table.is_contiguous():
-        raise ValueError("lsplm: table must be contiguous fp32 [R, %d] (2 m columns: gate | expert), got %s %s"
-                         % (2 * m, table.dtype, tuple(table.shape)))
+    row_base = _vec_arg("lsplm", row_base, F, "row_base", torch.int64)
+    _table_arg("lsplm", table, "table", 2 * m)
     bias = _dense_arg(bias, "lsplm: bias", numel=2 * m)
     if bias is None:
         raise ValueError("lsplm: bias [%d] is required" % (2 * m))
-    return F, m, ids.contiguous(), C, col_start, row_base.contiguous(), bias
-
-
-def _lsplm_vec(t, B, what):
-    if t is None:
-        return None
-    if t.dtype != torch.float32 or t.numel() != B:
-        raise ValueError("lsplm: %s must be fp32 with one value per example (%d), got %s %s" % (what, B, t.dtype, tuple(t.shape)))
-    return t.reshape(B).contiguous()
-
-
-def _lsplm_mat(t, B, cols, what, device):
-    """(t, its row stride) of a [B, cols] fp32 buffer the kernel writes; allocated when None"""
-    if t is None:
-        t = torch.empty((B, cols), dtype=torch.float32, device=device)
-    if t.dim() != 2 or t.shape[0] != B:
-        raise ValueError("lsplm: %s must be fp32 [%d, %d], got %s %s" % (what, B, cols, t.dtype, tuple(t.shape)))
-    return t, _row_pitch("lsplm", t, cols, what)
+    return F, m, ids, C, col_start, row_base, bias
 
 
 def lsplm_fwd(ids, F, col_start, row_base, table, m, bias, want_z=True, z=None):
@@ -3209,7 +3186,7 @@ def lsplm_fwd(ids, F, col_start, row_base, table, m, bias, want_z=True, z=None):
     B = ids.shape[0]
     ld_z = 0
     if want_z or z is not None:
-        z, ld_z = _lsplm_mat(z, B, 2 * m, "z", ids.device)
+        z, ld_z = _rows_arg("lsplm", z, 2 * m, "z", rows=B, device=ids.device)
     p = torch.empty((B,), dtype=torch.float32, device=ids.device)
     q = torch.empty((B,), dtype=torch.float32, device=ids.device)
     if B == 0:
@@ -3223,15 +3200,13 @@ def lsplm_bwd(z, F, m, d_p, d_z=None, d_rows=None):
     """(d_z [B, 2 m], d_rows [B, F * 2 m]) of dr_lsplm_bwd from the z that lsplm_fwd stored: d_z = d_p [pi (sg - p) ; pi sg (1 - sg)],
     d_rows = F copies of it (emb_pool_bwd's d_concat with D = 2 m).  d_z, d_rows: buffers to overwrite."""
     F, m = _lsplm_dims(F, m)
-    if z.dim() != 2:
-        raise ValueError("lsplm: z must be fp32 [B, %d], got %s" % (2 * m, tuple(z.shape)))
     ld_z = _row_pitch("lsplm", z, 2 * m, "z")
     B = z.shape[0]
-    d_p = _lsplm_vec(d_p, B, "d_p")
+    d_p = _vec_arg("lsplm", d_p, B, "d_p", none_ok=True)
     if d_p is None:
         raise ValueError("lsplm: d_p [%d] is required" % B)
-    d_z, ld_dz = _lsplm_mat(d_z, B, 2 * m, "d_z", z.device)
-    d_rows, ld_d = _lsplm_mat(d_rows, B, F * 2 * m, "d_rows", z.device)
+    d_z, ld_dz = _rows_arg("lsplm", d_z, 2 * m, "d_z", rows=B, device=z.device)
+    d_rows, ld_d = _rows_arg("lsplm", d_rows, F * 2 * m, "d_rows", rows=B, device=z.device)
     if B == 0:
         return d_z, d_rows
     _status(lib().dr_lsplm_bwd(ptr(z), ld_z, ptr(d_p), B, F, m, ptr(d_z), ld_dz, ptr(d_rows), ld_d, stream_ptr()), "dr_lsplm_bwd")
@@ -3244,12 +3219,12 @@ def lsplm_loss_fwd(ids, F, col_start, row_base, table, m, bias, labels, sample_w
     (row_scale * wt) * (-y / p + (1 - y) / q)."""
     F, m, ids, C, col_start, row_base, bias = _lsplm_pool_args(ids, F, col_start, row_base, table, m, bias)
     B = ids.shape[0]
-    labels = _lsplm_vec(labels, B, "labels")
+    labels = _vec_arg("lsplm", labels, B, "labels", none_ok=True)
     if labels is None:
         raise ValueError("lsplm: labels [%d] are required" % B)
-    sample_weight = _lsplm_vec(sample_weight, B, "sample_weight")
-    d_z, ld_dz = _lsplm_mat(d_z, B, 2 * m, "d_z", ids.device)
-    d_rows, ld_d = _lsplm_mat(d_rows, B, F * 2 * m, "d_rows", ids.device)
+    sample_weight = _vec_arg("lsplm", sample_weight, B, "sample_weight", none_ok=True)
+    d_z, ld_dz = _rows_arg("lsplm", d_z, 2 * m, "d_z", rows=B, device=ids.device)
+    d_rows, ld_d = _rows_arg("lsplm", d_rows, F * 2 * m, "d_rows", rows=B, device=ids.device)
     p, q, loss = (torch.empty((B,), dtype=torch.float32, device=ids.device) for _ in range(3))
     if B == 0:
         return p, q, loss, d_z, d_rows
@@ -3262,8 +3237,6 @@ def lsplm_loss_fwd(ids, F, col_start, row_base, table, m, bias, labels, sample_w
 def lsplm_bias_grad(d_z, m):
     """d_bias [2 m] of dr_lsplm_bias_grad: the column sum of d_z [B, 2 m] in a fixed order (two stages, no float atomics)"""
     _, m = _lsplm_dims(1, m)
-    if d_z.dim() != 2:
-        raise ValueError("lsplm: d_z must be fp32 [B, %d], got %s" % (2 * m, tuple(d_z.shape)))
     ld = _row_pitch("lsplm", d_z, 2 * m, "d_z")
     B = d_z.shape[0]
     d_bias = torch.empty((2 * m,), dtype=torch.float32, device=d_z.device)
@@ -3279,14 +3252,12 @@ SGNS_SKIP_EQUAL = 1     # DR_SGNS_SKIP_EQUAL
 
 def _sgns_args(in_table, out_table, centers, contexts, negatives):
     """validates the domain of dr_sgns_*; returns (B, K, D, centers, contexts, negatives) with the ids contiguous"""
-    for t, what in ((in_table, "in_table"), (out_table, "out_table")):
-        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
-            raise ValueError("sgns: %s must be contiguous fp32 [R, D], got %s %s" % (what, t.dtype, tuple(t.shape)))
+    _table_arg("sgns", in_table, "in_table")
+    _table_arg("sgns", out_table, "out_table")
     D = in_table.shape[1]
     if out_table.shape[1] != D:
         raise ValueError("sgns: in_table and out_table must share D, got %d and %d" % (D, out_table.shape[1]))
-    if D % 4 != 0 or not 4 <= D <= 256:
-        raise ValueError("sgns: D must be a multiple of 4 in [4, 256] (the slab's domain), got %d" % D)
+    _slab_width("sgns", D)
     if centers.dtype != torch.int64 or centers.dim() != 1:
         raise ValueError("sgns: centers must be int64 [B], got %s %s" % (centers.dtype, tuple(centers.shape)))
     B = centers.shape[0]
@@ -3294,30 +3265,11 @@ def _sgns_args(in_table, out_table, centers, contexts, negatives):
         raise ValueError("sgns: contexts must be int64 [%d], got %s %s" % (B, contexts.dtype, tuple(contexts.shape)))
     if negatives is None:
         negatives = torch.empty((B, 0), dtype=torch.int64, device=centers.device)
-    if negatives.dtype != torch.int64 or negatives.dim() != 2 or negatives.shape[0] != B:
-        raise ValueError("sgns: negatives must be int64 [%d, K], got %s %s" % (B, negatives.dtype, tuple(negatives.shape)))
+    negatives = _ids_arg("sgns", negatives, "negatives", rows=B)
     K = negatives.shape[1]
     if K > 63:
         raise ValueError("sgns: at most 63 negatives per example (ids [B, 1 + K] go through K4, F <= 64), got K = %d" % K)
-    return B, K, D, centers.contiguous(), contexts.contiguous(), negatives.contiguous()
-
-
-def _sgns_vec(t, B, what):
-    if t.dtype != torch.float32 or t.numel() != B:
-        raise ValueError("sgns: %s must be fp32 with one value per example (%d), got %s %s" % (what, B, t.dtype, tuple(t.shape)))
-    return t.reshape(B).contiguous()
-
-
-def _sgns_grad_buffers(B, K, D, d_center, d_ctx, device):
-    """(d_center [B, D], its pitch, d_ctx [B, (1 + K) D], its pitch): the caller's buffers, checked, or fresh ones"""
-    W = (1 + K) * D
-    if d_center is None:
-        d_center = torch.empty((B, D), dtype=torch.float32, device=device)
-    if d_ctx is None:
-        d_ctx = torch.empty((B, W), dtype=torch.float32, device=device)
-    if d_ctx.dim() == 3 and tuple(d_ctx.shape) == (B, 1 + K, D) and d_ctx.is_contiguous():
-        d_ctx = d_ctx.reshape(B, W)
-    return d_center, _row_pitch("sgns", d_center, D, "d_center"), d_ctx, _row_pitch("sgns", d_ctx, W, "d_ctx")
+    return B, K, D, centers.contiguous(), contexts.contiguous(), negatives
 
 
 def sgns_fwd(in_table, out_table, centers, contexts, negatives=None, sample_weight=None, skip_equal=True, want_scores=False,
@@ -3329,14 +3281,14 @@ def sgns_fwd(in_table, out_table, centers, contexts, negatives=None, sample_weig
     fresh ones) -- what K4 takes as d_concat for ids [B, 1] and [B, 1 + K]."""
     B, K, D, centers, contexts, negatives = _sgns_args(in_table, out_table, centers, contexts, negatives)
     dev = centers.device
-    if sample_weight is not None:
-        sample_weight = _sgns_vec(sample_weight, B, "sample_weight")
+    sample_weight = _vec_arg("sgns", sample_weight, B, "sample_weight", none_ok=True)
     loss = torch.empty((B,), dtype=torch.float32, device=dev)
     coeff = torch.empty((B, 1 + K), dtype=torch.float32, device=dev)
     scores = torch.empty((B, 1 + K), dtype=torch.float32, device=dev) if want_scores else None
     ld_dc = ld_dx = 0
     if row_scale is not None:
-        d_center, ld_dc, d_ctx, ld_dx = _sgns_grad_buffers(B, K, D, d_center, d_ctx, dev)
+        d_center, ld_dc = _rows_arg("sgns", d_center, D, "d_center", rows=B, device=dev)
+        d_ctx, ld_dx = _rows_arg("sgns", d_ctx, (1 + K) * D, "d_ctx", ((1 + K, D),), rows=B, device=dev)
     elif d_center is not None or d_ctx is not None:
         raise ValueError("sgns: gradient buffers are written only with a row_scale")
     if B == 0:
@@ -3354,8 +3306,9 @@ def sgns_bwd(in_table, out_table, centers, contexts, negatives, coeff, d_loss, s
     if coeff.dtype != torch.float32 or tuple(coeff.shape) != (B, 1 + K):
         raise ValueError("sgns: coeff must be fp32 [%d, %d], got %s %s" % (B, 1 + K, coeff.dtype, tuple(coeff.shape)))
     coeff = coeff.contiguous()
-    d_loss = _sgns_vec(d_loss, B, "d_loss")
-    d_center, ld_dc, d_ctx, ld_dx = _sgns_grad_buffers(B, K, D, d_center, d_ctx, centers.device)
+    d_loss = _vec_arg("sgns", d_loss, B, "d_loss")
+    d_center, ld_dc = _rows_arg("sgns", d_center, D, "d_center", rows=B, device=centers.device)
+    d_ctx, ld_dx = _rows_arg("sgns", d_ctx, (1 + K) * D, "d_ctx", ((1 + K, D),), rows=B, device=centers.device)
     if B == 0:
         return d_center, d_ctx
     _status(lib().dr_sgns_bwd(ptr(in_table), ptr(out_table), D, ptr(centers), ptr(contexts), ptr(negatives) if K else None, B, K,
@@ -3456,26 +3409,15 @@ def random_walk_weighted(row_ptr, col, cum, n_rows, starts, length, seed):
 
 
 # ---- skip-gram with side information (csrc/eges.hip) ----------------------------------------------------------------------------------------
-def _eges_one_device(dev, **tensors):
-    """every tensor a dr_eges_* call is handed lives where side_ids does"""
-    for what, t in tensors.items():
-        if t is not None and t.device != dev:
-            raise ValueError("eges: %s is on %s, side_ids on %s; one call takes tensors of one device" % (what, t.device, dev))
-
-
 def _eges_side_args(side_table, row_base, side_ids, att, att_ids):
     """validates the gather side of dr_eges_*; returns (B, S, D, row_base, side_ids, att, ld_att, att_ids), ids contiguous"""
-    if side_table.dtype != torch.float32 or side_table.dim() != 2 or not side_table.is_contiguous():
-        raise ValueError("eges: side_table must be contiguous fp32 [R, D], got %s %s" % (side_table.dtype, tuple(side_table.shape)))
-    D = side_table.shape[1]
-    if D % 4 != 0 or not 4 <= D <= 256:
-        raise ValueError("eges: D must be a multiple of 4 in [4, 256] (the slab's domain), got %d" % D)
-    if side_ids.dtype != torch.int64 or side_ids.dim() != 2:
-        raise ValueError("eges: side_ids must be int64 [B, S], got %s %s" % (side_ids.dtype, tuple(side_ids.shape)))
+    _table_arg("eges", side_table, "side_table")
+    D = _slab_width("eges", side_table.shape[1])
+    side_ids = _ids_arg("eges", side_ids, "side_ids")
     B, S = side_ids.shape
     if not 1 <= S <= 16:
         raise ValueError("eges: 1 <= S <= 16 fields, got %d" % S)
-    _eges_one_device(side_ids.device, side_table=side_table, att=att, att_ids=att_ids if att is not None else None)
+    _one_device("eges", "side_ids", side_ids.device, side_table=side_table, att=att, att_ids=att_ids if att is not None else None)
     if row_base.dtype != torch.int64 or tuple(row_base.shape) != (S,) or row_base.device != side_ids.device:
         raise ValueError("eges: row_base must be int64 [%d] on the ids' device, got %s %s" % (S, row_base.dtype, tuple(row_base.shape)))
     ld_att = 0
@@ -3488,47 +3430,38 @@ def _eges_side_args(side_table, row_base, side_ids, att, att_ids):
         att_ids = att_ids.contiguous()
     else:
         att_ids = None
-    return B, S, D, row_base.contiguous(), side_ids.contiguous(), att, ld_att, att_ids
+    return B, S, D, row_base.contiguous(), side_ids, att, ld_att, att_ids
 
 
 def _eges_slot_args(out_table, contexts, negatives, B, D):
     """validates the slot side of dr_eges_fwd / _bwd; returns (P, K, contexts [B, P], negatives [B, K]) contiguous"""
-    if out_table.dtype != torch.float32 or out_table.dim() != 2 or not out_table.is_contiguous() or out_table.shape[1] != D:
-        raise ValueError("eges: out_table must be contiguous fp32 [R, %d], got %s %s" % (D, out_table.dtype, tuple(out_table.shape)))
+    _table_arg("eges", out_table, "out_table", D)
     if contexts.dtype == torch.int64 and contexts.dim() == 1:
         contexts = contexts.reshape(-1, 1)
-    if contexts.dtype != torch.int64 or contexts.dim() != 2 or contexts.shape[0] != B:
-        raise ValueError("eges: contexts must be int64 [%d, P], got %s %s" % (B, contexts.dtype, tuple(contexts.shape)))
+    contexts = _ids_arg("eges", contexts, "contexts", rows=B)
     P = contexts.shape[1]
     if not 1 <= P <= 4:
         raise ValueError("eges: 1 <= P <= 4 positives per example, got %d" % P)
     if negatives is None:
         negatives = torch.empty((B, 0), dtype=torch.int64, device=contexts.device)
-    if negatives.dtype != torch.int64 or negatives.dim() != 2 or negatives.shape[0] != B:
-        raise ValueError("eges: negatives must be int64 [%d, K], got %s %s" % (B, negatives.dtype, tuple(negatives.shape)))
+    negatives = _ids_arg("eges", negatives, "negatives", rows=B)
     K = negatives.shape[1]
     if P + K > 64:
         raise ValueError("eges: at most 64 slots per example (ids [B, P + K] go through K4, F <= 64), got P + K = %d" % (P + K))
-    return P, K, contexts.contiguous(), negatives.contiguous()
-
-
-def _eges_slot_devices(dev, out_table, contexts, negatives, **more):
-    _eges_one_device(dev, out_table=out_table, contexts=contexts, negatives=negatives, **more)
+    return P, K, contexts, negatives
 
 
 def _eges_grad_buffers(B, S, J, D, d_side, d_att, d_ctx, device):
     """(d_side [B, S D], its pitch, d_att [B, pad4(S)], its width, d_ctx [B, J D], its pitch): the caller's buffers, checked, or fresh"""
     ld_da = _pad4(S)
-    if d_side is None:
-        d_side = torch.empty((B, S * D), dtype=torch.float32, device=device)
     if d_att is None:
         d_att = torch.empty((B, ld_da), dtype=torch.float32, device=device)
-    if d_ctx is None:
-        d_ctx = torch.empty((B, J * D), dtype=torch.float32, device=device)
     if d_att.dtype != torch.float32 or tuple(d_att.shape) != (B, ld_da) or not d_att.is_contiguous():
         raise ValueError("eges: d_att must be contiguous fp32 [%d, %d] (S rounded up to a multiple of 4), got %s %s"
                          % (B, ld_da, d_att.dtype, tuple(d_att.shape)))
-    return d_side, _row_pitch("eges", d_side, S * D, "d_side"), d_att, ld_da, d_ctx, _row_pitch("eges", d_ctx, J * D, "d_ctx")
+    d_side, ld_ds = _rows_arg("eges", d_side, S * D, "d_side", rows=B, device=device)
+    d_ctx, ld_dx = _rows_arg("eges", d_ctx, J * D, "d_ctx", rows=B, device=device)
+    return d_side, ld_ds, d_att, ld_da, d_ctx, ld_dx
 
 
 def eges_fwd(side_table, row_base, side_ids, att, att_ids, out_table, contexts, negatives=None, sample_weight=None, skip_equal=True,
@@ -3542,9 +3475,9 @@ def eges_fwd(side_table, row_base, side_ids, att, att_ids, out_table, contexts, 
     B, S, D, row_base, side_ids, att, ld_att, att_ids = _eges_side_args(side_table, row_base, side_ids, att, att_ids)
     P, K, contexts, negatives = _eges_slot_args(out_table, contexts, negatives, B, D)
     dev = side_ids.device
-    _eges_slot_devices(dev, out_table, contexts, negatives, sample_weight=sample_weight, d_side=d_side, d_att=d_att, d_ctx=d_ctx)
-    if sample_weight is not None:
-        sample_weight = _sgns_vec(sample_weight, B, "sample_weight")
+    _one_device("eges", "side_ids", dev, out_table=out_table, contexts=contexts, negatives=negatives, sample_weight=sample_weight,
+                d_side=d_side, d_att=d_att, d_ctx=d_ctx)
+    sample_weight = _vec_arg("eges", sample_weight, B, "sample_weight", none_ok=True)
     J = P + K
     loss = torch.empty((B,), dtype=torch.float32, device=dev)
     coeff = torch.empty((B, J), dtype=torch.float32, device=dev)
@@ -3570,15 +3503,15 @@ def eges_bwd(side_table, row_base, side_ids, att, att_ids, out_table, contexts, 
     from the forward's coeff and alpha, the rows gathered again.  Same ids, att / att_ids and skip_equal as the forward."""
     B, S, D, row_base, side_ids, att, _, att_ids = _eges_side_args(side_table, row_base, side_ids, att, att_ids)
     P, K, contexts, negatives = _eges_slot_args(out_table, contexts, negatives, B, D)
-    _eges_slot_devices(side_ids.device, out_table, contexts, negatives, coeff=coeff, alpha=alpha, d_loss=d_loss, d_side=d_side, d_att=d_att,
-                       d_ctx=d_ctx)
+    _one_device("eges", "side_ids", side_ids.device, out_table=out_table, contexts=contexts, negatives=negatives, coeff=coeff, alpha=alpha,
+                d_loss=d_loss, d_side=d_side, d_att=d_att, d_ctx=d_ctx)
     J = P + K
     if coeff.dtype != torch.float32 or tuple(coeff.shape) != (B, J):
         raise ValueError("eges: coeff must be fp32 [%d, %d], got %s %s" % (B, J, coeff.dtype, tuple(coeff.shape)))
     if alpha.dtype != torch.float32 or tuple(alpha.shape) != (B, S):
         raise ValueError("eges: alpha must be fp32 [%d, %d], got %s %s" % (B, S, alpha.dtype, tuple(alpha.shape)))
     coeff, alpha = coeff.contiguous(), alpha.contiguous()
-    d_loss = _sgns_vec(d_loss, B, "d_loss")
+    d_loss = _vec_arg("eges", d_loss, B, "d_loss")
     d_side, ld_ds, d_att, ld_da, d_ctx, ld_dx = _eges_grad_buffers(B, S, J, D, d_side, d_att, d_ctx, side_ids.device)
     if B == 0:
         return d_side, d_att, d_ctx
@@ -3591,12 +3524,8 @@ def eges_bwd(side_table, row_base, side_ids, att, att_ids, out_table, contexts, 
 def eges_embed(side_table, row_base, side_ids, att=None, att_ids=None, out=None):
     """out [n, D] of dr_eges_embed: the aggregated vector of every row of side_ids [n, S] alone; a row with no field present is +0.0"""
     n, S, D, row_base, side_ids, att, ld_att, att_ids = _eges_side_args(side_table, row_base, side_ids, att, att_ids)
-    if out is None:
-        out = torch.empty((n, D), dtype=torch.float32, device=side_ids.device)
-    _eges_one_device(side_ids.device, out=out)
-    ld_out = _row_pitch("eges", out, D, "out")
-    if out.shape[0] != n:
-        raise ValueError("eges: out must have %d rows, got %d" % (n, out.shape[0]))
+    _one_device("eges", "side_ids", side_ids.device, out=out)
+    out, ld_out = _rows_arg("eges", out, D, "out", rows=n, device=side_ids.device)
     if n == 0:
         return out
     _status(lib().dr_eges_embed(ptr(side_table), D, ptr(row_base), ptr(side_ids), S, ptr(att), ld_att, ptr(att_ids), n, ptr(out), ld_out,
@@ -3608,13 +3537,6 @@ def eges_embed(side_table, row_base, side_ids, att=None, att_ids=None, out=None)
 SAMPLE_LONG_ROW = 512      # DR_SAMPLE_LONG_ROW: a row with more edges is selected by a whole block (radix select), a shorter one by a wave
 SAMPLE_MAX_FANOUT = 64     # the largest fanout of dr_neighbor_sample / dr_block_csr and the largest T of dr_walk_neighbors
 WALK_MAX_VISITS = 1024     # dr_walk_neighbors: R (L - 1) at most
-
-
-def _block_one_device(family, dev, **tensors):
-    """every tensor a sampling call is handed lives on one device"""
-    for what, t in tensors.items():
-        if t is not None and t.device != dev:
-            raise ValueError("%s: %s is on %s, the call's first tensor on %s; one call takes tensors of one device" % (family, what, t.device, dev))
 
 
 def _fanout_arg(family, what, fanout):
@@ -3637,7 +3559,7 @@ def neighbor_sample(row_ptr, col, n_rows, nodes, fanout, seed):
     if nodes.dim() != 1:
         raise ValueError("neighbor_sample: nodes must be int64 [n], got %s %s" % (nodes.dtype, tuple(nodes.shape)))
     nodes = _dense_arg(nodes, "neighbor_sample: nodes", torch.int64)
-    _block_one_device("neighbor_sample", row_ptr.device, col=col, nodes=nodes)
+    _one_device("neighbor_sample", "the call's first tensor", row_ptr.device, col=col, nodes=nodes)
     n = nodes.numel()
     nbr = torch.empty((n, fanout), dtype=torch.int64, device=nodes.device)
     cnt = torch.empty((n,), dtype=torch.int32, device=nodes.device)
@@ -3678,7 +3600,7 @@ def frontier_build(dst, nbr, id_bound=0):
         raise ValueError("frontier_build: dst must be int64 [n_dst], got %s %s" % (dst.dtype, tuple(dst.shape)))
     dst = _dense_arg(dst, "frontier_build: dst", torch.int64)
     nbr = _dense_arg(nbr, "frontier_build: nbr", torch.int64)
-    _block_one_device("frontier_build", dst.device, nbr=nbr)
+    _one_device("frontier_build", "the call's first tensor", dst.device, nbr=nbr)
     n_dst, m = dst.numel(), nbr.numel()
     if n_dst + m >= 2 ** 31:
         raise ValueError("frontier_build: dst and nbr together must stay below 2^31 entries, got %d" % (n_dst + m))
@@ -3709,7 +3631,7 @@ def block_csr(cnt, local, weight=None, add_self=False, n_valid=None):
     weight = _dense_arg(weight, "block_csr: weight", torch.float32, shape=(n_dst, fanout))
     n_valid = _dense_arg(n_valid, "block_csr: n_valid", torch.int64, numel=1)
     dev = local.device
-    _block_one_device("block_csr", dev, cnt=cnt, weight=weight, n_valid=n_valid)
+    _one_device("block_csr", "the call's first tensor", dev, cnt=cnt, weight=weight, n_valid=n_valid)
     extra = 1 if add_self else 0
     row_ptr = torch.zeros((n_dst + 1,), dtype=torch.int64, device=dev)
     col = torch.empty((max(1, n_dst * (fanout + extra)),), dtype=torch.int32, device=dev)
@@ -3759,39 +3681,26 @@ def sampled_softmax_workspace(B, S, D, device):
     return torch.empty(max(16, sampled_softmax_workspace_bytes(B, S, D)), dtype=torch.uint8, device=device)
 
 
-def _ssm_vec(t, n, what, dtype=torch.float32):
-    if t is None:
-        return None
-    if t.dtype != dtype or t.numel() != n:
-        raise ValueError("sampled_softmax: %s must be %s with %d values, got %s %s" % (what, dtype, n, t.dtype, tuple(t.shape)))
-    return t.reshape(n).contiguous()
-
-
 def _ssm_args(u, table, labels, sampled, log_q_true, log_q_sampled, sample_weight):
     """validates the domain of dr_sampled_softmax_*; returns (B, S, V, D, ld_u, labels, sampled, log_q_true, log_q_sampled, sample_weight)"""
-    if table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
-        raise ValueError("sampled_softmax: table must be contiguous fp32 [V, D] (a view is refused: its rows are read in place by id), "
-                         "got %s %s with strides %s" % (table.dtype, tuple(table.shape), tuple(table.stride())))
+    _table_arg("sampled_softmax", table, "table")
     V, D = table.shape
-    if D % 4 != 0 or not 4 <= D <= 256:
-        raise ValueError("sampled_softmax: D must be a multiple of 4 in [4, 256] (the slab's domain), got %d" % D)
+    _slab_width("sampled_softmax", D)
     if not 1 <= V < 2 ** 31:
         raise ValueError("sampled_softmax: needs 1 <= V < 2^31 classes, got %d" % V)
     ld_u = _row_pitch("sampled_softmax", u, D, "u")
     B = u.shape[0]
-    if labels.dtype != torch.int64 or labels.numel() != B:
-        raise ValueError("sampled_softmax: labels must be int64 [%d], got %s %s" % (B, labels.dtype, tuple(labels.shape)))
+    labels = _vec_arg("sampled_softmax", labels, B, "labels", torch.int64)
     if sampled.dtype != torch.int64 or sampled.dim() != 1:
         raise ValueError("sampled_softmax: sampled must be int64 [S], got %s %s" % (sampled.dtype, tuple(sampled.shape)))
     S = sampled.shape[0]
     if not 1 <= S < 2 ** 31:
         raise ValueError("sampled_softmax: needs 1 <= S < 2^31 sampled classes, got %d" % S)
-    for t, what in ((u, "u"), (labels, "labels"), (sampled, "sampled"), (log_q_true, "log_q_true"), (log_q_sampled, "log_q_sampled"),
-                    (sample_weight, "sample_weight")):
-        if t is not None and t.device != table.device:
-            raise ValueError("sampled_softmax: %s is on %s, the table on %s" % (what, t.device, table.device))
-    return (B, S, V, D, ld_u, labels.reshape(B).contiguous(), sampled.contiguous(), _ssm_vec(log_q_true, B, "log_q_true"),
-            _ssm_vec(log_q_sampled, S, "log_q_sampled"), _ssm_vec(sample_weight, B, "sample_weight"))
+    _one_device("sampled_softmax", "the table", table.device, u=u, labels=labels, sampled=sampled, log_q_true=log_q_true,
+                log_q_sampled=log_q_sampled, sample_weight=sample_weight)
+    return (B, S, V, D, ld_u, labels, sampled.contiguous(), _vec_arg("sampled_softmax", log_q_true, B, "log_q_true", none_ok=True),
+            _vec_arg("sampled_softmax", log_q_sampled, S, "log_q_sampled", none_ok=True),
+            _vec_arg("sampled_softmax", sample_weight, B, "sample_weight", none_ok=True))
 
 
 def sampled_softmax_fwd(u, table, labels, sampled, log_q_true=None, log_q_sampled=None, sample_weight=None, remove_accidental_hits=True,
@@ -3826,12 +3735,9 @@ def sampled_softmax_bwd(u, table, labels, sampled, true_logit, row_lse, log_q_sa
     B, S, V, D, ld_u, labels, sampled, _, log_q_sampled, sample_weight = _ssm_args(u, table, labels, sampled, None, log_q_sampled,
                                                                                   sample_weight)
     dev = table.device
-    true_logit, row_lse = _ssm_vec(true_logit, B, "true_logit"), _ssm_vec(row_lse, B, "row_lse")
-    if d_u is None:
-        d_u = torch.empty((B, D), dtype=torch.float32, device=dev)
-    ld_du = _row_pitch("sampled_softmax", d_u, D, "d_u")
-    if d_u.shape[0] != B:
-        raise ValueError("sampled_softmax: d_u must have %d rows, got %d" % (B, d_u.shape[0]))
+    true_logit = _vec_arg("sampled_softmax", true_logit, B, "true_logit", none_ok=True)
+    row_lse = _vec_arg("sampled_softmax", row_lse, B, "row_lse", none_ok=True)
+    d_u, ld_du = _rows_arg("sampled_softmax", d_u, D, "d_u", rows=B, device=dev)
     d_true = torch.empty((B, D), dtype=torch.float32, device=dev)
     d_sampled = torch.empty((S, D), dtype=torch.float32, device=dev)
     if B == 0:
@@ -3893,23 +3799,12 @@ def margin_rank_workspace(B, S, D, num_hard, device):
 
 def margin_rank_options(D, metric, num_hard):
     """the host-side domain of the options, shared with the EBR model: (metric code, num_hard); ValueError otherwise"""
-    if int(D) % 4 != 0 or not 4 <= int(D) <= 256:
-        raise ValueError("margin_rank: D must be a multiple of 4 in [4, 256], got %d" % int(D))
+    _slab_width("margin_rank", D)
     if metric not in MARGIN_RANK_METRICS:
         raise ValueError("margin_rank: metric must be one of %s, got %r" % (sorted(MARGIN_RANK_METRICS), metric))
     if int(num_hard) != num_hard or not 0 <= int(num_hard) <= MARGIN_RANK_MAX_HARD:
         raise ValueError("margin_rank: num_hard must be an integer in [0, %d], got %r" % (MARGIN_RANK_MAX_HARD, num_hard))
     return MARGIN_RANK_METRICS[metric], int(num_hard)
-
-
-def _mr_vec(t, n, what, dtype, dev):
-    if t is None:
-        return None
-    if t.dtype != dtype or t.numel() != n:
-        raise ValueError("margin_rank: %s must be %s with %d values, got %s %s" % (what, dtype, n, t.dtype, tuple(t.shape)))
-    if t.device != dev:
-        raise ValueError("margin_rank: %s is on %s, q on %s" % (what, t.device, dev))
-    return t.reshape(n).contiguous()
 
 
 def _mr_args(q, pos, neg, pos_ids, neg_ids, sample_weight, metric, num_hard):
@@ -3931,11 +3826,10 @@ def _mr_args(q, pos, neg, pos_ids, neg_ids, sample_weight, metric, num_hard):
     if not in_batch and not 1 <= S < 2 ** 31:
         raise ValueError("margin_rank: needs 1 <= S < 2^31 negatives, got %d" % S)
     dev = q.device
-    for t, what in ((pos, "pos"), (neg, "neg")):
-        if t.device != dev:
-            raise ValueError("margin_rank: %s is on %s, q on %s" % (what, t.device, dev))
-    return (B, S, D, ld_q, ld_p, ld_n, neg, in_batch, _mr_vec(pos_ids, B, "pos_ids", torch.int64, dev),
-            _mr_vec(neg_ids, S, "neg_ids", torch.int64, dev), _mr_vec(sample_weight, B, "sample_weight", torch.float32, dev), code, K)
+    _one_device("margin_rank", "q", dev, pos=pos, neg=neg)
+    return (B, S, D, ld_q, ld_p, ld_n, neg, in_batch, _vec_arg("margin_rank", pos_ids, B, "pos_ids", torch.int64, none_ok=True, device=dev),
+            _vec_arg("margin_rank", neg_ids, S, "neg_ids", torch.int64, none_ok=True, device=dev),
+            _vec_arg("margin_rank", sample_weight, B, "sample_weight", torch.float32, none_ok=True, device=dev), code, K)
 
 
 def margin_rank_fwd(q, pos, neg=None, pos_ids=None, neg_ids=None, sample_weight=None, margin=0.2, metric="cosine", num_hard=0,
@@ -3975,18 +3869,14 @@ def margin_rank_bwd(q, pos, neg, pos_score, hard_idx, pos_ids=None, neg_ids=None
     B, S, D, ld_q, ld_p, ld_n, neg, in_batch, pos_ids, neg_ids, sample_weight, code, K = _mr_args(q, pos, neg, pos_ids, neg_ids,
                                                                                                  sample_weight, metric, num_hard)
     dev = q.device
-    pos_score = _mr_vec(pos_score, B, "pos_score", torch.float32, dev)
+    pos_score = _vec_arg("margin_rank", pos_score, B, "pos_score", torch.float32, none_ok=True, device=dev)
     if K > 0:
         if hard_idx is None:
             raise ValueError("margin_rank: num_hard = %d needs the forward's hard_idx" % K)
-        hard_idx = _mr_vec(hard_idx, B * K, "hard_idx", torch.int32, dev)
+        hard_idx = _vec_arg("margin_rank", hard_idx, B * K, "hard_idx", torch.int32, none_ok=True, device=dev)
     else:
         hard_idx = None
-    if d_q is None:
-        d_q = torch.empty((B, D), dtype=torch.float32, device=dev)
-    ld_dq = _row_pitch("margin_rank", d_q, D, "d_q")
-    if d_q.shape[0] != B:
-        raise ValueError("margin_rank: d_q must have %d rows, got %d" % (B, d_q.shape[0]))
+    d_q, ld_dq = _rows_arg("margin_rank", d_q, D, "d_q", rows=B, device=dev)
     d_pos = torch.empty((B, D), dtype=torch.float32, device=dev)
     d_neg = torch.empty((S, D), dtype=torch.float32, device=dev)
     if B == 0:
@@ -4015,22 +3905,13 @@ def _bert_arg(t, what, dtype, shape=None):
     return t
 
 
-def _bert_rows(t, what):
-    """[M, N] fp32 with unit column stride and a row pitch >= N (one row has no pitch); ValueError naming the argument otherwise"""
-    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < 1 or (t.shape[1] > 1 and t.stride(1) != 1)
-            or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
-        raise ValueError("%s must be fp32 [M, N] with unit column stride and a row stride >= N, got %s" % (
-            what, "%s %s with strides %s" % (t.dtype, tuple(t.shape), tuple(t.stride())) if isinstance(t, torch.Tensor) else type(t).__name__))
-    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-
-
 def gelu_fwd(z, out=None):
     """h [M, N] = z * Phi(z), the exact (erf) GELU of dr_gelu_fwd; z may be a view with a row pitch and is left as it is"""
-    ld_z = _bert_rows(z, "gelu_fwd: z")
+    ld_z = _pitched("gelu_fwd", z, "z")
     M, N = z.shape
     if out is None:
         out = torch.empty((M, _pad4(N)), dtype=torch.float32, device=z.device)[:, :N]
-    ld_h = _bert_rows(out, "gelu_fwd: out")
+    ld_h = _pitched("gelu_fwd", out, "out")
     if tuple(out.shape) != (M, N):
         raise ValueError("gelu_fwd: out must be %s, got %s" % ((M, N), tuple(out.shape)))
     check(lib().dr_gelu_fwd(ptr(z), ld_z, M, N, ptr(out), ld_h, stream_ptr()), "dr_gelu_fwd")
@@ -4039,8 +3920,8 @@ def gelu_fwd(z, out=None):
 
 def gelu_bwd_(z, dy):
     """in place: dy *= Phi(z) + z phi(z), the GELU's derivative through the saved pre-activation z"""
-    ld_z = _bert_rows(z, "gelu_bwd_: z")
-    ld_dy = _bert_rows(dy, "gelu_bwd_: dy")
+    ld_z = _pitched("gelu_bwd_", z, "z")
+    ld_dy = _pitched("gelu_bwd_", dy, "dy")
     if z.shape != dy.shape:
         raise ValueError("gelu_bwd_: z %s and dy %s differ in shape" % (tuple(z.shape), tuple(dy.shape)))
     check(lib().dr_gelu_bwd(ptr(z), ld_z, ptr(dy), ld_dy, z.shape[0], z.shape[1], stream_ptr()), "dr_gelu_bwd")
@@ -4094,7 +3975,7 @@ def bert_embed_bwd(ids, segment, tok, pos, seg, gamma, stats, d_out, d_tok, rate
     if not isinstance(d_out, torch.Tensor) or d_out.dtype != torch.float32 or d_out.numel() != N * D:
         raise ValueError("bert_embed_bwd: d_out must be fp32 with %d elements" % (N * D))
     d_out = d_out.reshape(N, D)
-    ld_do = _bert_rows(d_out, "bert_embed_bwd: d_out") if N > 0 else D
+    ld_do = _pitched("bert_embed_bwd", d_out, "d_out") if N > 0 else D
     dev = tok.device
     d_s = torch.empty((N, D), dtype=torch.float32, device=dev)
     d_gamma = torch.zeros(D, dtype=torch.float32, device=dev)
@@ -4119,7 +4000,7 @@ def softmax_ce_ids(logits, labels, bias=None, weight=None, smoothing=0.0, row_sc
     row_scale * w / (denom + denom_eps) * (softmax(logits + bias) - (1 - smoothing) * onehot(labels) - smoothing / C).  labels int64 [M],
     a negative one marks a padding row (loss 0, a zero gradient row, its logits never read); denom is a one-element DEVICE tensor.
     _path (tests only): 1 forces the kernel that stages the row in LDS, 2 the one that re-reads it from memory."""
-    ld = _bert_rows(logits, "softmax_ce_ids: logits")
+    ld = _pitched("softmax_ce_ids", logits, "logits")
     M, C = logits.shape
     _bert_arg(labels, "softmax_ce_ids: labels", torch.int64, (M,))
     if bias is not None:
@@ -4147,7 +4028,7 @@ def colsum_add_workspace(M, C, device):
 
 def colsum_add(g, dst, workspace=None):
     """dst [C] += the column sums of g [M, C] (a row pitch is honoured), in a fixed order: dr_colsum_add"""
-    ld = _bert_rows(g, "colsum_add: g")
+    ld = _pitched("colsum_add", g, "g")
     M, C = g.shape
     _bert_arg(dst, "colsum_add: dst", torch.float32, (C,))
     if workspace is None or workspace.numel() * 4 < lib().dr_colsum_add_workspace_bytes(M, C):
@@ -4189,11 +4070,12 @@ INTENT_MAX_TYPES = 7        # R, the neighbour types of a typed block
 INTENT_MAX_FILTERS = 16     # L, the local filters of a layer
 
 
+_INTENT_ROWS = dict(mult4=True, aligned=True, tight_row=True)     # how dr_intent_* take h, out and the gradients (_pitched's policy)
+
+
 def _intent_dims(R, D, L, act):
     """validates the domain of dr_intent_*; returns (R, D, L, act) as ints"""
-    R, D, L = int(R), int(D), int(L)
-    if D % 4 != 0 or not 4 <= D <= 256:
-        raise ValueError("intent_conv: the row width D must be a multiple of 4 in [4, 256], got D = %d" % D)
+    R, D, L = int(R), _slab_width("intent_conv", D, "the row width D"), int(L)
     if not 1 <= R <= INTENT_MAX_TYPES:
         raise ValueError("intent_conv: needs 1 <= R <= %d neighbour types, got R = %d" % (INTENT_MAX_TYPES, R))
     if not 1 <= L <= INTENT_MAX_FILTERS:
@@ -4201,21 +4083,6 @@ def _intent_dims(R, D, L, act):
     if act not in (0, 1):
         raise ValueError("intent_conv: act must be 0 (linear) or 1 (relu), got %r" % (act,))
     return R, D, L, int(act)
-
-
-def _intent_rows(t, rows, D, what, min_rows=False):
-    """the row pitch of an fp32 [rows, D] matrix the kernels take where it lies (a view with a pitch passes; nothing is copied): unit
-    column stride, a pitch that is a multiple of 4 floats and >= D, a 16-byte aligned base; ValueError naming `what` otherwise.
-    min_rows: at least `rows` rows (the source rows of a block, whose first n_dst are the destinations)."""
-    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != D or (t.shape[0] < rows if min_rows else t.shape[0] != rows):
-        raise ValueError("intent_conv: %s must be fp32 [%s%d, %d], got %s %s" % (what, ">= " if min_rows else "", rows, D, t.dtype,
-                                                                                 tuple(t.shape)))
-    if t.stride(1) != 1 or (t.shape[0] > 1 and (t.stride(0) % 4 != 0 or t.stride(0) < D)):
-        raise ValueError("intent_conv: %s needs unit column stride and a row pitch that is a multiple of 4 and >= %d, got strides %s"
-                         % (what, D, tuple(t.stride())))
-    if t.data_ptr() % 16 != 0:
-        raise ValueError("intent_conv: %s must start at a 16-byte aligned address (a view that begins inside a row does not)" % what)
-    return t.stride(0) if t.shape[0] > 1 else D
 
 
 def _intent_filters(W, theta, R=None):
@@ -4249,13 +4116,13 @@ def intent_conv_fwd(row_ptr, col, val, n_dst, R, h, W, theta, act=1, want_agg=Fa
     if h.dim() != 2:
         raise ValueError("intent_conv: h must be fp32 [n_src, D], got %s" % (tuple(h.shape),))
     R, D, L, act = _intent_dims(R, h.shape[1], L, act)
-    ld_h = _intent_rows(h, n_dst, D, "h", min_rows=True)
+    ld_h = _pitched("intent_conv", h, "h", D, n_dst, min_rows=True, **_INTENT_ROWS)
     row_ptr = _dense_arg(row_ptr, "intent_conv: row_ptr", torch.int64, shape=(n_dst * R + 1,))
     col = _dense_arg(col, "intent_conv: col", torch.int32)
     val = _dense_arg(val, "intent_conv: val", torch.float32, numel=col.numel())
     if out is None:
         out = torch.empty((n_dst, D), dtype=torch.float32, device=h.device)
-    ld_out = _intent_rows(out, n_dst, D, "out")
+    ld_out = _pitched("intent_conv", out, "out", D, n_dst, **_INTENT_ROWS)
     agg = torch.empty((n_dst, R, D), dtype=torch.float32, device=h.device) if want_agg else None
     if n_dst == 0:
         return out, agg
@@ -4273,11 +4140,11 @@ def intent_mix_fwd(h_self, agg, W, theta, act=1, out=None):
         raise ValueError("intent_conv: h_self must be fp32 [n_dst, D], got %s" % (tuple(h_self.shape),))
     n_dst = int(h_self.shape[0])
     R, D, L, act = _intent_dims(R, h_self.shape[1], L, act)
-    ld_h = _intent_rows(h_self, n_dst, D, "h_self")
+    ld_h = _pitched("intent_conv", h_self, "h_self", D, n_dst, **_INTENT_ROWS)
     agg = _intent_agg(agg, n_dst, R, D, "agg")
     if out is None:
         out = torch.empty((n_dst, D), dtype=torch.float32, device=h_self.device)
-    ld_out = _intent_rows(out, n_dst, D, "out")
+    ld_out = _pitched("intent_conv", out, "out", D, n_dst, **_INTENT_ROWS)
     if n_dst == 0:
         return out
     _status(lib().dr_intent_mix_fwd(ptr(h_self), ld_h, ptr(agg), n_dst, R, D, ptr(W), ptr(theta), L, act, ptr(out), ld_out, stream_ptr()),
@@ -4301,14 +4168,14 @@ def intent_conv_bwd(h_self, agg, d_out, W, theta, act=1, out=None, d_self=None, 
         raise ValueError("intent_conv: h_self must be fp32 [n_dst, D], got %s" % (tuple(h_self.shape),))
     n_dst = int(h_self.shape[0])
     R, D, L, act = _intent_dims(R, h_self.shape[1], L, act)
-    ld_h = _intent_rows(h_self, n_dst, D, "h_self")
+    ld_h = _pitched("intent_conv", h_self, "h_self", D, n_dst, **_INTENT_ROWS)
     agg = _intent_agg(agg, n_dst, R, D, "agg")
-    ld_do = _intent_rows(d_out, n_dst, D, "d_out")
-    ld_out = _intent_rows(out, n_dst, D, "out") if out is not None else 0
+    ld_do = _pitched("intent_conv", d_out, "d_out", D, n_dst, **_INTENT_ROWS)
+    ld_out = _pitched("intent_conv", out, "out", D, n_dst, **_INTENT_ROWS) if out is not None else 0
     dev = h_self.device
     if d_self is None:
         d_self = torch.empty((n_dst, D), dtype=torch.float32, device=dev)
-    ld_ds = _intent_rows(d_self, n_dst, D, "d_self")
+    ld_ds = _pitched("intent_conv", d_self, "d_self", D, n_dst, **_INTENT_ROWS)
     d_agg = torch.empty((n_dst, R, D), dtype=torch.float32, device=dev)
     d_W = torch.zeros((L, R + 1), dtype=torch.float32, device=dev)
     d_theta = torch.zeros((L,), dtype=torch.float32, device=dev)
